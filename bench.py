@@ -73,7 +73,12 @@ def parse():
                     "(they run by default for the contract's own command: N = 1, the headline workload, extras on; about 30 s)")
     ap.add_argument("--traffic", action="store_true", help="run those passes for any other N = 1 command too")
     ap.add_argument("--save-png", default=None)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step of the headline workload returned as DIR/<name>.npy "
+                    "(image.npy, ray_counts.npy; images over 64 MB as a fixed seeded sample of pixels), to compare two builds output for output")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def algorithmic_bytes(st):
@@ -97,6 +102,28 @@ def traffic_from_profiles(scene, height, spp):
         return None
     d = json.load(open(tpath))
     return {"file": os.path.relpath(tpath, ROOT), "source": d.get("source"), "bytes_per_launch": d["bytes_per_launch"]}
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21  # 2 M pixels: 24 MB of radiance + 16 MB of indices
+DUMP_SAMPLE_SEED = 0x5EED0D0D
+
+
+def dump_outputs(d, image, st):
+    """--dump-outputs: the arrays the timed path returned in its last step — the float32 image [height, width, 3] and the ray counts
+    [camera, shadow, indirect] of this rank's stats (float64, exact).  An image over DUMP_MAX_BYTES is written as a fixed sample
+    instead: image_sample.npy [n, 3] at the flat pixel indices of image_sample_pixels.npy (float64, sorted, drawn with a fixed seed)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(d, "image.npy"), image)
+    else:
+        flat = image.reshape(-1, 3)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.shape[0], size=DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(os.path.join(d, "image_sample.npy"), flat[idx])
+        np.save(os.path.join(d, "image_sample_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(d, "ray_counts.npy"), np.array([st.rays_camera, st.rays_shadow, st.rays_indirect], dtype=np.float64))
 
 
 def live_traffic(a):
@@ -171,7 +198,7 @@ class Bench:
             self.dist.barrier()
             self.torch.cuda.synchronize()
 
-    def measure(self, scene_name, width, height, spp, steps, warmup, seed, leaf=None, tris=None, base_flags=0, also_overlap=False, save_png=None, builder=None):
+    def measure(self, scene_name, width, height, spp, steps, warmup, seed, leaf=None, tris=None, base_flags=0, also_overlap=False, save_png=None, builder=None, dump_dir=None):
         """Counting render (untimed), warm-up, then `steps` timed renders of one workload.  Returns the result fields."""
         T, D, torch, a = self.T, self.D, self.torch, self.a
         world, rank, local_rank, dist = self.world, self.rank, self.local_rank, self.dist
@@ -226,6 +253,8 @@ class Bench:
             render_ms += st.render_ms
         self.sync()
         elapsed = time.perf_counter() - t_begin
+        if dump_dir and img is not None:  # before the profiling step below renders into the same buffer again
+            dump_outputs(dump_dir, img.cpu().numpy(), st)
         rank_render_ms, rank_gather_ms = step_times.totals_ms() if group is None else (0.0, 0.0)
         # the profiling step: the same render once more with hipEvents around every launch (on the launch stream, inside the
         # library); its per-kernel sums are scaled to `steps` so that every per-step figure below keeps its meaning
@@ -417,7 +446,7 @@ def main():
     B.live = live
     seed = a.seed if a.seed is not None else SEEDS[a.scene]
     res, scene = B.measure(a.scene, a.width, a.height, a.spp, a.steps, a.warmup, seed, leaf=a.leaf, tris=a.tris,
-                           base_flags=T.TRT_FLAG_OVERLAP if a.overlap else 0, also_overlap=not a.no_overlap_extra, save_png=a.save_png)
+                           base_flags=T.TRT_FLAG_OVERLAP if a.overlap else 0, also_overlap=not a.no_overlap_extra, save_png=a.save_png, dump_dir=a.dump_outputs)
     if rank == 0:
         result = {"metric": "Mrays/s", "value": res["value"], "unit": "Mrays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                   "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32"}

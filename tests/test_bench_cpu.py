@@ -64,3 +64,35 @@ def test_live_traffic_reports_why_it_could_not_run(tmp_path, monkeypatch):
     monkeypatch.setenv("ROCPROFILER_SOMETHING", "1")   # this process is itself being profiled: no nested passes
     by, note = bench.live_traffic(_args())
     assert by == {} and "not attempted" in note
+
+
+def test_dump_outputs_writes_the_image_and_ray_counts(tmp_path):
+    """--dump-outputs: the whole float32 image when it fits in 64 MB, the ray counts as exact float64."""
+    import numpy as np
+    from tinyraytracing_amd import Stats
+    img = np.random.default_rng(1).random((54, 96, 3), dtype=np.float32)
+    st = Stats(rays_camera=5184, rays_shadow=7000, rays_indirect=3001)
+    bench.dump_outputs(str(tmp_path / "d"), img, st)
+    assert sorted(os.listdir(tmp_path / "d")) == ["image.npy", "ray_counts.npy"]
+    got = np.load(tmp_path / "d" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, img)
+    rc = np.load(tmp_path / "d" / "ray_counts.npy")
+    assert rc.dtype == np.float64 and rc.tolist() == [5184, 7000, 3001]
+
+
+def test_dump_outputs_samples_a_large_image_the_same_way_every_time(tmp_path):
+    """An image over 64 MB (3840x2160 is 95 MB) is written as a fixed seeded sample of pixels: the same indices on every run, under 64 MB in all."""
+    import numpy as np
+    from tinyraytracing_amd import Stats
+    img = np.arange(2160 * 3840 * 3, dtype=np.float32).reshape(2160, 3840, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), img, Stats())
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["image_sample.npy", "image_sample_pixels.npy", "ray_counts.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    idx = np.load(tmp_path / "a" / "image_sample_pixels.npy")
+    px = np.load(tmp_path / "a" / "image_sample.npy")
+    assert idx.dtype == np.float64 and px.dtype == np.float32 and len(np.unique(idx)) == len(idx) == len(px)
+    assert np.array_equal(px, img.reshape(-1, 3)[idx.astype(np.int64)])
