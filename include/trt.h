@@ -87,7 +87,11 @@ typedef struct trt_material {
 
 /* One <light> element, XML order (scene.cpp:25-54).  area = Material::area
  * accumulated in readobj (scene.cpp:201-203).  `radiance` is kept for the caller's convenience only: both the emissive hit
- * (pathTracing.cpp:11) and the direct term (pathTracing.cpp:65) read materials[mat].radiance, and so does this library. */
+ * (pathTracing.cpp:11) and the direct term (pathTracing.cpp:65) read materials[mat].radiance, and so does this library.
+ * A scene may have 0 to TRT_MAX_SCENE_LIGHTS lights (trt_create refuses more with TRT_EINVAL).  Every light adds a 48-B shadow-ray
+ * record per path to the queue memory of a pass (trt_params::mem_budget: 132 + 48 * n_lights bytes per path), 16 KiB of
+ * counters per pass slot, and one shadow-ray launch per bounce. */
+#define TRT_MAX_SCENE_LIGHTS 65535u
 typedef struct trt_light {
     int32_t mat;          /* material id of mtlname */
     float radiance[3];
@@ -131,7 +135,7 @@ typedef struct trt_scene {
     uint32_t bvh_depth;      /* max number of inner nodes on a root->leaf path */
     uint32_t n_materials;
     const trt_material* materials;
-    uint32_t n_lights;
+    uint32_t n_lights;       /* <= TRT_MAX_SCENE_LIGHTS (see trt_light) */
     const trt_light* lights;
     uint32_t n_light_tris;
     const trt_light_tri* light_tris;
@@ -177,7 +181,8 @@ typedef struct trt_params {
     int32_t row_block, row_mod, row_rem;
     int32_t max_depth;       /* 0 = unbounded like the reference (pathTracing.cpp:78-99) */
     uint32_t flags;
-    uint64_t mem_budget;     /* bytes of HBM for path/queue state; 0 = three quarters of what is free (one pass when it fits) */
+    uint64_t mem_budget;     /* bytes of HBM for path/queue state (132 + 48 * n_lights per path and sample in a pass); 0 = three quarters of
+                              * what is free (one pass when it fits); too small for one sample of every pixel of the tile: TRT_ENOMEM */
 } trt_params;
 
 #define TRT_MAX_KERNELS 8

@@ -42,6 +42,9 @@ int trth_scene_drop_tris(trth_scene* s, uint32_t first, uint32_t count);
 /* Synthetic geometry added to a loaded base scene (scenes/back): see host/synth.cpp. */
 int trth_scene_add_soup(trth_scene* s, uint32_t seed, uint64_t n_random);
 int trth_scene_add_blob(trth_scene* s, uint32_t seed, uint64_t n_min_faces);
+/* n_lamps small area lights under the ceiling of the loaded `back` box (2 to 6 triangles each, own material and <light> entry,
+ * hashed radiance, size and placement; areas on both sides of light 0's); the box and its own light stay. */
+int trth_scene_add_lamps(trth_scene* s, uint32_t seed, uint32_t n_lamps);
 
 /* buildBVH(scene.triangles, 0, n-1, leaf_num) (main.cpp:76) + flattening. */
 int trth_scene_build(trth_scene* s, int leaf_num, int builder);

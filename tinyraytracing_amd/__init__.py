@@ -22,6 +22,7 @@ SEED_BACK = 0x5EED0001
 SEED_SOUP = 0x5EED0003
 SEED_STAIRCASE = 0x5EED0004
 SEED_BLOB = 0x5EED0005
+SEED_LAMPS = 0x5EED0006  # Scene.named("lamps"): placement, size and radiance of the added lamps
 
 _BUILDERS = {"sweep": 0, "binned": 1, "auto": 2}
 # Triangles per BVH leaf.  The reference calls buildBVH(..., 8) (main.cpp:76); on the GPU 2 measured fastest on every
@@ -66,11 +67,16 @@ class Scene:
     @classmethod
     def named(cls, name, width=0, height=0, leaf_num=None, builder="auto", n=None, seed=None, device=0):
         """Shipped and synthetic scenes: back, veach-mis, staircase, soup (n random triangles in
-        the back box, BASELINE config 3), blob (displaced geodesic sphere, config 5).  `device`: where builder="lbvh" runs
+        the back box, BASELINE config 3), blob (displaced geodesic sphere, config 5), lamps (back with n = 16 more area lights
+        under its ceiling: n + 1 lights, host/synth.cpp).  `device`: where builder="lbvh" runs
         (a rank of a multi-GPU job passes its own GPU; the host builders ignore it)."""
         if name in ("back", "veach-mis", "staircase"):
             d = os.path.join(SCENES_DIR, name)
             s = cls.load(os.path.join(d, name + ".xml"), os.path.join(d, name + ".obj"), os.path.join(d, name + ".mtl"), d, width, height)
+        elif name == "lamps":
+            d = os.path.join(SCENES_DIR, "back")
+            s = cls.load(os.path.join(d, "back.xml"), os.path.join(d, "back.obj"), os.path.join(d, "back.mtl"), d, width, height)
+            s._check(s._lib.trth_scene_add_lamps(s._h, SEED_LAMPS if seed is None else seed, 16 if n is None else int(n)))
         elif name in ("soup", "blob"):
             d = os.path.join(SCENES_DIR, "back")
             s = cls.load(os.path.join(d, "back.xml"), os.path.join(d, "back.obj"), os.path.join(d, "back.mtl"), d, width, height)

@@ -46,16 +46,20 @@ int fail(int code, const std::string& msg)
 constexpr uint32_t MAX_TRACE_BLOCKS = 8192;                       // persistent grid cap of the traversal kernels
 constexpr uint32_t SPILL_STRIDE = MAX_TRACE_BLOCKS * TRT_TRACE_BLOCK;
 constexpr uint32_t MAX_BOUNCES = TRT_MAX_PATH_DEPTH + 2;
-constexpr uint32_t COUNT_ROW = 16;                                // counters per bounce: [0] = queue length, [1+l] = shadow rays of light l
 // Device layout of the counters: counter c of bounce b lives at d_counts[c * COUNT_STRIDE + b], so the
 // counters k_shade bumps in one launch lie 16 KiB apart (different L2 channels: the atomic units work in
 // parallel) instead of in one cache line.
 constexpr uint32_t COUNT_STRIDE = (MAX_BOUNCES + 2 + 1023u) & ~1023u;
-// Rows PAIR_ROW and PAIR_ROW + 1 hold, as one 64-bit word per bounce b, the two counters k_shade reserves with one atomic:
-// low word = length of the queue of bounce b + 1, high word = shadow rays of the last light at bounce b.
-constexpr uint32_t PAIR_ROW = COUNT_ROW - 2;
-static_assert(1 + TRT_MAX_LIGHTS <= (int)PAIR_ROW, "counter rows overlap");
-inline unsigned long long* pairCounter(uint32_t* d_counts, uint32_t b) { return reinterpret_cast<unsigned long long*>(d_counts + (size_t)PAIR_ROW * COUNT_STRIDE) + b; }
+// Counter rows per bounce for a scene of nl lights: [0] = queue length, [1+l] = shadow rays of light l, and the last two rows
+// (the pair rows) hold, as one 64-bit word per bounce b, the two counters k_shade reserves with one atomic: low word = length of
+// the queue of bounce b + 1, high word = shadow rays of the last light at bounce b.  k_publish_counts also reads row nl (the
+// last light's own row, unused), so the pair rows start at nl + 1 or later: 16 rows up to 13 lights, multiples of 16 beyond.
+constexpr uint32_t COUNT_ROW_MIN = 16;
+inline uint32_t countRows(uint32_t nl) { return std::max(COUNT_ROW_MIN, (nl + 3u + 15u) & ~15u); }
+inline unsigned long long* pairCounter(uint32_t* d_counts, uint32_t rows, uint32_t b) { return reinterpret_cast<unsigned long long*>(d_counts + (size_t)(rows - 2u) * COUNT_STRIDE) + b; }
+// The most lights a scene may have: the counters take COUNT_STRIDE * 4 B = 16 KiB per light and pass slot (1 GiB per slot at the
+// bound), and every light costs a shadow launch per bounce (include/trt.h TRT_MAX_SCENE_LIGHTS).
+static_assert(TRT_MAX_SCENE_LIGHTS <= 65535u, "counter area");
 constexpr uint32_t MAX_BVH_DEPTH = 256;
 // node kind of the persistent traversal kernels when the tree qualifies for both (DESIGN.md §4.1 has the A/B)
 #ifndef TRT_DEFAULT_NODE_KIND
@@ -121,6 +125,7 @@ struct trt_handle {
     hipStream_t slot_streams[2] = {nullptr, nullptr};  // one per concurrent pass (trt_render_device)
     int n_slots = 2;                                   // TRT_SLOTS=1 in the environment vetoes TRT_FLAG_OVERLAP
     uint32_t* pinned_counts = nullptr;                 // host-pinned landing zone of the per-bounce queue lengths
+    uint32_t count_rows = COUNT_ROW_MIN;               // counter rows per bounce (countRows(n_lights)); the landing zone has 2 * count_rows + 16 words per slot
     uint32_t slot_seq[2] = {0, 0};                     // last sequence number published per slot: monotonic over the handle's life, so a
                                                        // word left behind by an earlier (even a failed) call never equals an expected one
     int fail_at_bounce = -1;                           // TRT_TEST_FAIL_AT_BOUNCE at trt_create: the next render reports an injected failure
@@ -417,7 +422,7 @@ int buildSceneImage(const trt_scene* s, SceneImage& im)
     if (s->n_nodes < 1 || !s->nodes) return fail(TRT_EINVAL, "scene needs at least the root node");
     if (s->n_tris > TRT_MAX_TRIS) return fail(TRT_EINVAL, "too many triangles");
     if (s->n_tris && (!s->tri_v || !s->tri_vn || !s->tri_vt || !s->tri_mat)) return fail(TRT_EINVAL, "null triangle arrays");
-    if (s->n_lights > (uint32_t)TRT_MAX_LIGHTS) return fail(TRT_EINVAL, "more than 8 lights");
+    if (s->n_lights > TRT_MAX_SCENE_LIGHTS) return fail(TRT_EINVAL, "more than TRT_MAX_SCENE_LIGHTS (65535) lights");
     if (s->n_materials < 1 || !s->materials) return fail(TRT_EINVAL, "scene needs materials");
     if (s->n_materials >= (1u << 24)) return fail(TRT_EINVAL, "too many materials");
     for (uint32_t i = 0; i < s->n_tris; ++i)
@@ -640,16 +645,19 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->spill_words_per_slot = (size_t)spill_levels * SPILL_STRIDE;
     if (int e = h->spill.ensure(h->spill_words_per_slot * 2 * sizeof(uint32_t))) return e;  // one area per concurrent pass
     for (hipStream_t& st : h->slot_streams) HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    HIPC(hipHostMalloc((void**)&h->pinned_counts, 2 * (2 * COUNT_ROW + 16) * sizeof(uint32_t), hipHostMallocDefault));  // per slot: counters + sequence word
-    std::memset(h->pinned_counts, 0, 2 * (2 * COUNT_ROW + 16) * sizeof(uint32_t));  // sequence words start at 0; the first one asked for is 1
+    h->count_rows = countRows(h->sc.n_lights);
+    const size_t pinned_words = 2 * (2 * (size_t)h->count_rows + 16);  // per slot: counters + sequence word
+    HIPC(hipHostMalloc((void**)&h->pinned_counts, pinned_words * sizeof(uint32_t), hipHostMallocDefault));
+    std::memset(h->pinned_counts, 0, pinned_words * sizeof(uint32_t));  // sequence words start at 0; the first one asked for is 1
     if (const char* e = std::getenv("TRT_SLOTS")) h->n_slots = std::atoi(e) >= 2 ? 2 : 1;
     if (const char* e = std::getenv("TRT_TEST_FAIL_AT_BOUNCE")) h->fail_at_bounce = std::atoi(e);
     if (const char* e = std::getenv("TRT_SHADE_PAD_LDS")) {
         h->shade_pad_lds = std::min(100000u, (uint32_t)std::strtoul(e, nullptr, 10));
         // more than 64 KiB per block needs the opt-in; a refusal shows as a launch error, not as a silent no-op
 #define TRT_PAD_ATTR(T) \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_ONE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_FEW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_MANY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
         TRT_PAD_ATTR(31u) TRT_PAD_ATTR(15u) TRT_PAD_ATTR(7u) TRT_PAD_ATTR(3u) TRT_PAD_ATTR(0u)
 #undef TRT_PAD_ATTR
     }
@@ -700,9 +708,9 @@ struct PassSlot {
     RayQueue Q[2];
     f4* hit = nullptr;
     f4* Lacc = nullptr;
-    ShadowQueue SQ[TRT_MAX_LIGHTS];
+    ShadowArena shadow{nullptr, 0};   // the shadow queues of every light
     uint32_t* d_counts = nullptr;
-    uint32_t* host_counts = nullptr;  // pinned, device-visible: 2 * COUNT_ROW counters + the sequence word
+    uint32_t* host_counts = nullptr;  // pinned, device-visible: 2 * count_rows counters + the sequence word
     uint32_t seq = 0;                 // last sequence number asked for
     uint32_t* spill = nullptr;
     RedoList redo{nullptr, nullptr};  // rays the traversal kernels hand to k_trace_fix (trt_kernels.h)
@@ -775,7 +783,8 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         budget /= 2;
     }
     const size_t rows_bytes = (rows.size() * sizeof(int32_t) + 255) & ~(size_t)255;
-    const size_t counts_bytes = (size_t)COUNT_STRIDE * COUNT_ROW * sizeof(uint32_t);
+    const uint32_t count_rows = h->count_rows;
+    const size_t counts_bytes = (size_t)COUNT_STRIDE * count_rows * sizeof(uint32_t);
     const size_t stats_bytes = 256;  // DeviceStats (128 B), then the redo counters of the pass slots (two words each)
     const size_t acc_bytes = (size_t)npix * 3 * sizeof(double);
     if (int e = h->small_buf.ensure(rows_bytes + counts_bytes * N_SLOTS + stats_bytes + acc_bytes)) return e;
@@ -795,12 +804,12 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         for (int q = 0; q < 2; ++q) { S.Q[q].ra = take(); S.Q[q].rb = take(); S.Q[q].bt = take(); }
         S.hit = take();
         S.Lacc = take();
-        for (uint32_t l = 0; l < (uint32_t)TRT_MAX_LIGHTS; ++l) S.SQ[l] = ShadowQueue{nullptr, nullptr, nullptr};
-        for (uint32_t l = 0; l < nl; ++l) { S.SQ[l].sa = take(); S.SQ[l].sb = take(); S.SQ[l].sw = take(); }
+        S.shadow = ShadowArena{base, N};  // light l: sa, sb, sw = the next three arrays (ShadowArena::queue)
+        base += (size_t)N * 3 * nl;
         S.redo.idx = (uint32_t*)base;  // N indices behind the queues
         S.redo.count = d_redo + 2 * k;
         S.d_counts = (uint32_t*)(sb + rows_bytes + counts_bytes * (size_t)k);
-        S.host_counts = h->pinned_counts + (size_t)k * (2 * COUNT_ROW + 16);
+        S.host_counts = h->pinned_counts + (size_t)k * (2 * count_rows + 16);
         S.seq = h->slot_seq[k];
         S.spill = (uint32_t*)h->spill.p + (size_t)k * h->spill_words_per_slot;
     }
@@ -897,8 +906,13 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         A.hit = S.hit;
         A.n = S.n_active;
         A.qout = S.Q[S.cur ^ 1];
-        for (int l = 0; l < TRT_MAX_LIGHTS; ++l) A.sq[l] = S.SQ[l];
-        A.pair_count = pairCounter(S.d_counts, S.b);
+        // k_shade's three flavours (trt_kernels.h): 512-thread blocks at 6 waves per SIMD for one light, 256-thread blocks at 5 for
+        // several; more than TRT_MAX_LIGHTS lights find their queues in the arena instead of in the kernel arguments
+        const int lights = nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY);
+        if (lights == SHADE_MANY) A.sq_arena = S.shadow;
+        else
+            for (uint32_t l = 0; l < (uint32_t)TRT_MAX_LIGHTS; ++l) A.sq[l] = l < nl ? S.shadow.queue(l) : ShadowQueue{nullptr, nullptr, nullptr};
+        A.pair_count = pairCounter(S.d_counts, count_rows, S.b);
         A.shadow_counts = S.d_counts + (size_t)COUNT_STRIDE + S.b;  // light l: + l * COUNT_STRIDE
         A.shadow_count_stride = COUNT_STRIDE;
         A.Lacc = S.Lacc;
@@ -913,16 +927,16 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         A.lds_tshade_bytes = h->lds_tab[4];
         A.lds_image = (const f4*)h->lds_image;
         A.lds_image_words = h->lds_image_bytes / 16u;
-        const bool one_light = nl == 1u;  // k_shade's two flavours (trt_kernels.h): 512-thread blocks at 6 waves per SIMD, or 256-thread blocks at 5
-        const uint32_t shade_block = one_light ? (uint32_t)TRT_SHADE1_BLOCK : (uint32_t)TRT_SHADEN_BLOCK;
+        const uint32_t shade_block = lights == SHADE_ONE ? (uint32_t)TRT_SHADE1_BLOCK : (uint32_t)TRT_SHADEN_BLOCK;
         A.rows_lds = (rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)rows.size() : 0u;
         A.stats = d_stats;
         tm.begin(TRT_K_SHADE, S.stream);
         {
             const dim3 grid(std::min<uint32_t>((S.n_active + shade_block - 1) / shade_block, 65536u)), blk(shade_block);
 #define TRT_LAUNCH_SHADE(T) \
-            if (one_light) hipLaunchKernelGGL((k_shade<T, true>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
-            else hipLaunchKernelGGL((k_shade<T, false>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A);
+            if (lights == SHADE_ONE) hipLaunchKernelGGL((k_shade<T, SHADE_ONE>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
+            else if (lights == SHADE_FEW) hipLaunchKernelGGL((k_shade<T, SHADE_FEW>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
+            else hipLaunchKernelGGL((k_shade<T, SHADE_MANY>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A);
             switch (h->shade_tabs) {
                 case 31u: TRT_LAUNCH_SHADE(31u) break;
                 case 15u: TRT_LAUNCH_SHADE(15u) break;
@@ -936,8 +950,9 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         st.launches[TRT_K_SHADE]++;
         // (b, c) and (b + 1, c) of the counters in use -> host_counts[2 * c], [2 * c + 1], then the sequence word
         S.seq++;
-        hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(64), 0, S.stream, S.d_counts, COUNT_STRIDE, S.b, 1u + nl, pairCounter(S.d_counts, S.b),
-                           (volatile uint32_t*)S.host_counts, S.seq);
+        const uint32_t publish_block = std::min(1024u, (2u * (1u + nl) + 63u) & ~63u);
+        hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(publish_block), 0, S.stream, S.d_counts, COUNT_STRIDE, S.b, 1u + nl,
+                           pairCounter(S.d_counts, count_rows, S.b), (volatile uint32_t*)S.host_counts, 2u * count_rows, S.seq);
         S.state = PassSlot::WAIT;
         if (h->fail_at_bounce >= 0 && (int)S.b == h->fail_at_bounce) {  // test hook: fail with this bounce's kernels in flight
             h->fail_at_bounce = -1;
@@ -948,7 +963,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     // queue lengths are back: shadow rays of this bounce, then the next bounce / the tail / the end of the pass
     auto completeBounce = [&](PassSlot& S) -> int {
         {   // spin on the sequence word the device writes after the counters; the stream is the fallback (and the error path)
-            volatile uint32_t* flag = (volatile uint32_t*)S.host_counts + 2 * COUNT_ROW;
+            volatile uint32_t* flag = (volatile uint32_t*)S.host_counts + 2 * count_rows;
             const auto t0 = std::chrono::steady_clock::now();
             uint32_t spins = 0;
             while (*flag != S.seq) {
@@ -965,8 +980,8 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
             if (ns > S.n_active) return fail(TRT_EHIP, "internal error: shadow queue longer than its input");
             if (!ns) continue;
             tm.begin(TRT_K_TRACE_SHADOW, S.stream);
-            if (count) launchTraceShadow<true>(h, S.stream, S.spill, S.SQ[l], ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee, S.redo, h->light_boxes[l]);
-            else launchTraceShadow<false>(h, S.stream, S.spill, S.SQ[l], ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee, S.redo, h->light_boxes[l]);
+            if (count) launchTraceShadow<true>(h, S.stream, S.spill, S.shadow.queue(l), ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee, S.redo, h->light_boxes[l]);
+            else launchTraceShadow<false>(h, S.stream, S.spill, S.shadow.queue(l), ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee, S.redo, h->light_boxes[l]);
             tm.end(S.stream);
             st.launches[TRT_K_TRACE_SHADOW]++;
             st.rays_shadow += ns;

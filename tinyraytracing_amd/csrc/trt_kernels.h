@@ -42,7 +42,7 @@ constexpr int TRT_TRACE_BLOCK = 256;
 #define TRT_LDS_STACK_MAX_LEVELS 16
 #endif
 constexpr int TRT_LDS_STACK_MAX = TRT_LDS_STACK_MAX_LEVELS;   // deepest LDS stack (x 256 lanes x 4 B per block); deeper levels spill to global
-// k_shade comes in two flavours, chosen by the scene's light count (round 4; profiles/r04_ab_shade_tail.txt).  The kernel waits on memory at low
+// k_shade comes in three flavours, chosen by the scene's light count (round 4; profiles/r04_ab_shade_tail.txt).  The kernel waits on memory at low
 // occupancy (one block per CU instead of two: 1.67x its time), and a CU takes whole blocks whose waves divide evenly over its 4 SIMDs:
 //   ONE light (back, soup, blob: nl known at compile time, no per-light stage pipeline): 80 VGPRs without scratch -> 512-thread blocks, THREE per CU
 //     = 6 waves per SIMD (was 108 VGPRs, 2 blocks, 4 waves): k_shade -13 % on `back`, -14 % on the 10 M mesh;
@@ -50,6 +50,8 @@ constexpr int TRT_LDS_STACK_MAX = TRT_LDS_STACK_MAX_LEVELS;   // deepest LDS sta
 //     per SIMD instead of two: -14 % on veach-mis, -10 % on staircase.  (256-thread blocks with one light LOSE 60 %: twice the queue
 //     reservations on ONE counter — same-address atomics serialise at ~6 ns —; with several lights they spread over the lights' counters
 //     and a tile takes longer.  640-thread blocks: 10 waves do not divide over 4 SIMDs and only one block lands on a CU: +55 %.)
+//   MORE than TRT_MAX_LIGHTS lights: the several-light kernel with the shadow-queue descriptors computed from ShadeArgs::sq_arena
+//     (scalar arithmetic) instead of read from the kernel arguments: also 96 VGPRs without scratch, 256-thread blocks, 5 waves per SIMD.
 #ifndef TRT_SHADE1_BLOCK
 #define TRT_SHADE1_BLOCK 512
 #endif
@@ -65,6 +67,12 @@ constexpr int TRT_LDS_STACK_MAX = TRT_LDS_STACK_MAX_LEVELS;   // deepest LDS sta
 #ifndef TRT_SHADE_PIPE
 #define TRT_SHADE_PIPE 0
 #endif
+// k_shade's light-count flavours (the LIGHTS template parameter).  SHADE_ONE and SHADE_FEW get the shadow-queue descriptors of the
+// scene's lights as kernel arguments (ShadeArgs::sq); a scene with more than TRT_MAX_LIGHTS lights runs SHADE_MANY, which computes
+// them from the queue arena instead (ShadeArgs::sq_arena): the kernarg segment cannot hold an unbounded array.
+constexpr int SHADE_ONE = 0;   // exactly one light: the loop over the lights' stages is empty at compile time
+constexpr int SHADE_FEW = 1;   // 0 or 2..TRT_MAX_LIGHTS lights
+constexpr int SHADE_MANY = 2;  // more than TRT_MAX_LIGHTS lights
 constexpr int TRT_MAX_LIGHTS = 8;
 
 struct RayQueue {
@@ -76,6 +84,17 @@ struct ShadowQueue {
     f4* sa;
     f4* sb;
     f4* sw;
+};
+// The shadow queues of all lights as the render loop carves them from its arena: light l's sa / sb / sw arrays start at
+// base + (3 l + 0 / 1 / 2) n records (n = paths of the pass).
+struct ShadowArena {
+    f4* base;
+    uint64_t n;
+    __host__ __device__ ShadowQueue queue(uint32_t l) const
+    {
+        f4* q = base + (uint64_t)l * 3u * n;
+        return ShadowQueue{q, q + n, q + 2u * n};
+    }
 };
 
 struct DeviceStats {
@@ -940,7 +959,10 @@ struct ShadeArgs {
     const f4* hit;
     uint32_t n;
     RayQueue qout;
-    ShadowQueue sq[TRT_MAX_LIGHTS];
+    union {
+        ShadowQueue sq[TRT_MAX_LIGHTS];  // SHADE_ONE / SHADE_FEW: the queues of lights 0..n_lights-1
+        ShadowArena sq_arena;            // SHADE_MANY: every light's queue, computed (scalar arithmetic on kernel arguments)
+    };
     unsigned long long* pair_count;  // low word: survivors -> qout, high word: shadow rays of the LAST light (one reservation for both)
     uint32_t* shadow_counts;  // light l < n_lights - 1: shadow_counts[l * shadow_count_stride]
     uint32_t shadow_count_stride;
@@ -990,8 +1012,15 @@ struct RowsShade {
 // run-time choice the pointers are generic, the accesses FLAT, and each of them waits for vmcnt(0) — i.e. for the ray
 // stores issued before it — as well as for the LDS.
 // (Round 3's probe `short` — weight and throughput records stored as 8 bytes, wrong images — bought k_shade 3 %: profiles/r03_ab_oct.txt (8).)
-// ONE_LIGHT: the scene has exactly one light (the loop over the lights' stages is empty at compile time).  BLOCK threads, WAVES per SIMD asked of the compiler.
-template <uint32_t TABS, bool ONE_LIGHT, int BLOCK = (ONE_LIGHT ? TRT_SHADE1_BLOCK : TRT_SHADEN_BLOCK), int WAVES = (ONE_LIGHT ? TRT_SHADE1_WAVES : TRT_SHADEN_WAVES)>
+// LIGHTS: SHADE_ONE, SHADE_FEW or SHADE_MANY (where the shadow-queue descriptors come from).  BLOCK threads, WAVES per SIMD asked of the compiler.
+template <int LIGHTS>
+__device__ inline ShadowQueue shadeQueue(const ShadeArgs& A, uint32_t li)
+{
+    if (LIGHTS == SHADE_MANY) return A.sq_arena.queue(li);
+    return A.sq[li];
+}
+template <uint32_t TABS, int LIGHTS, int BLOCK = (LIGHTS == SHADE_ONE ? TRT_SHADE1_BLOCK : TRT_SHADEN_BLOCK),
+          int WAVES = (LIGHTS == SHADE_ONE ? TRT_SHADE1_WAVES : TRT_SHADEN_WAVES)>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A)
 {
     constexpr int TRT_SHADE_BLOCK = BLOCK;
@@ -1093,7 +1122,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         uint32_t pend_rank = 0, pend_li = 0;
         f3 pend_wo = mk3(0, 0, 0), pend_w = mk3(0, 0, 0);
         float pend_tmax = TRT_INF;  // TRT_FLAG_FIXED_NEE: how far the occlusion test of the shadow ray reaches
-        const uint32_t nl = ONE_LIGHT ? 1u : sc.n_lights;
+        const uint32_t nl = LIGHTS == SHADE_ONE ? 1u : sc.n_lights;
         for (uint32_t li = 0; li + 1 < nl; ++li) {  // every light but the last: a stage of its own
             bool emit = false;
             f3 wo = mk3(0, 0, 0), contrib = mk3(0, 0, 0);
@@ -1105,9 +1134,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
             if (pend_emit) {
                 const uint32_t slot = pend_s[TRT_SHADE_BLOCK / 64] + pend_s[threadIdx.x >> 6] + pend_rank;
                 const f3 so = rayOrigin(c, pend_wo);  // Q6: the hit point itself unless TRT_FLAG_RAY_OFFSET
-                TRT_STQ(2, A.sq[pend_li].sa + slot, mk4(so.x, so.y, so.z, pend_wo.x));
-                TRT_STQ(2, A.sq[pend_li].sb + slot, mk4(pend_wo.y, pend_wo.z, u2f(c.pid), pend_tmax));
-                TRT_STQ(2, A.sq[pend_li].sw + slot, mk4(pend_w.x, pend_w.y, pend_w.z, 0.0f));
+                TRT_STQ(2, shadeQueue<LIGHTS>(A, pend_li).sa + slot, mk4(so.x, so.y, so.z, pend_wo.x));
+                TRT_STQ(2, shadeQueue<LIGHTS>(A, pend_li).sb + slot, mk4(pend_wo.y, pend_wo.z, u2f(c.pid), pend_tmax));
+                TRT_STQ(2, shadeQueue<LIGHTS>(A, pend_li).sw + slot, mk4(pend_w.x, pend_w.y, pend_w.z, 0.0f));
             }
             pend_s = s; pend_emit = emit; pend_rank = rank; pend_li = li; pend_wo = wo; pend_w = c.beta * contrib; pend_tmax = t_max;
         }
@@ -1134,9 +1163,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         if (pend_emit) {  // the last light but one (its base was published before the barrier above)
             const uint32_t slot = pend_s[TRT_SHADE_BLOCK / 64] + pend_s[threadIdx.x >> 6] + pend_rank;
             const f3 so = rayOrigin(c, pend_wo);
-            TRT_STQ(2, A.sq[pend_li].sa + slot, mk4(so.x, so.y, so.z, pend_wo.x));
-            TRT_STQ(2, A.sq[pend_li].sb + slot, mk4(pend_wo.y, pend_wo.z, u2f(c.pid), pend_tmax));
-            TRT_STQ(2, A.sq[pend_li].sw + slot, mk4(pend_w.x, pend_w.y, pend_w.z, 0.0f));
+            TRT_STQ(2, shadeQueue<LIGHTS>(A, pend_li).sa + slot, mk4(so.x, so.y, so.z, pend_wo.x));
+            TRT_STQ(2, shadeQueue<LIGHTS>(A, pend_li).sb + slot, mk4(pend_wo.y, pend_wo.z, u2f(c.pid), pend_tmax));
+            TRT_STQ(2, shadeQueue<LIGHTS>(A, pend_li).sw + slot, mk4(pend_w.x, pend_w.y, pend_w.z, 0.0f));
         }
         f4 nra = mk4(0, 0, 0, 0), nrb = nra, nbt = nra;
         if (emit_next) shadeNextFinish(c, plan, nra, nrb, nbt);
@@ -1148,9 +1177,9 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         if (emit_s) {
             const uint32_t slot = s2[2 * (TRT_SHADE_BLOCK / 64) + 1] + s2[TRT_SHADE_BLOCK / 64 + 1 + (threadIdx.x >> 6)] + rank_s;
             const f3 so = rayOrigin(c, wo_s);
-            TRT_STQ(2, A.sq[nl - 1u].sa + slot, mk4(so.x, so.y, so.z, wo_s.x));
-            TRT_STQ(2, A.sq[nl - 1u].sb + slot, mk4(wo_s.y, wo_s.z, u2f(c.pid), tmax_s));
-            TRT_STQ(2, A.sq[nl - 1u].sw + slot, mk4(w_s.x, w_s.y, w_s.z, 0.0f));
+            TRT_STQ(2, shadeQueue<LIGHTS>(A, nl - 1u).sa + slot, mk4(so.x, so.y, so.z, wo_s.x));
+            TRT_STQ(2, shadeQueue<LIGHTS>(A, nl - 1u).sb + slot, mk4(wo_s.y, wo_s.z, u2f(c.pid), tmax_s));
+            TRT_STQ(2, shadeQueue<LIGHTS>(A, nl - 1u).sw + slot, mk4(w_s.x, w_s.y, w_s.z, 0.0f));
         }
         if (emit_next) {
             const uint32_t slot = s2[TRT_SHADE_BLOCK / 64] + s2[threadIdx.x >> 6] + rank_next;
@@ -1296,13 +1325,12 @@ __global__ __launch_bounds__(256) void k_finalize(const double* __restrict__ acc
 }
 
 // The queue lengths of a bounce, pushed to the host: counters (b, c) and (b + 1, c), c = 0..n-1, into a pinned,
-// device-visible host buffer (out[2c], out[2c+1]), then a sequence number — the host spins on that word instead of
-// paying a DMA copy plus a stream-synchronise wake-up per bounce (one wave, launched behind k_shade).
-__global__ __launch_bounds__(64) void k_publish_counts(const uint32_t* __restrict__ counts, uint32_t stride, uint32_t b, uint32_t n,
-                                                        const unsigned long long* __restrict__ pair, volatile uint32_t* out, uint32_t seq)
+// device-visible host buffer (out[2c], out[2c+1]), then a sequence number at out[seq_word] — the host spins on that word instead
+// of paying a DMA copy plus a stream-synchronise wake-up per bounce (one block, launched behind k_shade; 64 threads up to 31 lights).
+__global__ __launch_bounds__(1024) void k_publish_counts(const uint32_t* __restrict__ counts, uint32_t stride, uint32_t b, uint32_t n,
+                                                          const unsigned long long* __restrict__ pair, volatile uint32_t* out, uint32_t seq_word, uint32_t seq)
 {
-    const uint32_t t = threadIdx.x;
-    if (t < 2u * n) {
+    for (uint32_t t = threadIdx.x; t < 2u * n; t += blockDim.x) {
         const uint32_t c = t >> 1, which = t & 1u;
         uint32_t v = counts[(size_t)c * stride + b + which];
         // the two counters k_shade keeps in one word (ShadeArgs::pair_count): queue length of bounce b + 1, shadow rays of the last light
@@ -1312,8 +1340,8 @@ __global__ __launch_bounds__(64) void k_publish_counts(const uint32_t* __restric
     }
     __threadfence_system();
     __syncthreads();
-    if (t == 0) {
-        __hip_atomic_store(const_cast<uint32_t*>(out) + 2u * 16u, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(const_cast<uint32_t*>(out) + seq_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 

@@ -79,6 +79,15 @@ int trth_scene_add_blob(trth_scene* s, uint32_t seed, uint64_t n)
     return 0;
 }
 
+int trth_scene_add_lamps(trth_scene* s, uint32_t seed, uint32_t n_lamps)
+{
+    if (!s) return fail("null scene");
+    if (s->flat) return fail("scene already built");
+    if ((uint64_t)s->scene.lights.size() + n_lamps > TRT_MAX_SCENE_LIGHTS) return fail("trth_scene_add_lamps: more than TRT_MAX_SCENE_LIGHTS lights");
+    try { trt::makeLampsScene(s->scene, seed, n_lamps); } catch (const std::exception& e) { return fail(e); }
+    return 0;
+}
+
 int trth_scene_build(trth_scene* s, int leaf_num, int builder)
 {
     if (!s) return fail("null scene");

@@ -96,5 +96,8 @@ void makeSoupScene(Scene& scene, uint32_t seed, uint64_t n_random, int width, in
 // A noise-displaced icosphere with >= n_min faces and smooth vertex normals inside the
 // `back` box.
 void makeBlobScene(Scene& scene, uint32_t seed, uint64_t n_min, int width, int height);
+// n_lamps small emissive polygons (2 to 6 triangles, facing down) under the ceiling of the `back` box, each with its own
+// material and <light> entry, hashed radiance, size and placement; areas on both sides of light 0's.
+void makeLampsScene(Scene& scene, uint32_t seed, uint32_t n_lamps);
 
 }  // namespace trt

@@ -1,11 +1,13 @@
 // synth.cpp — deterministic synthetic geometry for the large BASELINE.json
 // configurations: "soup" = n random small triangles inside the
 // Cornell box (config 3: deep-BVH stress), "blob" = a noise-displaced geodesic
-// sphere with smooth normals (config 5: Stanford-style mesh).  Both are added to
-// an already loaded base scene (scenes/back) whose walls and light close and
+// sphere with smooth normals (config 5: Stanford-style mesh), "lamps" = many small
+// area lights under the ceiling (scenes with any number of lights).  All are added
+// to an already loaded base scene (scenes/back) whose walls and light close and
 // light the scene.  Integer-hash based: no <random>, no files.
 #include <cmath>
 #include <stdexcept>
+#include <string>
 
 #include "scene.h"
 #include "trt_prims.h"
@@ -146,6 +148,71 @@ void makeBlobScene(Scene& scene, uint32_t seed, uint64_t n_min, int width, int h
         for (uint64_t j = 0; i + j < m; ++j) {
             emit(row0 + 2 * j, corner(faces[f], i, j), corner(faces[f], i + 1, j), corner(faces[f], i, j + 1));
             if (i + j + 1 < m) emit(row0 + 2 * j + 1, corner(faces[f], i + 1, j), corner(faces[f], i + 1, j + 1), corner(faces[f], i, j + 1));
+        }
+    }
+}
+
+void makeLampsScene(Scene& scene, uint32_t seed, uint32_t n_lamps)
+{
+    if (scene.lights.empty()) throw std::runtime_error("lamps: the base scene has no light");
+    const int mat0 = requireMaterial(scene, scene.lights[0].mtl_name.c_str());
+    const Material proto = scene.materials[(size_t)mat0];  // Kd / Ks / Tr / Ns / Ni of the lamps: those of the scene's first light
+    const double area0 = proto.area;
+    if (!(area0 > 0.0)) throw std::runtime_error("lamps: the base scene's first light has no area");
+    const Hash h{seed};
+    const float kPi = 3.14159265358979f;
+    for (uint32_t i = 0; i < n_lamps; ++i) {
+        // every fourth lamp (from lamp 1 on) is larger than light 0, the others smaller: with the reference's CDF draw over
+        // lights[0].area (Q3) the large ones always pick one of their first triangles, the small ones now and then none
+        const bool large = i % 4u == 1u;
+        const double area = area0 * (large ? 1.1 + 0.9 * h.u(i, 0) : 0.01 + 0.5 * h.u(i, 0));
+        const uint32_t n_tris = 2u + (uint32_t)(h.u(i, 1) * 5.0f);  // 2 (a rectangle) to 6 (a hexagon fan)
+        // size: rectangle w x d, or a regular n-gon of circumradius r around a centre vertex
+        const float aspect = 0.5f + 1.5f * h.u(i, 2);
+        const float r = n_tris == 2u ? 0.5f * std::sqrt((float)area * (aspect + 1.0f / aspect))
+                                     : std::sqrt(2.0f * (float)area / ((float)n_tris * std::sin(2.0f * kPi / (float)n_tris)));
+        const float x = r + 1.0f + h.u(i, 3) * std::max(0.0f, 556.0f - 2.0f * r - 2.0f);
+        const float z = r + 1.0f + h.u(i, 4) * std::max(0.0f, 559.2f - 2.0f * r - 2.0f);
+        const float y = 545.0f - 40.0f * h.u(i, 5);
+        const float phase = 2.0f * kPi * h.u(i, 6);
+        const vec3 c(x, y, z);
+        const vec3 radiance(1.0f + 15.0f * h.u(i, 7), 1.0f + 15.0f * h.u(i, 8), 1.0f + 15.0f * h.u(i, 9));
+
+        const std::string name = "lamps:Lamp" + std::to_string(i);
+        const int id = scene.materialId(name);
+        Material& m = scene.materials[(size_t)id];
+        m.Kd = proto.Kd; m.Ks = proto.Ks; m.Tr = proto.Tr; m.Ns = proto.Ns; m.Ni = proto.Ni;
+        m.is_emissive = true;
+        m.radiance = radiance;
+        scene.lights.push_back(Light(name, radiance));
+
+        std::vector<vec3> rim;  // counter-clockwise seen from below: the faces point down (-y)
+        if (n_tris == 2u) {
+            const float w = std::sqrt((float)area * aspect), d = (float)area / w;
+            const vec3 a(std::cos(phase), 0.0f, std::sin(phase)), b(-std::sin(phase), 0.0f, std::cos(phase));
+            rim = {c - a * (0.5f * w) - b * (0.5f * d), c + a * (0.5f * w) - b * (0.5f * d), c + a * (0.5f * w) + b * (0.5f * d),
+                   c - a * (0.5f * w) + b * (0.5f * d)};
+        } else {
+            for (uint32_t k = 0; k < n_tris; ++k) {
+                const float t = phase + 2.0f * kPi * (float)k / (float)n_tris;
+                rim.push_back(c + vec3(r * std::cos(t), 0.0f, r * std::sin(t)));
+            }
+        }
+        for (uint32_t k = 0; k < n_tris; ++k) {
+            Triangle t;
+            if (n_tris == 2u) { t.v[0] = rim[0]; t.v[1] = rim[k + 1]; t.v[2] = rim[k + 2]; }
+            else { t.v[0] = c; t.v[1] = rim[k]; t.v[2] = rim[(k + 1) % n_tris]; }
+            t.normal = normalize(cross(t.v[1] - t.v[0], t.v[2] - t.v[0]));
+            t.vn[0] = t.vn[1] = t.vn[2] = t.normal;
+            t.center = (t.v[0] + t.v[1] + t.v[2]) / 3.0f;
+            t.mtl_name = name;
+            t.mtl_id = id;
+            // as readobj does it (scene.cpp): the material's running area is the light's CDF
+            t.is_emissive = true;
+            m.area += t.calAera();
+            t.area = m.area;
+            m.triangles.push_back(t);
+            scene.triangles.push_back(std::move(t));
         }
     }
 }

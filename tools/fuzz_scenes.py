@@ -2,7 +2,7 @@
 """Parity on RANDOM scenes: every other parity test renders the three shipped scenes and two synthetic meshes; this one writes scenes nobody modelled —
 1 to 400 random triangles (slivers, points, duplicates, coplanar stacks, axis-aligned quads, far outliers), random per-vertex normals and texture coordinates,
 1 to 12 materials drawn from every branch of nextRay() (diffuse, Phong with Ns below / at / above 1, glass with Ni below / at / above 1, black, Kd = Ks = 0,
-textured, emissive and textured at once), 0 to 8 lights in any XML order (lights whose material no triangle uses, lights far larger or smaller than lights[0]:
+textured, emissive and textured at once), 0 to 33 lights in any XML order (lights whose material no triangle uses, lights far larger or smaller than lights[0]:
 quirk Q3), a random camera (inside the geometry, looking away from it, tiny / huge fovy) — through the loaders, both host builders, leaf sizes 1..15, and renders
 them with the oracle and with the device code: the CPU build (tests/hostsim, both node kinds) by default, the kernels through the C-ABI with --gpu.  Every image
 bit and every ray count must agree.
@@ -30,7 +30,9 @@ def fmt(x):
 
 def write_random_scene(d, rng, big=False):
     """returns (description, width, height); big: now and then a few thousand to tens of thousands of triangles (deep trees, spilled stacks, many waves)"""
-    n_mat = int(rng.integers(1, 13))
+    # lights: more than 8 now and then (k_shade's SHADE_MANY flavour); every light names a material of its own
+    n_light = int(rng.choice([0, 1, 1, 2, 3, 6, 8, 9, 12, 33]))
+    n_mat = max(int(rng.integers(1, 13)), n_light)
     mats = []
     tex_id = 0
     for m in range(n_mat):
@@ -122,8 +124,6 @@ def write_random_scene(d, rng, big=False):
             else:
                 f.write("f " + " ".join(f"{idx[k]}/{vn[k]}/{vt[k]}" for k in range(3)) + "\n")
     # lights
-    n_light = int(rng.choice([0, 1, 1, 2, 3, 6, 8]))
-    n_light = min(n_light, n_mat)
     light_mats = rng.permutation(n_mat)[:n_light]
     used = {m for _, m, _, _ in F}
     lights = "\n".join(f'<light mtlname="m{m}" radiance="{fmt(rng.uniform(0, 20))},{fmt(rng.uniform(0, 20))},{fmt(rng.uniform(0, 20))}"/>' for m in light_mats)
