@@ -210,3 +210,268 @@ def poison_tables(scene, rng):
             cam[c] = v
             what.append(("camera", c, v))
     return what
+
+
+# ---- fixtures for the k_shade variants, the row table and the deepest tree (tests/test_variant_fixtures.py, tests/test_gpu_variants.py)
+
+# k_shade's LDS staging (trt_api.hip, createOnDevice): record sizes of the five tables, the budget, and the table sets it is instantiated for
+SHADE_RECORD_BYTES = {"materials": 96, "lights": 32, "cdf": 4, "light_tris": 80, "shading_tris": 64}
+SHADE_LDS_TABLE_BYTES = 24 * 1024
+SHADE_TABS = (31, 15, 7, 3, 0)
+SHADE_ROWS_LDS = {"one": 8192, "few": 2304, "many": 2304}  # shadeRowsLds(block): 512-thread blocks for one light, 256 for several
+MAX_LIGHTS_FEW = 8            # TRT_MAX_LIGHTS: the most lights k_shade takes its shadow queues from kernel arguments for
+MAX_SCENE_LIGHTS = 65535      # TRT_MAX_SCENE_LIGHTS
+MAX_BVH_DEPTH = 256           # validateBvh
+GRID_MAX = 65536              # TileDesc::grid_ok: the reciprocal pixel grid for 2 <= width, height <= 65536
+
+
+def cdf_monotone(scene):
+    """Every light's cumulative areas non-decreasing and NaN-free: trt_create then uploads the packed CDF (light_cum) for the bisection."""
+    f = scene.flat.contents
+    for li in range(f.n_lights):
+        L = f.lights[li]
+        prev = None
+        for k in range(L.tri_first, L.tri_first + L.tri_count):
+            c = f.light_tris[k].cum_area
+            if c != c or (prev is not None and c < prev):
+                return False
+            prev = c
+    return True
+
+
+def expected_shade_tabs(scene):
+    """Which k_shade<TABS> trt_create picks for `scene`, restated from createOnDevice: the tables materials / lights / CDF / light
+    triangles / shading triangles (the last only for scenes of at most 64 triangles, the CDF only when cdf_monotone) are taken in that
+    order, each while it still fits the 24 KiB budget padded to 16 B; TABS is the largest of 31, 15, 7, 3 whose tables all were taken, else 0."""
+    f = scene.flat.contents
+    want = [f.n_materials * 96, f.n_lights * 32, f.n_light_tris * 4 if cdf_monotone(scene) else 0, f.n_light_tris * 80,
+            f.n_tris * 64 if f.n_tris <= 64 else 0]
+    used, have = 0, 0
+    for k, w in enumerate(want):
+        padded = (w + 15) & ~15
+        if w and used + padded <= SHADE_LDS_TABLE_BYTES:
+            have |= 1 << k
+            used += padded
+    return next((m for m in (31, 15, 7, 3) if have & m == m), 0)
+
+
+def shade_flavour(n_lights):
+    """k_shade's LIGHTS: one light, 2..8 (or none), more than 8."""
+    return "one" if n_lights == 1 else ("few" if n_lights <= MAX_LIGHTS_FEW else "many")
+
+
+def publish_passes(n_lights):
+    """Passes of k_publish_counts' stride loop: 2 * (1 + n_lights) counters over a block of min(1024, that rounded up to 64) threads."""
+    n = 2 * (1 + n_lights)
+    block = min(1024, (n + 63) & ~63)
+    return (n + block - 1) // block
+
+
+def tessellated_lamp(tmpdir, n_lights, quads_per_side, extra_materials=0, floor_quads=6, name="tlamp", w=64, h=36):
+    """A floor of floor_quads^2 quads (white), a shiny block and a glass pane under `n_lights` emissive lamps that face down, each a
+    grid of quads_per_side^2 quads (2 * quads_per_side^2 light triangles) with a material of its own; `extra_materials` plain
+    materials more, each on one small triangle of the floor.  With the default floor the scene has more than 64 triangles (no shading
+    triangles in LDS), so one light and FEW / MANY land on TABS 15, 7, 3 or 0 by the size of the light-triangle table, the CDF and the
+    materials (expected_shade_tabs)."""
+    v, vn, faces = [], ["vn 0 1 0", "vn 0 -1 0", "vn 0 0 1"], []
+    mtl = MTL_BASIC
+    vb = 1
+
+    def grid(x0, x1, z0, z1, y, q, n_idx, mat):
+        nonlocal vb
+        faces.append(f"usemtl {mat}")
+        for j in range(q + 1):
+            for i in range(q + 1):
+                v.append(f"v {x0 + (x1 - x0) * i / q:.6f} {y:.6f} {z0 + (z1 - z0) * j / q:.6f}")
+        for j in range(q):
+            for i in range(q):
+                a = vb + j * (q + 1) + i
+                b, c, d = a + 1, a + q + 2, a + q + 1
+                if n_idx == 1:  # facing up: counter-clockwise seen from above
+                    faces.extend([f"f {a}/1/1 {d}/1/1 {c}/1/1", f"f {a}/1/1 {c}/1/1 {b}/1/1"])
+                else:
+                    faces.extend([f"f {a}/1/2 {b}/1/2 {c}/1/2", f"f {a}/1/2 {c}/1/2 {d}/1/2"])
+        vb += (q + 1) * (q + 1)
+
+    grid(-4.0, 4.0, -4.0, 4.0, 0.0, floor_quads, 1, "white")
+    # a shiny block face and a glass pane standing on the floor
+    v += ["v -1.5 0 -1", "v -0.3 0 -1", "v -0.3 1.2 -1", "v -1.5 1.2 -1", "v 0.4 0 0.5", "v 1.6 0 0.5", "v 1.6 0.9 0.5", "v 0.4 0.9 0.5"]
+    faces += ["usemtl shiny", f"f {vb}/1/3 {vb + 1}/1/3 {vb + 2}/1/3", f"f {vb}/1/3 {vb + 2}/1/3 {vb + 3}/1/3",
+              "usemtl glass", f"f {vb + 4}/1/3 {vb + 5}/1/3 {vb + 6}/1/3", f"f {vb + 4}/1/3 {vb + 6}/1/3 {vb + 7}/1/3"]
+    vb += 8
+    lights = []
+    for k in range(n_lights):
+        x, z, y, e = -3.0 + 6.0 * (k + 0.5) / n_lights, -1.5 + 0.7 * (k % 4), 2.2 + 0.1 * (k % 3), 0.25 + 0.05 * (k % 3)
+        grid(x - e, x + e, z - e, z + e, y, quads_per_side, 2, f"lamp{k}")
+        mtl += f"newmtl lamp{k}\nKd 0 0 0\nKs 0 0 0\nNs 1\nNi 1\n"
+        lights.append((f"lamp{k}", (4.0 + k % 5, 6.0 - 0.5 * (k % 7), 3.0 + 0.25 * (k % 9))))
+    for k in range(extra_materials):
+        x = -3.9 + 7.8 * k / max(1, extra_materials)
+        v += [f"v {x:.6f} 0.001 3.5", f"v {x + 0.02:.6f} 0.001 3.5", f"v {x:.6f} 0.001 3.45"]
+        faces += [f"usemtl extra{k}", f"f {vb}/1/1 {vb + 2}/1/1 {vb + 1}/1/1"]
+        vb += 3
+        mtl += f"newmtl extra{k}\nKd {0.2 + 0.6 * (k % 7) / 7:.3f} 0.5 {0.8 - 0.6 * (k % 5) / 5:.3f}\nKs 0 0 0\nNs 1\nNi 1\n"
+    write_scene(tmpdir, name, "vt 0 0\n" + "\n".join(vn + v + faces) + "\n", mtl, lights=lights, w=w, h=h, fovy=50,
+                eye=(0, 3, 7), lookat=(0, 0.5, 0))
+    return load(tmpdir, name)
+
+
+def break_cdf_monotonicity(scene, light=0):
+    """Swaps the cumulative areas of the first two triangles of light `light` IN PLACE: that light's CDF is no longer
+    non-decreasing, so trt_create uploads no packed CDF (light_cum = nullptr: the linear light-triangle search) and the CDF
+    leaves k_shade's LDS tables.  Returns the two swapped values."""
+    f = scene.flat.contents
+    L = f.lights[light]
+    assert L.tri_count >= 2, "the light needs two triangles of different area sums"
+    a, b = f.light_tris[L.tri_first], f.light_tris[L.tri_first + 1]
+    assert a.cum_area < b.cum_area
+    a.cum_area, b.cum_area = b.cum_area, a.cum_area
+    return b.cum_area, a.cum_area
+
+
+def caterpillar_tree(scene, depth, pad=1e-3):
+    """Replaces the scene's BVH by a chain of `depth` inner nodes (the scene must have depth + 1 triangles): node i has child0 = a leaf
+    of triangle i and child1 = node i + 1; the last node's child1 is a leaf of the last triangle.  A leaf's box is its triangle's box
+    padded by `pad`, the box of an inner child is the union of that child's own two boxes (nested), and the triangles keep the scene's
+    order (post-BVH order: under every node, child0's triangle precedes child1's).  Adopted the way a caller's tree arrives
+    (trth_scene_adopt_bvh).  Returns the scene."""
+    import ctypes as C
+
+    import numpy as np
+    from tinyraytracing_amd._abi import BvhNode
+    n = scene.info["n_triangles"]
+    assert n == depth + 1, f"a caterpillar of {depth} levels needs {depth + 1} triangles, the scene has {n}"
+    v = np.empty(n * 9, np.float32)
+    scene._check(scene._lib.trth_scene_vertices(scene._h, v.ctypes.data_as(C.POINTER(C.c_float)), v.size))
+    v = v.reshape(n, 3, 3)
+    lo = v.min(axis=1) - np.float32(pad)
+    hi = v.max(axis=1) + np.float32(pad)
+    nodes = (BvhNode * depth)()
+    leaf = lambda t: 0x80000000 | (1 << 27) | t  # noqa: E731  (TRT_LEAF_BIT, count 1, first t)
+    sub_lo, sub_hi = lo[depth].copy(), hi[depth].copy()  # boxes of node i's child1
+    for i in range(depth - 1, -1, -1):
+        nd = nodes[i]
+        nd.lo0[:], nd.hi0[:] = lo[i].tolist(), hi[i].tolist()
+        nd.lo1[:], nd.hi1[:] = sub_lo.tolist(), sub_hi.tolist()
+        nd.child0 = leaf(i)
+        nd.child1 = leaf(depth) if i == depth - 1 else i + 1
+        sub_lo, sub_hi = np.minimum(lo[i], sub_lo), np.maximum(hi[i], sub_hi)
+    order = np.arange(n, dtype=np.uint32)
+    scene._check(scene._lib.trth_scene_adopt_bvh(scene._h, nodes, depth, order.ctypes.data_as(C.POINTER(C.c_uint32)), depth))
+    scene._built = True
+    return scene
+
+
+def caterpillar_scene(depth, width=48, height=32):
+    """The soup scene (back without its cube, random triangles in its box) with depth + 1 triangles, on a caterpillar_tree."""
+    base = T.Scene.named("soup", width, height, n=1)
+    n_back = base.info["n_triangles"] - 1
+    base.close()
+    s = T.Scene.named("soup", width, height, n=depth + 1 - n_back)
+    return caterpillar_tree(s, depth)
+
+
+def axis_rays(scene, n_per_axis=64, seed=11):
+    """Rays from inside the scene's box along +-x, +-y, +-z (a reciprocal direction that is infinite: raySpecial, the BVH2 walk of
+    k_trace_fix) and as many in random directions; (org, dir) as float32 arrays."""
+    import ctypes as C
+
+    import numpy as np
+    f = scene.flat.contents
+    v = np.ctypeslib.as_array(C.cast(f.tri_v, C.POINTER(C.c_float)), (f.n_tris, 9)).reshape(-1, 3)
+    lo, hi = v.min(0), v.max(0)
+    rng = np.random.default_rng(seed)
+    org = (lo + (hi - lo) * rng.uniform(0.05, 0.95, (7 * n_per_axis, 3))).astype(np.float32)
+    dirs = []
+    for a in range(3):
+        for s in (1.0, -1.0):
+            d = np.zeros((n_per_axis, 3), np.float32)
+            d[:, a] = s
+            dirs.append(d)
+    r = rng.normal(size=(n_per_axis, 3))
+    dirs.append((r / np.linalg.norm(r, axis=1, keepdims=True)).astype(np.float32))
+    return org, np.concatenate(dirs)
+
+
+def with_light_count(scene, n_lights):
+    """A copy of the scene's flat description whose light table holds `n_lights` copies of its first light (all of them legal lights:
+    same material, same triangles), for the light-count bound of trt_create.  Returns (SceneFlat, what keeps its arrays alive)."""
+    import ctypes as C
+    from tinyraytracing_amd._abi import Light, SceneFlat
+    src = scene.flat.contents
+    flat = SceneFlat.from_buffer_copy(src)
+    lights = (Light * n_lights)()
+    for i in range(n_lights):
+        C.memmove(C.byref(lights[i]), C.byref(src.lights[0]), C.sizeof(Light))
+    flat.n_lights = n_lights
+    flat.lights = C.cast(lights, C.POINTER(Light))
+    return flat, (scene, lights)
+
+
+def _named(name, w=64, h=36, **kw):
+    return lambda tmp: T.Scene.named(name, w, h, **kw)
+
+
+def _broken_cdf(name, w=64, h=36, **kw):
+    def make(tmp):
+        s = T.Scene.named(name, w, h, **kw)
+        break_cdf_monotonicity(s, 0)
+        return s
+    return make
+
+
+def _tlamp(*args, **kw):
+    return lambda tmp: tessellated_lamp(tmp, *args, **kw)
+
+
+# k_shade<TABS, LIGHTS>: id -> (TABS, LIGHTS, scene maker(tmpdir)); every cell on a natural scene, TABS 3 both ways
+SHADE_CELLS = {
+    "one-31-back": (31, "one", _named("back")),
+    "one-15-soup": (15, "one", _named("soup", n=2000)),
+    "one-7-tessellated": (7, "one", _tlamp(1, 16)),
+    "one-3-cdf_too_large": (3, "one", _tlamp(1, 56)),
+    "one-3-cdf_not_monotone": (3, "one", _broken_cdf("back")),
+    "one-0-materials": (0, "one", _tlamp(1, 1, extra_materials=300)),
+    "few-31-lamps": (31, "few", _named("lamps", n=3)),
+    "few-15-tessellated": (15, "few", _tlamp(3, 2)),
+    "few-7-tessellated": (7, "few", _tlamp(3, 16)),
+    "few-3-cdf_too_large": (3, "few", _tlamp(3, 32)),
+    "few-3-cdf_not_monotone": (3, "few", _broken_cdf("lamps", n=3)),
+    "few-0-materials": (0, "few", _tlamp(3, 1, extra_materials=300)),
+    "many-31-lamps": (31, "many", _named("lamps", n=8)),
+    "many-15-lamps": (15, "many", _named("lamps", n=16)),
+    "many-7-lamps": (7, "many", _named("lamps", n=64)),
+    "many-3-cdf_too_large": (3, "many", _tlamp(9, 19)),
+    "many-3-cdf_not_monotone": (3, "many", _broken_cdf("lamps", n=8)),
+    "many-0-lamps": (0, "many", _named("lamps", 32, 18, n=300)),
+}
+
+# the row table: id -> ((scene, kw), LIGHTS, image (width, height), tile, row interleave (block, mod, rem) or None, rows kept in LDS)
+ROW_CASES = {
+    "one-8192": (("back", {}), "one", (64, 8192), (31, 0, 33, 8192), None, 8192),
+    "one-8193": (("back", {}), "one", (64, 8193), (31, 0, 33, 8193), None, 0),
+    "few-2304": (("lamps", {"n": 3}), "few", (64, 2304), (31, 0, 33, 2304), None, 2304),
+    "few-2305": (("lamps", {"n": 3}), "few", (64, 2305), (31, 0, 33, 2305), None, 0),
+    "many-2304": (("lamps", {"n": 16}), "many", (64, 2304), (30, 0, 32, 2304), None, 2304),
+    "many-2305": (("lamps", {"n": 16}), "many", (64, 2305), (30, 0, 32, 2305), None, 0),
+    "few-4608-interleaved": (("lamps", {"n": 3}), "few", (64, 4608), (31, 0, 33, 4608), (1, 2, 1), 2304),
+    "one-16384-interleaved": (("back", {}), "one", (64, 16384), (31, 0, 33, 16384), (4, 2, 0), 8192),
+    "one-height-70000": (("back", {}), "one", (64, 70000), (20, 65528, 44, 65544), None, 0),  # rows 65528..65543: both sides of 16 bits
+}
+
+# the pixel grid: image sizes on either side of GRID_MAX, and a 24 x 12 tile at pixel indices above 49 000 on the long side of each
+# (the outermost columns and rows of these frames see no geometry: a tile there would compare black with black)
+GRID_SIZES = [(GRID_MAX, 36), (GRID_MAX + 1, 36), (64, GRID_MAX), (64, GRID_MAX + 1)]
+
+
+def grid_tile(w, h):
+    return (w * 3 // 4, 10, w * 3 // 4 + 24, 22) if w > h else (20, h * 7 // 8, 44, h * 7 // 8 + 12)
+
+
+# light counts: the ends of FEW, the first of MANY, the counter-row layout (13 / 14), the publish loop (511 / 512 / 1000)
+LIGHT_COUNTS = [2, 8, 9, 13, 14, 511, 512, 1000]
+
+
+def count_rows(n_lights):
+    """Counter rows per bounce (trt_api.hip countRows): 16 up to 13 lights, then multiples of 16 with room for n_lights + 3."""
+    return max(16, (n_lights + 3 + 15) & ~15)

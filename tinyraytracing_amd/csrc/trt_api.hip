@@ -103,6 +103,7 @@ struct trt_handle {
     int trace_impl = 3;       // wave driver of the traversal kernels (0 wave-uniform walk of a tiny tree, 3 persistent waves + step scheduler)
     int node_kind = 0;        // what the persistent traversal kernels walk: 0 exact 128-B 4-wide nodes, 1 compressed 80-B 8-wide nodes (trt_oct.h)
     uint32_t oct_levels = 0;  // nodes on the longest root path of the oct tree
+    bool dbg = false;         // TRT_DEBUG at trt_create: every render prints which k_shade variant it runs
     // Grid of the traversal kernels for a queue of n rays.  A persistent wave refills finished lanes from its own slice
     // of the queue, which only pays when the slice holds several batches: aim for rays_per_wave rays per wave, but do
     // not go below the fill_blocks that fill the chip's wave slots, nor above one block per 256 rays.
@@ -563,6 +564,7 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->trace_impl = im.trace_impl;
     h->node_kind = im.node_kind;
     h->oct_levels = im.oct.levels;
+    h->dbg = im.dbg;
     h->depth = im.wide.stack_need + 1;
     h->light_boxes = im.light_boxes;
 
@@ -616,6 +618,9 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
         h->shade_tabs = 0;
         for (uint32_t m : {31u, 15u, 7u, 3u})
             if ((have & m) == m) { h->shade_tabs = m; break; }
+        if (im.dbg)
+            std::fprintf(stderr, "trt_create: k_shade tables %u (lds bytes: materials %u, lights %u, cdf %u, light tris %u, shading tris %u)\n", h->shade_tabs,
+                         h->lds_tab[0], h->lds_tab[1], h->lds_tab[2], h->lds_tab[3], h->lds_tab[4]);
         // the staged tables once more, packed in LDS layout: a block fetches them with one coalesced pass
         const void* src[5] = {h->sc.materials, h->sc.lights, h->sc.light_cum, h->sc.light_tris, h->sc.tri_shade};
         size_t total = 0;
@@ -839,6 +844,14 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     td.grid_rcp[1] = 1.0 / double(p->height - 1.0);
     td.grid_rcp[2] = 1.0 / double(p->width);
     td.grid_rcp[3] = 1.0 / double(p->height);
+    // k_shade's three flavours (trt_kernels.h): 512-thread blocks at 6 waves per SIMD for one light, 256-thread blocks at 5 for
+    // several; more than TRT_MAX_LIGHTS lights find their queues in the arena instead of in the kernel arguments
+    const int lights = nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY);
+    const uint32_t shade_block = lights == SHADE_ONE ? (uint32_t)TRT_SHADE1_BLOCK : (uint32_t)TRT_SHADEN_BLOCK;
+    const uint32_t rows_lds = (rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)rows.size() : 0u;
+    if (h->dbg)
+        std::fprintf(stderr, "trt_render: k_shade %s, rows in lds %u, grid_ok %u\n", lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds,
+                     td.grid_ok);
 
     Timer tm;
     tm.h = h;
@@ -906,9 +919,6 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         A.hit = S.hit;
         A.n = S.n_active;
         A.qout = S.Q[S.cur ^ 1];
-        // k_shade's three flavours (trt_kernels.h): 512-thread blocks at 6 waves per SIMD for one light, 256-thread blocks at 5 for
-        // several; more than TRT_MAX_LIGHTS lights find their queues in the arena instead of in the kernel arguments
-        const int lights = nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY);
         if (lights == SHADE_MANY) A.sq_arena = S.shadow;
         else
             for (uint32_t l = 0; l < (uint32_t)TRT_MAX_LIGHTS; ++l) A.sq[l] = l < nl ? S.shadow.queue(l) : ShadowQueue{nullptr, nullptr, nullptr};
@@ -927,8 +937,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         A.lds_tshade_bytes = h->lds_tab[4];
         A.lds_image = (const f4*)h->lds_image;
         A.lds_image_words = h->lds_image_bytes / 16u;
-        const uint32_t shade_block = lights == SHADE_ONE ? (uint32_t)TRT_SHADE1_BLOCK : (uint32_t)TRT_SHADEN_BLOCK;
-        A.rows_lds = (rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)rows.size() : 0u;
+        A.rows_lds = rows_lds;
         A.stats = d_stats;
         tm.begin(TRT_K_SHADE, S.stream);
         {
