@@ -7,9 +7,10 @@
  * array; this one returns the same two things in flat form: the node array trt_create() takes (trt.h, trt_bvh_node) and the
  * permutation that puts the caller's triangles into leaf order.  The tree is an LBVH (Lauterbach et al. 2009; hierarchy of
  * Karras 2012): 63-bit Morton codes of the centres of the triangles' boxes, one radix sort, every inner node from its
- * own index, boxes bottom-up.  Its top is SAH: the radix tree is cut into its maximal subtrees of <= 2048 triangles
- * (n / 64 for scenes below 131 k triangles, at least 256; TRT_LBVH_CLUSTER in the environment overrides; 0 = keep the radix tree as it is), an exact sweep-SAH tree over those clusters — a few
- * thousand boxes, built on the host in milliseconds — becomes the upper part of the BVH, and each cluster's radix subtree
+ * own index, boxes bottom-up.  Its top is SAH: the radix tree is cut into its maximal subtrees of at most `cluster` triangles
+ * (2 below 50 k triangles, 16 below 500 k, 128 below 4 M, 2048 from there on; TRT_LBVH_CLUSTER in the environment overrides, raised to leaf_num
+ * if smaller; 0 = keep the radix tree as it is, as does a scene of no more than `cluster` triangles), an exact sweep-SAH tree over those clusters — a few
+ * thousand boxes for 10 M triangles, about n / 2 below 50 k, built on the host in milliseconds — becomes the upper part of the BVH, and each cluster's radix subtree
  * hangs below its leaf (node visits per ray within 4-7 % of the host SAH builder's tree on scenes of 1-10 M triangles, against
  * 4-23 % for the radix tree alone).  Topology is free
  * (SURVEY.md §8a Q10): hits, tie rules and images depend on the tree only through the leaf order, which trt_create checks

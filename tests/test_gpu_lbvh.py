@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import bvh_check as B
 import oracle_lib as O
 import raygen
 import tinyraytracing_amd as T
@@ -126,7 +127,7 @@ def test_lbvh_quality_and_speed_are_on_record(capsys):
 
 def test_config5_ten_million_triangles_built_on_the_device_tiles_vs_oracle():
     """Config 5's scene at full size with the tree built on the GPU (the device part: tens of milliseconds; the times are printed for the record),
-    a tree trt_create accepts and collapses into 8-wide nodes, tiles of the 4K image bit-identical to the oracle on the same tree."""
+    a tree tests/bvh_check.py accepts (its triangles in the adopted leaf order), a tree trt_create accepts and collapses into 8-wide nodes, tiles of the 4K image bit-identical to the oracle on the same tree."""
     d = os.path.join(T.SCENES_DIR, "back")
     s = T.Scene.load(os.path.join(d, "back.xml"), os.path.join(d, "back.obj"), os.path.join(d, "back.mtl"), d, 3840, 2160)
     s._check(s._lib.trth_scene_drop_tris(s._h, 6, 12))
@@ -138,6 +139,9 @@ def test_config5_ten_million_triangles_built_on_the_device_tiles_vs_oracle():
     assert s.info["n_triangles"] >= 10_000_000
     print(f"\nconfig 5, tree built on the device: {s.build_ms[0]:.1f} ms of kernels and host SAH top, {s.build_ms[1]:.1f} ms for the call with its copies")
     assert s.build_ms[0] < 500.0, s.build_ms  # device part only, loosely (tens of ms); the call's wall clock depends on the host's share of cores and PCIe
+    # the tree itself, by the builder-independent checker: exact padded boxes, every triangle in one leaf, post-BVH order, the reported depth
+    f = s.flat.contents
+    B.check_bvh(np.ctypeslib.as_array(f.tri_v, shape=(f.n_tris * 9,)), f.nodes, f.n_nodes, np.arange(f.n_tris), 2, f.bvh_depth)
     r = T.Renderer(s, 0)
     try:
         for (x0, y0) in ((1900, 1000), (2300, 1500)):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 from PIL import Image
 
+import bvh_check as B
 import oracle_lib as O
 import scene_util as SU
 import tinyraytracing_amd as T
@@ -366,12 +367,15 @@ def test_bvh_is_well_formed_for_both_builders():
                     assert not seen[first:first + cnt].any()
                     seen[first:first + cnt] = True
                     v = np.ctypeslib.as_array(f.tri_v, shape=(f.n_tris, 3, 3))[first:first + cnt].reshape(-1, 3)
-                    # padded by 0.001 (bvh.cpp:31-40)
-                    assert np.all(v.min(0) - 0.001 >= np.array(lo) - 1e-6) and np.all(v.max(0) + 0.001 <= np.array(hi) + 1e-6)
+                    # exactly the leaf's bounds padded by 0.001f (bvh.cpp:31-40), bit for bit
+                    assert np.array_equal(np.array(lo, np.float32).view(np.uint32), (v.min(0) - np.float32(0.001)).view(np.uint32))
+                    assert np.array_equal(np.array(hi, np.float32).view(np.uint32), (v.max(0) + np.float32(0.001)).view(np.uint32))
                 else:
                     assert 0 < ref < f.n_nodes
                     stack.append((ref, d + 1))
         assert seen.all() and visited == f.n_nodes and depth == f.bvh_depth
+        # and every inner node's boxes too (tests/bvh_check.py)
+        B.check_bvh(np.ctypeslib.as_array(f.tri_v, shape=(f.n_tris * 9,)), f.nodes, f.n_nodes, np.arange(f.n_tris), 8, f.bvh_depth)
 
 
 def test_obj_slot_order_quirk_and_extensions(tmp_path):

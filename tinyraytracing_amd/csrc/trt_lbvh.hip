@@ -14,7 +14,8 @@
 //                     64-B nodes of trt.h (a radix-tree node covers a contiguous range of the sorted order, so a subtree of
 //                     <= leaf_num triangles IS a leaf (first, count)); boxes padded like the reference's (bvh.cpp:31-40)
 //   K6 k_depth        inner nodes on the longest root path
-//   K7-K11 (default)  the top of the tree by SAH: the radix tree cut into clusters of <= 2048 triangles, an exact sweep-SAH tree over
+//   K7-K11 (default)  the top of the tree by SAH: the radix tree cut into clusters of <= 2 / 16 / 128 / 2048 triangles (by scene size, switching at
+//                     50 k, 500 k and 4 M triangles; TRT_LBVH_CLUSTER overrides), an exact sweep-SAH tree over
 //                     the clusters built on the host, the cluster subtrees emitted below it (see "the top of the tree by SAH" below)
 // All HBM-bound streaming or gather work, 4.1 ms of kernels for 10 M triangles (9 ms with the host's SAH over the clusters in between); the rest of the call is moving the
 // vertices in (360 MB) and the nodes out (< 640 MB) over PCIe.  No MFMA, no LDS tiling: nothing here is a contraction.
@@ -89,7 +90,8 @@ struct Box8 {  // (lo.xyz, hi.x) (hi.yz, -, -)
 // K1: bounds[0..2] = min of the box centres (keys), bounds[3..5] = max
 __global__ __launch_bounds__(256) void k_prim_boxes(const float* __restrict__ tri_v, uint32_t n, Box8* __restrict__ pbox, uint32_t* __restrict__ bounds)
 {
-    float cmin[3] = {3.0e38f, 3.0e38f, 3.0e38f}, cmax[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    const float inf = __builtin_huge_valf();  // (not +-3e38: centres beyond it would be clamped into the frame)
+    float cmin[3] = {inf, inf, inf}, cmax[3] = {-inf, -inf, -inf};
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float* v = tri_v + (size_t)i * 9;
@@ -279,15 +281,11 @@ __global__ __launch_bounds__(256) void k_span_round(const uint32_t* __restrict__
     for (int k = 0; k < 2; ++k)
         if (!(ch[k] & LEAF) && spansBlocks(first[ch[k]], last[ch[k]]) && !done_in[ch[k]]) ready = false;
     if (!ready) { atomicAdd(remaining, 1u); return; }
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-    for (int k = 0; k < 2; ++k) {
-        const Box8 x = (ch[k] & LEAF) ? pbox[order[ch[k] & ~LEAF]] : nbox[ch[k]];
-        lo[0] = fminf(lo[0], x.a.x); lo[1] = fminf(lo[1], x.a.y); lo[2] = fminf(lo[2], x.a.z);
-        hi[0] = fmaxf(hi[0], x.a.w); hi[1] = fmaxf(hi[1], x.b.x); hi[2] = fmaxf(hi[2], x.b.y);
-    }
+    Box8 x[2];  // (merged from the two children themselves: a +-3e38 start would clamp boxes that lie beyond it)
+    for (int k = 0; k < 2; ++k) x[k] = (ch[k] & LEAF) ? pbox[order[ch[k] & ~LEAF]] : nbox[ch[k]];
     Box8 out;
-    out.a = make_float4(lo[0], lo[1], lo[2], hi[0]);
-    out.b = make_float4(hi[1], hi[2], 0.0f, 0.0f);
+    out.a = make_float4(fminf(x[0].a.x, x[1].a.x), fminf(x[0].a.y, x[1].a.y), fminf(x[0].a.z, x[1].a.z), fmaxf(x[0].a.w, x[1].a.w));
+    out.b = make_float4(fmaxf(x[0].b.x, x[1].b.x), fmaxf(x[0].b.y, x[1].b.y), 0.0f, 0.0f);
     nbox[node] = out;
     done_out[node] = 1u;
 }
