@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TRT_ABI_VERSION 4
+#define TRT_ABI_VERSION 5
 
 /* error codes */
 #define TRT_OK 0
@@ -255,6 +255,27 @@ int trt_render_device(trt_handle* h, const trt_params* p, float* out_rgb_dev,
  * a long render can be shown while it converges, check-pointed (save accum + sample_end) and resumed. */
 int trt_render_samples(trt_handle* h, const trt_params* p, int32_t sample_begin, int32_t sample_end,
                        double* accum_host, float* out_rgb_host, trt_stats* stats);
+
+/* Adaptive sampling: render samples [sample_begin, sample_end) of the LISTED pixels only.  pixels[i] = y * p->width + x
+ * (< width * height), any order, duplicates allowed (every entry has its own slot).  For every entry i and every sample s, in
+ * increasing s:
+ *     v = (double)(L_s / (float)p->spp)             -- exactly the term trt_render_samples adds
+ *     sum[3i + c]   += v_c
+ *     sumsq[3i + c] += v_c * v_c                    -- a rounded double product, then a rounded double add (no fused multiply-add)
+ * sum / sumsq: HOST, n_pixels * 3 doubles, in/out (sumsq may be NULL).  Sample s of pixel q is the path trt_render traces for it
+ * (the random stream is keyed by (seed, q, s)), so a list holding every pixel of a tile in tile order, over [0, spp) from zeros,
+ * leaves in sum exactly trt_render_samples' accum.  The tile and row-interleave fields of p are ignored; width, height, seed,
+ * max_depth, flags and mem_budget mean what they mean for trt_render (mem_budget too small for one sample of every entry:
+ * TRT_ENOMEM).  sample_end may exceed p->spp (p->spp is only the scale of v).  n_pixels == 0 or an empty range: nothing to do,
+ * TRT_OK.  TRT_EINVAL: a null pointer while n_pixels > 0, an entry >= width * height, sample_begin < 0 or > sample_end, or
+ * n_pixels > 0x7FFF0000 (the path ids of one pass).  stats: as for a render, with rows_rendered = 0. */
+int trt_render_pixels(trt_handle* h, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels,
+                      int32_t sample_begin, int32_t sample_end, double* sum_host, double* sumsq_host, trt_stats* stats);
+/* The same with pixels, sum and sumsq in DEVICE memory of the handle's device, all work on hip_stream (NULL = default);
+ * returns after the stream has been synchronised. */
+int trt_render_pixels_device(trt_handle* h, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels_dev,
+                             int32_t sample_begin, int32_t sample_end, double* sum_dev, double* sumsq_dev,
+                             void* hip_stream, trt_stats* stats);
 
 /* traverseBVH (bvh.cpp:146-175) on a batch of n rays given as HOST arrays
  * org[n][3], dir[n][3].  Outputs (host): t[n] (TRT_INF on miss), tri[n]

@@ -9,9 +9,11 @@ the BVH, render(), imshow().
 import ctypes as C
 import os
 
+from typing import NamedTuple
+
 import numpy as np
 
-from . import _abi
+from . import _abi, adaptive
 from ._abi import Params, Stats, SceneFlat, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES  # noqa: F401
 
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,6 +194,30 @@ def rows_selected(p):
     return [y for y in ys if (y // p.row_block) % p.row_mod == p.row_rem]
 
 
+def _is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def _add_stats(total, st):
+    """Accumulates the Stats of one render call into `total` (counts and times summed, max_bounces the deepest)."""
+    for f in ("rays_camera", "rays_shadow", "rays_indirect", "shaded_hits", "render_ms", "passes", "rows_rendered", "redo_rays"):
+        setattr(total, f, getattr(total, f) + getattr(st, f))
+    for f in ("inner_visits", "tri_tests", "wave_steps", "launches", "kernel_ms", "lane_census"):
+        a, b = getattr(total, f), getattr(st, f)
+        for i in range(len(a)):
+            a[i] += b[i]
+    total.max_bounces = max(total.max_bounces, st.max_bounces)
+    total.inner_node_bytes = st.inner_node_bytes
+
+
+class AdaptiveResult(NamedTuple):
+    image: object    # sum * spp / n_q per pixel, float64 [rows, tile_w, 3] (numpy, or a torch tensor with on_device)
+    counts: object   # n_q: pixel q holds samples [0, n_q) of its stream
+    error: object    # the estimated relative standard error the policy stopped on (adaptive.relative_error)
+    stats: Stats     # summed over the render calls
+    rounds: int      # render calls made
+
+
 class Renderer:
     """Owns a trt_handle: the scene resident in HBM of one MI355X."""
 
@@ -237,6 +263,94 @@ class Renderer:
         if rc != 0:
             raise TrtError(f"trt_render_samples failed ({rc}): {self._lib.trt_last_error().decode()}")
         return out, accum, st
+
+    def render_pixels(self, params, pixels, sample_begin, sample_end, sums=None, sumsq=None):
+        """Samples [sample_begin, sample_end) of the listed pixels only (trt_render_pixels): pixels[i] = y * width + x, any order,
+        duplicates allowed.  Adds v = (double)(L_s / params.spp) and v * v of every sample onto sums / sumsq (float64 [n, 3];
+        None = zeros) and returns (sums, sumsq, Stats).  numpy uint32 pixels: host arrays.  A torch tensor on this device (int32 or
+        uint32): sums / sumsq are float64 tensors there, and the work runs on torch's current stream (trt_render_pixels_device)."""
+        if _is_torch(pixels):
+            return self._render_pixels_device(params, pixels, sample_begin, sample_end, sums, sumsq)
+        pixels = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        n = pixels.size
+        sums = self._moments(sums, n, "sums")
+        sumsq = self._moments(sumsq, n, "sumsq")
+        st = Stats()
+        fp = C.POINTER(C.c_double)
+        rc = self._lib.trt_render_pixels(self._h, C.byref(params), n, pixels.ctypes.data_as(C.POINTER(C.c_uint32)), int(sample_begin), int(sample_end),
+                                         sums.ctypes.data_as(fp), sumsq.ctypes.data_as(fp), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_render_pixels failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return sums, sumsq, st
+
+    @staticmethod
+    def _moments(a, n, what):
+        if a is None:
+            return np.zeros((n, 3), np.float64)
+        if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.shape != (n, 3) or not a.flags["C_CONTIGUOUS"]:
+            raise TrtError(f"render_pixels: {what} must be a contiguous float64 array of shape ({n}, 3)")
+        return a
+
+    def _render_pixels_device(self, params, pixels, sample_begin, sample_end, sums, sumsq):
+        import torch
+        dev = torch.device("cuda", self.device)
+        if pixels.device != dev or pixels.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or pixels.dim() != 1 or not pixels.is_contiguous():
+            raise TrtError(f"render_pixels: pixels must be a contiguous 1-D int32 / uint32 tensor on {dev}")
+        n = pixels.numel()
+        out = []
+        for a, what in ((sums, "sums"), (sumsq, "sumsq")):
+            if a is None:
+                a = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+            elif a.device != dev or a.dtype != torch.float64 or tuple(a.shape) != (n, 3) or not a.is_contiguous():
+                raise TrtError(f"render_pixels: {what} must be a contiguous float64 tensor of shape ({n}, 3) on {dev}")
+            out.append(a)
+        st = Stats()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self._lib.trt_render_pixels_device(self._h, C.byref(params), n, C.c_void_p(pixels.data_ptr()), int(sample_begin), int(sample_end),
+                                                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(stream), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_render_pixels_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return out[0], out[1], st
+
+    def render_adaptive(self, params, rel_error, min_spp, max_spp, batch, on_device=False):
+        """Adaptive sampling of the tile of `params` (tinyraytracing_amd/adaptive.py has the policy): every pixel gets [0, min_spp),
+        then rounds of `batch` more samples go to every pixel whose estimated relative standard error of its mean luminance is above
+        rel_error, until max_spp.  Pixel q ends with the samples [0, n_q) of its own stream.
+        -> AdaptiveResult(image = sum * spp / n_q, float64 [rows, tile_w, 3]; counts n_q [rows, tile_w]; error [rows, tile_w];
+        stats summed over the calls; rounds).  on_device: the sums, the estimates and the selection live in torch tensors on this
+        device (the image is returned there too) and nothing of the image crosses to the host between rounds."""
+        ys = np.asarray(rows_selected(params), np.int64)
+        xs = np.arange(params.x0, params.x1, dtype=np.int64)
+        if ys.size == 0 or xs.size == 0:
+            raise TrtError("render_adaptive: empty tile")
+        pixels = (ys[:, None] * params.width + xs[None, :]).reshape(-1)
+        k = pixels.size
+        total = Stats()
+
+        def render(pix, s0, s1, su, sq):
+            su, sq, st = self.render_pixels(params, pix, s0, s1, su, sq)
+            _add_stats(total, st)
+            return su, sq
+
+        if on_device:
+            import torch
+            if params.width * params.height > 0x7FFFFFFF:
+                raise TrtError("render_adaptive: on_device needs width * height < 2^31 (int32 pixel tensors)")
+            dev = torch.device("cuda", self.device)
+            pix = torch.from_numpy(pixels.astype(np.int32)).to(dev)
+            sums = torch.zeros((k, 3), dtype=torch.float64, device=dev)
+            sumsq = torch.zeros_like(sums)
+            counts = torch.zeros(k, dtype=torch.int64, device=dev)
+            sums, sumsq, counts, err, rounds = adaptive.run(render, pix, sums, sumsq, counts, rel_error, min_spp, max_spp, batch)
+            image = sums * float(params.spp) / counts.to(torch.float64)[:, None]
+        else:
+            pix = pixels.astype(np.uint32)
+            sums, sumsq = np.zeros((k, 3)), np.zeros((k, 3))
+            counts = np.zeros(k, np.int64)
+            sums, sumsq, counts, err, rounds = adaptive.run(render, pix, sums, sumsq, counts, rel_error, min_spp, max_spp, batch)
+            image = sums * float(params.spp) / counts[:, None]
+        shape = (ys.size, xs.size)
+        return AdaptiveResult(image.reshape(shape + (3,)), counts.reshape(shape), err.reshape(shape), total, rounds)
 
     def render_into(self, params, out_tensor, stream_ptr=0):
         """Renders into a CUDA/HIP torch tensor (float32, >= rows*tile_w*3 elements) on this device."""

@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 
-TRT_ABI_VERSION = 4
+TRT_ABI_VERSION = 5
 TRT_INF = 114514.0
 TRT_FLAG_TIMING = 1
 TRT_FLAG_COUNT = 2
@@ -83,7 +83,7 @@ class Stats(C.Structure):
 
 
 # the symbols include/trt.h declares (checked by tests/test_abi.py)
-HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_trace_closest",
+HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_trace_closest",
                "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
 HOST_SYMBOLS = ["trth_scene_load", "trth_scene_load_opts", "trth_scene_drop_tris", "trth_scene_add_soup", "trth_scene_add_blob", "trth_scene_add_lamps",
@@ -191,6 +191,10 @@ def load_hip():
     lib.trt_render.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_float), C.POINTER(Stats)]
     lib.trt_render_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_render_samples.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(Stats)]
+    lib.trt_render_pixels.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_int32,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
+    lib.trt_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_trace_closest.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                       C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(Stats)]
     lib.trt_destroy.argtypes = [C.c_void_p]

@@ -293,7 +293,7 @@ uint32_t tailGrid(uint32_t n)
 // Traversal kernels: the LDS stack holds 8 or 16 levels without spill code when the scene's verified BVH
 // depth fits, else 16 levels + a global spill area (16 KiB per block keeps 8 waves per SIMD resident);
 // the wave driver (trt_kernels.h) is the static one for shallow trees, the scheduler one otherwise.
-template <bool COUNT, bool PRIMARY>
+template <bool COUNT, int PRIMARY>
 void launchTraceClosest(const trt_handle* h, hipStream_t stream, uint32_t* spill, const RaySource& src, f4* hit, uint32_t n, DeviceStats* d_stats, RedoList redo);
 template <bool COUNT>
 void launchTraceShadow(const trt_handle* h, hipStream_t stream, uint32_t* spill, const ShadowQueue& sq, uint32_t n, uint32_t light_mat, f4* Lacc, DeviceStats* d_stats, uint32_t any, RedoList redo, const LightBox& lbox);
@@ -349,7 +349,7 @@ constexpr uint32_t OCT_LDS_LEVELS = 10;
 #define TRT_BY_OCT_DEPTH(LAUNCH) LAUNCH(10, true, 3, 1)
 // Behind every traversal launch of a per-lane driver: k_trace_fix (a few blocks) traces the rays of the launch's redo list again in the
 // exact form (trt_kernels.h, RedoList).  The wave-uniform walk applies the rule on the spot and has no list.
-template <bool COUNT, bool PRIMARY>
+template <bool COUNT, int PRIMARY>
 void launchTraceClosest(const trt_handle* h, hipStream_t stream, uint32_t* spill, const RaySource& src, f4* hit, uint32_t n, DeviceStats* d_stats, RedoList redo)
 {
     const dim3 g(h->traceGrid(n)), b(TRT_TRACE_BLOCK);
@@ -662,7 +662,10 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
 #define TRT_PAD_ATTR(T) \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_ONE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_FEW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_MANY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_MANY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_ONE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_FEW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_MANY, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
         TRT_PAD_ATTR(31u) TRT_PAD_ATTR(15u) TRT_PAD_ATTR(7u) TRT_PAD_ATTR(3u) TRT_PAD_ATTR(0u)
 #undef TRT_PAD_ATTR
     }
@@ -726,14 +729,28 @@ struct PassSlot {
 }  // namespace
 
 namespace {
+// A pixel-list render (trt_render_pixels): the paths of samples [s_begin, s_end) of `n` listed pixels instead of those of a tile.
+// pixels / sum / sumsq are host arrays (copied in and out here) or device arrays of the handle's device (used in place).
+struct PixelJob {
+    uint32_t n;
+    const uint32_t* pixels;
+    double* sum;
+    double* sumsq;  // may be null
+    bool host;
+};
+// Path ids of one pass run up to 0x7FFF0000 (the queue lengths of k_shade): one sample of every listed pixel must fit.
+constexpr uint32_t MAX_PASS_PATHS = 0x7FFF0000u;
+
 // The render loop behind trt_render_device / trt_render / trt_render_samples: samples [s_begin, s_end) of
 // p->spp, added in sample order onto the per-pixel double sums (`accum_host`: in/out when given, else the
-// sums start at zero and are dropped), then rounded to float into out_dev.
-int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_end, float* out_dev, void* hip_stream, trt_stats* stats_out, double* accum_host)
+// sums start at zero and are dropped), then rounded to float into out_dev.  With `job` (trt_render_pixels), the
+// paths are those of the job's pixel list, the sums (and sums of squares) are the job's, and out_dev / accum_host are unused.
+int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_end, float* out_dev, void* hip_stream, trt_stats* stats_out, double* accum_host,
+               const PixelJob* job = nullptr)
 {
     if (int e = checkParams(h, p)) return e;
-    if (!out_dev) return fail(TRT_EINVAL, "null output buffer");
-    if (s_begin >= s_end || s_end > (uint32_t)p->spp) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin < end <= spp");
+    if (!job && !out_dev) return fail(TRT_EINVAL, "null output buffer");
+    if (s_begin >= s_end || (!job && s_end > (uint32_t)p->spp)) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin < end <= spp");
     const uint32_t n_samples = s_end - s_begin;
     HIPC(hipSetDevice(h->device));
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -741,13 +758,18 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const uint32_t nl = h->sc.n_lights;
 
     std::vector<int32_t> rows;
-    for (int y = p->y0; y < p->y1; ++y)
-        if (rowSelected(p, y)) rows.push_back(y);
-    if (rows.empty()) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
-    const uint32_t tw = (uint32_t)(p->x1 - p->x0);
-    const uint64_t npix64 = (uint64_t)rows.size() * tw;
-    if (npix64 > 0x7FFFFFFFull) return fail(TRT_EINVAL, "tile too large");
-    const uint32_t npix = (uint32_t)npix64;
+    uint32_t tw = 0, npix = 0;
+    if (job) {
+        npix = job->n;
+    } else {
+        for (int y = p->y0; y < p->y1; ++y)
+            if (rowSelected(p, y)) rows.push_back(y);
+        if (rows.empty()) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
+        tw = (uint32_t)(p->x1 - p->x0);
+        const uint64_t npix64 = (uint64_t)rows.size() * tw;
+        if (npix64 > 0x7FFFFFFFull) return fail(TRT_EINVAL, "tile too large");
+        npix = (uint32_t)npix64;
+    }
 
     // ---- chunking: how many samples of every pixel one pass holds; >= N_SLOTS passes when spp allows ----
     // Passes are as large as HBM allows: every pass ends in a tail of few, long paths, so fewer and larger passes
@@ -767,9 +789,11 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     uint64_t N = 0;
     size_t q16 = 0, per_slot = 0;
     for (;;) {
-        const uint64_t cap_paths = std::min<uint64_t>(budget / bytes_per_path, 0x7FFF0000ull);
+        const uint64_t cap_paths = std::min<uint64_t>(budget / bytes_per_path, MAX_PASS_PATHS);
         uint64_t max_paths = cap_paths;
-        if (max_paths < npix) return fail(TRT_ENOMEM, "mem_budget too small for one sample of every pixel of the tile; render smaller tiles");
+        if (max_paths < npix)
+            return fail(TRT_ENOMEM, job ? "mem_budget too small for one sample of every listed pixel; render shorter lists"
+                                        : "mem_budget too small for one sample of every pixel of the tile; render smaller tiles");
         if (n_slots > 1 && max_paths / n_slots >= npix) max_paths /= n_slots;  // each slot gets its share of the budget
         slots_used = (max_paths * n_slots <= cap_paths) ? n_slots : 1;
         s_chunk = (uint32_t)std::min<uint64_t>((uint64_t)n_samples, max_paths / npix);
@@ -787,18 +811,29 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         (void)hipGetLastError();  // the failed hipMalloc
         budget /= 2;
     }
-    const size_t rows_bytes = (rows.size() * sizeof(int32_t) + 255) & ~(size_t)255;
+    // a pixel list given on the host is copied in where the row table goes, its sums (and sums of squares) where the tile's sums go
+    const bool job_host = job && job->host;
+    const size_t rows_bytes = job ? (job_host ? ((size_t)npix * sizeof(uint32_t) + 255) & ~(size_t)255 : 0) : (rows.size() * sizeof(int32_t) + 255) & ~(size_t)255;
     const uint32_t count_rows = h->count_rows;
     const size_t counts_bytes = (size_t)COUNT_STRIDE * count_rows * sizeof(uint32_t);
-    const size_t stats_bytes = 256;  // DeviceStats (128 B), then the redo counters of the pass slots (two words each)
+    const size_t stats_bytes = 256;  // DeviceStats (128 B), then the redo counters of the pass slots (two words each), the pixel list's maximum at 192
     const size_t acc_bytes = (size_t)npix * 3 * sizeof(double);
-    if (int e = h->small_buf.ensure(rows_bytes + counts_bytes * N_SLOTS + stats_bytes + acc_bytes)) return e;
+    const size_t acc_bufs = job ? (job_host ? (job->sumsq ? 2 : 1) : 0) : 1;
+    if (int e = h->small_buf.ensure(rows_bytes + counts_bytes * N_SLOTS + stats_bytes + acc_bytes * acc_bufs)) return e;
     char* sb = (char*)h->small_buf.p;
     int32_t* d_rows = (int32_t*)sb;
     DeviceStats* d_stats = (DeviceStats*)(sb + rows_bytes + counts_bytes * N_SLOTS);
     static_assert(sizeof(DeviceStats) <= 128, "the redo counters of the pass slots live behind the statistics");
     uint32_t* d_redo = (uint32_t*)(sb + rows_bytes + counts_bytes * N_SLOTS + 128);  // per slot: length of the redo list, blocks of k_trace_fix that are through
+    uint32_t* d_list_max = (uint32_t*)(sb + rows_bytes + counts_bytes * N_SLOTS + 192);
     double* d_acc = (double*)(sb + rows_bytes + counts_bytes * N_SLOTS + stats_bytes);
+    double* d_sq = nullptr;
+    const uint32_t* d_list = nullptr;
+    if (job) {
+        d_list = job_host ? (const uint32_t*)d_rows : job->pixels;
+        if (!job_host) d_acc = job->sum;
+        d_sq = job_host ? (job->sumsq ? d_acc + (size_t)npix * 3 : nullptr) : job->sumsq;
+    }
 
     PassSlot slots[N_SLOTS];
     for (int k = 0; k < slots_used; ++k) {
@@ -819,15 +854,29 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         S.spill = (uint32_t*)h->spill.p + (size_t)k * h->spill_words_per_slot;
     }
 
-    HIPC(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     HIPC(hipMemsetAsync(d_stats, 0, stats_bytes, stream));  // statistics and redo counters
-    if (accum_host) HIPC(hipMemcpyAsync(d_acc, accum_host, acc_bytes, hipMemcpyHostToDevice, stream));
-    else HIPC(hipMemsetAsync(d_acc, 0, acc_bytes, stream));
+    if (job) {
+        if (job_host) {
+            HIPC(hipMemcpyAsync(d_rows, job->pixels, (size_t)npix * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync(d_acc, job->sum, acc_bytes, hipMemcpyHostToDevice, stream));
+            if (d_sq) HIPC(hipMemcpyAsync(d_sq, job->sumsq, acc_bytes, hipMemcpyHostToDevice, stream));
+        }
+        // every entry must name a pixel of the image: one look at the list on the device before any path is traced
+        hipLaunchKernelGGL(k_list_max, dim3(std::min<uint32_t>((npix + 255) / 256, 1024u)), dim3(256), 0, stream, d_list, npix, d_list_max);
+        uint32_t list_max = 0;
+        HIPC(hipMemcpyAsync(&list_max, d_list_max, sizeof(list_max), hipMemcpyDeviceToHost, stream));
+        HIPC(hipStreamSynchronize(stream));
+        if ((uint64_t)list_max >= (uint64_t)p->width * (uint64_t)p->height) return fail(TRT_EINVAL, "pixel list holds an entry >= width * height");
+    } else {
+        HIPC(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        if (accum_host) HIPC(hipMemcpyAsync(d_acc, accum_host, acc_bytes, hipMemcpyHostToDevice, stream));
+        else HIPC(hipMemsetAsync(d_acc, 0, acc_bytes, stream));
+    }
 
     TileDesc td;
-    td.rows = d_rows;
-    td.tile_w = (int32_t)tw;
-    td.x0 = p->x0;
+    td.rows = job ? (const int32_t*)d_list : d_rows;
+    td.tile_w = job ? p->width : (int32_t)tw;
+    td.x0 = job ? 0 : p->x0;
     td.width = p->width;
     td.height = p->height;
     td.npix = npix;
@@ -838,7 +887,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     td.ray_offset = (p->flags & TRT_FLAG_RAY_OFFSET) ? 1u : 0u;
     td.specular_ks = (p->flags & TRT_FLAG_SPECULAR_KS) ? 1u : 0u;
     td.npix_magic = magicOf(npix);
-    td.tile_w_magic = magicOf(tw);
+    td.tile_w_magic = magicOf((uint32_t)td.tile_w);
     td.grid_ok = (p->width >= 2 && p->height >= 2 && p->width <= 65536 && p->height <= 65536) ? 1u : 0u;
     td.grid_rcp[0] = 1.0 / double(p->width - 1.0);
     td.grid_rcp[1] = 1.0 / double(p->height - 1.0);
@@ -848,10 +897,10 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     // several; more than TRT_MAX_LIGHTS lights find their queues in the arena instead of in the kernel arguments
     const int lights = nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY);
     const uint32_t shade_block = lights == SHADE_ONE ? (uint32_t)TRT_SHADE1_BLOCK : (uint32_t)TRT_SHADEN_BLOCK;
-    const uint32_t rows_lds = (rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)rows.size() : 0u;
+    const uint32_t rows_lds = (!job && rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)rows.size() : 0u;
     if (h->dbg)
-        std::fprintf(stderr, "trt_render: k_shade %s, rows in lds %u, grid_ok %u\n", lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds,
-                     td.grid_ok);
+        std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", job ? "trt_render_pixels" : "trt_render",
+                     lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds, td.grid_ok);
 
     Timer tm;
     tm.h = h;
@@ -904,7 +953,10 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         src.td = td;
         src.s0 = S.s0;
         tm.begin(TRT_K_TRACE_CLOSEST, S.stream);
-        if (S.b == 0) {
+        if (S.b == 0 && job) {
+            if (count) launchTraceClosest<true, PRIMARY_LIST>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
+            else launchTraceClosest<false, PRIMARY_LIST>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
+        } else if (S.b == 0) {
             if (count) launchTraceClosest<true, true>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
             else launchTraceClosest<false, true>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
         } else {
@@ -942,17 +994,21 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         tm.begin(TRT_K_SHADE, S.stream);
         {
             const dim3 grid(std::min<uint32_t>((S.n_active + shade_block - 1) / shade_block, 65536u)), blk(shade_block);
-#define TRT_LAUNCH_SHADE(T) \
-            if (lights == SHADE_ONE) hipLaunchKernelGGL((k_shade<T, SHADE_ONE>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
-            else if (lights == SHADE_FEW) hipLaunchKernelGGL((k_shade<T, SHADE_FEW>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
-            else hipLaunchKernelGGL((k_shade<T, SHADE_MANY>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A);
-            switch (h->shade_tabs) {
-                case 31u: TRT_LAUNCH_SHADE(31u) break;
-                case 15u: TRT_LAUNCH_SHADE(15u) break;
-                case 7u: TRT_LAUNCH_SHADE(7u) break;
-                case 3u: TRT_LAUNCH_SHADE(3u) break;
-                default: TRT_LAUNCH_SHADE(0u) break;
+#define TRT_LAUNCH_SHADE(T, LIST) \
+            if (lights == SHADE_ONE) hipLaunchKernelGGL((k_shade<T, SHADE_ONE, LIST>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
+            else if (lights == SHADE_FEW) hipLaunchKernelGGL((k_shade<T, SHADE_FEW, LIST>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
+            else hipLaunchKernelGGL((k_shade<T, SHADE_MANY, LIST>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A);
+#define TRT_LAUNCH_SHADE_TABS(LIST) \
+            switch (h->shade_tabs) { \
+                case 31u: TRT_LAUNCH_SHADE(31u, LIST) break; \
+                case 15u: TRT_LAUNCH_SHADE(15u, LIST) break; \
+                case 7u: TRT_LAUNCH_SHADE(7u, LIST) break; \
+                case 3u: TRT_LAUNCH_SHADE(3u, LIST) break; \
+                default: TRT_LAUNCH_SHADE(0u, LIST) break; \
             }
+            if (job) { TRT_LAUNCH_SHADE_TABS(true) }
+            else { TRT_LAUNCH_SHADE_TABS(false) }
+#undef TRT_LAUNCH_SHADE_TABS
 #undef TRT_LAUNCH_SHADE
         }
         tm.end(S.stream);
@@ -1015,8 +1071,14 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
             TA.uniform = h->trace_impl == 0 ? 1u : 0u;
             TA.stats = d_stats;
             tm.begin(TRT_K_TAIL, S.stream);
-            if (count) hipLaunchKernelGGL((k_tail<true, 0>), dim3(tailGrid(S.n_active)), dim3(TRT_TRACE_BLOCK), 0, S.stream, h->sc, TA);
-            else hipLaunchKernelGGL((k_tail<false, 0>), dim3(tailGrid(S.n_active)), dim3(TRT_TRACE_BLOCK), 0, S.stream, h->sc, TA);
+            const dim3 tg(tailGrid(S.n_active)), tb(TRT_TRACE_BLOCK);
+            if (job) {
+                if (count) hipLaunchKernelGGL((k_tail<true, 0, true>), tg, tb, 0, S.stream, h->sc, TA);
+                else hipLaunchKernelGGL((k_tail<false, 0, true>), tg, tb, 0, S.stream, h->sc, TA);
+            } else {
+                if (count) hipLaunchKernelGGL((k_tail<true, 0>), tg, tb, 0, S.stream, h->sc, TA);
+                else hipLaunchKernelGGL((k_tail<false, 0>), tg, tb, 0, S.stream, h->sc, TA);
+            }
             tm.end(S.stream);
             st.launches[TRT_K_TAIL]++;
             S.n_active = 0;
@@ -1029,7 +1091,9 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         if (S.chunk != resolved_upto) return TRT_OK;  // an earlier pass is still in flight on the other slot
         if (resolved_upto > 0) HIPC(hipStreamWaitEvent(S.stream, ev_resolved, 0));  // recorded by the previous resolve, earlier in host order
         tm.begin(TRT_K_RESOLVE, S.stream);
-        hipLaunchKernelGGL(k_resolve, dim3(std::min<uint32_t>((npix + 255) / 256, 65536u)), dim3(256), 0, S.stream, S.Lacc, d_acc, npix, S.sc_count, (float)p->spp);
+        const dim3 rg(std::min<uint32_t>((npix + 255) / 256, 65536u)), rb(256);
+        if (d_sq) hipLaunchKernelGGL(k_resolve_moments, rg, rb, 0, S.stream, S.Lacc, d_acc, d_sq, npix, S.sc_count, (float)p->spp);
+        else hipLaunchKernelGGL(k_resolve, rg, rb, 0, S.stream, S.Lacc, d_acc, npix, S.sc_count, (float)p->spp);
         tm.end(S.stream);
         st.launches[TRT_K_RESOLVE]++;
         HIPC(hipEventRecord(ev_resolved, S.stream));
@@ -1054,13 +1118,19 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     if (resolved_upto != n_chunks) return fail(TRT_EHIP, "internal error: passes left unresolved");
 
     HIPC(hipStreamWaitEvent(stream, ev_resolved, 0));
-    tm.begin(TRT_K_RESOLVE, stream);
-    hipLaunchKernelGGL(k_finalize, dim3(std::min<uint32_t>((npix * 3 + 255) / 256, 65536u)), dim3(256), 0, stream, d_acc, out_dev, npix * 3);
-    tm.end(stream);
+    if (!job) {
+        tm.begin(TRT_K_RESOLVE, stream);
+        hipLaunchKernelGGL(k_finalize, dim3(std::min<uint32_t>((npix * 3 + 255) / 256, 65536u)), dim3(256), 0, stream, d_acc, out_dev, npix * 3);
+        tm.end(stream);
+    }
     HIPC(hipEventRecord(ev_end, stream));
     DeviceStats ds;
     HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
     if (accum_host) HIPC(hipMemcpyAsync(accum_host, d_acc, acc_bytes, hipMemcpyDeviceToHost, stream));
+    if (job_host) {
+        HIPC(hipMemcpyAsync(job->sum, d_acc, acc_bytes, hipMemcpyDeviceToHost, stream));
+        if (d_sq) HIPC(hipMemcpyAsync(job->sumsq, d_sq, acc_bytes, hipMemcpyDeviceToHost, stream));
+    }
     HIPC(hipStreamSynchronize(stream));
     HIPC(hipGetLastError());
     drain.armed = false;  // everything this call enqueued has completed
@@ -1082,7 +1152,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     st.redo_rays = ds.redo_rays;
     st.lane_census[0] = ds.census_inner; st.lane_census[1] = ds.census_leaf; st.lane_census[2] = ds.census_done; st.lane_census[3] = ds.census_iters;
     st.passes = n_chunks;
-    st.rows_rendered = rows.size();
+    st.rows_rendered = rows.size();  // 0 for a pixel list
     st.inner_node_bytes = h->trace_impl == 0 ? (uint32_t)sizeof(trt_bvh_node) : (h->node_kind == 1 ? 80u : (uint32_t)sizeof(WideNode));
     if (stats_out) *stats_out = st;
     return TRT_OK;
@@ -1108,6 +1178,39 @@ int trt_render_samples(trt_handle* h, const trt_params* p, int32_t sample_begin,
     if (int e = renderCore(h, p, (uint32_t)sample_begin, (uint32_t)sample_end, (float*)h->out_buf.p, nullptr, stats, accum_host)) return e;
     if (out_host) HIPC(hipMemcpy(out_host, h->out_buf.p, bytes, hipMemcpyDeviceToHost));
     return TRT_OK;
+}
+
+namespace {
+// trt_render_pixels / _device: the checks of include/trt.h, then the render loop on the list.  The tile and row interleave of p are
+// ignored (checked as the whole image); sample_end may pass p->spp, which only scales the terms.
+int renderPixels(trt_handle* h, const trt_params* p_in, uint32_t n_pixels, const uint32_t* pixels, int32_t sample_begin, int32_t sample_end, double* sum,
+                 double* sumsq, void* hip_stream, trt_stats* stats, bool host)
+{
+    if (!h || !p_in) return fail(TRT_EINVAL, "null handle/params");
+    trt_params p = *p_in;
+    p.x0 = 0; p.y0 = 0; p.x1 = p.width; p.y1 = p.height;
+    p.row_block = 1; p.row_mod = 1; p.row_rem = 0;
+    if (int e = checkParams(h, &p)) return e;
+    if (sample_begin < 0 || sample_begin > sample_end) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin <= end");
+    if (n_pixels > 0 && (!pixels || !sum)) return fail(TRT_EINVAL, "null pixel list or sums");
+    if (n_pixels > MAX_PASS_PATHS) return fail(TRT_EINVAL, "pixel list longer than the path ids of one pass can number (0x7FFF0000)");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n_pixels == 0 || sample_begin == sample_end) return TRT_OK;
+    const PixelJob job{n_pixels, pixels, sum, sumsq, host};
+    return renderCore(h, &p, (uint32_t)sample_begin, (uint32_t)sample_end, nullptr, hip_stream, stats, nullptr, &job);
+}
+}  // namespace
+
+int trt_render_pixels(trt_handle* h, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels, int32_t sample_begin, int32_t sample_end,
+                      double* sum_host, double* sumsq_host, trt_stats* stats)
+{
+    return renderPixels(h, p, n_pixels, pixels, sample_begin, sample_end, sum_host, sumsq_host, nullptr, stats, true);
+}
+
+int trt_render_pixels_device(trt_handle* h, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels_dev, int32_t sample_begin, int32_t sample_end,
+                             double* sum_dev, double* sumsq_dev, void* hip_stream, trt_stats* stats)
+{
+    return renderPixels(h, p, n_pixels, pixels_dev, sample_begin, sample_end, sum_dev, sumsq_dev, hip_stream, stats, false);
 }
 
 int trt_render(trt_handle* h, const trt_params* p, float* out_host, trt_stats* stats)

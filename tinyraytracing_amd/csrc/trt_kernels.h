@@ -20,6 +20,7 @@
 // global area.  The per-lane traversals walk 4-wide nodes (trt_wide.h); tiny scenes are walked wave-uniformly.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #include "trt_path.h"
 #include "trt_oct.h"
@@ -199,7 +200,8 @@ __device__ inline unsigned long long waveSum(unsigned long long v)
 // utilisation.  Chosen per scene in trt_create: short traversals want large batches (staircase 454 -> 434 ms/step at 48
 // instead of 16), deep trees smaller ones (blob, soup: 32).
 
-// Where a traversal kernel takes ray `i` from: the queue in HBM, or (PRIMARY) the camera-ray generator.
+// Where a traversal kernel takes ray `i` from: the queue in HBM (PRIMARY 0), or the camera-ray generator over the tile's pixels (1) or over a
+// pixel list (PRIMARY_LIST, trt_render_pixels).
 struct RaySource {
     const f4* ra;
     const f4* rb;
@@ -229,10 +231,12 @@ __device__ __forceinline__ void stNT(f4* p, f4 v)
 #define TRT_LDQ(bit, ptr) (((TRT_NT) & (bit)) ? ldNT(ptr) : *(ptr))
 #define TRT_STQ(bit, ptr, val) do { if ((TRT_NT) & (bit)) stNT((ptr), (val)); else *(ptr) = (val); } while (0)
 
-template <bool PRIMARY>
+constexpr int PRIMARY_LIST = 2;
+template <int PRIMARY>
 __device__ __forceinline__ void fetchRay(const SceneDev& sc, const RaySource& src, uint32_t i, f4& a, f4& b)
 {
-    if (PRIMARY) primaryRay(sc, src.td, src.s0, i, a, b);
+    if constexpr (PRIMARY == PRIMARY_LIST) primaryRay(sc, src.td, src.s0, i, a, b, PixelList());
+    else if (PRIMARY) primaryRay(sc, src.td, src.s0, i, a, b);
     else { a = TRT_LDQ(4, src.ra + i); b = TRT_LDQ(4, src.rb + i); }
 }
 
@@ -428,7 +432,7 @@ __device__ __forceinline__ void uniformWalk(const SceneDev& sc, f3 o, f3 d, bool
     else uniformWalkImpl<COUNT, STRIDE, false>(sc, o, d, inv, valid, false, my_pend, best_t, best_tri, best_flags, n_inner, n_tri);
 }
 
-template <bool SHADOW, bool COUNT, bool PRIMARY>
+template <bool SHADOW, bool COUNT, int PRIMARY>
 __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                                   const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, DeviceStats* stats, bool any_flag,
                                                   f4* __restrict__ pend)
@@ -518,7 +522,7 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
 }
 
 
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, bool PRIMARY, int NK>
+template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK>
 __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo)
@@ -665,7 +669,7 @@ __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const R
 // brings a group of up to 24 triangles per node and gets a longer loop (trt_create; TRT_LEAF_LOOP in the environment overrides).
 // (Also measured: the root and its children read from an LDS copy — a fifth of all node fetches on veach-mis —: +-0.3 %.  These kernels
 // are bound by VALU issue, profiles/r03_roofs_stair.txt, not by the texture addresser.  Removed.)
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, bool PRIMARY>
+template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int PRIMARY>
 __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo, const LightBox& lbox)
@@ -796,7 +800,7 @@ __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, cons
     }
 }
 
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, bool PRIMARY, int NK>
+template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK>
 __device__ __forceinline__ void traceQueue(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo, const LightBox& lbox)
@@ -808,7 +812,7 @@ __device__ __forceinline__ void traceQueue(const SceneDev& sc, const RaySource& 
 
 // PRIMARY: bounce 0 — ray i is the camera ray of path i, generated in registers (K1 of SURVEY.md §7 fused
 // into K2: no primary-ray queue is ever written or read).
-template <bool COUNT, int DEPTH, bool SPILL, int IMPL, bool PRIMARY, int NK>
+template <bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK>
 __global__ TRT_TRACE_BOUNDS void k_trace_closest(SceneDev sc, RaySource src, f4* __restrict__ hit, uint32_t n,
                                                  uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, RedoList redo)
 {
@@ -838,7 +842,7 @@ __global__ TRT_TRACE_BOUNDS void k_trace_shadow(SceneDev sc, ShadowQueue sq, uin
 // on padded trees.  redo.count[0] = length of the list, redo.count[1] = blocks of this launch that are through: the last one adds
 // the length to DeviceStats::redo_rays (trt_stats.redo_rays: how often the slow path ran is visible to the caller) and empties the list.
 constexpr uint32_t TRT_FIX_BLOCKS = 32;
-template <bool SHADOW, bool PRIMARY, int NK>
+template <bool SHADOW, int PRIMARY, int NK>
 __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_trace_fix(SceneDev sc, RaySource src, f4* __restrict__ hit, const f4* __restrict__ sw, uint32_t light_mat,
                                                                f4* __restrict__ Lacc, uint32_t* __restrict__ spill, uint32_t spill_stride, RedoList redo, uint32_t any_flag,
                                                                DeviceStats* stats)
@@ -1012,14 +1016,15 @@ struct RowsShade {
 // run-time choice the pointers are generic, the accesses FLAT, and each of them waits for vmcnt(0) — i.e. for the ray
 // stores issued before it — as well as for the LDS.
 // (Round 3's probe `short` — weight and throughput records stored as 8 bytes, wrong images — bought k_shade 3 %: profiles/r03_ab_oct.txt (8).)
-// LIGHTS: SHADE_ONE, SHADE_FEW or SHADE_MANY (where the shadow-queue descriptors come from).  BLOCK threads, WAVES per SIMD asked of the compiler.
+// LIGHTS: SHADE_ONE, SHADE_FEW or SHADE_MANY (where the shadow-queue descriptors come from).  LIST: the paths are those of a pixel list
+// (trt_render_pixels; A.rows_lds is 0 there).  BLOCK threads, WAVES per SIMD asked of the compiler.
 template <int LIGHTS>
 __device__ inline ShadowQueue shadeQueue(const ShadeArgs& A, uint32_t li)
 {
     if (LIGHTS == SHADE_MANY) return A.sq_arena.queue(li);
     return A.sq[li];
 }
-template <uint32_t TABS, int LIGHTS, int BLOCK = (LIGHTS == SHADE_ONE ? TRT_SHADE1_BLOCK : TRT_SHADEN_BLOCK),
+template <uint32_t TABS, int LIGHTS, bool LIST = false, int BLOCK = (LIGHTS == SHADE_ONE ? TRT_SHADE1_BLOCK : TRT_SHADEN_BLOCK),
           int WAVES = (LIGHTS == SHADE_ONE ? TRT_SHADE1_WAVES : TRT_SHADEN_WAVES)>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A)
 {
@@ -1029,12 +1034,15 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
     __shared__ uint32_t s_cnt2[2 * (2 * (TRT_SHADE_BLOCK / 64) + 2)];  // blockStage2, two buffers used in turn
     __shared__ uint32_t s_shaded, s_depth;  // s_depth: 1 + the deepest vertex of the block that hit something (0: none)
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[TABS ? TRT_SHADE_LDS_TABLE_BYTES / 4 : 4];
-    __shared__ uint16_t s_rows[TRT_SHADE_ROWS_LDS];
+    __shared__ uint16_t s_rows[LIST ? 1 : TRT_SHADE_ROWS_LDS];
     if (threadIdx.x == 0) { s_shaded = 0; s_depth = 0; }
-    for (uint32_t r = threadIdx.x; r < A.rows_lds; r += TRT_SHADE_BLOCK) s_rows[r] = (uint16_t)A.td.rows[r];
-    RowsShade rows;
-    rows.lds = s_rows;
-    rows.in_lds = A.rows_lds != 0u;
+    if (!LIST)
+        for (uint32_t r = threadIdx.x; r < A.rows_lds; r += TRT_SHADE_BLOCK) s_rows[r] = (uint16_t)A.td.rows[r];
+    std::conditional_t<LIST, PixelList, RowsShade> rows;
+    if constexpr (!LIST) {
+        rows.lds = s_rows;
+        rows.in_lds = A.rows_lds != 0u;
+    }
     bool rows_visible = A.rows_lds == 0u;  // the copy above is visible to the block (a barrier lies in between)
     {   // this block's view of the staged tables: the copy itself happens in the first tile, next to that tile's own loads
         uint32_t off = 0;
@@ -1219,7 +1227,8 @@ struct TailArgs {
     DeviceStats* stats;
 };
 
-template <bool COUNT, int NK>
+// LIST: the paths of a pixel list (trt_render_pixels)
+template <bool COUNT, int NK, bool LIST = false>
 __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_tail(SceneDev sc, TailArgs A)
 {
     __shared__ __attribute__((aligned(16))) uint32_t smem[TRT_LDS_STACK_MAX * TRT_TRACE_BLOCK];  // the stacks, or (uniform) the candidate queues
@@ -1251,7 +1260,8 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_tail(SceneDev sc, TailArgs 
                 h = traceClosest<LdsStack<TRT_LDS_STACK_MAX, true>, COUNT, NK>(sc, mk3(ra.x, ra.y, ra.z), mk3(ra.w, rb.x, rb.y), stk, ni[0], nt[0]);
             }
             ShadeCtx c;
-            shadeBegin(sc, A.td, A.s0, ra, rb, bt, mk4(h.t, u2f((uint32_t)h.tri), h.u, h.v), c);
+            if constexpr (LIST) shadeBegin(sc, A.td, A.s0, ra, rb, bt, mk4(h.t, u2f((uint32_t)h.tri), h.u, h.v), c, PixelList());
+            else shadeBegin(sc, A.td, A.s0, ra, rb, bt, mk4(h.t, u2f((uint32_t)h.tri), h.u, h.v), c);
             if (c.had_hit) { any = true; deepest = c.depth > deepest ? c.depth : deepest; }
             if (c.add_L) { L.x = L.x + c.addL.x; L.y = L.y + c.addL.y; L.z = L.z + c.addL.z; }
             if (c.shade_ok) n_shaded++;
@@ -1320,6 +1330,37 @@ __global__ __launch_bounds__(256) void k_resolve(const f4* __restrict__ Lacc, do
         acc[(size_t)p * 3 + 1] = g;
         acc[(size_t)p * 3 + 2] = b;
     }
+}
+
+// The same for a pixel list (trt_render_pixels), with the sums of squares: v = (double)(L / spp), sum += v, sumsq += v * v — a rounded
+// double product, then a rounded double add (__dmul_rn / __dadd_rn: no contraction into an FMA whatever the flags), so a float64
+// restatement on the host gives the same bits.
+__global__ __launch_bounds__(256) void k_resolve_moments(const f4* __restrict__ Lacc, double* __restrict__ sum, double* __restrict__ sumsq, uint32_t npix,
+                                                         uint32_t s_count, float spp)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += stride) {
+        double s[3], q[3];
+        for (int k = 0; k < 3; ++k) { s[k] = sum[(size_t)p * 3 + k]; q[k] = sumsq[(size_t)p * 3 + k]; }
+        for (uint32_t i = 0; i < s_count; ++i) {
+            const f4 L = Lacc[(size_t)i * npix + p];
+            const double v[3] = {(double)(L.x / spp), (double)(L.y / spp), (double)(L.z / spp)};
+            for (int k = 0; k < 3; ++k) {
+                s[k] = __dadd_rn(s[k], v[k]);
+                q[k] = __dadd_rn(q[k], __dmul_rn(v[k], v[k]));
+            }
+        }
+        for (int k = 0; k < 3; ++k) { sum[(size_t)p * 3 + k] = s[k]; sumsq[(size_t)p * 3 + k] = q[k]; }
+    }
+}
+
+// The largest entry of a pixel list (trt_render_pixels refuses lists that leave the image): one atomicMax per wave into *out (zeroed first)
+__global__ __launch_bounds__(256) void k_list_max(const uint32_t* __restrict__ list, uint32_t n, uint32_t* __restrict__ out)
+{
+    uint32_t m = 0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = list[i] > m ? list[i] : m;
+    for (int off = 32; off > 0; off >>= 1) { const uint32_t o = __shfl_xor(m, off); m = o > m ? o : m; }
+    if ((threadIdx.x & 63u) == 0 && m) atomicMax(out, m);
 }
 
 __global__ __launch_bounds__(256) void k_finalize(const double* __restrict__ acc, float* __restrict__ out, uint32_t n)

@@ -849,6 +849,8 @@ TRT_HD inline uint32_t metaDepth(uint32_t m) { return m >> 20; }
 
 // ------------------------------------------------ one path vertex: shade() ----
 // Which image rows/pixels a render call covers, and the sample numbering.
+// A pixel-list render (trt_render_pixels) uses the same record: rows = the list (uint32 pixels y * width + x), npix = its length,
+// tile_w = width, x0 = 0, tile_w_magic = magicOf(width) (PixelList below).
 struct TileDesc {
     const int32_t* rows;  // image row of each packed output row
     int32_t tile_w, x0, width, height;
@@ -890,23 +892,44 @@ TRT_HD inline trt_rng_key pathKey(const TileDesc& td, uint32_t s0, uint32_t pid,
     return trt_rng_make_key(td.seed, pixel, s0 + s_local);
 }
 
+// Pixel-list renders: path id = s_local * npix + list entry, and the entry holds the pixel y * width + x itself (TileDesc).  One
+// dependent global load per look-up: unlike the row table, a list of any length has no LDS copy.
+struct PixelList {
+    TRT_HD uint32_t operator()(const TileDesc& td, uint32_t pl) const { return reinterpret_cast<const uint32_t*>(td.rows)[pl]; }
+};
+TRT_HD inline trt_rng_key pathKey(const TileDesc& td, uint32_t s0, uint32_t pid, PixelList list)
+{
+    const uint32_t s_local = divMagic(pid, td.npix, td.npix_magic), pl = pid - s_local * td.npix;
+    return trt_rng_make_key(td.seed, list(td, pl), s0 + s_local);
+}
+
 // The camera ray of path `pid` (main.cpp:88-95, camera.cpp:19-28) as the queue record (ra, rb): a pure
 // function of the path id, so bounce 0 never goes through HBM — the traversal kernel generates it and
 // k_shade generates the same bits again.
-template <class Rows = RowsGlobal>
-TRT_HD inline void primaryRay(const SceneDev& sc, const TileDesc& td, uint32_t s0, uint32_t pid, f4& ra, f4& rb, Rows rows = Rows())
+TRT_HD inline void cameraRecord(const SceneDev& sc, const TileDesc& td, int y, int x, uint32_t sample, uint32_t pid, f4& ra, f4& rb)
 {
-    const uint32_t s_local = divMagic(pid, td.npix, td.npix_magic), pl = pid - s_local * td.npix;
-    const uint32_t r = divMagic(pl, (uint32_t)td.tile_w, td.tile_w_magic), c = pl - r * (uint32_t)td.tile_w;
-    const int y = rows(td, r), x = td.x0 + (int)c;
     Stream rng;
-    rng.key = trt_rng_make_key(td.seed, (uint32_t)y * (uint32_t)td.width + (uint32_t)x, s0 + s_local);
+    rng.key = trt_rng_make_key(td.seed, (uint32_t)y * (uint32_t)td.width + (uint32_t)x, sample);
     rng.ctr = 0;
     const float u1 = rng.next(), u2 = rng.next();  // jitter x, then y (main.cpp:92-93)
     f3 o, d;
     cameraRay(sc.cam, td.width, td.height, y, x, u1, u2, o, d, td.fixed_pixels != 0u, td.grid_ok ? td.grid_rcp : nullptr);
     ra = mk4(o.x, o.y, o.z, d.x);
     rb = mk4(d.y, d.z, u2f(pid), u2f(packMeta(rng.ctr, TRT_META_CAMERA, 0)));
+}
+template <class Rows = RowsGlobal>
+TRT_HD inline void primaryRay(const SceneDev& sc, const TileDesc& td, uint32_t s0, uint32_t pid, f4& ra, f4& rb, Rows rows = Rows())
+{
+    const uint32_t s_local = divMagic(pid, td.npix, td.npix_magic), pl = pid - s_local * td.npix;
+    const uint32_t r = divMagic(pl, (uint32_t)td.tile_w, td.tile_w_magic), c = pl - r * (uint32_t)td.tile_w;
+    const int y = rows(td, r), x = td.x0 + (int)c;
+    cameraRecord(sc, td, y, x, s0 + s_local, pid, ra, rb);
+}
+TRT_HD inline void primaryRay(const SceneDev& sc, const TileDesc& td, uint32_t s0, uint32_t pid, f4& ra, f4& rb, PixelList list)
+{
+    const uint32_t s_local = divMagic(pid, td.npix, td.npix_magic), pl = pid - s_local * td.npix;
+    const uint32_t q = list(td, pl), y = divMagic(q, (uint32_t)td.tile_w, td.tile_w_magic);
+    cameraRecord(sc, td, (int)y, (int)(q - y * (uint32_t)td.tile_w), s0 + s_local, pid, ra, rb);
 }
 
 struct ShadeCtx {
