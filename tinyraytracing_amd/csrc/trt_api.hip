@@ -290,20 +290,12 @@ uint32_t tailGrid(uint32_t n)
     b = std::min(std::max(b, 8u), MAX_TRACE_BLOCKS);
     return (b + 7u) & ~7u;
 }
-// Traversal kernels: the LDS stack holds 8 or 16 levels without spill code when the scene's verified BVH
-// depth fits, else 16 levels + a global spill area (16 KiB per block keeps 8 waves per SIMD resident);
-// the wave driver (trt_kernels.h) is the static one for shallow trees, the scheduler one otherwise.
-template <bool COUNT, int PRIMARY>
-void launchTraceClosest(const trt_handle* h, hipStream_t stream, uint32_t* spill, const RaySource& src, f4* hit, uint32_t n, DeviceStats* d_stats, RedoList redo);
-template <bool COUNT>
-void launchTraceShadow(const trt_handle* h, hipStream_t stream, uint32_t* spill, const ShadowQueue& sq, uint32_t n, uint32_t light_mat, f4* Lacc, DeviceStats* d_stats, uint32_t any, RedoList redo, const LightBox& lbox);
-
 struct Timer {
     trt_handle* h;
     bool on;
     size_t used = 0;
     struct Span { int k; size_t e0, e1; };
-    std::vector<Span> spans;
+    std::vector<Span> spans{};
     static constexpr size_t RESERVED = 3;  // render begin / end / resolve chain
     hipEvent_t get(size_t i)
     {
@@ -315,62 +307,99 @@ struct Timer {
         return h->events[i];
     }
     // per-kernel spans only with TRT_FLAG_TIMING; recorded on the stream the kernel is launched on
-    void begin(int k, hipStream_t stream)
+    size_t mark(hipStream_t stream)
     {
-        if (!on) return;
         hipEvent_t e = get(RESERVED + used);
         if (e) (void)hipEventRecord(e, stream);
-        spans.push_back({k, RESERVED + used, 0});
-        used++;
+        return RESERVED + used++;
     }
-    void end(hipStream_t stream)
+    void begin(int k, hipStream_t stream) { if (on) spans.push_back({k, mark(stream), 0}); }
+    void end(hipStream_t stream) { if (on) spans.back().e1 = mark(stream); }
+    template <class F>
+    void launch(int k, hipStream_t stream, trt_stats& st, F&& f)
     {
-        if (!on) return;
-        hipEvent_t e = get(RESERVED + used);
-        if (e) (void)hipEventRecord(e, stream);
-        spans.back().e1 = RESERVED + used;
-        used++;
+        begin(k, stream);
+        f();
+        end(stream);
+        st.launches[k]++;
     }
 };
 
-// One kernel per (driver, LDS depth, node kind); the scene picks the combination once, in trt_create.
-#define TRT_LAUNCH_CLOSEST(DEPTH, SPILL, IMPL, NK) \
-    hipLaunchKernelGGL((k_trace_closest<COUNT, DEPTH, SPILL, IMPL, PRIMARY, NK>), g, b, 0, stream, h->sc, src, hit, n, spill, SPILL_STRIDE, d_stats, redo)
-#define TRT_LAUNCH_SHADOW(DEPTH, SPILL, IMPL, NK) \
-    hipLaunchKernelGGL((k_trace_shadow<COUNT, DEPTH, SPILL, IMPL, NK>), g, b, 0, stream, h->sc, sq, n, light_mat, Lacc, spill, SPILL_STRIDE, d_stats, any, redo, lbox)
-#define TRT_BY_DEPTH(LAUNCH, IMPL, NK)                                       \
-    do {                                                                     \
-        if (h->depth <= 16) LAUNCH(16, false, IMPL, NK);                     \
-        else LAUNCH(TRT_LDS_STACK_MAX, true, IMPL, NK);                      \
-    } while (0)
-// The oct tree needs one 8-byte entry per level below the root: OCT_LDS_LEVELS of them in LDS (20 KiB per block: eight blocks per CU),
-// deeper ones — staircase has 10 levels, the 10 M-triangle mesh 11 — in the global spill area.  One instantiation serves every tree.
+using ClosestKernel = void (*)(SceneDev, RaySource, f4*, uint32_t, uint32_t*, uint32_t, DeviceStats*, RedoList);
+using ShadowKernel = void (*)(SceneDev, ShadowQueue, uint32_t, uint32_t, f4*, uint32_t*, uint32_t, DeviceStats*, uint32_t, RedoList, LightBox);
+using FixKernel = void (*)(SceneDev, RaySource, f4*, const f4*, uint32_t, f4*, uint32_t*, uint32_t, RedoList, uint32_t, DeviceStats*);
+using ShadeKernel = void (*)(SceneDev, ShadeArgs);
+using TailKernel = void (*)(SceneDev, TailArgs);
+
+// Traversal kernels: one per (driver, LDS depth, node kind), the combination the scene picked in trt_create.  The LDS stack holds 16 levels
+// without spill code when the verified BVH depth fits, else TRT_LDS_STACK_MAX levels + a global spill area (16 KiB per block keeps 8 waves per
+// SIMD resident); the wave-uniform walk (trt_kernels.h) serves tiny trees.  The oct tree needs one 8-byte entry per level below the root:
+// OCT_LDS_LEVELS of them in LDS (20 KiB per block: eight blocks per CU), deeper ones — staircase has 10 levels, the 10 M-triangle mesh 11 —
+// in the spill area.  One instantiation serves every tree.  traversalOf: the row of the tables below.
 constexpr uint32_t OCT_LDS_LEVELS = 10;
-#define TRT_BY_OCT_DEPTH(LAUNCH) LAUNCH(10, true, 3, 1)
-// Behind every traversal launch of a per-lane driver: k_trace_fix (a few blocks) traces the rays of the launch's redo list again in the
-// exact form (trt_kernels.h, RedoList).  The wave-uniform walk applies the rule on the spot and has no list.
-template <bool COUNT, int PRIMARY>
-void launchTraceClosest(const trt_handle* h, hipStream_t stream, uint32_t* spill, const RaySource& src, f4* hit, uint32_t n, DeviceStats* d_stats, RedoList redo)
+int traversalOf(const trt_handle* h) { return h->trace_impl == 0 ? 0 : (h->node_kind == 1 ? 1 : (h->depth <= 16 ? 2 : 3)); }
+// primary: 0 the queue, 1 the camera rays of a tile, PRIMARY_LIST those of a pixel list
+ClosestKernel closestKernel(const trt_handle* h, bool count, int primary)
 {
-    const dim3 g(h->traceGrid(n)), b(TRT_TRACE_BLOCK);
-    if (h->trace_impl == 0) { TRT_LAUNCH_CLOSEST(1, false, 0, 0); return; }
-    if (h->node_kind == 1) TRT_BY_OCT_DEPTH(TRT_LAUNCH_CLOSEST);
-    else TRT_BY_DEPTH(TRT_LAUNCH_CLOSEST, 3, 0);
-    hipLaunchKernelGGL((k_trace_fix<false, PRIMARY, 0>), dim3(TRT_FIX_BLOCKS), b, 0, stream, h->sc, src, hit, (const f4*)nullptr, 0u, (f4*)nullptr, spill, SPILL_STRIDE, redo, 0u, d_stats);
+    const ClosestKernel k[4][2][3] = {
+        {{k_trace_closest<false, 1, false, 0, 0, 0>, k_trace_closest<false, 1, false, 0, 1, 0>, k_trace_closest<false, 1, false, 0, PRIMARY_LIST, 0>},
+         {k_trace_closest<true, 1, false, 0, 0, 0>, k_trace_closest<true, 1, false, 0, 1, 0>, k_trace_closest<true, 1, false, 0, PRIMARY_LIST, 0>}},
+        {{k_trace_closest<false, OCT_LDS_LEVELS, true, 3, 0, 1>, k_trace_closest<false, OCT_LDS_LEVELS, true, 3, 1, 1>, k_trace_closest<false, OCT_LDS_LEVELS, true, 3, PRIMARY_LIST, 1>},
+         {k_trace_closest<true, OCT_LDS_LEVELS, true, 3, 0, 1>, k_trace_closest<true, OCT_LDS_LEVELS, true, 3, 1, 1>, k_trace_closest<true, OCT_LDS_LEVELS, true, 3, PRIMARY_LIST, 1>}},
+        {{k_trace_closest<false, 16, false, 3, 0, 0>, k_trace_closest<false, 16, false, 3, 1, 0>, k_trace_closest<false, 16, false, 3, PRIMARY_LIST, 0>},
+         {k_trace_closest<true, 16, false, 3, 0, 0>, k_trace_closest<true, 16, false, 3, 1, 0>, k_trace_closest<true, 16, false, 3, PRIMARY_LIST, 0>}},
+        {{k_trace_closest<false, TRT_LDS_STACK_MAX, true, 3, 0, 0>, k_trace_closest<false, TRT_LDS_STACK_MAX, true, 3, 1, 0>, k_trace_closest<false, TRT_LDS_STACK_MAX, true, 3, PRIMARY_LIST, 0>},
+         {k_trace_closest<true, TRT_LDS_STACK_MAX, true, 3, 0, 0>, k_trace_closest<true, TRT_LDS_STACK_MAX, true, 3, 1, 0>, k_trace_closest<true, TRT_LDS_STACK_MAX, true, 3, PRIMARY_LIST, 0>}}};
+    return k[traversalOf(h)][count][primary];
+}
+ShadowKernel shadowKernel(const trt_handle* h, bool count)
+{
+    const ShadowKernel k[4][2] = {{k_trace_shadow<false, 1, false, 0, 0>, k_trace_shadow<true, 1, false, 0, 0>},
+                                  {k_trace_shadow<false, OCT_LDS_LEVELS, true, 3, 1>, k_trace_shadow<true, OCT_LDS_LEVELS, true, 3, 1>},
+                                  {k_trace_shadow<false, 16, false, 3, 0>, k_trace_shadow<true, 16, false, 3, 0>},
+                                  {k_trace_shadow<false, TRT_LDS_STACK_MAX, true, 3, 0>, k_trace_shadow<true, TRT_LDS_STACK_MAX, true, 3, 0>}};
+    return k[traversalOf(h)][count];
+}
+// Behind every traversal launch of a per-lane driver: k_trace_fix (a few blocks) traces the rays of the launch's redo list again in the
+// exact form (trt_kernels.h, RedoList).  The wave-uniform walk applies the rule on the spot and has no list: nullptr.
+FixKernel fixKernel(const trt_handle* h, bool shadow, int primary)
+{
+    const FixKernel k[4] = {k_trace_fix<false, 0, 0>, k_trace_fix<false, 1, 0>, k_trace_fix<false, PRIMARY_LIST, 0>, k_trace_fix<true, false, 0>};
+    return h->trace_impl == 0 ? nullptr : k[shadow ? 3 : primary];
+}
+ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list)
+{
+    const ShadeKernel k[5][2][3] = {
+        {{k_shade<31u, SHADE_ONE>, k_shade<31u, SHADE_FEW>, k_shade<31u, SHADE_MANY>}, {k_shade<31u, SHADE_ONE, true>, k_shade<31u, SHADE_FEW, true>, k_shade<31u, SHADE_MANY, true>}},
+        {{k_shade<15u, SHADE_ONE>, k_shade<15u, SHADE_FEW>, k_shade<15u, SHADE_MANY>}, {k_shade<15u, SHADE_ONE, true>, k_shade<15u, SHADE_FEW, true>, k_shade<15u, SHADE_MANY, true>}},
+        {{k_shade<7u, SHADE_ONE>, k_shade<7u, SHADE_FEW>, k_shade<7u, SHADE_MANY>}, {k_shade<7u, SHADE_ONE, true>, k_shade<7u, SHADE_FEW, true>, k_shade<7u, SHADE_MANY, true>}},
+        {{k_shade<3u, SHADE_ONE>, k_shade<3u, SHADE_FEW>, k_shade<3u, SHADE_MANY>}, {k_shade<3u, SHADE_ONE, true>, k_shade<3u, SHADE_FEW, true>, k_shade<3u, SHADE_MANY, true>}},
+        {{k_shade<0u, SHADE_ONE>, k_shade<0u, SHADE_FEW>, k_shade<0u, SHADE_MANY>}, {k_shade<0u, SHADE_ONE, true>, k_shade<0u, SHADE_FEW, true>, k_shade<0u, SHADE_MANY, true>}}};
+    return k[tabs == 31u ? 0 : (tabs == 15u ? 1 : (tabs == 7u ? 2 : (tabs == 3u ? 3 : 4)))][list][lights];
+}
+// (named in this order: named the other way round, k_tail<true, 0, true> / <false, 0, false> build 1 instruction shorter / longer, tools/isa_diff.py)
+TailKernel tailKernel(bool count, bool list)
+{
+    if (list) return count ? k_tail<true, 0, true> : k_tail<false, 0, true>;
+    return count ? k_tail<true, 0> : k_tail<false, 0>;
 }
 
-template <bool COUNT>
-void launchTraceShadow(const trt_handle* h, hipStream_t stream, uint32_t* spill, const ShadowQueue& sq, uint32_t n, uint32_t light_mat, f4* Lacc, DeviceStats* d_stats, uint32_t any, RedoList redo, const LightBox& lbox)
+void launchTraceClosest(const trt_handle* h, ClosestKernel k, FixKernel fix, hipStream_t stream, uint32_t* spill, const RaySource& src, f4* hit, uint32_t n,
+                        DeviceStats* d_stats, RedoList redo)
 {
-    const dim3 g(h->traceGrid(n)), b(TRT_TRACE_BLOCK);
-    if (h->trace_impl == 0) { TRT_LAUNCH_SHADOW(1, false, 0, 0); return; }
-    if (h->node_kind == 1) TRT_BY_OCT_DEPTH(TRT_LAUNCH_SHADOW);
-    else TRT_BY_DEPTH(TRT_LAUNCH_SHADOW, 3, 0);
-    RaySource src;
-    src.ra = sq.sa;
-    src.rb = sq.sb;
-    src.s0 = 0;
-    hipLaunchKernelGGL((k_trace_fix<true, false, 0>), dim3(TRT_FIX_BLOCKS), b, 0, stream, h->sc, src, (f4*)nullptr, (const f4*)sq.sw, light_mat, Lacc, spill, SPILL_STRIDE, redo, any, d_stats);
+    const dim3 b(TRT_TRACE_BLOCK);
+    hipLaunchKernelGGL(k, dim3(h->traceGrid(n)), b, 0, stream, h->sc, src, hit, n, spill, SPILL_STRIDE, d_stats, redo);
+    if (fix) hipLaunchKernelGGL(fix, dim3(TRT_FIX_BLOCKS), b, 0, stream, h->sc, src, hit, (const f4*)nullptr, 0u, (f4*)nullptr, spill, SPILL_STRIDE, redo, 0u, d_stats);
+}
+
+void launchTraceShadow(const trt_handle* h, ShadowKernel k, FixKernel fix, hipStream_t stream, uint32_t* spill, const ShadowQueue& sq, uint32_t n, uint32_t light_mat,
+                       f4* Lacc, DeviceStats* d_stats, uint32_t any, RedoList redo, const LightBox& lbox)
+{
+    const dim3 b(TRT_TRACE_BLOCK);
+    hipLaunchKernelGGL(k, dim3(h->traceGrid(n)), b, 0, stream, h->sc, sq, n, light_mat, Lacc, spill, SPILL_STRIDE, d_stats, any, redo, lbox);
+    if (!fix) return;
+    const RaySource src{sq.sa, sq.sb, TileDesc{}, 0u};
+    hipLaunchKernelGGL(fix, dim3(TRT_FIX_BLOCKS), b, 0, stream, h->sc, src, (f4*)nullptr, (const f4*)sq.sw, light_mat, Lacc, spill, SPILL_STRIDE, redo, any, d_stats);
 }
 
 }  // namespace
@@ -659,15 +688,10 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     if (const char* e = std::getenv("TRT_SHADE_PAD_LDS")) {
         h->shade_pad_lds = std::min(100000u, (uint32_t)std::strtoul(e, nullptr, 10));
         // more than 64 KiB per block needs the opt-in; a refusal shows as a launch error, not as a silent no-op
-#define TRT_PAD_ATTR(T) \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_ONE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_FEW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_MANY>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_ONE, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_FEW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds); \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_shade<T, SHADE_MANY, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
-        TRT_PAD_ATTR(31u) TRT_PAD_ATTR(15u) TRT_PAD_ATTR(7u) TRT_PAD_ATTR(3u) TRT_PAD_ATTR(0u)
-#undef TRT_PAD_ATTR
+        for (uint32_t tabs : {31u, 15u, 7u, 3u, 0u})
+            for (bool list : {false, true})
+                for (int lights : {SHADE_ONE, SHADE_FEW, SHADE_MANY})
+                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shadeKernel(tabs, lights, list)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
     }
 
     *out = h.release();
@@ -726,56 +750,166 @@ struct PassSlot {
     uint32_t chunk = 0, s0 = 0, sc_count = 0, n_active = 0, b = 0;
     int cur = 0;
 };
-}  // namespace
-
-namespace {
-// A pixel-list render (trt_render_pixels): the paths of samples [s_begin, s_end) of `n` listed pixels instead of those of a tile.
-// pixels / sum / sumsq are host arrays (copied in and out here) or device arrays of the handle's device (used in place).
-struct PixelJob {
-    uint32_t n;
-    const uint32_t* pixels;
-    double* sum;
-    double* sumsq;  // may be null
-    bool host;
-};
 // Path ids of one pass run up to 0x7FFF0000 (the queue lengths of k_shade): one sample of every listed pixel must fit.
 constexpr uint32_t MAX_PASS_PATHS = 0x7FFF0000u;
 
-// The render loop behind trt_render_device / trt_render / trt_render_samples: samples [s_begin, s_end) of
-// p->spp, added in sample order onto the per-pixel double sums (`accum_host`: in/out when given, else the
-// sums start at zero and are dropped), then rounded to float into out_dev.  With `job` (trt_render_pixels), the
-// paths are those of the job's pixel list, the sums (and sums of squares) are the job's, and out_dev / accum_host are unused.
-int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_end, float* out_dev, void* hip_stream, trt_stats* stats_out, double* accum_host,
-               const PixelJob* job = nullptr)
-{
-    if (int e = checkParams(h, p)) return e;
-    if (!job && !out_dev) return fail(TRT_EINVAL, "null output buffer");
-    if (s_begin >= s_end || (!job && s_end > (uint32_t)p->spp)) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin < end <= spp");
-    const uint32_t n_samples = s_end - s_begin;
-    HIPC(hipSetDevice(h->device));
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const bool count = (p->flags & TRT_FLAG_COUNT) != 0;
-    const uint32_t nl = h->sc.n_lights;
-
-    std::vector<int32_t> rows;
-    uint32_t tw = 0, npix = 0;
-    if (job) {
-        npix = job->n;
-    } else {
-        for (int y = p->y0; y < p->y1; ++y)
-            if (rowSelected(p, y)) rows.push_back(y);
-        if (rows.empty()) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
-        tw = (uint32_t)(p->x1 - p->x0);
-        const uint64_t npix64 = (uint64_t)rows.size() * tw;
-        if (npix64 > 0x7FFFFFFFull) return fail(TRT_EINVAL, "tile too large");
-        npix = (uint32_t)npix64;
+// A pass slot's share of the arena, the one statement of a path's footprint: arrays of N 16-B records in this order — two ray queues
+// (ra, rb, bt each), the hits, Lacc, three per light (its shadow queue: ShadowArena::queue) — then the redo list, one index per path.
+struct SlotLayout {
+    static constexpr uint64_t arrays(uint32_t nl) { return 3 * 2 + 1 + 1 + 3ull * nl; }
+    static constexpr uint64_t bytesPerPath(uint32_t nl) { return arrays(nl) * sizeof(f4) + sizeof(uint32_t); }
+    static size_t bytes(uint64_t N, uint32_t nl) { return (size_t)(N * arrays(nl) + (N + 3) / 4) * sizeof(f4); }  // the redo list in whole 16-B words
+    static void carve(PassSlot& S, f4* base, uint64_t N, uint32_t nl)
+    {
+        auto take = [&](uint64_t k) { f4* r = base; base += k * N; return r; };
+        for (RayQueue& q : S.Q) { q.ra = take(1); q.rb = take(1); q.bt = take(1); }
+        S.hit = take(1);
+        S.Lacc = take(1);
+        S.shadow = ShadowArena{take(3 * nl), N};
+        S.redo.idx = (uint32_t*)base;
     }
+};
 
-    // ---- chunking: how many samples of every pixel one pass holds; >= N_SLOTS passes when spp allows ----
-    // Passes are as large as HBM allows: every pass ends in a tail of few, long paths, so fewer and larger passes
-    // are faster (back 1080p x 256 spp: 3 passes in 32 GiB 101.4 ms, 1 pass in 93 GB 96.8 ms).  Default budget:
-    // three quarters of what is free on the device (the scene is already resident); halved on an allocation failure.
-    const uint64_t bytes_per_path = 2ull * 48 + 16 + 16 + (uint64_t)nl * 48 + 4;  // queues, hit, Lacc, shadow queues, redo list
+// How a render call splits its samples into passes: `slots` passes in flight at once, each of `chunk` samples of every pixel (the last one
+// may hold fewer), N paths and slot_bytes of arena.  Passes are as large as the budget allows: every pass ends in a tail of few, long paths,
+// so fewer and larger passes are faster (back 1080p x 256 spp: 3 passes in 32 GiB 101.4 ms, 1 pass in 93 GB 96.8 ms); >= slots_wanted
+// passes when the samples allow.  planPasses is false when the budget holds less than one sample of every pixel.
+struct PassPlan { int slots; uint32_t chunk, n_chunks; uint64_t N; size_t slot_bytes; };
+bool planPasses(uint32_t npix, uint32_t n_samples, uint32_t nl, uint64_t budget, int slots_wanted, PassPlan& pl)
+{
+    const uint64_t cap_paths = std::min<uint64_t>(budget / SlotLayout::bytesPerPath(nl), MAX_PASS_PATHS);
+    uint64_t max_paths = cap_paths;
+    if (max_paths < npix) return false;
+    if (slots_wanted > 1 && max_paths / slots_wanted >= npix) max_paths /= slots_wanted;  // each slot gets its share of the budget
+    pl.slots = (max_paths * slots_wanted <= cap_paths) ? slots_wanted : 1;
+    pl.chunk = (uint32_t)std::min<uint64_t>((uint64_t)n_samples, max_paths / npix);
+    pl.n_chunks = (n_samples + pl.chunk - 1) / pl.chunk;
+    if (pl.slots > 1 && pl.n_chunks < (uint32_t)pl.slots) pl.n_chunks = std::min<uint32_t>((uint32_t)pl.slots, n_samples);
+    pl.chunk = (n_samples + pl.n_chunks - 1) / pl.n_chunks;
+    pl.n_chunks = (n_samples + pl.chunk - 1) / pl.chunk;
+    pl.N = (uint64_t)npix * pl.chunk;
+    pl.slot_bytes = SlotLayout::bytes(pl.N, nl);
+    return true;
+}
+
+// Offsets of a buffer's regions, in the order they are added, each at the alignment it asks for.
+struct Layout {
+    size_t bytes = 0;
+    size_t add(size_t n, size_t align)
+    {
+        const size_t at = (bytes + align - 1) & ~(align - 1);
+        bytes = at + n;
+        return at;
+    }
+};
+
+// What one render call traces, and where its per-pixel sums come from and go.  A tile (trt_render*): its selected rows; the sums are the
+// caller's host accumulator (in/out) or, without one, start at zero and are dropped; out_dev receives them rounded to float.  A pixel list
+// (trt_render_pixels*) of the whole image: pixels, sum and sumsq (may be null) are host arrays (`host`, staged) or device arrays used in place.
+struct RenderInput {
+    bool list = false, host = true;
+    std::vector<int32_t> rows;
+    const uint32_t* pixels = nullptr;
+    uint32_t npix = 0;
+    int32_t tile_w = 0, x0 = 0;  // TileDesc
+    double* sum = nullptr;
+    double* sumsq = nullptr;
+    float* out_dev = nullptr;
+};
+
+// The arguments of k_shade that every bounce of a render call shares, its TileDesc among them (d_table: the row table or the list on the device)
+ShadeArgs shadeArgsOf(const trt_handle* h, const trt_params* p, const RenderInput& in, const void* d_table, uint32_t rows_lds, DeviceStats* d_stats)
+{
+    ShadeArgs A;
+    TileDesc& td = A.td;
+    td.rows = (const int32_t*)d_table;
+    td.tile_w = in.tile_w;
+    td.x0 = in.x0;
+    td.width = p->width;
+    td.height = p->height;
+    td.npix = in.npix;
+    td.seed = p->seed;
+    td.spp = (uint32_t)p->spp;
+    td.fixed_nee = (p->flags & TRT_FLAG_FIXED_NEE) ? 1u : 0u;
+    td.fixed_pixels = (p->flags & TRT_FLAG_FIXED_PIXELS) ? 1u : 0u;
+    td.ray_offset = (p->flags & TRT_FLAG_RAY_OFFSET) ? 1u : 0u;
+    td.specular_ks = (p->flags & TRT_FLAG_SPECULAR_KS) ? 1u : 0u;
+    td.npix_magic = magicOf(in.npix);
+    td.tile_w_magic = magicOf((uint32_t)td.tile_w);
+    td.grid_ok = (p->width >= 2 && p->height >= 2 && p->width <= 65536 && p->height <= 65536) ? 1u : 0u;
+    td.grid_rcp[0] = 1.0 / double(p->width - 1.0);
+    td.grid_rcp[1] = 1.0 / double(p->height - 1.0);
+    td.grid_rcp[2] = 1.0 / double(p->width);
+    td.grid_rcp[3] = 1.0 / double(p->height);
+    A.shadow_count_stride = COUNT_STRIDE;
+    A.max_depth = p->max_depth;
+    A.lds_mat_bytes = h->lds_tab[0];
+    A.lds_light_bytes = h->lds_tab[1];
+    A.lds_cum_bytes = h->lds_tab[2];
+    A.lds_ltri_bytes = h->lds_tab[3];
+    A.lds_tshade_bytes = h->lds_tab[4];
+    A.lds_image = (const f4*)h->lds_image;
+    A.lds_image_words = h->lds_image_bytes / 16u;
+    A.rows_lds = rows_lds;
+    A.stats = d_stats;
+    return A;
+}
+
+// The queue lengths of the slot's bounce: spin on the sequence word the device writes after them; the stream is the fallback (and the error path)
+int awaitCounts(const PassSlot& S, uint32_t count_rows)
+{
+    volatile uint32_t* flag = (volatile uint32_t*)S.host_counts + 2 * count_rows;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint32_t spins = 0;
+    while (*flag != S.seq) {
+        if ((++spins & 0x3FFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
+            HIPC(hipStreamSynchronize(S.stream));  // long kernels: let the runtime wait; also surfaces a device error
+            if (*flag != S.seq) return fail(TRT_EHIP, "queue lengths did not arrive");
+            break;
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return TRT_OK;
+}
+
+void addDeviceStats(trt_stats& st, const DeviceStats& ds, const trt_handle* h)
+{
+    st.shaded_hits = ds.shaded_hits;
+    st.wave_steps[0] = ds.wave_inner_steps;
+    st.wave_steps[1] = ds.wave_leaf_steps;
+    st.rays_shadow += ds.tail_rays_shadow;
+    st.rays_indirect += ds.tail_rays_indirect;
+    for (int i = 0; i < 2; ++i) { st.inner_visits[i] = ds.inner_visits[i]; st.tri_tests[i] = ds.tri_tests[i]; }
+    st.max_bounces = ds.max_depth_hit;
+    st.redo_rays = ds.redo_rays;
+    st.lane_census[0] = ds.census_inner; st.lane_census[1] = ds.census_leaf; st.lane_census[2] = ds.census_done; st.lane_census[3] = ds.census_iters;
+    st.inner_node_bytes = h->trace_impl == 0 ? (uint32_t)sizeof(trt_bvh_node) : (h->node_kind == 1 ? 80u : (uint32_t)sizeof(WideNode));
+}
+
+// From the first pass on, work is in flight on the slot streams.  Whatever way renderCore is left, nothing may still be running on
+// them when it returns: a late kernel of a failed call would write the arena, Lacc and the pinned counters of the NEXT call on this
+// handle.  The guard drains them (and keeps the sequence numbers monotonic).
+struct Drain {
+    trt_handle* h;
+    PassSlot* slots;
+    int n;
+    hipStream_t caller;
+    bool armed = true;
+    ~Drain()
+    {
+        for (int k = 0; k < n; ++k) h->slot_seq[k] = slots[k].seq;
+        if (!armed) return;
+        for (int k = 0; k < n; ++k) (void)hipStreamSynchronize(slots[k].stream);
+        (void)hipStreamSynchronize(caller);
+        (void)hipGetLastError();
+    }
+};
+
+// The passes of a render call and the arena for them.  Default budget: three quarters of what is free on the device (the scene is already
+// resident); halved while the arena cannot be had.
+int planArena(trt_handle* h, const trt_params* p, uint32_t npix, uint32_t n_samples, bool list, PassPlan& plan)
+{
+    const uint32_t nl = h->sc.n_lights;
     uint64_t budget = p->mem_budget;
     const bool own_budget = budget == 0;
     if (own_budget) {
@@ -784,159 +918,106 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         budget = (uint64_t)(free_b + h->arena.bytes) / 4 * 3;
     }
     const int n_slots = (n_samples >= 2 && (p->flags & TRT_FLAG_OVERLAP) && h->n_slots > 1) ? N_SLOTS : 1;
-    int slots_used = 1;
-    uint32_t s_chunk = 1, n_chunks = 1;
-    uint64_t N = 0;
-    size_t q16 = 0, per_slot = 0;
     for (;;) {
-        const uint64_t cap_paths = std::min<uint64_t>(budget / bytes_per_path, MAX_PASS_PATHS);
-        uint64_t max_paths = cap_paths;
-        if (max_paths < npix)
-            return fail(TRT_ENOMEM, job ? "mem_budget too small for one sample of every listed pixel; render shorter lists"
-                                        : "mem_budget too small for one sample of every pixel of the tile; render smaller tiles");
-        if (n_slots > 1 && max_paths / n_slots >= npix) max_paths /= n_slots;  // each slot gets its share of the budget
-        slots_used = (max_paths * n_slots <= cap_paths) ? n_slots : 1;
-        s_chunk = (uint32_t)std::min<uint64_t>((uint64_t)n_samples, max_paths / npix);
-        n_chunks = (n_samples + s_chunk - 1) / s_chunk;
-        if (slots_used > 1 && n_chunks < (uint32_t)slots_used) n_chunks = (uint32_t)std::min<uint32_t>((uint32_t)slots_used, n_samples);
-        s_chunk = (n_samples + n_chunks - 1) / n_chunks;
-        n_chunks = (n_samples + s_chunk - 1) / s_chunk;
-        N = (uint64_t)npix * s_chunk;
-        // ---- carve the arena: one set of queues per slot
-        q16 = (size_t)N * sizeof(f4);
-        per_slot = q16 * (3 * 2 + 1 + 1 + 3 * (size_t)nl) + (((size_t)N + 3) / 4) * sizeof(f4);  // + the redo list (one index per path)
-        const int e = h->arena.ensure(per_slot * (size_t)slots_used);
-        if (e == TRT_OK) break;
-        if (e != TRT_ENOMEM || !own_budget || budget / 2 < bytes_per_path * npix) return e;
+        if (!planPasses(npix, n_samples, nl, budget, n_slots, plan))
+            return fail(TRT_ENOMEM, list ? "mem_budget too small for one sample of every listed pixel; render shorter lists"
+                                         : "mem_budget too small for one sample of every pixel of the tile; render smaller tiles");
+        const int e = h->arena.ensure(plan.slot_bytes * (size_t)plan.slots);
+        if (e == TRT_OK) return TRT_OK;
+        if (e != TRT_ENOMEM || !own_budget || budget / 2 < SlotLayout::bytesPerPath(nl) * npix) return e;
         (void)hipGetLastError();  // the failed hipMalloc
         budget /= 2;
     }
-    // a pixel list given on the host is copied in where the row table goes, its sums (and sums of squares) where the tile's sums go
-    const bool job_host = job && job->host;
-    const size_t rows_bytes = job ? (job_host ? ((size_t)npix * sizeof(uint32_t) + 255) & ~(size_t)255 : 0) : (rows.size() * sizeof(int32_t) + 255) & ~(size_t)255;
-    const uint32_t count_rows = h->count_rows;
-    const size_t counts_bytes = (size_t)COUNT_STRIDE * count_rows * sizeof(uint32_t);
-    const size_t stats_bytes = 256;  // DeviceStats (128 B), then the redo counters of the pass slots (two words each), the pixel list's maximum at 192
-    const size_t acc_bytes = (size_t)npix * 3 * sizeof(double);
-    const size_t acc_bufs = job ? (job_host ? (job->sumsq ? 2 : 1) : 0) : 1;
-    if (int e = h->small_buf.ensure(rows_bytes + counts_bytes * N_SLOTS + stats_bytes + acc_bytes * acc_bufs)) return e;
-    char* sb = (char*)h->small_buf.p;
-    int32_t* d_rows = (int32_t*)sb;
-    DeviceStats* d_stats = (DeviceStats*)(sb + rows_bytes + counts_bytes * N_SLOTS);
-    static_assert(sizeof(DeviceStats) <= 128, "the redo counters of the pass slots live behind the statistics");
-    uint32_t* d_redo = (uint32_t*)(sb + rows_bytes + counts_bytes * N_SLOTS + 128);  // per slot: length of the redo list, blocks of k_trace_fix that are through
-    uint32_t* d_list_max = (uint32_t*)(sb + rows_bytes + counts_bytes * N_SLOTS + 192);
-    double* d_acc = (double*)(sb + rows_bytes + counts_bytes * N_SLOTS + stats_bytes);
-    double* d_sq = nullptr;
-    const uint32_t* d_list = nullptr;
-    if (job) {
-        d_list = job_host ? (const uint32_t*)d_rows : job->pixels;
-        if (!job_host) d_acc = job->sum;
-        d_sq = job_host ? (job->sumsq ? d_acc + (size_t)npix * 3 : nullptr) : job->sumsq;
-    }
+}
 
+// Host arrays to their places in small_buf (a tile without sums starts them at zero), then a pixel list is checked before any path is traced
+int stageInput(const RenderInput& in, const trt_params* p, void* d_table, size_t table_bytes, double* d_sum, double* d_sq, uint32_t* d_list_max, hipStream_t stream)
+{
+    const size_t acc_bytes = (size_t)in.npix * 3 * sizeof(double);
+    if (in.host) {
+        HIPC(hipMemcpyAsync(d_table, in.list ? (const void*)in.pixels : (const void*)in.rows.data(), table_bytes, hipMemcpyHostToDevice, stream));
+        if (in.sum) HIPC(hipMemcpyAsync(d_sum, in.sum, acc_bytes, hipMemcpyHostToDevice, stream));
+        else HIPC(hipMemsetAsync(d_sum, 0, acc_bytes, stream));
+        if (d_sq) HIPC(hipMemcpyAsync(d_sq, in.sumsq, acc_bytes, hipMemcpyHostToDevice, stream));
+    }
+    if (!in.list) return TRT_OK;
+    uint32_t list_max = 0;
+    hipLaunchKernelGGL(k_list_max, dim3(std::min<uint32_t>((in.npix + 255) / 256, 1024u)), dim3(256), 0, stream, in.host ? (const uint32_t*)d_table : in.pixels, in.npix, d_list_max);
+    HIPC(hipMemcpyAsync(&list_max, d_list_max, sizeof(list_max), hipMemcpyDeviceToHost, stream));
+    HIPC(hipStreamSynchronize(stream));
+    if ((uint64_t)list_max >= (uint64_t)p->width * (uint64_t)p->height) return fail(TRT_EINVAL, "pixel list holds an entry >= width * height");
+    return TRT_OK;
+}
+
+// The render loop behind every render entry: samples [s_begin, s_end) of p->spp of what `in` describes, added in sample order onto
+// its per-pixel sums.  The entry points have checked p and the sample range and made h's device current.
+int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_end, const RenderInput& in, hipStream_t stream, trt_stats* stats_out)
+{
+    const uint32_t n_samples = s_end - s_begin, npix = in.npix, nl = h->sc.n_lights, count_rows = h->count_rows;
+    PassPlan plan;
+    if (int e = planArena(h, p, npix, n_samples, in.list, plan)) return e;
+    // ---- small_buf: the row table or the staged pixel list, the counters of each slot, the block cleared first (DeviceStats; per slot the
+    // length of its redo list and the blocks of k_trace_fix that are through; the list's maximum), the staged sums and sums of squares
+    const size_t counts_bytes = (size_t)COUNT_STRIDE * count_rows * sizeof(uint32_t), acc_bytes = (size_t)npix * 3 * sizeof(double);
+    const size_t table_bytes = !in.host ? 0 : (in.list ? (size_t)npix * sizeof(uint32_t) : in.rows.size() * sizeof(int32_t));
+    Layout L;
+    const size_t o_table = L.add(table_bytes, 256), o_counts = L.add(counts_bytes * N_SLOTS, 256);
+    const size_t o_stats = L.add(sizeof(DeviceStats), 256), o_redo = L.add(2 * N_SLOTS * sizeof(uint32_t), 64), o_list_max = L.add(sizeof(uint32_t), 64);
+    const size_t o_sum = L.add(in.host ? acc_bytes : 0, 256), o_sumsq = L.add(in.host && in.sumsq ? acc_bytes : 0, sizeof(double));
+    if (int e = h->small_buf.ensure(L.bytes)) return e;
+    char* sb = (char*)h->small_buf.p;
+    DeviceStats* d_stats = (DeviceStats*)(sb + o_stats);
+    const void* d_table = in.host ? (const void*)(sb + o_table) : (const void*)in.pixels;
+    double* d_sum = in.host ? (double*)(sb + o_sum) : in.sum;
+    double* d_sq = !in.sumsq ? nullptr : (in.host ? (double*)(sb + o_sumsq) : in.sumsq);
+    HIPC(hipMemsetAsync(d_stats, 0, o_sum - o_stats, stream));
+    if (int e = stageInput(in, p, sb + o_table, table_bytes, d_sum, d_sq, (uint32_t*)(sb + o_list_max), stream)) return e;
     PassSlot slots[N_SLOTS];
-    for (int k = 0; k < slots_used; ++k) {
+    for (int k = 0; k < plan.slots; ++k) {
         PassSlot& S = slots[k];
         S.stream = h->slot_streams[k];
-        f4* base = (f4*)((char*)h->arena.p + per_slot * (size_t)k);
-        auto take = [&]() { f4* r = base; base += N; return r; };
-        for (int q = 0; q < 2; ++q) { S.Q[q].ra = take(); S.Q[q].rb = take(); S.Q[q].bt = take(); }
-        S.hit = take();
-        S.Lacc = take();
-        S.shadow = ShadowArena{base, N};  // light l: sa, sb, sw = the next three arrays (ShadowArena::queue)
-        base += (size_t)N * 3 * nl;
-        S.redo.idx = (uint32_t*)base;  // N indices behind the queues
-        S.redo.count = d_redo + 2 * k;
-        S.d_counts = (uint32_t*)(sb + rows_bytes + counts_bytes * (size_t)k);
+        SlotLayout::carve(S, (f4*)((char*)h->arena.p + plan.slot_bytes * (size_t)k), plan.N, nl);
+        S.redo.count = (uint32_t*)(sb + o_redo) + 2 * k;
+        S.d_counts = (uint32_t*)(sb + o_counts + counts_bytes * (size_t)k);
         S.host_counts = h->pinned_counts + (size_t)k * (2 * count_rows + 16);
         S.seq = h->slot_seq[k];
         S.spill = (uint32_t*)h->spill.p + (size_t)k * h->spill_words_per_slot;
     }
-
-    HIPC(hipMemsetAsync(d_stats, 0, stats_bytes, stream));  // statistics and redo counters
-    if (job) {
-        if (job_host) {
-            HIPC(hipMemcpyAsync(d_rows, job->pixels, (size_t)npix * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync(d_acc, job->sum, acc_bytes, hipMemcpyHostToDevice, stream));
-            if (d_sq) HIPC(hipMemcpyAsync(d_sq, job->sumsq, acc_bytes, hipMemcpyHostToDevice, stream));
-        }
-        // every entry must name a pixel of the image: one look at the list on the device before any path is traced
-        hipLaunchKernelGGL(k_list_max, dim3(std::min<uint32_t>((npix + 255) / 256, 1024u)), dim3(256), 0, stream, d_list, npix, d_list_max);
-        uint32_t list_max = 0;
-        HIPC(hipMemcpyAsync(&list_max, d_list_max, sizeof(list_max), hipMemcpyDeviceToHost, stream));
-        HIPC(hipStreamSynchronize(stream));
-        if ((uint64_t)list_max >= (uint64_t)p->width * (uint64_t)p->height) return fail(TRT_EINVAL, "pixel list holds an entry >= width * height");
-    } else {
-        HIPC(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-        if (accum_host) HIPC(hipMemcpyAsync(d_acc, accum_host, acc_bytes, hipMemcpyHostToDevice, stream));
-        else HIPC(hipMemsetAsync(d_acc, 0, acc_bytes, stream));
-    }
-
-    TileDesc td;
-    td.rows = job ? (const int32_t*)d_list : d_rows;
-    td.tile_w = job ? p->width : (int32_t)tw;
-    td.x0 = job ? 0 : p->x0;
-    td.width = p->width;
-    td.height = p->height;
-    td.npix = npix;
-    td.seed = p->seed;
-    td.spp = (uint32_t)p->spp;
-    td.fixed_nee = (p->flags & TRT_FLAG_FIXED_NEE) ? 1u : 0u;
-    td.fixed_pixels = (p->flags & TRT_FLAG_FIXED_PIXELS) ? 1u : 0u;
-    td.ray_offset = (p->flags & TRT_FLAG_RAY_OFFSET) ? 1u : 0u;
-    td.specular_ks = (p->flags & TRT_FLAG_SPECULAR_KS) ? 1u : 0u;
-    td.npix_magic = magicOf(npix);
-    td.tile_w_magic = magicOf((uint32_t)td.tile_w);
-    td.grid_ok = (p->width >= 2 && p->height >= 2 && p->width <= 65536 && p->height <= 65536) ? 1u : 0u;
-    td.grid_rcp[0] = 1.0 / double(p->width - 1.0);
-    td.grid_rcp[1] = 1.0 / double(p->height - 1.0);
-    td.grid_rcp[2] = 1.0 / double(p->width);
-    td.grid_rcp[3] = 1.0 / double(p->height);
     // k_shade's three flavours (trt_kernels.h): 512-thread blocks at 6 waves per SIMD for one light, 256-thread blocks at 5 for
     // several; more than TRT_MAX_LIGHTS lights find their queues in the arena instead of in the kernel arguments
     const int lights = nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY);
     const uint32_t shade_block = lights == SHADE_ONE ? (uint32_t)TRT_SHADE1_BLOCK : (uint32_t)TRT_SHADEN_BLOCK;
-    const uint32_t rows_lds = (!job && rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)rows.size() : 0u;
+    const uint32_t rows_lds = (in.rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)in.rows.size() : 0u;  // 0 for a list
+    // the kernels of this call: bounce 0 traces the camera rays of the tile or of the list, later bounces the queue
+    const bool count = (p->flags & TRT_FLAG_COUNT) != 0;
+    const int camera = in.list ? PRIMARY_LIST : 1;
+    const ClosestKernel camera_k = closestKernel(h, count, camera), queue_k = closestKernel(h, count, 0);
+    const FixKernel camera_fix = fixKernel(h, false, camera), queue_fix = fixKernel(h, false, 0), shadow_fix = fixKernel(h, true, 0);
+    const ShadowKernel shadow_k = shadowKernel(h, count);
+    const ShadeKernel shade_k = shadeKernel(h->shade_tabs, lights, in.list);
+    const TailKernel tail_k = tailKernel(count, in.list);
+    const ShadeArgs shade_args = shadeArgsOf(h, p, in, d_table, rows_lds, d_stats);
+    const TileDesc& td = shade_args.td;
     if (h->dbg)
-        std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", job ? "trt_render_pixels" : "trt_render",
+        std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.list ? "trt_render_pixels" : "trt_render",
                      lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds, td.grid_ok);
 
-    Timer tm;
-    tm.h = h;
-    tm.on = (p->flags & TRT_FLAG_TIMING) != 0;
+    Timer tm{h, (p->flags & TRT_FLAG_TIMING) != 0};
     trt_stats st;
     std::memset(&st, 0, sizeof(st));
     // events 0/1 bracket the render on the caller's stream, 2 chains the ordered resolves
     hipEvent_t ev_begin = tm.get(0), ev_end = tm.get(1), ev_resolved = tm.get(2);
     if (!ev_begin || !ev_end || !ev_resolved) return fail(TRT_EHIP, "hipEventCreate failed");
     HIPC(hipEventRecord(ev_begin, stream));
-    // From here on work is in flight on the slot streams.  Whatever way this function is left, nothing may still be
-    // running on them when it returns: a late kernel of a failed call would write the arena, Lacc and the pinned
-    // counters of the NEXT call on this handle.  The guard drains them (and keeps the sequence numbers monotonic).
-    struct Drain {
-        trt_handle* h;
-        PassSlot* slots;
-        int n;
-        hipStream_t caller;
-        bool armed = true;
-        ~Drain()
-        {
-            for (int k = 0; k < n; ++k) h->slot_seq[k] = slots[k].seq;
-            if (!armed) return;
-            for (int k = 0; k < n; ++k) (void)hipStreamSynchronize(slots[k].stream);
-            (void)hipStreamSynchronize(caller);
-            (void)hipGetLastError();
-        }
-    } drain{h, slots, slots_used, stream};
-    for (int k = 0; k < slots_used; ++k) HIPC(hipStreamWaitEvent(slots[k].stream, ev_begin, 0));
+    Drain drain{h, slots, plan.slots, stream};
+    for (int k = 0; k < plan.slots; ++k) HIPC(hipStreamWaitEvent(slots[k].stream, ev_begin, 0));
 
     uint32_t next_chunk = 0, resolved_upto = 0;
     auto startPass = [&](PassSlot& S) -> int {
-        if (next_chunk >= n_chunks) { S.state = PassSlot::IDLE; return TRT_OK; }
+        if (next_chunk >= plan.n_chunks) { S.state = PassSlot::IDLE; return TRT_OK; }
         S.chunk = next_chunk++;
-        S.s0 = s_begin + S.chunk * s_chunk;
-        S.sc_count = std::min(s_chunk, s_end - S.s0);
+        S.s0 = s_begin + S.chunk * plan.chunk;
+        S.sc_count = std::min(plan.chunk, s_end - S.s0);
         S.n_active = npix * S.sc_count;
         S.b = 0;
         S.cur = 0;
@@ -947,26 +1028,11 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     };
     // trace + shade of the slot's current bounce, then the queue lengths on their way to the host
     auto issueFront = [&](PassSlot& S) -> int {
-        RaySource src;
-        src.ra = S.Q[S.cur].ra;
-        src.rb = S.Q[S.cur].rb;
-        src.td = td;
-        src.s0 = S.s0;
-        tm.begin(TRT_K_TRACE_CLOSEST, S.stream);
-        if (S.b == 0 && job) {
-            if (count) launchTraceClosest<true, PRIMARY_LIST>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
-            else launchTraceClosest<false, PRIMARY_LIST>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
-        } else if (S.b == 0) {
-            if (count) launchTraceClosest<true, true>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
-            else launchTraceClosest<false, true>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
-        } else {
-            if (count) launchTraceClosest<true, false>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
-            else launchTraceClosest<false, false>(h, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
-        }
-        tm.end(S.stream);
-        st.launches[TRT_K_TRACE_CLOSEST]++;
-
-        ShadeArgs A;
+        const RaySource src{S.Q[S.cur].ra, S.Q[S.cur].rb, td, S.s0};
+        tm.launch(TRT_K_TRACE_CLOSEST, S.stream, st, [&] {
+            launchTraceClosest(h, S.b == 0 ? camera_k : queue_k, S.b == 0 ? camera_fix : queue_fix, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
+        });
+        ShadeArgs A = shade_args;
         A.qin = S.Q[S.cur];
         A.hit = S.hit;
         A.n = S.n_active;
@@ -976,43 +1042,12 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
             for (uint32_t l = 0; l < (uint32_t)TRT_MAX_LIGHTS; ++l) A.sq[l] = l < nl ? S.shadow.queue(l) : ShadowQueue{nullptr, nullptr, nullptr};
         A.pair_count = pairCounter(S.d_counts, count_rows, S.b);
         A.shadow_counts = S.d_counts + (size_t)COUNT_STRIDE + S.b;  // light l: + l * COUNT_STRIDE
-        A.shadow_count_stride = COUNT_STRIDE;
         A.Lacc = S.Lacc;
-        A.td = td;
         A.s0 = S.s0;
-        A.max_depth = p->max_depth;
         A.primary = S.b == 0 ? 1u : 0u;
-        A.lds_mat_bytes = h->lds_tab[0];
-        A.lds_light_bytes = h->lds_tab[1];
-        A.lds_cum_bytes = h->lds_tab[2];
-        A.lds_ltri_bytes = h->lds_tab[3];
-        A.lds_tshade_bytes = h->lds_tab[4];
-        A.lds_image = (const f4*)h->lds_image;
-        A.lds_image_words = h->lds_image_bytes / 16u;
-        A.rows_lds = rows_lds;
-        A.stats = d_stats;
-        tm.begin(TRT_K_SHADE, S.stream);
-        {
-            const dim3 grid(std::min<uint32_t>((S.n_active + shade_block - 1) / shade_block, 65536u)), blk(shade_block);
-#define TRT_LAUNCH_SHADE(T, LIST) \
-            if (lights == SHADE_ONE) hipLaunchKernelGGL((k_shade<T, SHADE_ONE, LIST>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
-            else if (lights == SHADE_FEW) hipLaunchKernelGGL((k_shade<T, SHADE_FEW, LIST>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A); \
-            else hipLaunchKernelGGL((k_shade<T, SHADE_MANY, LIST>), grid, blk, h->shade_pad_lds, S.stream, h->sc, A);
-#define TRT_LAUNCH_SHADE_TABS(LIST) \
-            switch (h->shade_tabs) { \
-                case 31u: TRT_LAUNCH_SHADE(31u, LIST) break; \
-                case 15u: TRT_LAUNCH_SHADE(15u, LIST) break; \
-                case 7u: TRT_LAUNCH_SHADE(7u, LIST) break; \
-                case 3u: TRT_LAUNCH_SHADE(3u, LIST) break; \
-                default: TRT_LAUNCH_SHADE(0u, LIST) break; \
-            }
-            if (job) { TRT_LAUNCH_SHADE_TABS(true) }
-            else { TRT_LAUNCH_SHADE_TABS(false) }
-#undef TRT_LAUNCH_SHADE_TABS
-#undef TRT_LAUNCH_SHADE
-        }
-        tm.end(S.stream);
-        st.launches[TRT_K_SHADE]++;
+        tm.launch(TRT_K_SHADE, S.stream, st, [&] {
+            hipLaunchKernelGGL(shade_k, dim3(std::min<uint32_t>((S.n_active + shade_block - 1) / shade_block, 65536u)), dim3(shade_block), h->shade_pad_lds, S.stream, h->sc, A);
+        });
         // (b, c) and (b + 1, c) of the counters in use -> host_counts[2 * c], [2 * c + 1], then the sequence word
         S.seq++;
         const uint32_t publish_block = std::min(1024u, (2u * (1u + nl) + 63u) & ~63u);
@@ -1027,28 +1062,14 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     };
     // queue lengths are back: shadow rays of this bounce, then the next bounce / the tail / the end of the pass
     auto completeBounce = [&](PassSlot& S) -> int {
-        {   // spin on the sequence word the device writes after the counters; the stream is the fallback (and the error path)
-            volatile uint32_t* flag = (volatile uint32_t*)S.host_counts + 2 * count_rows;
-            const auto t0 = std::chrono::steady_clock::now();
-            uint32_t spins = 0;
-            while (*flag != S.seq) {
-                if ((++spins & 0x3FFu) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(20)) {
-                    HIPC(hipStreamSynchronize(S.stream));  // long kernels: let the runtime wait; also surfaces a device error
-                    if (*flag != S.seq) return fail(TRT_EHIP, "queue lengths did not arrive");
-                    break;
-                }
-            }
-            std::atomic_thread_fence(std::memory_order_acquire);
-        }
+        if (int e = awaitCounts(S, count_rows)) return e;
         for (uint32_t l = 0; l < nl; ++l) {
             const uint32_t ns = S.host_counts[2 * (1 + l)];
             if (ns > S.n_active) return fail(TRT_EHIP, "internal error: shadow queue longer than its input");
             if (!ns) continue;
-            tm.begin(TRT_K_TRACE_SHADOW, S.stream);
-            if (count) launchTraceShadow<true>(h, S.stream, S.spill, S.shadow.queue(l), ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee, S.redo, h->light_boxes[l]);
-            else launchTraceShadow<false>(h, S.stream, S.spill, S.shadow.queue(l), ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee, S.redo, h->light_boxes[l]);
-            tm.end(S.stream);
-            st.launches[TRT_K_TRACE_SHADOW]++;
+            tm.launch(TRT_K_TRACE_SHADOW, S.stream, st, [&] {
+                launchTraceShadow(h, shadow_k, shadow_fix, S.stream, S.spill, S.shadow.queue(l), ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee, S.redo, h->light_boxes[l]);
+            });
             st.rays_shadow += ns;
         }
         const uint32_t n_next = S.host_counts[1];
@@ -1059,28 +1080,8 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         S.b++;
         if (S.n_active > 0 && (S.n_active <= h->tail_n || S.b >= MAX_BOUNCES)) {
             // few paths left: finish them in one launch (k_tail) instead of ~3 launches + a host round trip per bounce
-            TailArgs TA;
-            TA.q = S.Q[S.cur];
-            TA.n = S.n_active;
-            TA.Lacc = S.Lacc;
-            TA.td = td;
-            TA.s0 = S.s0;
-            TA.max_depth = p->max_depth;
-            TA.spill = S.spill;
-            TA.spill_stride = SPILL_STRIDE;
-            TA.uniform = h->trace_impl == 0 ? 1u : 0u;
-            TA.stats = d_stats;
-            tm.begin(TRT_K_TAIL, S.stream);
-            const dim3 tg(tailGrid(S.n_active)), tb(TRT_TRACE_BLOCK);
-            if (job) {
-                if (count) hipLaunchKernelGGL((k_tail<true, 0, true>), tg, tb, 0, S.stream, h->sc, TA);
-                else hipLaunchKernelGGL((k_tail<false, 0, true>), tg, tb, 0, S.stream, h->sc, TA);
-            } else {
-                if (count) hipLaunchKernelGGL((k_tail<true, 0>), tg, tb, 0, S.stream, h->sc, TA);
-                else hipLaunchKernelGGL((k_tail<false, 0>), tg, tb, 0, S.stream, h->sc, TA);
-            }
-            tm.end(S.stream);
-            st.launches[TRT_K_TAIL]++;
+            const TailArgs TA{S.Q[S.cur], S.n_active, S.Lacc, td, S.s0, p->max_depth, S.spill, SPILL_STRIDE, h->trace_impl == 0 ? 1u : 0u, d_stats};
+            tm.launch(TRT_K_TAIL, S.stream, st, [&] { hipLaunchKernelGGL(tail_k, dim3(tailGrid(S.n_active)), dim3(TRT_TRACE_BLOCK), 0, S.stream, h->sc, TA); });
             S.n_active = 0;
         }
         S.state = S.n_active ? PassSlot::ISSUE : PassSlot::RESOLVE;
@@ -1090,24 +1091,23 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     auto tryResolve = [&](PassSlot& S) -> int {
         if (S.chunk != resolved_upto) return TRT_OK;  // an earlier pass is still in flight on the other slot
         if (resolved_upto > 0) HIPC(hipStreamWaitEvent(S.stream, ev_resolved, 0));  // recorded by the previous resolve, earlier in host order
-        tm.begin(TRT_K_RESOLVE, S.stream);
-        const dim3 rg(std::min<uint32_t>((npix + 255) / 256, 65536u)), rb(256);
-        if (d_sq) hipLaunchKernelGGL(k_resolve_moments, rg, rb, 0, S.stream, S.Lacc, d_acc, d_sq, npix, S.sc_count, (float)p->spp);
-        else hipLaunchKernelGGL(k_resolve, rg, rb, 0, S.stream, S.Lacc, d_acc, npix, S.sc_count, (float)p->spp);
-        tm.end(S.stream);
-        st.launches[TRT_K_RESOLVE]++;
+        tm.launch(TRT_K_RESOLVE, S.stream, st, [&] {
+            const dim3 rg(std::min<uint32_t>((npix + 255) / 256, 65536u)), rb(256);
+            if (d_sq) hipLaunchKernelGGL(k_resolve_moments, rg, rb, 0, S.stream, S.Lacc, d_sum, d_sq, npix, S.sc_count, (float)p->spp);
+            else hipLaunchKernelGGL(k_resolve, rg, rb, 0, S.stream, S.Lacc, d_sum, npix, S.sc_count, (float)p->spp);
+        });
         HIPC(hipEventRecord(ev_resolved, S.stream));
         resolved_upto++;
         return startPass(S);
     };
 
-    for (int k = 0; k < slots_used; ++k)
+    for (int k = 0; k < plan.slots; ++k)
         if (int e = startPass(slots[k])) return e;
     for (;;) {
         bool any = false;
-        for (int k = 0; k < slots_used; ++k)
+        for (int k = 0; k < plan.slots; ++k)
             if (slots[k].state == PassSlot::ISSUE) { if (int e = issueFront(slots[k])) return e; }
-        for (int k = 0; k < slots_used; ++k) {
+        for (int k = 0; k < plan.slots; ++k) {
             PassSlot& S = slots[k];
             if (S.state == PassSlot::WAIT) { if (int e = completeBounce(S)) return e; }
             if (S.state == PassSlot::RESOLVE) { if (int e = tryResolve(S)) return e; }
@@ -1115,21 +1115,20 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         }
         if (!any) break;
     }
-    if (resolved_upto != n_chunks) return fail(TRT_EHIP, "internal error: passes left unresolved");
+    if (resolved_upto != plan.n_chunks) return fail(TRT_EHIP, "internal error: passes left unresolved");
 
     HIPC(hipStreamWaitEvent(stream, ev_resolved, 0));
-    if (!job) {
+    if (in.out_dev) {
         tm.begin(TRT_K_RESOLVE, stream);
-        hipLaunchKernelGGL(k_finalize, dim3(std::min<uint32_t>((npix * 3 + 255) / 256, 65536u)), dim3(256), 0, stream, d_acc, out_dev, npix * 3);
+        hipLaunchKernelGGL(k_finalize, dim3(std::min<uint32_t>((npix * 3 + 255) / 256, 65536u)), dim3(256), 0, stream, d_sum, in.out_dev, npix * 3);
         tm.end(stream);
     }
     HIPC(hipEventRecord(ev_end, stream));
     DeviceStats ds;
     HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
-    if (accum_host) HIPC(hipMemcpyAsync(accum_host, d_acc, acc_bytes, hipMemcpyDeviceToHost, stream));
-    if (job_host) {
-        HIPC(hipMemcpyAsync(job->sum, d_acc, acc_bytes, hipMemcpyDeviceToHost, stream));
-        if (d_sq) HIPC(hipMemcpyAsync(job->sumsq, d_sq, acc_bytes, hipMemcpyDeviceToHost, stream));
+    if (in.host && in.sum) {
+        HIPC(hipMemcpyAsync(in.sum, d_sum, acc_bytes, hipMemcpyDeviceToHost, stream));
+        if (d_sq) HIPC(hipMemcpyAsync(in.sumsq, d_sq, acc_bytes, hipMemcpyDeviceToHost, stream));
     }
     HIPC(hipStreamSynchronize(stream));
     HIPC(hipGetLastError());
@@ -1142,19 +1141,37 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         float k_ms = 0.f;
         if (hipEventElapsedTime(&k_ms, h->events[sp.e0], h->events[sp.e1]) == hipSuccess) st.kernel_ms[sp.k] += k_ms;
     }
-    st.shaded_hits = ds.shaded_hits;
-    st.wave_steps[0] = ds.wave_inner_steps;
-    st.wave_steps[1] = ds.wave_leaf_steps;
-    st.rays_shadow += ds.tail_rays_shadow;
-    st.rays_indirect += ds.tail_rays_indirect;
-    for (int i = 0; i < 2; ++i) { st.inner_visits[i] = ds.inner_visits[i]; st.tri_tests[i] = ds.tri_tests[i]; }
-    st.max_bounces = ds.max_depth_hit;
-    st.redo_rays = ds.redo_rays;
-    st.lane_census[0] = ds.census_inner; st.lane_census[1] = ds.census_leaf; st.lane_census[2] = ds.census_done; st.lane_census[3] = ds.census_iters;
-    st.passes = n_chunks;
-    st.rows_rendered = rows.size();  // 0 for a pixel list
-    st.inner_node_bytes = h->trace_impl == 0 ? (uint32_t)sizeof(trt_bvh_node) : (h->node_kind == 1 ? 80u : (uint32_t)sizeof(WideNode));
+    addDeviceStats(st, ds, h);
+    st.passes = plan.n_chunks;
+    st.rows_rendered = in.rows.size();  // 0 for a pixel list
     if (stats_out) *stats_out = st;
+    return TRT_OK;
+}
+
+// A tile of p (checked): samples [s_begin, s_end), onto accum_host's sums when given, rounded into out_dev; without out_dev into the
+// handle's out_buf (rows x width) and from there to out_host (trt_render, trt_render_samples)
+int renderTile(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_end, float* out_dev, float* out_host, void* hip_stream, trt_stats* stats,
+               double* accum_host)
+{
+    HIPC(hipSetDevice(h->device));
+    RenderInput in;
+    for (int y = p->y0; y < p->y1; ++y)
+        if (rowSelected(p, y)) in.rows.push_back(y);
+    if (in.rows.empty()) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
+    in.tile_w = p->x1 - p->x0;
+    in.x0 = p->x0;
+    const size_t out_bytes = in.rows.size() * (size_t)in.tile_w * 3 * sizeof(float);
+    if (!out_dev) {
+        if (int e = h->out_buf.ensure(out_bytes)) return e;
+        out_dev = (float*)h->out_buf.p;
+    }
+    const uint64_t npix64 = (uint64_t)in.rows.size() * (uint32_t)in.tile_w;
+    if (npix64 > 0x7FFFFFFFull) return fail(TRT_EINVAL, "tile too large");
+    in.npix = (uint32_t)npix64;
+    in.sum = accum_host;
+    in.out_dev = out_dev;
+    if (int e = renderCore(h, p, s_begin, s_end, in, (hipStream_t)hip_stream, stats)) return e;
+    if (out_host) HIPC(hipMemcpy(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost));
     return TRT_OK;
 }
 }  // namespace
@@ -1162,7 +1179,8 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
 int trt_render_device(trt_handle* h, const trt_params* p, float* out_dev, void* hip_stream, trt_stats* stats_out)
 {
     if (int e = checkParams(h, p)) return e;
-    return renderCore(h, p, 0u, (uint32_t)p->spp, out_dev, hip_stream, stats_out, nullptr);
+    if (!out_dev) return fail(TRT_EINVAL, "null output buffer");
+    return renderTile(h, p, 0u, (uint32_t)p->spp, out_dev, nullptr, hip_stream, stats_out, nullptr);
 }
 
 int trt_render_samples(trt_handle* h, const trt_params* p, int32_t sample_begin, int32_t sample_end, double* accum_host, float* out_host, trt_stats* stats)
@@ -1170,14 +1188,7 @@ int trt_render_samples(trt_handle* h, const trt_params* p, int32_t sample_begin,
     if (int e = checkParams(h, p)) return e;
     if (!accum_host) return fail(TRT_EINVAL, "null accumulator");
     if (sample_begin < 0 || sample_end <= sample_begin || sample_end > p->spp) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin < end <= spp");
-    HIPC(hipSetDevice(h->device));
-    const int nrows = trt_rows_selected(p);
-    if (nrows < 1) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
-    const size_t bytes = (size_t)nrows * (size_t)(p->x1 - p->x0) * 3 * sizeof(float);
-    if (int e = h->out_buf.ensure(bytes)) return e;
-    if (int e = renderCore(h, p, (uint32_t)sample_begin, (uint32_t)sample_end, (float*)h->out_buf.p, nullptr, stats, accum_host)) return e;
-    if (out_host) HIPC(hipMemcpy(out_host, h->out_buf.p, bytes, hipMemcpyDeviceToHost));
-    return TRT_OK;
+    return renderTile(h, p, (uint32_t)sample_begin, (uint32_t)sample_end, nullptr, out_host, nullptr, stats, accum_host);
 }
 
 namespace {
@@ -1196,8 +1207,16 @@ int renderPixels(trt_handle* h, const trt_params* p_in, uint32_t n_pixels, const
     if (n_pixels > MAX_PASS_PATHS) return fail(TRT_EINVAL, "pixel list longer than the path ids of one pass can number (0x7FFF0000)");
     if (stats) std::memset(stats, 0, sizeof(*stats));
     if (n_pixels == 0 || sample_begin == sample_end) return TRT_OK;
-    const PixelJob job{n_pixels, pixels, sum, sumsq, host};
-    return renderCore(h, &p, (uint32_t)sample_begin, (uint32_t)sample_end, nullptr, hip_stream, stats, nullptr, &job);
+    HIPC(hipSetDevice(h->device));
+    RenderInput in;
+    in.list = true;
+    in.host = host;
+    in.pixels = pixels;
+    in.npix = n_pixels;
+    in.tile_w = p.width;
+    in.sum = sum;
+    in.sumsq = sumsq;
+    return renderCore(h, &p, (uint32_t)sample_begin, (uint32_t)sample_end, in, (hipStream_t)hip_stream, stats);
 }
 }  // namespace
 
@@ -1217,14 +1236,7 @@ int trt_render(trt_handle* h, const trt_params* p, float* out_host, trt_stats* s
 {
     if (int e = checkParams(h, p)) return e;
     if (!out_host) return fail(TRT_EINVAL, "null output buffer");
-    HIPC(hipSetDevice(h->device));
-    const int nrows = trt_rows_selected(p);
-    if (nrows < 1) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
-    const size_t bytes = (size_t)nrows * (size_t)(p->x1 - p->x0) * 3 * sizeof(float);
-    if (int e = h->out_buf.ensure(bytes)) return e;
-    if (int e = trt_render_device(h, p, (float*)h->out_buf.p, nullptr, stats)) return e;
-    HIPC(hipMemcpy(out_host, h->out_buf.p, bytes, hipMemcpyDeviceToHost));
-    return TRT_OK;
+    return renderTile(h, p, 0u, (uint32_t)p->spp, nullptr, out_host, nullptr, stats, nullptr);
 }
 
 int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* dir, float* t, int32_t* tri, float* uv, trt_stats* stats_out)
@@ -1236,38 +1248,31 @@ int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* 
     const uint32_t n32 = (uint32_t)n;
     const size_t in_bytes = (size_t)n * 3 * sizeof(float);
     const size_t q16 = (size_t)n * sizeof(f4);
-    if (int e = h->io_buf.ensure(2 * in_bytes + 3 * q16 + 256 + 256 + (size_t)n * sizeof(uint32_t))) return e;  // + statistics, counters, redo list
+    // io_buf: the packed rays, the hits, the caller's rays, then the block cleared first (DeviceStats, the redo counters) and the redo list
+    Layout L;
+    const size_t o_ra = L.add(q16, 16), o_rb = L.add(q16, 16), o_hit = L.add(q16, 16), o_org = L.add(in_bytes, 16), o_dir = L.add(in_bytes, 4);
+    const size_t o_stats = L.add(sizeof(DeviceStats), 256), o_redo = L.add(2 * sizeof(uint32_t), 64), o_idx = L.add((size_t)n * sizeof(uint32_t), 256);
+    if (int e = h->io_buf.ensure(L.bytes)) return e;
     char* b = (char*)h->io_buf.p;
-    f4* ra = (f4*)b;
-    f4* rb = ra + n;
-    f4* hit = rb + n;
-    float* d_org = (float*)(hit + n);
-    float* d_dir = d_org + (size_t)n * 3;
-    DeviceStats* d_stats = (DeviceStats*)(d_dir + (size_t)n * 3);
-    d_stats = (DeviceStats*)(((uintptr_t)d_stats + 15) & ~(uintptr_t)15);
-    RedoList redo;  // rays for k_trace_fix (trt_kernels.h): the counter sits behind the statistics, the list behind it
-    redo.count = (uint32_t*)((char*)d_stats + 128);
-    redo.idx = (uint32_t*)((char*)d_stats + 256);
+    f4* ra = (f4*)(b + o_ra);
+    f4* rb = (f4*)(b + o_rb);
+    f4* hit = (f4*)(b + o_hit);
+    float* d_org = (float*)(b + o_org);
+    float* d_dir = (float*)(b + o_dir);
+    DeviceStats* d_stats = (DeviceStats*)(b + o_stats);
+    const RedoList redo{(uint32_t*)(b + o_redo), (uint32_t*)(b + o_idx)};  // rays for k_trace_fix (trt_kernels.h)
     HIPC(hipMemcpy(d_org, org, in_bytes, hipMemcpyHostToDevice));
     HIPC(hipMemcpy(d_dir, dir, in_bytes, hipMemcpyHostToDevice));
-    HIPC(hipMemset(d_stats, 0, 256));
+    HIPC(hipMemset(d_stats, 0, o_idx - o_stats));
     hipLaunchKernelGGL(k_pack_rays, dim3(std::min<uint32_t>((n32 + 255) / 256, 65536u)), dim3(256), 0, nullptr, d_org, d_dir, ra, rb, n32);
-    struct Events {  // destroyed on every path out of this function
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events()
-        {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } ev;
-    HIPC(hipEventCreate(&ev.e0));
-    HIPC(hipEventCreate(&ev.e1));
-    hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    Timer tm{h, false};  // for the handle's events 0 and 1, which bracket the traversal
+    hipEvent_t e0 = tm.get(0), e1 = tm.get(1);
+    if (!e0 || !e1) return fail(TRT_EHIP, "hipEventCreate failed");
     HIPC(hipEventRecord(e0, nullptr));
     RaySource src{};
     src.ra = ra;
     src.rb = rb;
-    launchTraceClosest<true, false>(h, nullptr, (uint32_t*)h->spill.p, src, hit, n32, d_stats, redo);
+    launchTraceClosest(h, closestKernel(h, true, 0), fixKernel(h, false, 0), nullptr, (uint32_t*)h->spill.p, src, hit, n32, d_stats, redo);
     HIPC(hipEventRecord(e1, nullptr));
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
@@ -1284,15 +1289,9 @@ int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* 
         DeviceStats ds;
         HIPC(hipMemcpy(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost));
         std::memset(stats_out, 0, sizeof(*stats_out));
-        stats_out->inner_visits[0] = ds.inner_visits[0];
-        stats_out->tri_tests[0] = ds.tri_tests[0];
-        stats_out->wave_steps[0] = ds.wave_inner_steps;
-        stats_out->wave_steps[1] = ds.wave_leaf_steps;
+        addDeviceStats(*stats_out, ds, h);  // what the closest-hit and fix kernels do not count stays zero: d_stats was cleared
         stats_out->kernel_ms[TRT_K_TRACE_CLOSEST] = ms;
         stats_out->launches[TRT_K_TRACE_CLOSEST] = 1;
-        stats_out->inner_node_bytes = h->trace_impl == 0 ? (uint32_t)sizeof(trt_bvh_node) : (h->node_kind == 1 ? 80u : (uint32_t)sizeof(WideNode));
-        stats_out->redo_rays = ds.redo_rays;
-        stats_out->lane_census[0] = ds.census_inner; stats_out->lane_census[1] = ds.census_leaf; stats_out->lane_census[2] = ds.census_done; stats_out->lane_census[3] = ds.census_iters;
     }
     return TRT_OK;
 }
