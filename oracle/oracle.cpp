@@ -618,7 +618,7 @@ int oracle_render(const trt_scene* scene, const trt_params* p, float* out_rgb, o
     for (int y = p->y0; y < p->y1; ++y)
         if (rowSelected(p, y)) rows.push_back(y);
     const int tw = p->x1 - p->x0;
-    if (threads <= 0) threads = omp_get_num_procs();
+    if (threads <= 0) threads = omp_get_max_threads();
     Counters total;
     const auto t_begin = std::chrono::steady_clock::now();
 #pragma omp parallel num_threads(threads)

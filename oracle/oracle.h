@@ -40,7 +40,7 @@ typedef struct oracle_stats {
 #define ORACLE_MODE_EXPERIMENT_NO_NEE_ON_GLASS 0x1000   /* no next-event estimation at vertices on Ni > 1 surfaces (pathTracing.cpp:34-74 samples the lights there too) */
 
 /* main.cpp:80-113 restated.  Same trt_params semantics as trt_render (tile,
- * row interleave, packed float output).  threads <= 0 -> all cores. */
+ * row interleave, packed float output).  threads <= 0 -> omp_get_max_threads(): OMP_NUM_THREADS when set, else all cores. */
 int oracle_render(const trt_scene* scene, const trt_params* p, float* out_rgb, oracle_stats* stats,
                   int threads, int mode);
 

@@ -431,7 +431,7 @@ int oracle_render_literal(const trt_scene* scene, const trt_params* p, float* ou
     for (int y = p->y0; y < p->y1; ++y)
         if (rowSelected(p, y)) rows.push_back(y);
     const int tw = p->x1 - p->x0;
-    if (threads <= 0) threads = omp_get_num_procs();
+    if (threads <= 0) threads = omp_get_max_threads();
     Counters total;
     const auto t_begin = std::chrono::steady_clock::now();
 #pragma omp parallel num_threads(threads)
@@ -516,7 +516,7 @@ int oracle_render_literal_experiment(const trt_scene* scene, const trt_params* p
     std::vector<double> image((size_t)W * H * 3, 0.0);  // main.cpp:74-75
     Engines eng(p->seed, p->seed + 1u, experiment == ORACLE_EXP_SHARED_ENGINES ? p->seed + 1u : p->seed + 2u,
                 experiment == ORACLE_EXP_SHARED_ENGINES ? p->seed + 1u : p->seed + 3u);
-    if (threads <= 0) threads = omp_get_num_procs();
+    if (threads <= 0) threads = omp_get_max_threads();
     if (!racy) threads = 1;
     double* const base = image.data();
 #pragma omp parallel for num_threads(threads) schedule(static, 1)

@@ -5,6 +5,9 @@ are analytic: each checks one restated function against a value derived by hand 
 """
 import ctypes as C
 import math
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -13,7 +16,7 @@ import oracle_lib as O
 import raygen
 import scene_util as SU
 import tinyraytracing_amd as T
-from conftest import get_scene
+from conftest import ROOT, get_scene
 
 TRI = [0, 0, 0, 1, 0, 0, 0, 1, 0]  # v0, v1, v2 in the plane z = 0
 
@@ -410,3 +413,18 @@ def test_row_interleave_and_tiles_compose():
     assert np.array_equal(full, parts)
     tile, _ = O.render(s.flat, T.make_params(40, 30, 3, 9, tile=(5, 7, 22, 19)))
     assert np.array_equal(tile, full[7:19, 5:22])
+
+
+def test_default_thread_count_honours_omp_num_threads():
+    """threads <= 0 means OMP_NUM_THREADS when it is set (omp_get_max_threads), not every processor of the machine: a job given a
+    share of a large host must not oversubscribe it.  A child process, because the OpenMP runtime reads the variable once."""
+    machine = {os.cpu_count(), len(os.sched_getaffinity(0))}
+    n = next(k for k in (3, 2, 5) if k not in machine)
+    code = ("import oracle_lib as O, tinyraytracing_amd as T\n"
+            "s = T.Scene.named('back', 16, 16)\n"
+            "p = T.make_params(16, 16, 1, 7, tile=(4, 4, 6, 6))\n"
+            "print(O.render(s.flat, p, threads=0)[1].threads, O.render_literal(s.flat, p, threads=0)[1].threads)\n")
+    env = dict(os.environ, OMP_NUM_THREADS=str(n), PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]))
+    out = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.split() == [str(n), str(n)], (out.stdout, n)
