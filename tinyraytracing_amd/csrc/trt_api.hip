@@ -101,6 +101,9 @@ struct trt_handle {
     uint32_t lds_image_bytes = 0;
     uint32_t lds_tab[5] = {0, 0, 0, 0, 0};  // bytes of materials / lights / light CDF / light triangles / (tiny scenes) shading triangles that k_shade stages in LDS
     int trace_impl = 3;       // wave driver of the traversal kernels (0 wave-uniform walk of a tiny tree, 3 persistent waves + step scheduler)
+    // The wave-uniform walk's faster kernels (trt_kernels.h traceQueueUniform PIPE / HIT8); TRT_SLIM_WALK=0 at trt_create keeps the earlier ones (A/B, tests):
+    bool slim_walk = false;   // both walk kernels read the triangles' flag words from an LDS copy
+    bool hit8 = false;        // and the render's hit records are 8 bytes (t, bits(tri)); k_shade forms (u, v) itself — needs k_shade<31> (every table in LDS)
     int node_kind = 0;        // what the persistent traversal kernels walk: 0 exact 128-B 4-wide nodes, 1 compressed 80-B 8-wide nodes (trt_oct.h)
     uint32_t oct_levels = 0;  // nodes on the longest root path of the oct tree
     bool dbg = false;         // TRT_DEBUG at trt_create: every render prints which k_shade variant it runs
@@ -338,9 +341,15 @@ using TailKernel = void (*)(SceneDev, TailArgs);
 // in the spill area.  One instantiation serves every tree.  traversalOf: the row of the tables below.
 constexpr uint32_t OCT_LDS_LEVELS = 10;
 int traversalOf(const trt_handle* h) { return h->trace_impl == 0 ? 0 : (h->node_kind == 1 ? 1 : (h->depth <= 16 ? 2 : 3)); }
-// primary: 0 the queue, 1 the camera rays of a tile, PRIMARY_LIST those of a pixel list
+// primary: 0 the queue, 1 the camera rays of a tile, PRIMARY_LIST those of a pixel list.  With h->hit8 the kernel stores 8-byte hit records.
 ClosestKernel closestKernel(const trt_handle* h, bool count, int primary)
 {
+    if (h->trace_impl == 0 && h->hit8) {
+        const ClosestKernel s[2][3] = {
+            {k_trace_closest<false, 1, false, 0, 0, 0, true, true>, k_trace_closest<false, 1, false, 0, 1, 0, true, true>, k_trace_closest<false, 1, false, 0, PRIMARY_LIST, 0, true, true>},
+            {k_trace_closest<true, 1, false, 0, 0, 0, true, true>, k_trace_closest<true, 1, false, 0, 1, 0, true, true>, k_trace_closest<true, 1, false, 0, PRIMARY_LIST, 0, true, true>}};
+        return s[count][primary];
+    }
     const ClosestKernel k[4][2][3] = {
         {{k_trace_closest<false, 1, false, 0, 0, 0>, k_trace_closest<false, 1, false, 0, 1, 0>, k_trace_closest<false, 1, false, 0, PRIMARY_LIST, 0>},
          {k_trace_closest<true, 1, false, 0, 0, 0>, k_trace_closest<true, 1, false, 0, 1, 0>, k_trace_closest<true, 1, false, 0, PRIMARY_LIST, 0>}},
@@ -354,6 +363,7 @@ ClosestKernel closestKernel(const trt_handle* h, bool count, int primary)
 }
 ShadowKernel shadowKernel(const trt_handle* h, bool count)
 {
+    if (h->trace_impl == 0 && h->slim_walk) return count ? k_trace_shadow<true, 1, false, 0, 0, true> : k_trace_shadow<false, 1, false, 0, 0, true>;
     const ShadowKernel k[4][2] = {{k_trace_shadow<false, 1, false, 0, 0>, k_trace_shadow<true, 1, false, 0, 0>},
                                   {k_trace_shadow<false, OCT_LDS_LEVELS, true, 3, 1>, k_trace_shadow<true, OCT_LDS_LEVELS, true, 3, 1>},
                                   {k_trace_shadow<false, 16, false, 3, 0>, k_trace_shadow<true, 16, false, 3, 0>},
@@ -367,8 +377,16 @@ FixKernel fixKernel(const trt_handle* h, bool shadow, int primary)
     const FixKernel k[4] = {k_trace_fix<false, 0, 0>, k_trace_fix<false, 1, 0>, k_trace_fix<false, PRIMARY_LIST, 0>, k_trace_fix<true, false, 0>};
     return h->trace_impl == 0 ? nullptr : k[shadow ? 3 : primary];
 }
-ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list)
+ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list, bool hit8)
 {
+    if (hit8) {  // trt_create sets hit8 only with tabs == 31
+        const ShadeKernel s[2][3] = {
+            {k_shade<31u, SHADE_ONE, false, TRT_SHADE1_BLOCK, TRT_SHADE1_WAVES, true>, k_shade<31u, SHADE_FEW, false, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>,
+             k_shade<31u, SHADE_MANY, false, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>},
+            {k_shade<31u, SHADE_ONE, true, TRT_SHADE1_BLOCK, TRT_SHADE1_WAVES, true>, k_shade<31u, SHADE_FEW, true, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>,
+             k_shade<31u, SHADE_MANY, true, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>}};
+        return s[list][lights];
+    }
     const ShadeKernel k[5][2][3] = {
         {{k_shade<31u, SHADE_ONE>, k_shade<31u, SHADE_FEW>, k_shade<31u, SHADE_MANY>}, {k_shade<31u, SHADE_ONE, true>, k_shade<31u, SHADE_FEW, true>, k_shade<31u, SHADE_MANY, true>}},
         {{k_shade<15u, SHADE_ONE>, k_shade<15u, SHADE_FEW>, k_shade<15u, SHADE_MANY>}, {k_shade<15u, SHADE_ONE, true>, k_shade<15u, SHADE_FEW, true>, k_shade<15u, SHADE_MANY, true>}},
@@ -670,6 +688,10 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
             h->lds_image_bytes = (uint32_t)total;
         }
     }
+    h->slim_walk = h->trace_impl == 0 && s->n_tris <= 64;  // (trace_impl 0 implies <= 64 triangles: the LDS copies of trt_kernels.h hold 64)
+    if (const char* e = std::getenv("TRT_SLIM_WALK")) h->slim_walk = h->slim_walk && std::atoi(e) != 0;
+    h->hit8 = h->slim_walk && h->shade_tabs == 31u;
+    if (im.dbg) std::fprintf(stderr, "trt_create: slim walk %d, 8-byte hit records %d\n", (int)h->slim_walk, (int)h->hit8);
 
     // traversal spill area: levels beyond the LDS stack, for the largest grid
     // (k_trace_fix / k_tail walk the caller's BVH2 itself for the rays of raySpecial(), trt_path.h: one entry per level of it)
@@ -691,7 +713,9 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
         for (uint32_t tabs : {31u, 15u, 7u, 3u, 0u})
             for (bool list : {false, true})
                 for (int lights : {SHADE_ONE, SHADE_FEW, SHADE_MANY})
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shadeKernel(tabs, lights, list)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
+                    for (bool hit8 : {false, true})
+                        if (!hit8 || tabs == 31u)
+                            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shadeKernel(tabs, lights, list, hit8)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
     }
 
     *out = h.release();
@@ -994,7 +1018,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const ClosestKernel camera_k = closestKernel(h, count, camera), queue_k = closestKernel(h, count, 0);
     const FixKernel camera_fix = fixKernel(h, false, camera), queue_fix = fixKernel(h, false, 0), shadow_fix = fixKernel(h, true, 0);
     const ShadowKernel shadow_k = shadowKernel(h, count);
-    const ShadeKernel shade_k = shadeKernel(h->shade_tabs, lights, in.list);
+    const ShadeKernel shade_k = shadeKernel(h->shade_tabs, lights, in.list, h->hit8);
     const TailKernel tail_k = tailKernel(count, in.list);
     const ShadeArgs shade_args = shadeArgsOf(h, p, in, d_table, rows_lds, d_stats);
     const TileDesc& td = shade_args.td;
@@ -1250,7 +1274,7 @@ int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* 
     const size_t q16 = (size_t)n * sizeof(f4);
     // io_buf: the packed rays, the hits, the caller's rays, then the block cleared first (DeviceStats, the redo counters) and the redo list
     Layout L;
-    const size_t o_ra = L.add(q16, 16), o_rb = L.add(q16, 16), o_hit = L.add(q16, 16), o_org = L.add(in_bytes, 16), o_dir = L.add(in_bytes, 4);
+    const size_t o_ra = L.add(q16, 16), o_rb = L.add(q16, 16), o_hit = L.add(q16, 16), o_hit8 = L.add(h->hit8 ? q16 / 2 : 0, 16), o_org = L.add(in_bytes, 16), o_dir = L.add(in_bytes, 4);
     const size_t o_stats = L.add(sizeof(DeviceStats), 256), o_redo = L.add(2 * sizeof(uint32_t), 64), o_idx = L.add((size_t)n * sizeof(uint32_t), 256);
     if (int e = h->io_buf.ensure(L.bytes)) return e;
     char* b = (char*)h->io_buf.p;
@@ -1272,8 +1296,11 @@ int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* 
     RaySource src{};
     src.ra = ra;
     src.rb = rb;
-    launchTraceClosest(h, closestKernel(h, true, 0), fixKernel(h, false, 0), nullptr, (uint32_t*)h->spill.p, src, hit, n32, d_stats, redo);
+    // a scene with 8-byte hit records traces the batch with the render's kernel, and k_hit_uv widens its records
+    f4* hit8 = (f4*)(b + o_hit8);
+    launchTraceClosest(h, closestKernel(h, true, 0), fixKernel(h, false, 0), nullptr, (uint32_t*)h->spill.p, src, h->hit8 ? hit8 : hit, n32, d_stats, redo);
     HIPC(hipEventRecord(e1, nullptr));
+    if (h->hit8) hipLaunchKernelGGL(k_hit_uv, dim3(std::min<uint32_t>((n32 + 255) / 256, 65536u)), dim3(256), 0, nullptr, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit8, hit, n32);
     HIPC(hipDeviceSynchronize());
     HIPC(hipGetLastError());
     float ms = 0.f;

@@ -5,7 +5,7 @@
 // widest coalesced access, 1 KiB per wave instruction):
 //   ray queue   ra = (o.x, o.y, o.z, d.x)   rb = (d.y, d.z, bits(path id), bits(meta))
 //               bt = (beta.r, beta.g, beta.b, -)
-//   hit buffer  (t, bits(tri), u, v)
+//   hit buffer  (t, bits(tri), u, v); on scenes of the wave-uniform walk 8 B: (t, bits(tri)) at hit + 8 i, and k_shade re-derives (u, v)
 //   shadow queue per light   sa = (o.xyz, d.x)  sb = (d.y, d.z, bits(path id), t_max: search hint / occlusion range)
 //                            sw = (w.r, w.g, w.b, -)   w = beta * unoccluded contribution
 //   accumulator Lacc[path id] = (L.r, L.g, L.b, -)
@@ -228,8 +228,12 @@ __device__ __forceinline__ void stNT(f4* p, f4 v)
     const trt_v4f q = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(q, reinterpret_cast<trt_v4f*>(p));
 }
+typedef float trt_v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ trt_v2f ldNT2(const trt_v2f* p) { return __builtin_nontemporal_load(p); }
 #define TRT_LDQ(bit, ptr) (((TRT_NT) & (bit)) ? ldNT(ptr) : *(ptr))
+#define TRT_LDQ2(bit, ptr) (((TRT_NT) & (bit)) ? ldNT2(ptr) : *(ptr))
 #define TRT_STQ(bit, ptr, val) do { if ((TRT_NT) & (bit)) stNT((ptr), (val)); else *(ptr) = (val); } while (0)
+#define TRT_STQ2(bit, ptr, val) do { if ((TRT_NT) & (bit)) __builtin_nontemporal_store((val), (ptr)); else *(ptr) = (val); } while (0)
 
 constexpr int PRIMARY_LIST = 2;
 template <int PRIMARY>
@@ -258,12 +262,16 @@ struct TraceProbe {  // COUNT builds only: work and SIMD utilisation of the two 
     uint32_t c_in = 0, c_lf = 0, c_done = 0, c_it = 0;  // lane 0: the census of DeviceStats
 };
 
-// result of one ray: hit record (closest) or the NEE accumulation (shadow)
-template <bool SHADOW>
+// result of one ray: hit record (closest) or the NEE accumulation (shadow).  HIT8: the 8-byte record (t, bits(tri)) of the wave-uniform
+// walk; k_shade re-evaluates the winner for (u, v) itself (hitBarycentrics).
+template <bool SHADOW, bool HIT8 = false>
 __device__ __forceinline__ void storeResult(const SceneDev& sc, f3 o, f3 d, float best_t, int32_t best_tri, uint32_t best_flags, uint32_t idx, uint32_t pid,
                                             f4* __restrict__ hit, const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, bool any)
 {
-    if (!SHADOW) {
+    if (!SHADOW && HIT8) {
+        const trt_v2f r = {best_t, u2f((uint32_t)best_tri)};
+        TRT_STQ2(8, reinterpret_cast<trt_v2f*>(hit) + idx, r);
+    } else if (!SHADOW) {
         // barycentric weights of v1, v2 (what findBaryCor feeds bvh.cpp:224): re-evaluated on the winning
         // triangle once per ray instead of carrying three more registers through the traversal
         float u = 0.f, v = 0.f;
@@ -345,9 +353,11 @@ constexpr int TRT_PEND_SLOTS = 4;
 // bound of the search (TRT_INF, or an occlusion range) and goes out with best_tri / best_flags as the closest hit.
 // GLM: this wave holds a ray with a zero direction component (`special` lanes): those lanes take the literal slab test (trt_path.h boxTestGlm: a NaN from 0 * inf
 // counts as the reference counts it); the walk is the reference's own visit set already, so nothing else changes for them.
-template <bool COUNT, int STRIDE, bool GLM>
+// FLAGS_LDS: the candidates' flag words (TriIsect::c.z) come from `tri_flags`, a copy in LDS, instead of a per-lane global load: the walk then issues no
+// vector memory access at all.
+template <bool COUNT, int STRIDE, bool GLM, bool FLAGS_LDS = false>
 __device__ __forceinline__ void uniformWalkImpl(const SceneDev& sc, f3 o, f3 d, f3 inv, bool valid, bool special, f4* __restrict__ my_pend, float& best_t, int32_t& best_tri,
-                                                uint32_t& best_flags, uint32_t& n_inner, uint32_t& n_tri)
+                                                uint32_t& best_flags, uint32_t& n_inner, uint32_t& n_tri, const uint32_t* tri_flags = nullptr)
 {
     const uint32_t n_nodes = sc.n_nodes;
     uint32_t reach = valid ? 1u : 0u;  // bit k: the ray reaches inner node k
@@ -361,7 +371,7 @@ __device__ __forceinline__ void uniformWalkImpl(const SceneDev& sc, f3 o, f3 d, 
                 if (!(t < TRT_T_MIN) && !(t < e.w)) {  // bvh.cpp:189; and not in front of the box of its leaf (leafFloor(), trt_path.h)
                     const uint32_t pk = f2u(e.z);  // triangle index | first triangle of its leaf << 8 | triangles in the leaf << 16 (<= 64 triangles here)
                     const int32_t j = (int32_t)(pk & 0xFFu);
-                    const uint32_t fl = f2u(sc.tri_isect[j].c.z);
+                    const uint32_t fl = FLAGS_LDS ? tri_flags[j] : f2u(sc.tri_isect[j].c.z);
                     bool take = t < best_t;
                     if (t == best_t && best_tri >= 0) {
                         const bool em = (fl & 1u) != 0, bem = (best_flags & 1u) != 0;
@@ -432,7 +442,10 @@ __device__ __forceinline__ void uniformWalk(const SceneDev& sc, f3 o, f3 d, bool
     else uniformWalkImpl<COUNT, STRIDE, false>(sc, o, d, inv, valid, false, my_pend, best_t, best_tri, best_flags, n_inner, n_tri);
 }
 
-template <bool SHADOW, bool COUNT, int PRIMARY>
+// HIT8: closest hits are stored as 8-byte records (storeResult).  PIPE (trt_create: every scene of this walk, unless TRT_SLIM_WALK=0): the flag words
+// of the triangles are staged in LDS (uniformWalkImpl FLAGS_LDS), so the walk issues no vector memory access.  (Also measured: the queue rays of the
+// next batch requested before the walk of this one — +0.2 % on `back`, inside the noise of the A/B: removed, profiles/r05_slim_walk.txt.)
+template <bool SHADOW, bool COUNT, int PRIMARY, bool HIT8 = false, bool PIPE = false>
 __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                                   const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, DeviceStats* stats, bool any_flag,
                                                   f4* __restrict__ pend)
@@ -442,6 +455,11 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
     const uint32_t lb = xcdSwizzle(blockIdx.x, gridDim.x);
     const uint32_t stride = gridDim.x * TRT_TRACE_BLOCK;
     f4* my_pend = pend + threadIdx.x;  // slot s of this lane: my_pend[s * TRT_TRACE_BLOCK]
+    __shared__ uint32_t s_flags[PIPE ? 64 : 1];   // <= 64 triangles on this walk (trt_create)
+    if (PIPE) {
+        if (threadIdx.x < (sc.n_tris < 64u ? sc.n_tris : 64u)) s_flags[threadIdx.x] = f2u(sc.tri_isect[threadIdx.x].c.z);
+        __syncthreads();
+    }
     // Rays with a zero direction component (raySpecial, trt_path.h: the literal slab test may see 0 * inf where the clean one does not) are not stored by the
     // walk below but parked — queue index only, per wave, in LDS — and walked again with the literal test by their own wave when it runs out of rays (up to 128
     // of them; a wave that meets more goes over its share a second time).  About one ray in 10^5 on the Cornell box.  Nothing of this sits inside the walk or
@@ -463,8 +481,8 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
             int32_t best_tri = -1;
             uint32_t best_flags = 0u;
             uint32_t ni = 0, nt = 0;
-            uniformWalkImpl<false, TRT_TRACE_BLOCK, true>(sc, o, d, mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), valid, valid, my_pend, best_t, best_tri, best_flags, ni, nt);
-            if (valid) storeResult<SHADOW>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
+            uniformWalkImpl<false, TRT_TRACE_BLOCK, true, PIPE>(sc, o, d, mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), valid, valid, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
+            if (valid) storeResult<SHADOW, HIT8>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         }
         if (lane == 0 && n_parked) atomicAdd(&stats->redo_rays, n_parked);
         n_parked = 0;
@@ -480,9 +498,9 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
         float best_t = any ? b.w : TRT_INF;
         int32_t best_tri = -1;
         uint32_t best_flags = 0u;
-        uniformWalkImpl<COUNT, TRT_TRACE_BLOCK, false>(sc, o, d, inv, valid, false, my_pend, best_t, best_tri, best_flags, n_inner, n_tri);
+        uniformWalkImpl<COUNT, TRT_TRACE_BLOCK, false, PIPE>(sc, o, d, inv, valid, false, my_pend, best_t, best_tri, best_flags, n_inner, n_tri, s_flags);
         const bool special = valid && raySpecial(inv);
-        if (valid && !special) storeResult<SHADOW>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
+        if (valid && !special) storeResult<SHADOW, HIT8>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         const unsigned long long m_sp = ballotb(special);
         if (m_sp != 0ull) {  // (wave-uniform, rare)
             const uint32_t at = n_parked + (uint32_t)__popcll(m_sp & ((1ull << lane) - 1ull));
@@ -507,8 +525,8 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
             int32_t best_tri = -1;
             uint32_t best_flags = 0u;
             uint32_t ni = 0, nt = 0;
-            uniformWalkImpl<false, TRT_TRACE_BLOCK, true>(sc, o, d, inv, special, special, my_pend, best_t, best_tri, best_flags, ni, nt);
-            if (special) storeResult<SHADOW>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
+            uniformWalkImpl<false, TRT_TRACE_BLOCK, true, PIPE>(sc, o, d, inv, special, special, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
+            if (special) storeResult<SHADOW, HIT8>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         }
         if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
     }
@@ -800,32 +818,33 @@ __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, cons
     }
 }
 
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK>
+template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, bool HIT8 = false, bool PIPE = false>
 __device__ __forceinline__ void traceQueue(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo, const LightBox& lbox)
 {
-    if constexpr (IMPL == 0) traceQueueUniform<SHADOW, COUNT, PRIMARY>(sc, src, n, hit, sw, light_mat, Lacc, stats, any_flag, reinterpret_cast<f4*>(smem));
+    static_assert(IMPL == 0 || !(HIT8 || PIPE), "8-byte hit records and the flags in LDS belong to the wave-uniform walk");
+    if constexpr (IMPL == 0) traceQueueUniform<SHADOW, COUNT, PRIMARY, HIT8, PIPE>(sc, src, n, hit, sw, light_mat, Lacc, stats, any_flag, reinterpret_cast<f4*>(smem));
     else if constexpr (NK == 1) traceQueuePersistentOct<SHADOW, COUNT, DEPTH, SPILL, PRIMARY>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo, lbox);
     else traceQueuePersistent<SHADOW, COUNT, DEPTH, SPILL, IMPL, PRIMARY, NK>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo);
 }
 
 // PRIMARY: bounce 0 — ray i is the camera ray of path i, generated in registers (K1 of SURVEY.md §7 fused
-// into K2: no primary-ray queue is ever written or read).
-template <bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK>
+// into K2: no primary-ray queue is ever written or read).  HIT8, PIPE: traceQueueUniform.
+template <bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, bool HIT8 = false, bool PIPE = false>
 __global__ TRT_TRACE_BOUNDS void k_trace_closest(SceneDev sc, RaySource src, f4* __restrict__ hit, uint32_t n,
                                                  uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, RedoList redo)
 {
     __shared__ __attribute__((aligned(16))) uint32_t smem[IMPL == 0 ? TRT_PEND_SLOTS * 4 * TRT_TRACE_BLOCK : (NK == 1 ? 2 : 1) * DEPTH * TRT_TRACE_BLOCK];  // stack (8-byte entries on the oct tree), or (uniform walk) the candidate queue
     const LightBox nobox = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-    traceQueue<false, COUNT, DEPTH, SPILL, IMPL, PRIMARY, NK>(sc, src, n, hit, nullptr, 0u, nullptr, spill, spill_stride, stats, smem, false, redo, nobox);
+    traceQueue<false, COUNT, DEPTH, SPILL, IMPL, PRIMARY, NK, HIT8, PIPE>(sc, src, n, hit, nullptr, 0u, nullptr, spill, spill_stride, stats, smem, false, redo, nobox);
 }
 
 // Shadow test of shade() (pathTracing.cpp:51-58): CLOSEST hit, visible iff
 // its material is the light's (Q5); then L += w.  One launch per light, in
 // light order; each path has at most one ray per launch, so the read-modify-
 // write of Lacc needs no atomic and the sum order is fixed.
-template <bool COUNT, int DEPTH, bool SPILL, int IMPL, int NK>
+template <bool COUNT, int DEPTH, bool SPILL, int IMPL, int NK, bool PIPE = false>
 __global__ TRT_TRACE_BOUNDS void k_trace_shadow(SceneDev sc, ShadowQueue sq, uint32_t n, uint32_t light_mat, f4* __restrict__ Lacc,
                                                 uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, uint32_t any, RedoList redo, LightBox lbox)
 {
@@ -834,7 +853,7 @@ __global__ TRT_TRACE_BOUNDS void k_trace_shadow(SceneDev sc, ShadowQueue sq, uin
     src.ra = sq.sa;
     src.rb = sq.sb;
     src.s0 = 0;
-    traceQueue<true, COUNT, DEPTH, SPILL, IMPL, false, NK>(sc, src, n, nullptr, sq.sw, light_mat, Lacc, spill, spill_stride, stats, smem, any != 0u, redo, lbox);
+    traceQueue<true, COUNT, DEPTH, SPILL, IMPL, false, NK, false, PIPE>(sc, src, n, nullptr, sq.sw, light_mat, Lacc, spill, spill_stride, stats, smem, any != 0u, redo, lbox);
 }
 
 // The exact form of the traversal for the rays a traversal launch put on its redo list (see RedoList): a few blocks, launched
@@ -1018,6 +1037,20 @@ struct RowsShade {
 // (Round 3's probe `short` — weight and throughput records stored as 8 bytes, wrong images — bought k_shade 3 %: profiles/r03_ab_oct.txt (8).)
 // LIGHTS: SHADE_ONE, SHADE_FEW or SHADE_MANY (where the shadow-queue descriptors come from).  LIST: the paths are those of a pixel list
 // (trt_render_pixels; A.rows_lds is 0 there).  BLOCK threads, WAVES per SIMD asked of the compiler.
+// HIT8: the hit records are the 8-byte ones of the wave-uniform walk (storeResult), and the barycentrics of the winner are formed here, with the code
+// storeResult<false> runs for the 16-byte record: the same triangle test on the same ray, so the same bits.  The <= 64 intersection records of such a scene
+// (48 B each) are staged in LDS beside the tables of TABS, outside that mask.
+__device__ __forceinline__ void hitBarycentrics(const TriIsect* isect, const f4& ra, const f4& rb, f4& hit4)
+{
+    const int32_t tri = (int32_t)f2u(hit4.y);
+    float u = 0.f, v = 0.f;
+    if (tri >= 0) {
+        float t, un, vn, det;
+        if (triTest(isect[tri], mk3(ra.x, ra.y, ra.z), mk3(ra.w, rb.x, rb.y), t, un, vn, det)) { u = un / det; v = vn / det; }
+    }
+    hit4.z = u;
+    hit4.w = v;
+}
 template <int LIGHTS>
 __device__ inline ShadowQueue shadeQueue(const ShadeArgs& A, uint32_t li)
 {
@@ -1025,7 +1058,7 @@ __device__ inline ShadowQueue shadeQueue(const ShadeArgs& A, uint32_t li)
     return A.sq[li];
 }
 template <uint32_t TABS, int LIGHTS, bool LIST = false, int BLOCK = (LIGHTS == SHADE_ONE ? TRT_SHADE1_BLOCK : TRT_SHADEN_BLOCK),
-          int WAVES = (LIGHTS == SHADE_ONE ? TRT_SHADE1_WAVES : TRT_SHADEN_WAVES)>
+          int WAVES = (LIGHTS == SHADE_ONE ? TRT_SHADE1_WAVES : TRT_SHADEN_WAVES), bool HIT8 = false>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A)
 {
     constexpr int TRT_SHADE_BLOCK = BLOCK;
@@ -1035,6 +1068,8 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
     __shared__ uint32_t s_shaded, s_depth;  // s_depth: 1 + the deepest vertex of the block that hit something (0: none)
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[TABS ? TRT_SHADE_LDS_TABLE_BYTES / 4 : 4];
     __shared__ uint16_t s_rows[LIST ? 1 : TRT_SHADE_ROWS_LDS];
+    __shared__ __attribute__((aligned(16))) uint32_t s_isect[HIT8 ? 64 * 12 : 4];  // HIT8: the scene's intersection records (<= 64, trt_create)
+    const TriIsect* isect = reinterpret_cast<const TriIsect*>(s_isect);
     if (threadIdx.x == 0) { s_shaded = 0; s_depth = 0; }
     if (!LIST)
         for (uint32_t r = threadIdx.x; r < A.rows_lds; r += TRT_SHADE_BLOCK) s_rows[r] = (uint16_t)A.td.rows[r];
@@ -1053,7 +1088,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         if (TABS & 8u) sc.light_tris = static_cast<const LightTriDev*>(at(A.lds_ltri_bytes));
         if (TABS & 16u) sc.tri_shade = static_cast<const TriShade*>(at(A.lds_tshade_bytes));
     }
-    bool staged = TABS == 0u;
+    bool staged = TABS == 0u && !HIT8;
     int parity = 0, parity2 = 0;
     uint32_t bounce_depth = 0;  // 1 + the deepest vertex of this thread that hit something (0: none)
     const uint32_t per_grid = gridDim.x * TRT_SHADE_BLOCK;
@@ -1064,7 +1099,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
     auto loadTile = [&](uint32_t i, f4& hit4, f4& ra, f4& rb, f4& bt) {
         hit4 = mk4(TRT_INF, u2f(0xFFFFFFFFu), 0.0f, 0.0f); ra = mk4(0, 0, 0, 0); rb = ra; bt = mk4(1.0f, 1.0f, 1.0f, 0.0f);
         if (i < A.n) {
-            hit4 = TRT_LDQ(1, A.hit + i);
+            if (HIT8) {
+                const trt_v2f h = TRT_LDQ2(1, reinterpret_cast<const trt_v2f*>(A.hit) + i);
+                hit4.x = h.x; hit4.y = h.y;
+            } else {
+                hit4 = TRT_LDQ(1, A.hit + i);
+            }
             if (!A.primary) { ra = TRT_LDQ(1, A.qin.ra + i); rb = TRT_LDQ(1, A.qin.rb + i); bt = TRT_LDQ(1, A.qin.bt + i); }
         }
     };
@@ -1084,7 +1124,13 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
             // the staged tables lie packed, in LDS layout, in one device buffer (trt_create): 16-byte words, coalesced
             if (!staged) {
                 f4* l = reinterpret_cast<f4*>(s_tab);
-                for (uint32_t w = threadIdx.x; w < A.lds_image_words; w += TRT_SHADE_BLOCK) l[w] = A.lds_image[w];
+                if (TABS)
+                    for (uint32_t w = threadIdx.x; w < A.lds_image_words; w += TRT_SHADE_BLOCK) l[w] = A.lds_image[w];
+                if (HIT8) {
+                    f4* li = reinterpret_cast<f4*>(s_isect);
+                    const uint32_t words = 3u * (sc.n_tris < 64u ? sc.n_tris : 64u);
+                    for (uint32_t w = threadIdx.x; w < words; w += TRT_SHADE_BLOCK) li[w] = reinterpret_cast<const f4*>(sc.tri_isect)[w];
+                }
             }
             __syncthreads();
             staged = true;
@@ -1103,9 +1149,11 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
                 // every path passes here exactly once, hit or miss: L starts at 0 (+ the radiance of a directly
                 // visible light, pathTracing.cpp:9-12 through main.cpp:101)
                 primaryRay(sc, A.td, A.s0, i, ra, rb, rows);
+                if (HIT8) hitBarycentrics(isect, ra, rb, hit4);
                 shadeBegin(sc, A.td, A.s0, ra, rb, bt, hit4, c, rows);
                 A.Lacc[i] = c.add_L ? mk4(0.0f + c.addL.x, 0.0f + c.addL.y, 0.0f + c.addL.z, 0.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
             } else {
+                if (HIT8) hitBarycentrics(isect, ra, rb, hit4);
                 shadeBegin(sc, A.td, A.s0, ra, rb, bt, hit4, c, rows);
                 if (c.add_L) {
                     f4 L = A.Lacc[c.pid];
@@ -1387,6 +1435,18 @@ __global__ __launch_bounds__(1024) void k_publish_counts(const uint32_t* __restr
     __syncthreads();
     if (threadIdx.x == 0) {
         __hip_atomic_store(const_cast<uint32_t*>(out) + seq_word, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// ray-batch entry on a scene with 8-byte hit records (trt_handle::hit8): the 16-byte records the caller gets, (u, v) formed as k_shade forms them
+__global__ __launch_bounds__(256) void k_hit_uv(SceneDev sc, const f4* __restrict__ ra, const f4* __restrict__ rb, const f4* __restrict__ hit8, f4* __restrict__ out, uint32_t n)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const trt_v2f h = reinterpret_cast<const trt_v2f*>(hit8)[i];
+        f4 hit4 = mk4(h.x, h.y, 0.0f, 0.0f);
+        hitBarycentrics(sc.tri_isect, ra[i], rb[i], hit4);
+        out[i] = hit4;
     }
 }
 
