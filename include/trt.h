@@ -277,6 +277,31 @@ int trt_render_pixels_device(trt_handle* h, const trt_params* p, uint32_t n_pixe
                              int32_t sample_begin, int32_t sample_end, double* sum_dev, double* sumsq_dev,
                              void* hip_stream, trt_stats* stats);
 
+/* First-hit feature buffers ("AOVs") for denoisers: per-pixel albedo, shading normal and depth, the inputs OIDN / OptiX / SVGF-style
+ * filters take beside a low-spp render.  For every selected pixel (x, y) of the tile (tile and row interleave exactly as trt_render)
+ * and every sample s in [0, p->spp):
+ *   - the camera ray trt_render traces for (pixel y * width + x, sample s): same random stream, same jitter, TRT_FLAG_FIXED_PIXELS honoured;
+ *   - its closest hit (t, tri, u, v) as trt_render's bounce 0 and trt_trace_closest define it;
+ *   - a hit, on any material (emissive ones included): albedo = the texel or Kd that shade() weights by (pathTracing.cpp:15-30, nearest
+ *     texel), normal = the normalised interpolated vertex normal (bvh.cpp:223-224), depth = t;
+ *     a miss: albedo = normal = (0, 0, 0), depth = TRT_INF;
+ *   - per channel v = value / (float)p->spp (a float division, as trt_render's resolve makes it), added as (double)v in increasing s onto a
+ *     per-pixel double sum; the output is (float)sum.
+ * So a call with spp = S gives the mean over the primary hits of samples 0..S-1 of any render with the same seed and flags: the beauty may
+ * be rendered at 1024 spp and the AOVs at 16.  The normal is a mean of unit vectors and is NOT renormalised (it is shorter than 1 where
+ * the samples of a pixel hit differently oriented surfaces, and (0, 0, 0) where they all miss).
+ * Flags other than TRT_FLAG_FIXED_PIXELS, TRT_FLAG_TIMING and TRT_FLAG_COUNT, and max_depth, do not change the result (TRT_FLAG_OVERLAP
+ * is ignored).  Buffers (HOST): albedo and normal rows_selected * (x1-x0) * 3 floats, RGB / XYZ interleaved, rows packed as in
+ * trt_render; depth rows_selected * (x1-x0) floats.  Any of the three may be NULL, not all three (TRT_EINVAL).  Parameters are checked
+ * as for trt_render.  mem_budget counts this call's path state, 20 bytes per path and sample in a pass (TRT_ENOMEM when one sample of
+ * every pixel does not fit).  stats: rays_camera = paths traced; the traversal under TRT_K_TRACE_CLOSEST, the per-pixel accumulation under
+ * TRT_K_RESOLVE; passes, rows_rendered, redo_rays and the TRT_FLAG_COUNT counters as for a render. */
+int trt_render_aov(trt_handle* h, const trt_params* p, float* albedo_host, float* normal_host, float* depth_host, trt_stats* stats);
+/* The same with the three buffers in DEVICE memory of the handle's device, all work on hip_stream (NULL = default stream); returns
+ * after the stream has been synchronised. */
+int trt_render_aov_device(trt_handle* h, const trt_params* p, float* albedo_dev, float* normal_dev, float* depth_dev,
+                          void* hip_stream, trt_stats* stats);
+
 /* traverseBVH (bvh.cpp:146-175) on a batch of n rays given as HOST arrays
  * org[n][3], dir[n][3].  Outputs (host): t[n] (TRT_INF on miss), tri[n]
  * (post-BVH triangle index, -1 on miss), uv[n][2] (barycentrics of v1,v2).

@@ -73,6 +73,9 @@ int trth_tonemap(const float* linear_rgb, int width, int height, uint8_t* out);
 /* tonemap + stored-deflate PNG. */
 int trth_write_png(const char* path, int width, int height, const float* linear_rgb);
 int trth_write_png_bytes(const char* path, int width, int height, const uint8_t* rgb);
+/* Portable float map, what denoisers such as oidnDenoise read: channels 3 ("PF", RGB / XYZ) or 1 ("Pf"), scale -1.0 (little-endian floats),
+ * rows stored bottom to top.  data: height rows, top row first, width * channels floats each (trt_render / trt_render_aov output). */
+int trth_write_pfm(const char* path, int width, int height, int channels, const float* data);
 
 /* Material::readinMap()'s JPEG path (material.cpp:3-11 uses cv::imread): baseline or progressive JPEG -> 8-bit RGB with libjpeg's
  * arithmetic.  Call with rgb = NULL to get the size first. */

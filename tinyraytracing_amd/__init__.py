@@ -365,6 +365,49 @@ class Renderer:
             raise TrtError(f"trt_render_device failed ({rc}): {self._lib.trt_last_error().decode()}")
         return st
 
+    def _aov_shapes(self, params, what):
+        nrows = self._lib.trt_rows_selected(C.byref(params))
+        tw = params.x1 - params.x0
+        if nrows <= 0 or tw <= 0:
+            raise TrtError(f"{what}: empty tile")
+        return {"albedo": (nrows, tw, 3), "normal": (nrows, tw, 3), "depth": (nrows, tw)}
+
+    def render_aov(self, params, want_stats=False):
+        """First-hit feature buffers for denoisers (trt_render_aov): the mean over samples [0, params.spp) of the camera ray's first hit's
+        albedo (texel or Kd), shading normal (not renormalised) and distance; a miss counts as 0, 0 and TRT_INF.
+        -> dict(albedo=float32 [rows, tile_w, 3], normal=float32 [rows, tile_w, 3], depth=float32 [rows, tile_w])[, Stats]."""
+        out = {k: np.empty(shape, np.float32) for k, shape in self._aov_shapes(params, "render_aov").items()}
+        st = Stats()
+        fp = C.POINTER(C.c_float)
+        rc = self._lib.trt_render_aov(self._h, C.byref(params), out["albedo"].ctypes.data_as(fp), out["normal"].ctypes.data_as(fp),
+                                      out["depth"].ctypes.data_as(fp), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_render_aov failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return (out, st) if want_stats else out
+
+    def render_aov_into(self, params, albedo=None, normal=None, depth=None, stream_ptr=0):
+        """trt_render_aov_device: the feature buffers into contiguous float32 torch tensors on this device (albedo / normal >= rows*tile_w*3
+        elements, depth >= rows*tile_w; None = not wanted, at least one given), the work on stream `stream_ptr` (0 = default).  -> Stats."""
+        shapes = self._aov_shapes(params, "render_aov_into")
+        given = {"albedo": albedo, "normal": normal, "depth": depth}
+        if all(t is None for t in given.values()):
+            raise TrtError("render_aov_into: at least one of albedo, normal, depth is needed")
+        ptrs = []
+        for k, t in given.items():
+            if t is None:
+                ptrs.append(None)
+                continue
+            need = int(np.prod(shapes[k]))
+            if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or t.numel() < need
+                    or (t.device.index is not None and t.device.index != self.device)):
+                raise TrtError(f"render_aov_into: {k} must be a contiguous float32 tensor on cuda:{self.device} with {need} elements")
+            ptrs.append(C.c_void_p(t.data_ptr()))
+        st = Stats()
+        rc = self._lib.trt_render_aov_device(self._h, C.byref(params), ptrs[0], ptrs[1], ptrs[2], C.c_void_p(stream_ptr), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_render_aov_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return st
+
     def trace_closest(self, org, direction, want_stats=False):
         """traverseBVH on a ray batch: returns (t, tri, uv[, Stats])."""
         org = np.ascontiguousarray(org, dtype=np.float32).reshape(-1, 3)
@@ -464,4 +507,18 @@ def imshow(image, path):
     img = np.ascontiguousarray(image, dtype=np.float32)
     h, w = img.shape[0], img.shape[1]
     if lib.trth_write_png(os.fsencode(path), w, h, img.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise TrtError(lib.trth_last_error().decode())
+
+
+def write_pfm(path, data):
+    """Writes float32 [h, w, 3] (PF) or [h, w] (Pf) as a portable float map (trth_write_pfm): scale -1.0, little-endian, rows bottom to top."""
+    lib = _abi.load_host()
+    a = np.ascontiguousarray(data, dtype=np.float32)
+    if a.ndim == 2:
+        channels = 1
+    elif a.ndim == 3 and a.shape[2] == 3:
+        channels = 3
+    else:
+        raise TrtError("write_pfm: data must be [h, w] or [h, w, 3]")
+    if lib.trth_write_pfm(os.fsencode(path), a.shape[1], a.shape[0], channels, a.ctypes.data_as(C.POINTER(C.c_float))) != 0:
         raise TrtError(lib.trth_last_error().decode())

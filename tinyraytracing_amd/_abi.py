@@ -83,12 +83,13 @@ class Stats(C.Structure):
 
 
 # the symbols include/trt.h declares (checked by tests/test_abi.py)
-HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_trace_closest",
+HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_aov",
+               "trt_render_aov_device", "trt_trace_closest",
                "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
 HOST_SYMBOLS = ["trth_scene_load", "trth_scene_load_opts", "trth_scene_drop_tris", "trth_scene_add_soup", "trth_scene_add_blob", "trth_scene_add_lamps",
                 "trth_scene_build", "trth_scene_vertices", "trth_scene_adopt_bvh", "trth_scene_flat", "trth_scene_info", "trth_scene_light_area",
-                "trth_scene_material_name", "trth_scene_free", "trth_tonemap", "trth_write_png",
+                "trth_scene_material_name", "trth_scene_free", "trth_tonemap", "trth_write_png", "trth_write_pfm",
                 "trth_write_png_bytes", "trth_decode_jpeg", "trth_decode_png", "trth_abi_sizes", "trth_last_error"]
 
 _hip = None
@@ -144,6 +145,7 @@ def load_host():
     lib.trth_scene_free.restype = None
     lib.trth_tonemap.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_uint8)]
     lib.trth_write_png.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+    lib.trth_write_pfm.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.trth_abi_sizes.argtypes = [C.POINTER(C.c_int64)]
     lib.trth_decode_jpeg.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint8), C.c_uint64]
     lib.trth_decode_png.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint8), C.c_uint64]
@@ -195,6 +197,8 @@ def load_hip():
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
     lib.trt_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.trt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Stats)]
+    lib.trt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_trace_closest.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                       C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(Stats)]
     lib.trt_destroy.argtypes = [C.c_void_p]

@@ -794,14 +794,34 @@ struct SlotLayout {
     }
 };
 
+// A trt_render_aov pass's share of the arena: N hit records of 16 B (the wave-uniform walk writes 8-byte ones into the first half), then the
+// redo list, one index per path.  One pass at a time (TRT_FLAG_OVERLAP does not apply).
+struct AovLayout {
+    static constexpr uint64_t bytes_per_path = sizeof(f4) + sizeof(uint32_t);
+    static size_t bytes(uint64_t N, uint32_t) { return (size_t)(N + (N + 3) / 4) * sizeof(f4); }
+    static void carve(f4* base, uint64_t N, f4*& hit, uint32_t*& redo_idx)
+    {
+        hit = base;
+        redo_idx = (uint32_t*)(base + N);
+    }
+};
+
 // How a render call splits its samples into passes: `slots` passes in flight at once, each of `chunk` samples of every pixel (the last one
 // may hold fewer), N paths and slot_bytes of arena.  Passes are as large as the budget allows: every pass ends in a tail of few, long paths,
 // so fewer and larger passes are faster (back 1080p x 256 spp: 3 passes in 32 GiB 101.4 ms, 1 pass in 93 GB 96.8 ms); >= slots_wanted
 // passes when the samples allow.  planPasses is false when the budget holds less than one sample of every pixel.
+// fp: what a path of the call occupies (SlotLayout for a render, AovLayout for trt_render_aov).
 struct PassPlan { int slots; uint32_t chunk, n_chunks; uint64_t N; size_t slot_bytes; };
-bool planPasses(uint32_t npix, uint32_t n_samples, uint32_t nl, uint64_t budget, int slots_wanted, PassPlan& pl)
+struct Footprint {
+    int max_slots;                             // passes in flight at once
+    uint64_t per_path;                         // bytes of arena per path
+    size_t (*bytes)(uint64_t N, uint32_t nl);  // the arena of a pass of N paths
+};
+Footprint renderFootprint(uint32_t nl) { return Footprint{N_SLOTS, SlotLayout::bytesPerPath(nl), SlotLayout::bytes}; }
+Footprint aovFootprint() { return Footprint{1, AovLayout::bytes_per_path, AovLayout::bytes}; }
+bool planPasses(uint32_t npix, uint32_t n_samples, uint32_t nl, uint64_t budget, int slots_wanted, const Footprint& fp, PassPlan& pl)
 {
-    const uint64_t cap_paths = std::min<uint64_t>(budget / SlotLayout::bytesPerPath(nl), MAX_PASS_PATHS);
+    const uint64_t cap_paths = std::min<uint64_t>(budget / fp.per_path, MAX_PASS_PATHS);
     uint64_t max_paths = cap_paths;
     if (max_paths < npix) return false;
     if (slots_wanted > 1 && max_paths / slots_wanted >= npix) max_paths /= slots_wanted;  // each slot gets its share of the budget
@@ -812,7 +832,7 @@ bool planPasses(uint32_t npix, uint32_t n_samples, uint32_t nl, uint64_t budget,
     pl.chunk = (n_samples + pl.n_chunks - 1) / pl.n_chunks;
     pl.n_chunks = (n_samples + pl.chunk - 1) / pl.chunk;
     pl.N = (uint64_t)npix * pl.chunk;
-    pl.slot_bytes = SlotLayout::bytes(pl.N, nl);
+    pl.slot_bytes = fp.bytes(pl.N, nl);
     return true;
 }
 
@@ -931,7 +951,7 @@ struct Drain {
 
 // The passes of a render call and the arena for them.  Default budget: three quarters of what is free on the device (the scene is already
 // resident); halved while the arena cannot be had.
-int planArena(trt_handle* h, const trt_params* p, uint32_t npix, uint32_t n_samples, bool list, PassPlan& plan)
+int planArena(trt_handle* h, const trt_params* p, uint32_t npix, uint32_t n_samples, bool list, const Footprint& fp, PassPlan& plan)
 {
     const uint32_t nl = h->sc.n_lights;
     uint64_t budget = p->mem_budget;
@@ -941,14 +961,14 @@ int planArena(trt_handle* h, const trt_params* p, uint32_t npix, uint32_t n_samp
         HIPC(hipMemGetInfo(&free_b, &total_b));
         budget = (uint64_t)(free_b + h->arena.bytes) / 4 * 3;
     }
-    const int n_slots = (n_samples >= 2 && (p->flags & TRT_FLAG_OVERLAP) && h->n_slots > 1) ? N_SLOTS : 1;
+    const int n_slots = (fp.max_slots > 1 && n_samples >= 2 && (p->flags & TRT_FLAG_OVERLAP) && h->n_slots > 1) ? N_SLOTS : 1;
     for (;;) {
-        if (!planPasses(npix, n_samples, nl, budget, n_slots, plan))
+        if (!planPasses(npix, n_samples, nl, budget, n_slots, fp, plan))
             return fail(TRT_ENOMEM, list ? "mem_budget too small for one sample of every listed pixel; render shorter lists"
                                          : "mem_budget too small for one sample of every pixel of the tile; render smaller tiles");
         const int e = h->arena.ensure(plan.slot_bytes * (size_t)plan.slots);
         if (e == TRT_OK) return TRT_OK;
-        if (e != TRT_ENOMEM || !own_budget || budget / 2 < SlotLayout::bytesPerPath(nl) * npix) return e;
+        if (e != TRT_ENOMEM || !own_budget || budget / 2 < fp.per_path * npix) return e;
         (void)hipGetLastError();  // the failed hipMalloc
         budget /= 2;
     }
@@ -979,7 +999,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
 {
     const uint32_t n_samples = s_end - s_begin, npix = in.npix, nl = h->sc.n_lights, count_rows = h->count_rows;
     PassPlan plan;
-    if (int e = planArena(h, p, npix, n_samples, in.list, plan)) return e;
+    if (int e = planArena(h, p, npix, n_samples, in.list, renderFootprint(nl), plan)) return e;
     // ---- small_buf: the row table or the staged pixel list, the counters of each slot, the block cleared first (DeviceStats; per slot the
     // length of its redo list and the blocks of k_trace_fix that are through; the list's maximum), the staged sums and sums of squares
     const size_t counts_bytes = (size_t)COUNT_STRIDE * count_rows * sizeof(uint32_t), acc_bytes = (size_t)npix * 3 * sizeof(double);
@@ -1198,6 +1218,117 @@ int renderTile(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     if (out_host) HIPC(hipMemcpy(out_host, out_dev, out_bytes, hipMemcpyDeviceToHost));
     return TRT_OK;
 }
+
+// trt_render_aov / _device: the camera rays of every sample of the tile through the render's bounce-0 traversal (k_trace_closest with
+// PRIMARY = 1, k_trace_fix behind it), then k_aov adds each pass's first hits onto the seven per-pixel sums in small_buf, and k_finalize
+// rounds them into out[0..2] (albedo, normal, depth; device pointers, null = not wanted).  Everything runs on `stream`, one pass at a time.
+int aovCore(trt_handle* h, const trt_params* p, const RenderInput& in, float* const out[3], hipStream_t stream, trt_stats* stats_out)
+{
+    const uint32_t npix = in.npix, spp = (uint32_t)p->spp;
+    PassPlan plan;
+    if (int e = planArena(h, p, npix, spp, false, aovFootprint(), plan)) return e;
+    // small_buf: the row table, the block cleared first (DeviceStats, the redo list's length and the blocks of k_trace_fix that are through),
+    // the sums (albedo, normal: 3 per pixel; depth: 1 per pixel)
+    const size_t table_bytes = in.rows.size() * sizeof(int32_t), sum_bytes = (size_t)npix * 7 * sizeof(double);
+    Layout L;
+    const size_t o_table = L.add(table_bytes, 256), o_stats = L.add(sizeof(DeviceStats), 256), o_redo = L.add(2 * sizeof(uint32_t), 64);
+    const size_t o_sum = L.add(sum_bytes, 256);
+    if (int e = h->small_buf.ensure(L.bytes)) return e;
+    char* sb = (char*)h->small_buf.p;
+    DeviceStats* d_stats = (DeviceStats*)(sb + o_stats);
+    double* d_sum = (double*)(sb + o_sum);
+    HIPC(hipMemsetAsync(d_stats, 0, o_sum - o_stats, stream));
+    HIPC(hipMemsetAsync(d_sum, 0, sum_bytes, stream));
+    HIPC(hipMemcpyAsync(sb + o_table, in.rows.data(), table_bytes, hipMemcpyHostToDevice, stream));
+    f4* hit = nullptr;
+    RedoList redo{(uint32_t*)(sb + o_redo), nullptr};
+    AovLayout::carve((f4*)h->arena.p, plan.N, hit, redo.idx);
+    uint32_t* spill = (uint32_t*)h->spill.p;
+    const bool count = (p->flags & TRT_FLAG_COUNT) != 0;
+    const ClosestKernel camera_k = closestKernel(h, count, 1);
+    const FixKernel camera_fix = fixKernel(h, false, 1);
+    const TileDesc td = shadeArgsOf(h, p, in, sb + o_table, 0u, d_stats).td;
+    const dim3 rg(std::min<uint32_t>((npix + 255) / 256, 65536u)), rb(256);
+
+    Timer tm{h, (p->flags & TRT_FLAG_TIMING) != 0};
+    trt_stats st;
+    std::memset(&st, 0, sizeof(st));
+    hipEvent_t ev_begin = tm.get(0), ev_end = tm.get(1);
+    if (!ev_begin || !ev_end) return fail(TRT_EHIP, "hipEventCreate failed");
+    HIPC(hipEventRecord(ev_begin, stream));
+    Drain drain{h, nullptr, 0, stream};
+    for (uint32_t c = 0; c < plan.n_chunks; ++c) {
+        const uint32_t s0 = c * plan.chunk, sc_count = std::min(plan.chunk, spp - s0), n = npix * sc_count;
+        const RaySource src{nullptr, nullptr, td, s0};
+        tm.launch(TRT_K_TRACE_CLOSEST, stream, st, [&] { launchTraceClosest(h, camera_k, camera_fix, stream, spill, src, hit, n, d_stats, redo); });
+        tm.launch(TRT_K_RESOLVE, stream, st, [&] {
+            if (h->hit8) hipLaunchKernelGGL(k_aov<true>, rg, rb, 0, stream, h->sc, td, s0, (const f4*)hit, d_sum, npix, sc_count, (float)p->spp);
+            else hipLaunchKernelGGL(k_aov<false>, rg, rb, 0, stream, h->sc, td, s0, (const f4*)hit, d_sum, npix, sc_count, (float)p->spp);
+        });
+        st.rays_camera += n;
+    }
+    tm.begin(TRT_K_RESOLVE, stream);
+    const uint32_t per_pixel[3] = {3u, 3u, 1u};
+    const size_t sum_at[3] = {0, (size_t)npix * 3, (size_t)npix * 6};
+    for (int k = 0; k < 3; ++k)
+        if (out[k]) {
+            const uint32_t m = npix * per_pixel[k];
+            hipLaunchKernelGGL(k_finalize, dim3(std::min<uint32_t>((m + 255) / 256, 65536u)), dim3(256), 0, stream, d_sum + sum_at[k], out[k], m);
+        }
+    tm.end(stream);
+    HIPC(hipEventRecord(ev_end, stream));
+    DeviceStats ds;
+    HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+    drain.armed = false;
+
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev_begin, ev_end));
+    st.render_ms = ms;
+    for (const auto& span : tm.spans) {
+        float k_ms = 0.f;
+        if (hipEventElapsedTime(&k_ms, h->events[span.e0], h->events[span.e1]) == hipSuccess) st.kernel_ms[span.k] += k_ms;
+    }
+    addDeviceStats(st, ds, h);
+    st.passes = plan.n_chunks;
+    st.rows_rendered = in.rows.size();
+    if (stats_out) *stats_out = st;
+    return TRT_OK;
+}
+
+// The checks of include/trt.h, then aovCore into the caller's device buffers (`host` false) or into out_buf and from there to the host
+int renderAov(trt_handle* h, const trt_params* p, float* albedo, float* normal, float* depth, bool host, void* hip_stream, trt_stats* stats)
+{
+    if (int e = checkParams(h, p)) return e;
+    if (!albedo && !normal && !depth) return fail(TRT_EINVAL, "trt_render_aov: every output buffer is null");
+    HIPC(hipSetDevice(h->device));
+    RenderInput in;
+    for (int y = p->y0; y < p->y1; ++y)
+        if (rowSelected(p, y)) in.rows.push_back(y);
+    if (in.rows.empty()) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
+    in.tile_w = p->x1 - p->x0;
+    in.x0 = p->x0;
+    const uint64_t npix64 = (uint64_t)in.rows.size() * (uint32_t)in.tile_w;
+    if (npix64 > 0x7FFFFFFFull / 7) return fail(TRT_EINVAL, "tile too large");
+    in.npix = (uint32_t)npix64;
+    float* const user[3] = {albedo, normal, depth};
+    const size_t floats[3] = {(size_t)in.npix * 3, (size_t)in.npix * 3, (size_t)in.npix};
+    float* out[3] = {albedo, normal, depth};
+    if (host) {
+        if (int e = h->out_buf.ensure((floats[0] + floats[1] + floats[2]) * sizeof(float))) return e;
+        float* q = (float*)h->out_buf.p;
+        for (int k = 0; k < 3; ++k) {
+            out[k] = user[k] ? q : nullptr;
+            q += floats[k];
+        }
+    }
+    if (int e = aovCore(h, p, in, out, host ? nullptr : (hipStream_t)hip_stream, stats)) return e;
+    if (host)
+        for (int k = 0; k < 3; ++k)
+            if (user[k]) HIPC(hipMemcpy(user[k], out[k], floats[k] * sizeof(float), hipMemcpyDeviceToHost));
+    return TRT_OK;
+}
 }  // namespace
 
 int trt_render_device(trt_handle* h, const trt_params* p, float* out_dev, void* hip_stream, trt_stats* stats_out)
@@ -1261,6 +1392,16 @@ int trt_render(trt_handle* h, const trt_params* p, float* out_host, trt_stats* s
     if (int e = checkParams(h, p)) return e;
     if (!out_host) return fail(TRT_EINVAL, "null output buffer");
     return renderTile(h, p, 0u, (uint32_t)p->spp, nullptr, out_host, nullptr, stats, nullptr);
+}
+
+int trt_render_aov(trt_handle* h, const trt_params* p, float* albedo_host, float* normal_host, float* depth_host, trt_stats* stats)
+{
+    return renderAov(h, p, albedo_host, normal_host, depth_host, true, nullptr, stats);
+}
+
+int trt_render_aov_device(trt_handle* h, const trt_params* p, float* albedo_dev, float* normal_dev, float* depth_dev, void* hip_stream, trt_stats* stats)
+{
+    return renderAov(h, p, albedo_dev, normal_dev, depth_dev, false, hip_stream, stats);
 }
 
 int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* dir, float* t, int32_t* tri, float* uv, trt_stats* stats_out)

@@ -1402,6 +1402,58 @@ __global__ __launch_bounds__(256) void k_resolve_moments(const f4* __restrict__ 
     }
 }
 
+// First-hit feature buffers for denoisers (trt_render_aov, the counterpart of k_resolve): one thread per pixel of the tile, the pass's
+// samples in order.  Sample s of pixel p is path s * npix + p of the pass, traced by the render's own k_trace_closest<PRIMARY = 1>; on a
+// hit, makeVertex() — the call shade() makes at bounce 0 — gives the texel-or-Kd albedo and the interpolated shading normal, the depth
+// is the hit's t; a miss gives 0, 0 and TRT_INF.  Every value is divided by spp as a float and added as a double onto the pixel's
+// seven sums, which stay in registers for the pass: sum[3p + c] albedo, sum[3 (npix + p) + c] normal, sum[6 npix + p] depth.
+// HIT8: the 8-byte records (t, bits(tri)) of the wave-uniform walk; (u, v) is formed on the camera ray as k_shade forms it.
+template <bool HIT8>
+__global__ __launch_bounds__(256) void k_aov(SceneDev sc, TileDesc td, uint32_t s0, const f4* __restrict__ hit, double* __restrict__ sum, uint32_t npix,
+                                             uint32_t s_count, float spp)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += stride) {
+        double a[3], n[3], z;
+        for (int k = 0; k < 3; ++k) { a[k] = sum[(size_t)p * 3 + k]; n[k] = sum[((size_t)npix + p) * 3 + k]; }
+        z = sum[(size_t)npix * 6 + p];
+        for (uint32_t s = 0; s < s_count; ++s) {
+            const uint32_t i = s * npix + p;  // < npix * s_count <= 0x7FFF0000 (MAX_PASS_PATHS)
+            f4 hit4;
+            if constexpr (HIT8) {
+                const trt_v2f r = reinterpret_cast<const trt_v2f*>(hit)[i];
+                hit4 = mk4(r.x, r.y, 0.0f, 0.0f);
+            } else {
+                hit4 = hit[i];
+            }
+            Hit h;
+            h.t = hit4.x; h.tri = (int32_t)f2u(hit4.y); h.u = hit4.z; h.v = hit4.w; h.flags = 0;
+            f3 alb = mk3(0.0f, 0.0f, 0.0f), nrm = alb;
+            float t = TRT_INF;
+            if (h.tri >= 0) {
+                f3 o = alb, d = alb;  // makeVertex needs the ray only for the hit point, which is not used here
+                if constexpr (HIT8) {
+                    f4 ra, rb;
+                    primaryRay(sc, td, s0, i, ra, rb);
+                    hitBarycentrics(sc.tri_isect, ra, rb, hit4);
+                    h.u = hit4.z; h.v = hit4.w;
+                    o = mk3(ra.x, ra.y, ra.z); d = mk3(ra.w, rb.x, rb.y);
+                }
+                const TriShade ts = sc.tri_shade[h.tri];
+                const Vertex vx = makeVertex(sc, h, o, d, ts, sc.materials[ts.mat]);
+                alb = vx.Kd;
+                nrm = vx.pn;
+                t = h.t;
+            }
+            a[0] += (double)(alb.x / spp); a[1] += (double)(alb.y / spp); a[2] += (double)(alb.z / spp);
+            n[0] += (double)(nrm.x / spp); n[1] += (double)(nrm.y / spp); n[2] += (double)(nrm.z / spp);
+            z += (double)(t / spp);
+        }
+        for (int k = 0; k < 3; ++k) { sum[(size_t)p * 3 + k] = a[k]; sum[((size_t)npix + p) * 3 + k] = n[k]; }
+        sum[(size_t)npix * 6 + p] = z;
+    }
+}
+
 // The largest entry of a pixel list (trt_render_pixels refuses lists that leave the image): one atomicMax per wave into *out (zeroed first)
 __global__ __launch_bounds__(256) void k_list_max(const uint32_t* __restrict__ list, uint32_t n, uint32_t* __restrict__ out)
 {

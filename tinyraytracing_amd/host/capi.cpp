@@ -239,6 +239,12 @@ int trth_write_png(const char* path, int width, int height, const float* linear_
     return trt::writePNG(path, width, height, tmp.data()) ? 0 : fail("trth_write_png: I/O error");
 }
 
+int trth_write_pfm(const char* path, int width, int height, int channels, const float* data)
+{
+    if (!path || !data || width <= 0 || height <= 0 || (channels != 1 && channels != 3)) return fail("trth_write_pfm: bad argument");
+    return trt::writePFM(path, width, height, channels, data) ? 0 : fail("trth_write_pfm: I/O error");
+}
+
 int trth_write_png_bytes(const char* path, int width, int height, const uint8_t* rgb)
 {
     if (!path || !rgb || width <= 0 || height <= 0) return fail("trth_write_png_bytes: bad argument");

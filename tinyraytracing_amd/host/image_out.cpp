@@ -2,6 +2,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 
 namespace trt {
 namespace {
@@ -111,6 +112,26 @@ bool writePNG(const std::string& path, int w, int h, const uint8_t* rgb)
     const bool ok = std::ferror(fp) == 0;
     std::fclose(fp);
     return ok;
+}
+
+bool writePFM(const std::string& path, int w, int h, int channels, const float* data)
+{
+    if (w <= 0 || h <= 0 || (channels != 1 && channels != 3) || !data) return false;
+    FILE* f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    bool ok = std::fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", w, h) > 0;
+    const size_t row = (size_t)w * channels;
+    std::vector<uint8_t> bytes(row * 4);
+    for (int y = h - 1; ok && y >= 0; --y) {
+        const float* src = data + (size_t)y * row;
+        for (size_t i = 0; i < row; ++i) {
+            uint32_t b;
+            std::memcpy(&b, src + i, 4);
+            for (int k = 0; k < 4; ++k) bytes[i * 4 + k] = (uint8_t)(b >> (8 * k));  // little-endian whatever the host
+        }
+        ok = std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    }
+    return std::fclose(f) == 0 && ok;
 }
 
 bool imshow(const double* src, const std::string& basedir, const std::string& index, int w, int h)

@@ -15,6 +15,11 @@ void tonemap(const float* linear_rgb, int width, int height, std::vector<uint8_t
 // Writes an 8-bit RGB PNG with stored (uncompressed) deflate blocks.  Returns false on I/O error.
 bool writePNG(const std::string& path, int width, int height, const uint8_t* rgb);
 
+// Portable float map (PFM): "PF" (3 channels) or "Pf" (1 channel), scale -1.0 (little-endian), rows written bottom to top as the format
+// stores them; `data` holds `height` rows top to bottom, `channels` floats per pixel (what trt_render / trt_render_aov return).
+// Returns false on a bad argument or an I/O error.
+bool writePFM(const std::string& path, int width, int height, int channels, const float* data);
+
 // imshow(SRC, index, w, h) of the reference: writes <basedir>/image<index>.png.
 bool imshow(const double* src, const std::string& basedir, const std::string& index, int img_width, int img_height);
 

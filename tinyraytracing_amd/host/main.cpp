@@ -3,6 +3,7 @@
 // The reference prompts on stdin for basedir / mtl / xml / obj / SPP
 // (main.cpp:46-55); the same five values are taken from argv here, plus
 // optional overrides.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -19,9 +20,11 @@ static void usage()
     std::fprintf(stderr,
                  "usage: tinyrt <basedir> <mtl> <xml> <obj> <spp> [--width W --height H] [--seed S] [--device D | --gpus N | --devices a,b,..]\n"
                  "              [--leaf N] [--gpu-bvh] [--max-depth D] [--out file.png] [--fixed | --fixed-nee | --fixed-pixels] [--ray-offset] [--specular-ks] [--polygons]\n"
-                 "              [--every N] [--checkpoint file.acc] [--stop-after M]\n"
+                 "              [--every N] [--checkpoint file.acc] [--stop-after M] [--aov PREFIX [--aov-spp N]]\n"
                  "                                                    progressive: N samples per step, image rewritten after\n"
-                 "                                                    every step, accumulator kept in file.acc (resumes from it)\n");
+                 "                                                    every step, accumulator kept in file.acc (resumes from it)\n"
+                 "                                                    --aov: denoiser inputs PREFIX_{color,albedo,normal,depth}.pfm, the\n"
+                 "                                                    feature buffers averaged over N samples (default min(spp, 16))\n");
 }
 
 int main(int argc, char** argv)
@@ -33,7 +36,8 @@ int main(int argc, char** argv)
     opts.timing = true;
     int width = 0, height = 0;
     bool polygons = false;  // fan-triangulate faces of more than three vertices (the reference keeps their first three only)
-    std::string out_path;
+    std::string out_path, aov_prefix;
+    int aov_spp = 0;
     for (int i = 6; i < argc; ++i) {
         auto need = [&](const char* flag) -> const char* {
             if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", flag); std::exit(2); }
@@ -72,7 +76,16 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--every")) opts.every = std::atoi(need("--every"));
         else if (!std::strcmp(argv[i], "--checkpoint")) opts.checkpoint = need("--checkpoint");
         else if (!std::strcmp(argv[i], "--stop-after")) opts.stop_after = std::atoi(need("--stop-after"));
+        else if (!std::strcmp(argv[i], "--aov")) aov_prefix = need("--aov");
+        else if (!std::strcmp(argv[i], "--aov-spp")) aov_spp = std::atoi(need("--aov-spp"));
         else { usage(); return 2; }
+    }
+    if (!aov_prefix.empty()) {
+        opts.aov_spp = aov_spp > 0 ? aov_spp : std::min(opts.spp, 16);
+        if (opts.aov_spp < 1) { std::fprintf(stderr, "--aov needs spp >= 1\n"); return 2; }
+    } else if (aov_spp > 0) {
+        std::fprintf(stderr, "--aov-spp needs --aov PREFIX\n");
+        return 2;
     }
     try {
         const auto t0 = std::chrono::steady_clock::now();
@@ -99,7 +112,8 @@ int main(int argc, char** argv)
                 std::fprintf(stderr, "\r%d / %d samples", done, opts.spp);
             };
         }
-        trt::render(scene, opts, image.data(), &st);
+        trt::AovImages aov;
+        trt::render(scene, opts, image.data(), &st, aov_prefix.empty() ? nullptr : &aov);
         const uint64_t rays = st.rays_camera + st.rays_shadow + st.rays_indirect;
         std::printf("rays: %llu (camera %llu, shadow %llu, indirect %llu)  render %.3f ms  %.1f Mrays/s\n", (unsigned long long)rays,
                     (unsigned long long)st.rays_camera, (unsigned long long)st.rays_shadow, (unsigned long long)st.rays_indirect, st.render_ms,
@@ -112,6 +126,15 @@ int main(int argc, char** argv)
             ok = trt::writePNG(out_path, scene.img_width, scene.img_height, bytes.data());
         }
         if (!ok) { std::fprintf(stderr, "cannot write the PNG\n"); return 1; }
+        if (!aov_prefix.empty()) {
+            // the inputs of a denoiser (oidnDenoise --hdr PREFIX_color.pfm --alb PREFIX_albedo.pfm --nrm PREFIX_normal.pfm): the linear beauty and the feature buffers
+            const int w = scene.img_width, hgt = scene.img_height;
+            const std::vector<float> color(image.begin(), image.end());
+            const struct { const char* name; int channels; const float* data; } files[4] = {
+                {"_color.pfm", 3, color.data()}, {"_albedo.pfm", 3, aov.albedo.data()}, {"_normal.pfm", 3, aov.normal.data()}, {"_depth.pfm", 1, aov.depth.data()}};
+            for (const auto& f : files)
+                if (!trt::writePFM(aov_prefix + f.name, w, hgt, f.channels, f.data)) { std::fprintf(stderr, "cannot write %s%s\n", aov_prefix.c_str(), f.name); return 1; }
+        }
         std::fprintf(stderr, "\nDone.\n");
         std::printf("%f\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
     } catch (const std::exception& e) {

@@ -77,8 +77,9 @@ void writeCheckpoint(const std::string& path, const Checkpoint& head, const std:
     if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + path);
 }
 
-void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stats)
+void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stats, AovImages* aov)
 {
+    const bool want_aov = aov && opts.aov_spp > 0;
     FlatBVH bvh;
     std::vector<uint32_t> gpu_order;
     if (opts.gpu_builder) {
@@ -142,6 +143,7 @@ void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stat
     if (opts.devices.size() > 1) {
         // several GPUs: one host thread and one replica of the scene per device, one gather (trt_group_render)
         if (progressive) throw std::runtime_error("progressive / check-pointed renders run on one device");
+        if (want_aov) throw std::runtime_error("feature buffers (--aov) are rendered on one device");
         trt_group* g = nullptr;
         if (trt_group_create(flat.c_scene(), (int)opts.devices.size(), opts.devices.data(), &g) != TRT_OK) throw std::runtime_error(std::string("trt_group_create: ") + trt_last_error());
         p.row_block = opts.row_block > 0 ? opts.row_block : 8;
@@ -206,8 +208,21 @@ void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stat
         if (rc == TRT_OK && done < p.spp)
             std::fprintf(stderr, "warning: stopped after %d of %d samples: the image holds the sum of %d samples divided by %d (resume from the checkpoint to finish it)\n", done, p.spp, done, p.spp);
     }
+    if (rc == TRT_OK && want_aov) {
+        // the primary hits of samples [0, aov_spp) of the render above: same seed and flags
+        trt_params pa = p;
+        pa.spp = opts.aov_spp;
+        const size_t n = (size_t)p.width * p.height;
+        aov->albedo.resize(n * 3);
+        aov->normal.resize(n * 3);
+        aov->depth.resize(n);
+        rc = trt_render_aov(h, &pa, aov->albedo.data(), aov->normal.data(), aov->depth.data(), nullptr);
+        if (rc) msg = std::string("trt_render_aov: ") + trt_last_error();
+    } else if (rc != TRT_OK) {
+        msg = "trt_render: " + msg;
+    }
     trt_destroy(h);
-    if (rc != TRT_OK) throw std::runtime_error("trt_render: " + msg);
+    if (rc != TRT_OK) throw std::runtime_error(msg);
     for (size_t i = 0; i < out.size(); ++i) image[i] += (double)out[i];
 }
 

@@ -37,6 +37,12 @@ struct RenderOpts {
     int stop_after = 0;       // > 0: return once this many samples are done (a time-boxed run; resume from the checkpoint later)
     std::string checkpoint;
     std::function<void(int samples_done, const float* rgb)> on_progress;
+    int aov_spp = 0;          // > 0: after the render, the first-hit albedo / normal / depth of samples [0, aov_spp) (trt_render_aov) into render()'s `aov`
+};
+
+// First-hit feature buffers of the whole image for a denoiser (trt_render_aov): albedo and normal width*height*3, depth width*height floats.
+struct AovImages {
+    std::vector<float> albedo, normal, depth;
 };
 
 // Accumulator file of a progressive render: header + width*height*3 doubles (the sums of trt_render_samples).
@@ -53,6 +59,7 @@ void writeCheckpoint(const std::string& path, const Checkpoint& head, const std:
 // image: img_width*img_height*3 doubles, zero-initialised by the caller like
 // main.cpp:74-75; the averaged linear radiance is ADDED to it (main.cpp:103-108).
 // Throws std::runtime_error with the library's message on failure.
-void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stats = nullptr);
+// With opts.aov_spp > 0 and `aov` given, the same handle then renders the feature buffers into it (one device only).
+void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stats = nullptr, AovImages* aov = nullptr);
 
 }  // namespace trt
