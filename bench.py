@@ -6,14 +6,17 @@ example-scenes-cg22 at 1920x1080, 256 spp — the configuration BASELINE.json's 
 With N > 1 the image rows are dealt to the ranks in interleaved 8-row stripes and gathered on rank 0
 with a single RCCL gather inside the timed region (total work fixed: strong scaling).
 
-Prints ONE JSON line on rank 0 (DESIGN.md §5 explains every field):
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints its line; everything else it can measure
+runs only with --full.  Prints ONE JSON line on rank 0 (DESIGN.md §5 explains every field):
   value / ms_per_step     wall clock of the K timed steps (barrier + synchronize on both sides, max over ranks)
+With --full, also:
   roofline                dominant kernel of the headline: algorithmic bytes (SURVEY.md §8d canonical sizes x counts
                           from an untimed counting render) / that kernel's hipEvent time in one profiling step after the timed
                           region; `traffic` = its HBM-side bytes per launch from two rocprofv3 --pmc child passes of the same
                           command (FETCH_SIZE, WRITE_SIZE; run before this process touches the GPU — live_traffic()), null with
                           the reason in `traffic_note` when the profiler cannot run; `traffic_from_profiles` = the committed
-                          counter files of profiles/ beside it
+                          counter files of profiles/ beside it; kernels_rank0 = every kernel's time from the same profiling step
+  with_pass_overlap       (N = 1) the same steps once more with two sample passes in flight
   extra_workloads         (N = 1) the other rows of BASELINE.md §3 — veach-mis, staircase at 1080p/256 spp, the 1 M-triangle
                           soup of config 3 and config 5's 10 M-triangle scene at 3840x2160 / 64 spp per pass — timed the same
                           way with fewer steps, each with its own roofline
@@ -59,6 +62,8 @@ def parse():
     ap.add_argument("--builder", default="auto", choices=["auto", "sweep", "binned", "lbvh"], help="BVH builder: the host SAH builders, or the GPU LBVH builder of include/trt_build.h")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=None)
     ap.add_argument("--mem-gb", type=float, default=0.0, help="HBM budget for path state (0 = library default)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: the live counter passes, the profiling step "
+                    "(roofline, kernels_rank0), with_pass_overlap, extra_workloads and the CPU baseline; the --no-* options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip extra_workloads (veach-mis, staircase, soup after the headline)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target duration of the CPU baseline sample")
@@ -70,14 +75,16 @@ def parse():
     ap.add_argument("--group", type=int, default=0, metavar="N", help="(N=1 process) time the C boundary of the multi-GPU path instead: trt_group_render_device over a "
                     "group of N entries, all naming device 0 on a one-GPU box (its overhead against trt_render_device is then on record)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic live "
-                    "(they run by default for the contract's own command: N = 1, the headline workload, extras on; about 30 s)")
-    ap.add_argument("--traffic", action="store_true", help="run those passes for any other N = 1 command too")
+                    "(with --full they run by default for the contract's own command: N = 1, the headline workload, extras on; about 30 s)")
+    ap.add_argument("--traffic", action="store_true", help="with --full: run those passes for any other N = 1 command too")
     ap.add_argument("--save-png", default=None)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step of the headline workload returned as DIR/<name>.npy "
                     "(image.npy, ray_counts.npy; images over 64 MB as a fixed seeded sample of pixels), to compare two builds output for output")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.traffic and not a.full:
+        ap.error("--traffic needs --full")
     return a
 
 
@@ -144,7 +151,7 @@ def live_traffic(a):
     import pmc_summary as P
     tmp = tempfile.mkdtemp(prefix="trt_pmc_", dir="/tmp")
     child = [sys.executable, os.path.abspath(__file__), "--scene", a.scene, "--width", str(a.width), "--height", str(a.height), "--spp", str(a.spp),
-             "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-overlap-extra", "--no-traffic", "--builder", a.builder]
+             "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra", "--no-overlap-extra", "--no-traffic", "--builder", a.builder]
     if a.tris:
         child += ["--tris", str(a.tris)]
     if a.leaf:
@@ -198,8 +205,71 @@ class Bench:
             self.dist.barrier()
             self.torch.cuda.synchronize()
 
-    def measure(self, scene_name, width, height, spp, steps, warmup, seed, leaf=None, tris=None, base_flags=0, also_overlap=False, save_png=None, builder=None, dump_dir=None):
-        """Counting render (untimed), warm-up, then `steps` timed renders of one workload.  Returns the result fields."""
+    def roofline(self, scene_name, width, height, spp, steps, by, st_prof):
+        """--full: the roofline of the dominant kernel and every kernel's time from the profiling step `st_prof`, whose per-kernel sums are
+        scaled to `steps` so that every per-step figure keeps its meaning; `by` = algorithmic bytes per step.  -> (roofline, kernels_rank0)"""
+        T, world = self.T, self.world
+        kernel_ms = [st_prof.kernel_ms[k] * steps for k in range(8)]
+        launches = [st_prof.launches[k] * steps for k in range(8)]
+        # roofline of the dominant kernel of THIS rank: algorithmic bytes (counting pass, same seed -> same
+        # counts every step) / its summed launch time in the timed region (hipEvents on the launch stream)
+        names = T.KERNEL_NAMES
+        dom = max(range(len(names)), key=lambda k: kernel_ms[k])
+        dom_name = names[dom]
+        dom_bytes_step = by.get(dom_name, 0)
+        dom_ms = kernel_ms[dom]
+        achieved = dom_bytes_step * steps / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        roofline = {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": None,  # filled below from the live PMC passes (live_traffic) when they ran; null with the reason otherwise
+                    "launches_per_step": launches[dom] // max(steps, 1),
+                    "avg_launch_ms": round(dom_ms / max(launches[dom], 1), 5),
+                    "algorithmic_bytes_per_launch": int(dom_bytes_step * steps / max(launches[dom], 1)),
+                    "frac_of_measured_copy_peak": round(achieved / 6290.0, 4)}
+        lt = getattr(self, "live", None)
+        if lt and (scene_name, width, height, spp) == lt["key"]:
+            roofline["traffic_note"] = lt["note"]
+            if dom_name in lt["bytes"] and launches[dom] and dom_ms > 0:
+                tb = lt["bytes"][dom_name]
+                roofline["traffic"] = tb  # HBM-side bytes per launch of the dominant kernel, measured by the PMC passes of this very invocation
+                roofline["traffic_GBps"] = round(tb / (dom_ms / launches[dom] * 1e-3) / 1e9, 1)
+                roofline["traffic_frac_of_peak"] = round(roofline["traffic_GBps"] / HBM_PEAK_GBS, 4)
+                roofline["traffic_over_algorithmic"] = round(tb / max(roofline["algorithmic_bytes_per_launch"], 1), 3)
+                roofline["traffic_all_kernels"] = lt["bytes"]
+        tp = traffic_from_profiles(scene_name, height, spp) if (world == 1 and width * 9 == height * 16) else None
+        if tp and dom_name in tp["bytes_per_launch"] and launches[dom] and dom_ms > 0:
+            tb = tp["bytes_per_launch"][dom_name]
+            meas = tb / (dom_ms / launches[dom] * 1e-3) / 1e9
+            roofline["traffic_from_profiles"] = {"file": tp["file"], "bytes_per_launch": tb, "GBps_at_live_launch_time": round(meas, 1),
+                                                 "frac": round(meas / HBM_PEAK_GBS, 4),
+                                                 "over_algorithmic": round(tb / max(roofline["algorithmic_bytes_per_launch"], 1), 3)}
+        # the same account for every path kernel (the dominant one changes with the workload: since round 4 `back` spends 28 / 26 / 23 ms in closest hits /
+        # shade / shadow rays): algorithmic bytes per launch, live launch time, and the live counter bytes where the PMC passes ran
+        per_kernel = {}
+        for k in range(len(names)):
+            if names[k] in by and kernel_ms[k] > 0 and launches[k]:
+                alg_pl = by[names[k]] * steps / launches[k]
+                e = {"avg_launch_ms": round(kernel_ms[k] / launches[k], 5), "algorithmic_bytes_per_launch": int(alg_pl),
+                     "achieved_GBps": round(alg_pl / (kernel_ms[k] / launches[k] * 1e-3) / 1e9, 1)}
+                e["frac"] = round(e["achieved_GBps"] / HBM_PEAK_GBS, 4)
+                if lt and (scene_name, width, height, spp) == lt["key"] and names[k] in lt["bytes"]:
+                    e["traffic"] = lt["bytes"][names[k]]
+                    e["traffic_GBps"] = round(e["traffic"] / (kernel_ms[k] / launches[k] * 1e-3) / 1e9, 1)
+                    e["traffic_frac_of_peak"] = round(e["traffic_GBps"] / HBM_PEAK_GBS, 4)
+                per_kernel[names[k]] = e
+        roofline["by_kernel"] = per_kernel
+        if achieved > HBM_PEAK_GBS:
+            roofline["note"] = ("algorithmic bytes (every node / triangle record a ray touches) exceed the HBM peak because the scene is "
+                                "served from L1/L2/Infinity Cache; the kernel is bound by VALU/SALU issue and the CU's texture-address rate, not by HBM (DESIGN.md 5)")
+        kernels = {names[k]: {"ms_per_step": round(kernel_ms[k] / steps, 3), "launches_per_step": launches[k] // max(steps, 1),
+                              "algorithmic_GBps": round(by.get(names[k], 0) * steps / (kernel_ms[k] * 1e-3) / 1e9, 1) if kernel_ms[k] > 0 and names[k] in by else None}
+                   for k in range(len(names))}
+        return roofline, kernels
+
+    def measure(self, scene_name, width, height, spp, steps, warmup, seed, leaf=None, tris=None, base_flags=0, also_overlap=False, save_png=None, builder=None, dump_dir=None,
+                full=False):
+        """Counting render (untimed), warm-up, then `steps` timed renders of one workload; with `full` the profiling step after them
+        (roofline, kernels_rank0) and, with `also_overlap`, the steps again with two passes in flight.  Returns the result fields."""
         T, D, torch, a = self.T, self.D, self.torch, self.a
         world, rank, local_rank, dist = self.world, self.rank, self.local_rank, self.dist
         t0 = time.time()
@@ -256,14 +326,14 @@ class Bench:
         if dump_dir and img is not None:  # before the profiling step below renders into the same buffer again
             dump_outputs(dump_dir, img.cpu().numpy(), st)
         rank_render_ms, rank_gather_ms = step_times.totals_ms() if group is None else (0.0, 0.0)
-        # the profiling step: the same render once more with hipEvents around every launch (on the launch stream, inside the
-        # library); its per-kernel sums are scaled to `steps` so that every per-step figure below keeps its meaning
-        img, st_prof = step(flags_prof)
-        self.sync()
-        kernel_ms = [st_prof.kernel_ms[k] * steps for k in range(8)]
-        launches = [st_prof.launches[k] * steps for k in range(8)]
+        st_prof = None
+        if full:
+            # the profiling step: the same render once more with hipEvents around every launch (on the launch stream, inside the
+            # library); its per-kernel sums are scaled to `steps` so that every per-step figure below keeps its meaning
+            img, st_prof = step(flags_prof)
+            self.sync()
         # beside the contract's number, the same steps with two sample passes in flight (TRT_FLAG_OVERLAP, what render()/tinyrt
-        # use).  Not `value`: per-kernel hipEvent times of overlapping passes contain each other.  On by default at N = 1
+        # use).  Not `value`: per-kernel hipEvent times of overlapping passes contain each other.  On by default at N = 1 with --full
         # (--no-overlap-extra skips it, e.g. so that a rocprofv3 run of the command sees the timed launches and the profiling step only).
         overlap_extra = None
         if world == 1 and also_overlap and not (base_flags & T.TRT_FLAG_OVERLAP) and spp >= 2:
@@ -285,74 +355,21 @@ class Bench:
             dist.all_reduce(rr)
             rays_total = int(rr.item())
             # every rank's own step, for the first run on a real node: [device render ms (trt_stats), render ms and gather ms between this
-            # rank's marks (a rank that finishes early waits in the gather), k_tail ms, rays] per step
-            mine = torch.tensor([render_ms / steps, rank_render_ms / steps, rank_gather_ms / steps, st_prof.kernel_ms[T.KERNEL_NAMES.index("tail")] if "tail" in T.KERNEL_NAMES else 0.0,
-                                 rays_rank / steps], dtype=torch.float64, device=red_dev)
+            # rank's marks (a rank that finishes early waits in the gather), k_tail ms (--full: from the profiling step), rays] per step
+            tail_ms = st_prof.kernel_ms[T.KERNEL_NAMES.index("tail")] if st_prof is not None and "tail" in T.KERNEL_NAMES else 0.0
+            mine = torch.tensor([render_ms / steps, rank_render_ms / steps, rank_gather_ms / steps, tail_ms, rays_rank / steps], dtype=torch.float64, device=red_dev)
             every = [torch.zeros_like(mine) for _ in range(world)]
             dist.all_gather(every, mine)
             per_rank = [{"rank": r, "device_render_ms": round(float(v[0]), 3), "render_ms": round(float(v[1]), 3), "gather_wait_ms": round(float(v[2]), 3),
-                         "tail_ms": round(float(v[3]), 3), "rays_per_step": int(v[4])} for r, v in enumerate(every)]
+                         "tail_ms": round(float(v[3]), 3) if st_prof is not None else None, "rays_per_step": int(v[4])} for r, v in enumerate(every)]
         else:
             rays_total = rays_rank
             per_rank = None
         res = None
         if rank == 0:
             mrays = rays_total / elapsed / 1e6
-            # roofline of the dominant kernel of THIS rank: algorithmic bytes (counting pass, same seed -> same
-            # counts every step) / its summed launch time in the timed region (hipEvents on the launch stream)
-            by = algorithmic_bytes(st_count)
-            names = T.KERNEL_NAMES
-            dom = max(range(len(names)), key=lambda k: kernel_ms[k])
-            dom_name = names[dom]
-            dom_bytes_step = by.get(dom_name, 0)
-            dom_ms = kernel_ms[dom]
-            achieved = dom_bytes_step * steps / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-            roofline = {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": round(achieved / HBM_PEAK_GBS, 4),
-                        "traffic": None,  # filled below from the live PMC passes (live_traffic) when they ran; null with the reason otherwise
-                        "launches_per_step": launches[dom] // max(steps, 1),
-                        "avg_launch_ms": round(dom_ms / max(launches[dom], 1), 5),
-                        "algorithmic_bytes_per_launch": int(dom_bytes_step * steps / max(launches[dom], 1)),
-                        "frac_of_measured_copy_peak": round(achieved / 6290.0, 4)}
-            lt = getattr(self, "live", None)
-            if lt and (scene_name, width, height, spp) == lt["key"]:
-                roofline["traffic_note"] = lt["note"]
-                if dom_name in lt["bytes"] and launches[dom] and dom_ms > 0:
-                    tb = lt["bytes"][dom_name]
-                    roofline["traffic"] = tb  # HBM-side bytes per launch of the dominant kernel, measured by the PMC passes of this very invocation
-                    roofline["traffic_GBps"] = round(tb / (dom_ms / launches[dom] * 1e-3) / 1e9, 1)
-                    roofline["traffic_frac_of_peak"] = round(roofline["traffic_GBps"] / HBM_PEAK_GBS, 4)
-                    roofline["traffic_over_algorithmic"] = round(tb / max(roofline["algorithmic_bytes_per_launch"], 1), 3)
-                    roofline["traffic_all_kernels"] = lt["bytes"]
-            tp = traffic_from_profiles(scene_name, height, spp) if (world == 1 and width * 9 == height * 16) else None
-            if tp and dom_name in tp["bytes_per_launch"] and launches[dom] and dom_ms > 0:
-                tb = tp["bytes_per_launch"][dom_name]
-                meas = tb / (dom_ms / launches[dom] * 1e-3) / 1e9
-                roofline["traffic_from_profiles"] = {"file": tp["file"], "bytes_per_launch": tb, "GBps_at_live_launch_time": round(meas, 1),
-                                                     "frac": round(meas / HBM_PEAK_GBS, 4),
-                                                     "over_algorithmic": round(tb / max(roofline["algorithmic_bytes_per_launch"], 1), 3)}
-            # the same account for every path kernel (the dominant one changes with the workload: since round 4 `back` spends 28 / 26 / 23 ms in closest hits /
-            # shade / shadow rays): algorithmic bytes per launch, live launch time, and the live counter bytes where the PMC passes ran
-            per_kernel = {}
-            for k in range(len(names)):
-                if names[k] in by and kernel_ms[k] > 0 and launches[k]:
-                    alg_pl = by[names[k]] * steps / launches[k]
-                    e = {"avg_launch_ms": round(kernel_ms[k] / launches[k], 5), "algorithmic_bytes_per_launch": int(alg_pl),
-                         "achieved_GBps": round(alg_pl / (kernel_ms[k] / launches[k] * 1e-3) / 1e9, 1)}
-                    e["frac"] = round(e["achieved_GBps"] / HBM_PEAK_GBS, 4)
-                    if lt and (scene_name, width, height, spp) == lt["key"] and names[k] in lt["bytes"]:
-                        e["traffic"] = lt["bytes"][names[k]]
-                        e["traffic_GBps"] = round(e["traffic"] / (kernel_ms[k] / launches[k] * 1e-3) / 1e9, 1)
-                        e["traffic_frac_of_peak"] = round(e["traffic_GBps"] / HBM_PEAK_GBS, 4)
-                    per_kernel[names[k]] = e
-            roofline["by_kernel"] = per_kernel
-            if achieved > HBM_PEAK_GBS:
-                roofline["note"] = ("algorithmic bytes (every node / triangle record a ray touches) exceed the HBM peak because the scene is "
-                                    "served from L1/L2/Infinity Cache; the kernel is bound by VALU/SALU issue and the CU's texture-address rate, not by HBM (DESIGN.md 5)")
+            by = algorithmic_bytes(st_count)  # counting render, same seed -> same counts every step
             total_bytes_step = sum(by.values()) + 12 * width * nrows
-            kernels = {names[k]: {"ms_per_step": round(kernel_ms[k] / steps, 3), "launches_per_step": launches[k] // max(steps, 1),
-                                  "algorithmic_GBps": round(by.get(names[k], 0) * steps / (kernel_ms[k] * 1e-3) / 1e9, 1) if kernel_ms[k] > 0 and names[k] in by else None}
-                       for k in range(len(names))}
             res = {
                 "value": round(mrays, 2), "unit": "Mrays/s", "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 3),
                 "data": f"scene '{scene_name}' ({WORKLOADS[scene_name]}), counter RNG seed {seed:#x}",
@@ -372,13 +389,15 @@ class Bench:
                     "leaf_steps": round((st_count.tri_tests[0] + st_count.tri_tests[1]) / (64.0 * st_count.wave_steps[1]), 3) if st_count.wave_steps[1] else None,
                     "visits_per_ray": round((st_count.inner_visits[0] + st_count.inner_visits[1]) / max(st_count.rays, 1), 2),
                     "tri_tests_per_ray": round((st_count.tri_tests[0] + st_count.tri_tests[1]) / max(st_count.rays, 1), 2)},
-                "roofline": roofline, "kernels_rank0": kernels, "passes": st.passes, "max_path_vertices": st.max_bounces + 1,
-                "scene_load_build_s": round(t_load, 2), "with_pass_overlap": overlap_extra,
+                "passes": st.passes, "max_path_vertices": st.max_bounces + 1, "scene_load_build_s": round(t_load, 2),
                 # how the numbers above were taken (rounds 1-2 had hipEvents around every launch of the timed steps; since round 3 they have none)
-                "timing": {"events_in_timed_steps": False, "kernel_ms_from": f"1 profiling step (TRT_FLAG_TIMING) after the timed region x {steps}",
-                           "value_from": "wall clock of the timed steps between barriers, max over ranks"},
+                "timing": {"events_in_timed_steps": False, "value_from": "wall clock of the timed steps between barriers, max over ranks"},
                 "per_rank": per_rank,
             }
+            if st_prof is not None:
+                res["roofline"], res["kernels_rank0"] = self.roofline(scene_name, width, height, spp, steps, by, st_prof)
+                res["with_pass_overlap"] = overlap_extra
+                res["timing"]["kernel_ms_from"] = f"1 profiling step (TRT_FLAG_TIMING) after the timed region x {steps}"
             if save_png and img is not None:
                 T.imshow(img.cpu().numpy(), save_png)
         renderer.close()
@@ -407,13 +426,18 @@ def self_launch(a):
     return subprocess.run(cmd, env=env).returncode
 
 
+def wants_live_traffic(a):
+    """--full runs the live counter passes for the contract's own command (N = 1, the headline workload, extras on), --traffic for any other."""
+    contract_cmd = (a.scene, a.width, a.height, a.spp) == ("back", 1920, 1080, 256) and not a.no_extra and not a.fixed_nee and not a.overlap and a.leaf is None and a.tris is None
+    return a.full and a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_traffic and not a.group and (contract_cmd or a.traffic)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a))
     live = None
-    contract_cmd = (a.scene, a.width, a.height, a.spp) == ("back", 1920, 1080, 256) and not a.no_extra and not a.fixed_nee and not a.overlap and a.leaf is None and a.tris is None
-    if a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_traffic and not a.group and (contract_cmd or a.traffic):
+    if wants_live_traffic(a):
         t_pmc = time.time()
         by, note = live_traffic(a)  # child processes; this process has not touched the GPU yet
         live = {"key": (a.scene, a.width, a.height, a.spp), "bytes": by, "note": note + f" ({time.time() - t_pmc:.0f} s)"}
@@ -446,20 +470,21 @@ def main():
     B.live = live
     seed = a.seed if a.seed is not None else SEEDS[a.scene]
     res, scene = B.measure(a.scene, a.width, a.height, a.spp, a.steps, a.warmup, seed, leaf=a.leaf, tris=a.tris,
-                           base_flags=T.TRT_FLAG_OVERLAP if a.overlap else 0, also_overlap=not a.no_overlap_extra, save_png=a.save_png, dump_dir=a.dump_outputs)
+                           base_flags=T.TRT_FLAG_OVERLAP if a.overlap else 0, also_overlap=a.full and not a.no_overlap_extra, save_png=a.save_png, dump_dir=a.dump_outputs,
+                           full=a.full)
     if rank == 0:
         result = {"metric": "Mrays/s", "value": res["value"], "unit": "Mrays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                   "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32"}
         result.update({k: v for k, v in res.items() if k not in result})
         headline = (a.scene, a.width, a.height, a.spp) == ("back", 1920, 1080, 256)
-        if world == 1 and headline and not a.no_extra and not a.fixed_nee and not a.overlap:
+        if a.full and world == 1 and headline and not a.no_extra and not a.fixed_nee and not a.overlap:
             extra = []
             for name, spp, steps, ew, eh, etris in EXTRA:
-                r, sc = B.measure(name, ew or a.width, eh or a.height, spp, steps, 1, SEEDS[name], tris=etris)
+                r, sc = B.measure(name, ew or a.width, eh or a.height, spp, steps, 1, SEEDS[name], tris=etris, full=True)
                 extra.append({k: r[k] for k in ("value", "unit", "steps", "ms_per_step", "config", "rays_per_step", "roofline", "kernels_rank0", "simd_utilisation_traversal")})
                 sc.close()
             result["extra_workloads"] = extra
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(a, seed)
             if result["cpu_baseline"] and result["cpu_baseline"].get("value"):
                 result["gpu_over_cpu"] = round(res["value"] / result["cpu_baseline"]["value"], 1)

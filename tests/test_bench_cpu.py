@@ -1,8 +1,11 @@
-"""bench.py's pieces that need no GPU: the live counter passes (roofline.traffic) against a stand-in profiler."""
+"""bench.py's pieces that need no GPU: the live counter passes (roofline.traffic) against a stand-in profiler, and what a plain run
+renders against what --full adds, with a stand-in renderer."""
 import argparse
 import os
 import stat
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -52,7 +55,7 @@ def test_live_traffic_turns_the_counter_passes_into_bytes_per_launch(tmp_path, m
     assert len(log) == 2  # one child per counter, each the program itself behind `--` (no shell, no env wrapper)
     for line in log:
         assert line.split()[0] == sys.executable and "bench.py" in line.split()[1]
-        assert "--no-traffic" in line and "--steps 1" in line and "--leaf 8" in line and "--tris 5000" in line
+        assert "--full" in line and "--no-traffic" in line and "--steps 1" in line and "--leaf 8" in line and "--tris 5000" in line
 
 
 def test_live_traffic_reports_why_it_could_not_run(tmp_path, monkeypatch):
@@ -96,3 +99,82 @@ def test_dump_outputs_samples_a_large_image_the_same_way_every_time(tmp_path):
     px = np.load(tmp_path / "a" / "image_sample.npy")
     assert idx.dtype == np.float64 and px.dtype == np.float32 and len(np.unique(idx)) == len(idx) == len(px)
     assert np.array_equal(px, img.reshape(-1, 3)[idx.astype(np.int64)])
+
+
+def _parse(*argv, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    return bench.parse()
+
+
+def test_the_live_counter_passes_run_only_with_full(monkeypatch):
+    """A plain run of the contract's command starts no profiler children; --full does, unless told otherwise."""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    assert not _parse("--gpus", "1", "--steps", "3", "--warmup", "1", monkeypatch=monkeypatch).full
+    assert not bench.wants_live_traffic(_parse("--gpus", "1", "--steps", "3", "--warmup", "1", monkeypatch=monkeypatch))
+    assert bench.wants_live_traffic(_parse("--gpus", "1", "--full", monkeypatch=monkeypatch))
+    assert not bench.wants_live_traffic(_parse("--full", "--no-traffic", monkeypatch=monkeypatch))
+    assert not bench.wants_live_traffic(_parse("--full", "--scene", "veach-mis", monkeypatch=monkeypatch))
+    assert bench.wants_live_traffic(_parse("--full", "--traffic", "--scene", "veach-mis", monkeypatch=monkeypatch))
+    with pytest.raises(SystemExit):
+        _parse("--traffic", monkeypatch=monkeypatch)
+
+
+class _FakeRenderer:
+    """Stands in for T.Renderer: records the flags of every render and returns fixed counts."""
+    flags = []
+
+    def __init__(self, scene, device=0):
+        pass
+
+    def render_into(self, p, out, stream):
+        import tinyraytracing_amd as T
+        _FakeRenderer.flags.append(p.flags)
+        st = T.Stats(rays_camera=100, rays_shadow=50, rays_indirect=25, render_ms=1.0, passes=1)
+        if p.flags & T.TRT_FLAG_TIMING:
+            for k in range(len(T.KERNEL_NAMES)):
+                st.launches[k], st.kernel_ms[k] = 2, 0.5 + k
+        return st
+
+    def close(self):
+        pass
+
+
+def _fake_bench(a, monkeypatch):
+    """A Bench on the CPU: the real scene, params and stripe logic, a recording renderer, host tensors."""
+    import types
+    import torch
+    import tinyraytracing_amd as T
+    monkeypatch.setattr(T, "Renderer", _FakeRenderer)
+    _FakeRenderer.flags = []
+    B = bench.Bench(a, 1, 0, 0, None, "nccl")
+    cuda = types.SimpleNamespace(current_stream=lambda: types.SimpleNamespace(cuda_stream=0), synchronize=lambda: None, empty_cache=lambda: None)
+    B.torch = types.SimpleNamespace(float32=torch.float32, cuda=cuda,
+                                    empty=lambda shape, dtype, device: torch.empty(shape, dtype=dtype))
+    D = B.D
+    B.D = types.SimpleNamespace(shard_params=D.shard_params, StepTimes=D.StepTimes,
+                                render_distributed=lambda *args, device=None, **kw: D.render_distributed(*args, **kw))
+    return B, T
+
+
+def test_a_plain_run_renders_only_its_warmup_and_timed_steps(monkeypatch, tmp_path):
+    """Without --full a workload is the counting render (the first warm-up step), the other warm-ups and the timed steps — nothing after
+    them — and its line carries no figure that needs a render of its own; --dump-outputs is still written."""
+    a = _parse("--steps", "3", "--warmup", "2", monkeypatch=monkeypatch)
+    B, T = _fake_bench(a, monkeypatch)
+    res, scene = B.measure("back", 32, 16, 4, a.steps, a.warmup, 7, also_overlap=a.full and not a.no_overlap_extra, dump_dir=str(tmp_path), full=a.full)
+    assert _FakeRenderer.flags == [T.TRT_FLAG_COUNT, 0, 0, 0, 0]
+    assert res["steps"] == 3 and res["warmup"] == 2 and res["rays_per_step"] == 175 and res["ms_per_step"] > 0
+    for k in ("roofline", "kernels_rank0", "with_pass_overlap"):
+        assert k not in res, k
+    assert "kernel_ms_from" not in res["timing"]
+    assert sorted(os.listdir(tmp_path)) == ["image.npy", "ray_counts.npy"]
+
+
+def test_full_adds_the_profiling_step_and_the_overlapped_steps(monkeypatch):
+    a = _parse("--steps", "3", "--warmup", "2", "--full", monkeypatch=monkeypatch)
+    B, T = _fake_bench(a, monkeypatch)
+    res, scene = B.measure("back", 32, 16, 4, a.steps, a.warmup, 7, also_overlap=a.full and not a.no_overlap_extra, full=a.full)
+    assert _FakeRenderer.flags == [T.TRT_FLAG_COUNT, 0, 0, 0, 0, T.TRT_FLAG_TIMING] + [T.TRT_FLAG_OVERLAP] * 4
+    assert res["kernels_rank0"]["trace_closest"] == {"ms_per_step": 1.5, "launches_per_step": 2, "algorithmic_GBps": 0.0}
+    assert res["roofline"]["kernel"] == T.KERNEL_NAMES[-1] and res["with_pass_overlap"]["unit"] == "Mrays/s"
+    assert res["timing"]["kernel_ms_from"].startswith("1 profiling step")

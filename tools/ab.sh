@@ -2,7 +2,7 @@
 # A/B on the GPU box: each remaining argument is "label|ENV=val ...|bench args"; prints one line per run.
 for spec in "$@"; do
   IFS='|' read -r label envs args <<< "$spec"
-  env $envs timeout -k 10 400 python bench.py $args --no-cpu-baseline 2>/dev/null | python -c "
+  env $envs timeout -k 10 400 python bench.py --full $args --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 line=sys.stdin.readline()
 if not line.strip(): print('%-34s FAILED' % '$label'); sys.exit(0)

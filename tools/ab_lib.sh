@@ -18,8 +18,8 @@ PY
 }
 for v in "$@"; do
   lib=TRT_HIP_LIB=$root/tinyraytracing_amd/lib/variants/libtrt_hip_$v.so
-  run back_$v $lib --steps 10 --warmup 2
-  run veach_$v $lib --scene veach-mis --steps 2
-  run stair_$v $lib --scene staircase --spp 64 --steps 2
-  run soup_$v $lib --scene soup --spp 16 --steps 2
+  run back_$v $lib --full --steps 10 --warmup 2
+  run veach_$v $lib --full --scene veach-mis --steps 2
+  run stair_$v $lib --full --scene staircase --spp 64 --steps 2
+  run soup_$v $lib --full --scene soup --spp 16 --steps 2
 done

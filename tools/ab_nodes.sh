@@ -16,9 +16,9 @@ except Exception as e:
 PY
 }
 for nk in 0 1; do
-  run veach_nk$nk TRT_NODE_KIND=$nk --scene veach-mis --steps 2
-  run stair_nk$nk TRT_NODE_KIND=$nk --scene staircase --spp 64 --steps 2
-  run soup_nk$nk TRT_NODE_KIND=$nk --scene soup --spp 16 --steps 2
-  run blob2m_nk$nk TRT_NODE_KIND=$nk --scene blob --tris 2000000 --spp 64 --steps 2
-  run blob10m_nk$nk TRT_NODE_KIND=$nk --scene blob --tris 10000000 --width 3840 --height 2160 --spp 16 --steps 2
+  run veach_nk$nk TRT_NODE_KIND=$nk --full --scene veach-mis --steps 2
+  run stair_nk$nk TRT_NODE_KIND=$nk --full --scene staircase --spp 64 --steps 2
+  run soup_nk$nk TRT_NODE_KIND=$nk --full --scene soup --spp 16 --steps 2
+  run blob2m_nk$nk TRT_NODE_KIND=$nk --full --scene blob --tris 2000000 --spp 64 --steps 2
+  run blob10m_nk$nk TRT_NODE_KIND=$nk --full --scene blob --tris 10000000 --width 3840 --height 2160 --spp 16 --steps 2
 done

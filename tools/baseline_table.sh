@@ -4,16 +4,16 @@
 root=${GRAFT_REPO_ROOT:-/root/repo}
 cd $root
 out=gpurun_out/baseline; mkdir -p $out
-python bench.py --width 1024 --height 1024 --no-extra > $out/c2.json 2> $out/c2.err; echo "c2 done" >&2
-python bench.py --scene soup --spp 64 --steps 2 > $out/c3.json 2> $out/c3.err; echo "c3 done" >&2
-python bench.py --scene staircase --spp 1024 --steps 1 > $out/c4.json 2> $out/c4.err; echo "c4 done" >&2
-python bench.py --scene blob --tris 10000000 --width 3840 --height 2160 --spp 4096 --steps 1 > $out/c5.json 2> $out/c5.err; echo "c5 done" >&2
-python bench.py --no-extra > $out/h_back.json 2> $out/h_back.err
-python bench.py --scene veach-mis --steps 2 > $out/h_veach.json 2> $out/h_veach.err
-python bench.py --scene staircase --steps 1 > $out/h_stair.json 2> $out/h_stair.err; echo "headline done" >&2
+python bench.py --full --width 1024 --height 1024 --no-extra > $out/c2.json 2> $out/c2.err; echo "c2 done" >&2
+python bench.py --full --scene soup --spp 64 --steps 2 > $out/c3.json 2> $out/c3.err; echo "c3 done" >&2
+python bench.py --full --scene staircase --spp 1024 --steps 1 > $out/c4.json 2> $out/c4.err; echo "c4 done" >&2
+python bench.py --full --scene blob --tris 10000000 --width 3840 --height 2160 --spp 4096 --steps 1 > $out/c5.json 2> $out/c5.err; echo "c5 done" >&2
+python bench.py --full --no-extra > $out/h_back.json 2> $out/h_back.err
+python bench.py --full --scene veach-mis --steps 2 > $out/h_veach.json 2> $out/h_veach.err
+python bench.py --full --scene staircase --steps 1 > $out/h_stair.json 2> $out/h_stair.err; echo "headline done" >&2
 # the reference's own leaf size (main.cpp:76 builds with 8; every other row is on this repository's leaf-2 tree)
-python bench.py --scene veach-mis --steps 2 --leaf 8 --no-cpu-baseline > $out/h_veach_l8.json 2> $out/h_veach_l8.err
-python bench.py --scene staircase --steps 1 --leaf 8 --no-cpu-baseline > $out/h_stair_l8.json 2> $out/h_stair_l8.err; echo "leaf 8 done" >&2
+python bench.py --full --scene veach-mis --steps 2 --leaf 8 --no-cpu-baseline > $out/h_veach_l8.json 2> $out/h_veach_l8.err
+python bench.py --full --scene staircase --steps 1 --leaf 8 --no-cpu-baseline > $out/h_stair_l8.json 2> $out/h_stair_l8.err; echo "leaf 8 done" >&2
 python tools/cpu_baseline.py --scene back --width 256 --height 256 --spp 4 --seconds 1 > $out/c1.json 2> $out/c1.err
 python - <<'PY'
 import json, os

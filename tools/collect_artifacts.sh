@@ -1,7 +1,8 @@
 #!/bin/bash
-# Copies the judged summaries of tools/round_artifacts.sh from gpurun_out/ (scratch) to profiles/ (tracked).
-# usage: tools/collect_artifacts.sh r02
+# Copies the judged summaries of tools/round_artifacts.sh (tools/prof.sh's folders and the bench lines in its output dir) to profiles/ (tracked).
+# usage: tools/collect_artifacts.sh r02 <output dir of tools/round_artifacts.sh>
 r=$1
+out=$(cd "${2:?usage: tools/collect_artifacts.sh <round> <output dir of tools/round_artifacts.sh>}" && pwd) || exit 1
 root=$(cd "$(dirname "$0")/.." && pwd)
 cd $root
 for tag in back soup blob10m; do
@@ -14,5 +15,5 @@ done
 python3 tools/pmc_summary.py gpurun_out/prof_${r}_back ${r}_back_1080p_256spp back 1080 256
 python3 tools/pmc_summary.py gpurun_out/prof_${r}_soup ${r}_soup_1080p_16spp soup 1080 16
 python3 tools/pmc_summary.py gpurun_out/prof_${r}_blob10m ${r}_blob10m_2160p_8spp blob 2160 8
-for f in gpurun_out/${r}_bench_*.json; do cp $f profiles/; done
+for f in $out/${r}_bench_*.json; do cp $f profiles/; done
 ls -la profiles | tail -20
