@@ -314,6 +314,32 @@ int trt_render_aov_device(trt_handle* h, const trt_params* p, float* albedo_dev,
 int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* dir,
                       float* t, int32_t* tri, float* uv, trt_stats* stats);
 
+/* Ray queries with a per-ray search range.  t_max[n] (may be NULL: TRT_INF for every ray) bounds each ray: a hit counts iff
+ * TRT_T_MIN <= t < bound (strict), bound = t_max > TRT_T_MIN ? fminf(t_max, TRT_INF) : TRT_T_MIN — so NaN, negative values, 0 and
+ * TRT_T_MIN find nothing, and +inf or anything beyond TRT_INF is TRT_INF (Q7).  t_min stays the reference's 0.0005.  Whether a hit is
+ * accepted (the leaf-box rule above, the emissive tie rules) does not depend on the bound: at equal t every tied candidate lies on the same
+ * side of it.  Arguments are checked as for trt_trace_closest: a null handle or array (uv and t_max excepted) or n > 0x7FFF0000 is
+ * TRT_EINVAL, n == 0 is TRT_OK.
+ *
+ * trt_trace_closest_range: the record trt_trace_closest returns when that hit lies inside the bound, otherwise exactly its miss record
+ * (t = TRT_INF, not the bound; tri = -1; uv = (0, 0)).  uv may be NULL.  With t_max NULL it IS trt_trace_closest.  stats: the slots
+ * trt_trace_closest fills (inner_visits[0], tri_tests[0], launches / kernel_ms[TRT_K_TRACE_CLOSEST], redo_rays). */
+int trt_trace_closest_range(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max,
+                            float* t, int32_t* tri, float* uv, trt_stats* stats);
+/* The same with org, dir, t_max, t, tri and uv in DEVICE memory of the handle's device; all work on hip_stream (NULL = default stream), and
+ * the call returns after that stream has been synchronised.  Nothing but the stats crosses PCIe. */
+int trt_trace_closest_device(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max,
+                             float* t, int32_t* tri, float* uv, void* hip_stream, trt_stats* stats);
+/* Occlusion ("is anything between here and there?"): occluded[i] = 1 iff some hit counts for ray i, else 0 — one byte per ray.  The walk
+ * stops at the first leaf that yields an accepted hit (no closest hit is searched for, no hit record is written), so it costs at most what
+ * trt_trace_closest_range costs on the same rays.  stats: the shadow slots — inner_visits[1], tri_tests[1], launches /
+ * kernel_ms[TRT_K_TRACE_SHADOW], rays_shadow = n — and redo_rays. */
+int trt_trace_occluded(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max,
+                       uint8_t* occluded, trt_stats* stats);
+/* The same with org, dir, t_max and occluded in DEVICE memory, as trt_trace_closest_device. */
+int trt_trace_occluded_device(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max,
+                              uint8_t* occluded, void* hip_stream, trt_stats* stats);
+
 void trt_destroy(trt_handle* h);
 
 /* ---- one node, several GPUs -------------------------------------------------------------------------------------

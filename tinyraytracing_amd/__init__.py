@@ -408,23 +408,102 @@ class Renderer:
             raise TrtError(f"trt_render_aov_device failed ({rc}): {self._lib.trt_last_error().decode()}")
         return st
 
-    def trace_closest(self, org, direction, want_stats=False):
-        """traverseBVH on a ray batch: returns (t, tri, uv[, Stats])."""
+    @staticmethod
+    def _rays(org, direction, t_max, what):
         org = np.ascontiguousarray(org, dtype=np.float32).reshape(-1, 3)
         direction = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1, 3)
         n = org.shape[0]
         if direction.shape[0] != n:
-            raise TrtError("trace_closest: org/dir length mismatch")
+            raise TrtError(f"{what}: org/dir length mismatch")
+        if t_max is not None:
+            t_max = np.ascontiguousarray(t_max, dtype=np.float32).reshape(-1)
+            if t_max.shape[0] != n:
+                raise TrtError(f"{what}: t_max must hold one bound per ray")
+        return org, direction, t_max, n
+
+    def trace_closest(self, org, direction, want_stats=False, t_max=None):
+        """traverseBVH on a ray batch: returns (t, tri, uv[, Stats]).  t_max (one bound per ray, None = TRT_INF): only hits with
+        t < bound count (trt_trace_closest_range, include/trt.h); a ray with nothing inside its bound gets the miss record."""
+        org, direction, t_max, n = self._rays(org, direction, t_max, "trace_closest")
         t = np.empty(n, np.float32)
         tri = np.empty(n, np.int32)
         uv = np.empty((n, 2), np.float32)
         st = Stats()
         fp = C.POINTER(C.c_float)
-        rc = self._lib.trt_trace_closest(self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp), t.ctypes.data_as(fp),
-                                         tri.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(fp), C.byref(st))
+        if t_max is None:
+            rc = self._lib.trt_trace_closest(self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp), t.ctypes.data_as(fp),
+                                             tri.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(fp), C.byref(st))
+        else:
+            rc = self._lib.trt_trace_closest_range(self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp), t_max.ctypes.data_as(fp),
+                                                   t.ctypes.data_as(fp), tri.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(fp), C.byref(st))
         if rc != 0:
-            raise TrtError(f"trt_trace_closest failed ({rc}): {self._lib.trt_last_error().decode()}")
+            name = "trt_trace_closest" if t_max is None else "trt_trace_closest_range"
+            raise TrtError(f"{name} failed ({rc}): {self._lib.trt_last_error().decode()}")
         return (t, tri, uv, st) if want_stats else (t, tri, uv)
+
+    def trace_occluded(self, org, direction, t_max=None, want_stats=False):
+        """Occlusion on a ray batch (trt_trace_occluded): a bool per ray, True iff some hit with t < bound counts (t_max: one bound per
+        ray, None = TRT_INF).  The walk stops at the first such hit.  Returns occluded[, Stats]."""
+        org, direction, t_max, n = self._rays(org, direction, t_max, "trace_occluded")
+        occ = np.empty(n, np.uint8)
+        st = Stats()
+        fp = C.POINTER(C.c_float)
+        rc = self._lib.trt_trace_occluded(self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp),
+                                          None if t_max is None else t_max.ctypes.data_as(fp), occ.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_trace_occluded failed ({rc}): {self._lib.trt_last_error().decode()}")
+        occ = occ.view(np.bool_)
+        return (occ, st) if want_stats else occ
+
+    def _device_arrays(self, what, n, arrays):
+        """Checks torch tensors of this device for the *_into entries: arrays = [(name, tensor or None, dtypes, elements)].  -> pointers."""
+        ptrs = []
+        for name, t, dtypes, need in arrays:
+            if t is None:
+                ptrs.append(None)
+                continue
+            if (not _is_torch(t) or str(t.dtype) not in dtypes or not t.is_cuda or not t.is_contiguous() or t.numel() != need
+                    or (t.device.index is not None and t.device.index != self.device)):
+                raise TrtError(f"{what}: {name} must be a contiguous {' or '.join(d[6:] for d in dtypes)} tensor on cuda:{self.device} "
+                               f"with {need} elements")
+            ptrs.append(C.c_void_p(t.data_ptr()))
+        return ptrs
+
+    def _ray_count(self, org, what):
+        if not _is_torch(org) or org.dim() != 2 or org.shape[1] != 3:
+            raise TrtError(f"{what}: org must be a float32 tensor of shape (n, 3)")
+        return org.shape[0]
+
+    def trace_closest_into(self, org, direction, t, tri, uv=None, t_max=None, stream_ptr=0):
+        """trt_trace_closest_device: the rays org / direction (float32 [n, 3]) and t_max (float32 [n], None = TRT_INF) are torch tensors on this
+        device, and so are the outputs t (float32 [n]), tri (int32 [n]) and uv (float32 [n, 2], None = not wanted); the work runs on
+        stream `stream_ptr` (0 = default).  -> Stats."""
+        n = self._ray_count(org, "trace_closest_into")
+        f32 = ("torch.float32",)
+        p = self._device_arrays("trace_closest_into", n, [("org", org, f32, 3 * n), ("direction", direction, f32, 3 * n), ("t_max", t_max, f32, n),
+                                                          ("t", t, f32, n), ("tri", tri, ("torch.int32",), n), ("uv", uv, f32, 2 * n)])
+        if t is None or tri is None:
+            raise TrtError("trace_closest_into: t and tri are needed")
+        st = Stats()
+        rc = self._lib.trt_trace_closest_device(self._h, n, *p, C.c_void_p(stream_ptr), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_trace_closest_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return st
+
+    def trace_occluded_into(self, org, direction, occluded, t_max=None, stream_ptr=0):
+        """trt_trace_occluded_device: org / direction / t_max as for trace_closest_into; occluded: a uint8 or bool tensor [n] on this device that
+        receives 1 / True where some hit counts.  The work runs on stream `stream_ptr` (0 = default).  -> Stats."""
+        n = self._ray_count(org, "trace_occluded_into")
+        f32 = ("torch.float32",)
+        p = self._device_arrays("trace_occluded_into", n, [("org", org, f32, 3 * n), ("direction", direction, f32, 3 * n), ("t_max", t_max, f32, n),
+                                                           ("occluded", occluded, ("torch.uint8", "torch.bool"), n)])
+        if occluded is None:
+            raise TrtError("trace_occluded_into: occluded is needed")
+        st = Stats()
+        rc = self._lib.trt_trace_occluded_device(self._h, n, *p, C.c_void_p(stream_ptr), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_trace_occluded_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return st
 
     def close(self):
         if getattr(self, "_h", None):

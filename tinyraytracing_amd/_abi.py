@@ -84,7 +84,8 @@ class Stats(C.Structure):
 
 # the symbols include/trt.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_aov",
-               "trt_render_aov_device", "trt_trace_closest",
+               "trt_render_aov_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
+               "trt_trace_occluded_device",
                "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
 HOST_SYMBOLS = ["trth_scene_load", "trth_scene_load_opts", "trth_scene_drop_tris", "trth_scene_add_soup", "trth_scene_add_blob", "trth_scene_add_lamps",
@@ -201,6 +202,13 @@ def load_hip():
     lib.trt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_trace_closest.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                       C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(Stats)]
+    lib.trt_trace_closest_range.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(Stats)]
+    lib.trt_trace_closest_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(Stats)]
+    lib.trt_trace_occluded.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_uint8), C.POINTER(Stats)]
+    lib.trt_trace_occluded_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_destroy.argtypes = [C.c_void_p]
     lib.trt_destroy.restype = None
     lib.trt_group_create.argtypes = [C.POINTER(SceneFlat), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]

@@ -377,6 +377,24 @@ FixKernel fixKernel(const trt_handle* h, bool shadow, int primary)
     const FixKernel k[4] = {k_trace_fix<false, 0, 0>, k_trace_fix<false, 1, 0>, k_trace_fix<false, PRIMARY_LIST, 0>, k_trace_fix<true, false, 0>};
     return h->trace_impl == 0 ? nullptr : k[shadow ? 3 : primary];
 }
+// The ray queries (QUERY_CLOSEST, QUERY_OCCLUDED) on the rows of closestKernel / shadowKernel: the same driver, LDS depth and node kind, with
+// the counters on (as trt_trace_closest); the wave-uniform walk as the render runs it (8-byte records with hit8, flags in LDS with slim_walk).
+ClosestKernel queryKernel(const trt_handle* h, int query)
+{
+    const bool occ = query == QUERY_OCCLUDED;
+    if (h->trace_impl == 0 && h->hit8 && !occ) return k_trace_query<QUERY_CLOSEST, true, 1, false, 0, 0, true, true>;
+    if (h->trace_impl == 0 && h->slim_walk && occ) return k_trace_query<QUERY_OCCLUDED, true, 1, false, 0, 0, false, true>;
+    const ClosestKernel k[4][2] = {{k_trace_query<QUERY_CLOSEST, true, 1, false, 0, 0>, k_trace_query<QUERY_OCCLUDED, true, 1, false, 0, 0>},
+                                   {k_trace_query<QUERY_CLOSEST, true, OCT_LDS_LEVELS, true, 3, 1>, k_trace_query<QUERY_OCCLUDED, true, OCT_LDS_LEVELS, true, 3, 1>},
+                                   {k_trace_query<QUERY_CLOSEST, true, 16, false, 3, 0>, k_trace_query<QUERY_OCCLUDED, true, 16, false, 3, 0>},
+                                   {k_trace_query<QUERY_CLOSEST, true, TRT_LDS_STACK_MAX, true, 3, 0>, k_trace_query<QUERY_OCCLUDED, true, TRT_LDS_STACK_MAX, true, 3, 0>}};
+    return k[traversalOf(h)][occ];
+}
+FixKernel queryFixKernel(const trt_handle* h, int query)
+{
+    if (h->trace_impl == 0) return nullptr;
+    return query == QUERY_OCCLUDED ? k_trace_fix<true, 0, 0, QUERY_OCCLUDED> : k_trace_fix<false, 0, 0, QUERY_CLOSEST>;
+}
 ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list, bool hit8)
 {
     if (hit8) {  // trt_create sets hit8 only with tabs == 31
@@ -1404,64 +1422,134 @@ int trt_render_aov_device(trt_handle* h, const trt_params* p, float* albedo_dev,
     return renderAov(h, p, albedo_dev, normal_dev, depth_dev, false, hip_stream, stats);
 }
 
-int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* dir, float* t, int32_t* tri, float* uv, trt_stats* stats_out)
+namespace {
+// A ray batch of the query entries: the caller's arrays, on the host or on the handle's device.
+struct RayBatch {
+    const float* org;
+    const float* dir;
+    const float* t_max;  // null: TRT_INF for every ray
+    float* t;            // closest hits (t, tri, uv); uv may be null
+    int32_t* tri;
+    float* uv;
+    uint8_t* occluded;   // occlusion
+};
+
+// The ray-batch entries (trt_trace_closest*, trt_trace_occluded*): the checks of include/trt.h, the rays packed into io_buf (host arrays staged
+// there first), one traversal launch with k_trace_fix behind it, then for closest hits k_unpack_hits into the caller's arrays (device entries) or
+// into io_buf and from there to the host.  query: QUERY_NONE (no bound: trt_trace_closest's own kernels, k_trace_closest), QUERY_CLOSEST or
+// QUERY_OCCLUDED (k_trace_query, the bound in rb.w).  Host entries run on the null stream and copy after it is synchronised.
+int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool host, hipStream_t stream, trt_stats* stats_out, const char* what)
 {
-    if (!h || !org || !dir || !t || !tri) return fail(TRT_EINVAL, "trt_trace_closest: null argument");
+    const bool occ = query == QUERY_OCCLUDED;
+    if (!h || !io.org || !io.dir || (occ ? !io.occluded : (!io.t || !io.tri))) return fail(TRT_EINVAL, std::string(what) + ": null argument");
     if (n == 0) return TRT_OK;
     if (n > 0x7FFF0000ull) return fail(TRT_EINVAL, "ray batch too large");
     HIPC(hipSetDevice(h->device));
     const uint32_t n32 = (uint32_t)n;
-    const size_t in_bytes = (size_t)n * 3 * sizeof(float);
-    const size_t q16 = (size_t)n * sizeof(f4);
-    // io_buf: the packed rays, the hits, the caller's rays, then the block cleared first (DeviceStats, the redo counters) and the redo list
+    const size_t in_bytes = (size_t)n * 3 * sizeof(float), q16 = (size_t)n * sizeof(f4), f_bytes = (size_t)n * sizeof(float);
+    // host entries stage the caller's rays (org, dir, t_max) and, once they are packed, the results over them (t, tri, uv; or the bytes)
+    const size_t stage_in = 2 * in_bytes + (io.t_max ? f_bytes : 0), stage_out = occ ? (size_t)n : (io.uv ? 4 : 2) * f_bytes;
+    // io_buf: the packed rays, the hit records (8 bytes on a hit8 scene; none for occlusion), the staging area of a host call, then the block
+    // cleared first (DeviceStats, the redo counters) and the redo list
     Layout L;
-    const size_t o_ra = L.add(q16, 16), o_rb = L.add(q16, 16), o_hit = L.add(q16, 16), o_hit8 = L.add(h->hit8 ? q16 / 2 : 0, 16), o_org = L.add(in_bytes, 16), o_dir = L.add(in_bytes, 4);
+    const size_t o_ra = L.add(q16, 16), o_rb = L.add(q16, 16), o_hit = L.add(occ ? 0 : (h->hit8 ? q16 / 2 : q16), 16);
+    const size_t o_stage = L.add(host ? std::max(stage_in, stage_out) : 0, 16);
     const size_t o_stats = L.add(sizeof(DeviceStats), 256), o_redo = L.add(2 * sizeof(uint32_t), 64), o_idx = L.add((size_t)n * sizeof(uint32_t), 256);
     if (int e = h->io_buf.ensure(L.bytes)) return e;
     char* b = (char*)h->io_buf.p;
     f4* ra = (f4*)(b + o_ra);
     f4* rb = (f4*)(b + o_rb);
     f4* hit = (f4*)(b + o_hit);
-    float* d_org = (float*)(b + o_org);
-    float* d_dir = (float*)(b + o_dir);
+    char* stage = b + o_stage;
     DeviceStats* d_stats = (DeviceStats*)(b + o_stats);
     const RedoList redo{(uint32_t*)(b + o_redo), (uint32_t*)(b + o_idx)};  // rays for k_trace_fix (trt_kernels.h)
-    HIPC(hipMemcpy(d_org, org, in_bytes, hipMemcpyHostToDevice));
-    HIPC(hipMemcpy(d_dir, dir, in_bytes, hipMemcpyHostToDevice));
-    HIPC(hipMemset(d_stats, 0, o_idx - o_stats));
-    hipLaunchKernelGGL(k_pack_rays, dim3(std::min<uint32_t>((n32 + 255) / 256, 65536u)), dim3(256), 0, nullptr, d_org, d_dir, ra, rb, n32);
+    RayBatch dev = io;  // where the kernels read and write
+    if (host) {
+        dev.org = (const float*)stage;
+        dev.dir = (const float*)(stage + in_bytes);
+        dev.t_max = io.t_max ? (const float*)(stage + 2 * in_bytes) : nullptr;
+        dev.t = (float*)stage;
+        dev.tri = (int32_t*)(stage + f_bytes);
+        dev.uv = io.uv ? (float*)(stage + 2 * f_bytes) : nullptr;
+        dev.occluded = (uint8_t*)stage;
+        HIPC(hipMemcpyAsync((void*)dev.org, io.org, in_bytes, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.dir, io.dir, in_bytes, hipMemcpyHostToDevice, stream));
+        if (io.t_max) HIPC(hipMemcpyAsync((void*)dev.t_max, io.t_max, f_bytes, hipMemcpyHostToDevice, stream));
+    }
+    HIPC(hipMemsetAsync(d_stats, 0, o_idx - o_stats, stream));
+    const dim3 grid(std::min<uint32_t>((n32 + 255) / 256, 65536u)), block(256);
+    if (query == QUERY_NONE) hipLaunchKernelGGL(k_pack_rays, grid, block, 0, stream, dev.org, dev.dir, ra, rb, n32);
+    else hipLaunchKernelGGL(k_pack_rays_bounded, grid, block, 0, stream, dev.org, dev.dir, dev.t_max, ra, rb, n32);
     Timer tm{h, false};  // for the handle's events 0 and 1, which bracket the traversal
     hipEvent_t e0 = tm.get(0), e1 = tm.get(1);
     if (!e0 || !e1) return fail(TRT_EHIP, "hipEventCreate failed");
-    HIPC(hipEventRecord(e0, nullptr));
+    HIPC(hipEventRecord(e0, stream));
     RaySource src{};
     src.ra = ra;
     src.rb = rb;
-    // a scene with 8-byte hit records traces the batch with the render's kernel, and k_hit_uv widens its records
-    f4* hit8 = (f4*)(b + o_hit8);
-    launchTraceClosest(h, closestKernel(h, true, 0), fixKernel(h, false, 0), nullptr, (uint32_t*)h->spill.p, src, h->hit8 ? hit8 : hit, n32, d_stats, redo);
-    HIPC(hipEventRecord(e1, nullptr));
-    if (h->hit8) hipLaunchKernelGGL(k_hit_uv, dim3(std::min<uint32_t>((n32 + 255) / 256, 65536u)), dim3(256), 0, nullptr, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit8, hit, n32);
-    HIPC(hipDeviceSynchronize());
+    if (query == QUERY_NONE)  // a scene with 8-byte hit records traces the batch with the render's kernel, and k_unpack_hits<true> widens its records
+        launchTraceClosest(h, closestKernel(h, true, 0), fixKernel(h, false, 0), stream, (uint32_t*)h->spill.p, src, hit, n32, d_stats, redo);
+    else
+        launchTraceClosest(h, queryKernel(h, query), queryFixKernel(h, query), stream, (uint32_t*)h->spill.p, src, occ ? (f4*)dev.occluded : hit, n32, d_stats, redo);
+    HIPC(hipEventRecord(e1, stream));
+    if (!occ) {
+        if (h->hit8) hipLaunchKernelGGL(k_unpack_hits<true>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.t, dev.tri, dev.uv, n32);
+        else hipLaunchKernelGGL(k_unpack_hits<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.t, dev.tri, dev.uv, n32);
+    }
+    DeviceStats ds;
+    HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
+    HIPC(hipStreamSynchronize(stream));
     HIPC(hipGetLastError());
     float ms = 0.f;
     HIPC(hipEventElapsedTime(&ms, e0, e1));
-    std::vector<f4> hh(n);
-    HIPC(hipMemcpy(hh.data(), hit, q16, hipMemcpyDeviceToHost));
-    for (uint64_t i = 0; i < n; ++i) {
-        t[i] = hh[i].x;
-        tri[i] = (int32_t)f2u(hh[i].y);
-        if (uv) { uv[i * 2] = hh[i].z; uv[i * 2 + 1] = hh[i].w; }
+    if (host) {
+        if (occ) HIPC(hipMemcpy(io.occluded, dev.occluded, n, hipMemcpyDeviceToHost));
+        else {
+            HIPC(hipMemcpy(io.t, dev.t, f_bytes, hipMemcpyDeviceToHost));
+            HIPC(hipMemcpy(io.tri, dev.tri, f_bytes, hipMemcpyDeviceToHost));
+            if (io.uv) HIPC(hipMemcpy(io.uv, dev.uv, 2 * f_bytes, hipMemcpyDeviceToHost));
+        }
     }
     if (stats_out) {
-        DeviceStats ds;
-        HIPC(hipMemcpy(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost));
         std::memset(stats_out, 0, sizeof(*stats_out));
-        addDeviceStats(*stats_out, ds, h);  // what the closest-hit and fix kernels do not count stays zero: d_stats was cleared
-        stats_out->kernel_ms[TRT_K_TRACE_CLOSEST] = ms;
-        stats_out->launches[TRT_K_TRACE_CLOSEST] = 1;
+        addDeviceStats(*stats_out, ds, h);  // what the traversal and fix kernels do not count stays zero: d_stats was cleared
+        const int k = occ ? TRT_K_TRACE_SHADOW : TRT_K_TRACE_CLOSEST;
+        stats_out->kernel_ms[k] = ms;
+        stats_out->launches[k] = 1;
+        if (occ) stats_out->rays_shadow = n;
     }
     return TRT_OK;
+}
+}  // namespace
+
+int trt_trace_closest(trt_handle* h, uint64_t n, const float* org, const float* dir, float* t, int32_t* tri, float* uv, trt_stats* stats_out)
+{
+    return traceBatch(h, n, RayBatch{org, dir, nullptr, t, tri, uv, nullptr}, QUERY_NONE, true, nullptr, stats_out, "trt_trace_closest");
+}
+
+int trt_trace_closest_range(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max, float* t, int32_t* tri, float* uv,
+                            trt_stats* stats)
+{
+    return traceBatch(h, n, RayBatch{org, dir, t_max, t, tri, uv, nullptr}, t_max ? QUERY_CLOSEST : QUERY_NONE, true, nullptr, stats, "trt_trace_closest_range");
+}
+
+int trt_trace_closest_device(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max, float* t, int32_t* tri, float* uv,
+                             void* hip_stream, trt_stats* stats)
+{
+    return traceBatch(h, n, RayBatch{org, dir, t_max, t, tri, uv, nullptr}, t_max ? QUERY_CLOSEST : QUERY_NONE, false, (hipStream_t)hip_stream, stats,
+                      "trt_trace_closest_device");
+}
+
+int trt_trace_occluded(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max, uint8_t* occluded, trt_stats* stats)
+{
+    return traceBatch(h, n, RayBatch{org, dir, t_max, nullptr, nullptr, nullptr, occluded}, QUERY_OCCLUDED, true, nullptr, stats, "trt_trace_occluded");
+}
+
+int trt_trace_occluded_device(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max, uint8_t* occluded, void* hip_stream,
+                              trt_stats* stats)
+{
+    return traceBatch(h, n, RayBatch{org, dir, t_max, nullptr, nullptr, nullptr, occluded}, QUERY_OCCLUDED, false, (hipStream_t)hip_stream, stats,
+                      "trt_trace_occluded_device");
 }
 
 }  // extern "C"

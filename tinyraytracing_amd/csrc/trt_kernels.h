@@ -262,13 +262,23 @@ struct TraceProbe {  // COUNT builds only: work and SIMD utilisation of the two 
     uint32_t c_in = 0, c_lf = 0, c_done = 0, c_it = 0;  // lane 0: the census of DeviceStats
 };
 
+// The ray queries of trt_trace_closest_range / trt_trace_occluded (include/trt.h): a third store mode of the traversal drivers, the QUERY
+// template parameter.  Both read the ray's bound from rb.w (k_pack_rays_bounded): the walk starts with best_t = bound, so only hits STRICTLY
+// nearer count (traceClosestPass's t_init).  QUERY_NONE is the render's closest hit or shadow ray and leaves those kernels as they were.
+constexpr int QUERY_NONE = 0;
+constexpr int QUERY_CLOSEST = 1;   // the closest-hit record; nothing in front of the bound: the miss record (TRT_INF, -1, 0, 0)
+constexpr int QUERY_OCCLUDED = 2;  // the `any` walk of TRT_FLAG_FIXED_NEE's shadow rays (SHADOW = true); one byte per ray, no sw / Lacc
+
 // result of one ray: hit record (closest) or the NEE accumulation (shadow).  HIT8: the 8-byte record (t, bits(tri)) of the wave-uniform
-// walk; k_shade re-evaluates the winner for (u, v) itself (hitBarycentrics).
-template <bool SHADOW, bool HIT8 = false>
+// walk; k_shade re-evaluates the winner for (u, v) itself (hitBarycentrics).  QUERY_OCCLUDED: `hit` is the byte array of the query.
+template <bool SHADOW, bool HIT8 = false, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void storeResult(const SceneDev& sc, f3 o, f3 d, float best_t, int32_t best_tri, uint32_t best_flags, uint32_t idx, uint32_t pid,
                                             f4* __restrict__ hit, const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, bool any)
 {
-    if (!SHADOW && HIT8) {
+    if (QUERY == QUERY_CLOSEST && best_tri < 0) best_t = TRT_INF;  // (best_t still holds the bound)
+    if constexpr (QUERY == QUERY_OCCLUDED) {
+        reinterpret_cast<uint8_t*>(hit)[idx] = best_tri >= 0 ? 1u : 0u;
+    } else if (!SHADOW && HIT8) {
         const trt_v2f r = {best_t, u2f((uint32_t)best_tri)};
         TRT_STQ2(8, reinterpret_cast<trt_v2f*>(hit) + idx, r);
     } else if (!SHADOW) {
@@ -296,7 +306,7 @@ __device__ __forceinline__ void storeResult(const SceneDev& sc, f3 o, f3 d, floa
 // the check: nothing is stored then and the caller puts the ray on the redo list.
 // OCT: the result of a traversal of the quantised 8-wide nodes (trt_oct.h) counts only if the ray also passes the reference's test of the
 // exact box of the triangle's leaf.
-template <bool SHADOW, bool OCT = false>
+template <bool SHADOW, bool OCT = false, int QUERY = QUERY_NONE>
 __device__ __forceinline__ bool checkedStore(const SceneDev& sc, f3 o, f3 d, f3 inv, float best_t, int32_t best_tri, uint32_t best_flags, uint32_t idx, uint32_t pid,
                                              f4* __restrict__ hit, const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, bool any)
 {
@@ -315,7 +325,12 @@ __device__ __forceinline__ bool checkedStore(const SceneDev& sc, f3 o, f3 d, f3 
             float t, un, vn, det;
             if (triTest(T, o, d, t, un, vn, det)) { u = un / det; v = vn / det; }
         }
-        TRT_STQ(8, hit + idx, mk4(best_t, u2f((uint32_t)best_tri), u, v));
+        TRT_STQ(8, hit + idx, mk4(QUERY == QUERY_CLOSEST && best_tri < 0 ? TRT_INF : best_t, u2f((uint32_t)best_tri), u, v));
+    } else if constexpr (QUERY == QUERY_OCCLUDED) {
+        float e;
+        const bool pass = boxTest(ba.x, ba.y, ba.z, ba.w, bb.x, bb.y, o, inv, e);
+        if (special || (best_tri >= 0 && ((OCT && !pass) || best_t < trt_leaf_floor(e, sc.leaf_alpha)))) return true;
+        reinterpret_cast<uint8_t*>(hit)[idx] = best_tri >= 0 ? 1u : 0u;
     } else {
         const bool vis = any ? best_tri < 0 : (best_tri >= 0 && (best_flags >> 8) == light_mat);
         f4 w = mk4(0, 0, 0, 0), L = w;
@@ -445,12 +460,13 @@ __device__ __forceinline__ void uniformWalk(const SceneDev& sc, f3 o, f3 d, bool
 // HIT8: closest hits are stored as 8-byte records (storeResult).  PIPE (trt_create: every scene of this walk, unless TRT_SLIM_WALK=0): the flag words
 // of the triangles are staged in LDS (uniformWalkImpl FLAGS_LDS), so the walk issues no vector memory access.  (Also measured: the queue rays of the
 // next batch requested before the walk of this one — +0.2 % on `back`, inside the noise of the A/B: removed, profiles/r05_slim_walk.txt.)
-template <bool SHADOW, bool COUNT, int PRIMARY, bool HIT8 = false, bool PIPE = false>
+template <bool SHADOW, bool COUNT, int PRIMARY, bool HIT8 = false, bool PIPE = false, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                                   const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, DeviceStats* stats, bool any_flag,
                                                   f4* __restrict__ pend)
 {
-    const bool any = SHADOW && any_flag;  // occlusion test (TRT_FLAG_FIXED_NEE): the ray carries its own t_max in rb.w
+    const bool any = SHADOW && (QUERY == QUERY_OCCLUDED || any_flag);  // occlusion test (TRT_FLAG_FIXED_NEE): the ray carries its own t_max in rb.w
+    const bool bounded = any || QUERY != QUERY_NONE;                      // so do the rays of a query
     uint32_t n_inner = 0, n_tri = 0;
     const uint32_t lb = xcdSwizzle(blockIdx.x, gridDim.x);
     const uint32_t stride = gridDim.x * TRT_TRACE_BLOCK;
@@ -477,12 +493,12 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
             f4 a, b;
             fetchRay<PRIMARY>(sc, src, i, a, b);
             const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
-            float best_t = any ? b.w : TRT_INF;
+            float best_t = bounded ? b.w : TRT_INF;
             int32_t best_tri = -1;
             uint32_t best_flags = 0u;
             uint32_t ni = 0, nt = 0;
             uniformWalkImpl<false, TRT_TRACE_BLOCK, true, PIPE>(sc, o, d, mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), valid, valid, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
-            if (valid) storeResult<SHADOW, HIT8>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
+            if (valid) storeResult<SHADOW, HIT8, QUERY>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         }
         if (lane == 0 && n_parked) atomicAdd(&stats->redo_rays, n_parked);
         n_parked = 0;
@@ -495,12 +511,12 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
         fetchRay<PRIMARY>(sc, src, ii, a, b);
         const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
         const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-        float best_t = any ? b.w : TRT_INF;
+        float best_t = bounded ? b.w : TRT_INF;
         int32_t best_tri = -1;
         uint32_t best_flags = 0u;
         uniformWalkImpl<COUNT, TRT_TRACE_BLOCK, false, PIPE>(sc, o, d, inv, valid, false, my_pend, best_t, best_tri, best_flags, n_inner, n_tri, s_flags);
         const bool special = valid && raySpecial(inv);
-        if (valid && !special) storeResult<SHADOW, HIT8>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
+        if (valid && !special) storeResult<SHADOW, HIT8, QUERY>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         const unsigned long long m_sp = ballotb(special);
         if (m_sp != 0ull) {  // (wave-uniform, rare)
             const uint32_t at = n_parked + (uint32_t)__popcll(m_sp & ((1ull << lane) - 1ull));
@@ -521,12 +537,12 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
             const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
             const bool special = valid && raySpecial(inv);
             if (ballotb(special) == 0ull) continue;
-            float best_t = any ? b.w : TRT_INF;
+            float best_t = bounded ? b.w : TRT_INF;
             int32_t best_tri = -1;
             uint32_t best_flags = 0u;
             uint32_t ni = 0, nt = 0;
             uniformWalkImpl<false, TRT_TRACE_BLOCK, true, PIPE>(sc, o, d, inv, special, special, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
-            if (special) storeResult<SHADOW, HIT8>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
+            if (special) storeResult<SHADOW, HIT8, QUERY>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         }
         if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
     }
@@ -540,7 +556,7 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
 }
 
 
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK>
+template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo)
@@ -549,7 +565,7 @@ __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const R
     stk.lds = smem + threadIdx.x;
     stk.spill = spill + (size_t)blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x;
     stk.spill_stride = spill_stride;
-    const bool any = SHADOW && any_flag;  // occlusion test (TRT_FLAG_FIXED_NEE): the ray carries its own t_max in rb.w
+    const bool any = SHADOW && (QUERY == QUERY_OCCLUDED || any_flag);  // occlusion test (TRT_FLAG_FIXED_NEE): the ray carries its own t_max in rb.w
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long lower = (1ull << lane) - 1ull;
     // contiguous queue slice of this wave (XCD-aware: neighbouring slices share an L2)
@@ -584,7 +600,7 @@ __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const R
             if (cur == TRT_REF_DONE) {
                 // a hit in front of the box of its own leaf does not count (leafEntry(), trt_path.h): the result is checked once per ray,
                 // and the (one in ~10^7) rays that end on such a hit go to k_trace_fix instead of being stored
-                if (checkedStore<SHADOW>(sc, o, d, inv, best_t, best_tri, best_flags, idx, pid, hit, sw, light_mat, Lacc, any)) redo.idx[atomicAdd(redo.count, 1u)] = idx;
+                if (checkedStore<SHADOW, false, QUERY>(sc, o, d, inv, best_t, best_tri, best_flags, idx, pid, hit, sw, light_mat, Lacc, any)) redo.idx[atomicAdd(redo.count, 1u)] = idx;
                 cur = TRT_REF_IDLE;
             }
             if (can_fill) {
@@ -597,7 +613,7 @@ __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const R
                     d = mk3(a.w, b.x, b.y);
                     if (SHADOW) pid = f2u(b.z);
                     inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-                    best_t = SHADOW ? b.w : TRT_INF; best_tri = -1; best_flags = 0u;  // shadow rays carry a bound: t_max (any) or a search hint
+                    best_t = (SHADOW || QUERY != QUERY_NONE) ? b.w : TRT_INF; best_tri = -1; best_flags = 0u;  // shadow rays carry a bound: t_max (any) or a search hint; queries their bound
                     sp = 0;
                     cur = 0u;  // nodes[0] is always an inner node
                     lk = 0; lt = TRT_INF; li = -1;
@@ -687,7 +703,7 @@ __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const R
 // brings a group of up to 24 triangles per node and gets a longer loop (trt_create; TRT_LEAF_LOOP in the environment overrides).
 // (Also measured: the root and its children read from an LDS copy — a fifth of all node fetches on veach-mis —: +-0.3 %.  These kernels
 // are bound by VALU issue, profiles/r03_roofs_stair.txt, not by the texture addresser.  Removed.)
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int PRIMARY>
+template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int PRIMARY, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo, const LightBox& lbox)
@@ -696,7 +712,7 @@ __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, cons
     stk.lds = smem + threadIdx.x;
     stk.spill = spill + (size_t)blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x;
     stk.spill_stride = spill_stride;
-    const bool any = SHADOW && any_flag;
+    const bool any = SHADOW && (QUERY == QUERY_OCCLUDED || any_flag);
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long lower = (1ull << lane) - 1ull;
     const uint32_t n_waves = gridDim.x * (TRT_TRACE_BLOCK / 64);
@@ -730,8 +746,8 @@ __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, cons
         if (m_work == 0ull || (m_done != 0ull && (uint32_t)__popcll(can_fill ? m_free : m_done) >= sc.refill_min)) {
             if (done) {
                 const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);  // the exact reciprocals (R.inv stands in 2^40 for an infinite one)
-                const uint32_t pid = SHADOW ? f2u(src.rb[idx].z) : 0u;    // read again here instead of carried through the traversal
-                if (checkedStore<SHADOW, true>(sc, R.o, d, inv, best_t, best_tri, best_flags, idx, pid, hit, sw, light_mat, Lacc, any)) redo.idx[atomicAdd(redo.count, 1u)] = idx;
+                const uint32_t pid = (SHADOW && QUERY == QUERY_NONE) ? f2u(src.rb[idx].z) : 0u;    // read again here instead of carried through the traversal
+                if (checkedStore<SHADOW, true, QUERY>(sc, R.o, d, inv, best_t, best_tri, best_flags, idx, pid, hit, sw, light_mat, Lacc, any)) redo.idx[atomicAdd(redo.count, 1u)] = idx;
                 idx = NO_RAY;
             }
             if (can_fill) {
@@ -743,7 +759,7 @@ __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, cons
                     d = mk3(a.w, b.x, b.y);
                     const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
                     R = makeOctRay(mk3(a.x, a.y, a.z), d, inv);
-                    best_t = SHADOW ? b.w : TRT_INF; best_tri = -1; best_flags = 0u;
+                    best_t = (SHADOW || QUERY != QUERY_NONE) ? b.w : TRT_INF; best_tri = -1; best_flags = 0u;
                     sp = 0;
                     ng.x = 0u; ng.y = 0x80000000u;  // the root
                     tg.y = 0u;
@@ -818,15 +834,15 @@ __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, cons
     }
 }
 
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, bool HIT8 = false, bool PIPE = false>
+template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, bool HIT8 = false, bool PIPE = false, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void traceQueue(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo, const LightBox& lbox)
 {
     static_assert(IMPL == 0 || !(HIT8 || PIPE), "8-byte hit records and the flags in LDS belong to the wave-uniform walk");
-    if constexpr (IMPL == 0) traceQueueUniform<SHADOW, COUNT, PRIMARY, HIT8, PIPE>(sc, src, n, hit, sw, light_mat, Lacc, stats, any_flag, reinterpret_cast<f4*>(smem));
-    else if constexpr (NK == 1) traceQueuePersistentOct<SHADOW, COUNT, DEPTH, SPILL, PRIMARY>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo, lbox);
-    else traceQueuePersistent<SHADOW, COUNT, DEPTH, SPILL, IMPL, PRIMARY, NK>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo);
+    if constexpr (IMPL == 0) traceQueueUniform<SHADOW, COUNT, PRIMARY, HIT8, PIPE, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, stats, any_flag, reinterpret_cast<f4*>(smem));
+    else if constexpr (NK == 1) traceQueuePersistentOct<SHADOW, COUNT, DEPTH, SPILL, PRIMARY, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo, lbox);
+    else traceQueuePersistent<SHADOW, COUNT, DEPTH, SPILL, IMPL, PRIMARY, NK, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo);
 }
 
 // PRIMARY: bounce 0 — ray i is the camera ray of path i, generated in registers (K1 of SURVEY.md §7 fused
@@ -856,12 +872,25 @@ __global__ TRT_TRACE_BOUNDS void k_trace_shadow(SceneDev sc, ShadowQueue sq, uin
     traceQueue<true, COUNT, DEPTH, SPILL, IMPL, false, NK, false, PIPE>(sc, src, n, nullptr, sq.sw, light_mat, Lacc, spill, spill_stride, stats, smem, any != 0u, redo, lbox);
 }
 
+// The ray-batch queries (QUERY_CLOSEST, QUERY_OCCLUDED) on the packed rays of src (rb.w: the bound), on the driver the scene picked.  Same arguments
+// as k_trace_closest; QUERY_OCCLUDED takes `hit` as its byte array and counts as a shadow walk (DeviceStats slot 1).  HIT8, PIPE: traceQueueUniform.
+template <int QUERY, bool COUNT, int DEPTH, bool SPILL, int IMPL, int NK, bool HIT8 = false, bool PIPE = false>
+__global__ TRT_TRACE_BOUNDS void k_trace_query(SceneDev sc, RaySource src, f4* __restrict__ hit, uint32_t n,
+                                               uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, RedoList redo)
+{
+    static_assert(QUERY == QUERY_CLOSEST || QUERY == QUERY_OCCLUDED, "k_trace_closest serves the unbounded closest hit");
+    __shared__ __attribute__((aligned(16))) uint32_t smem[IMPL == 0 ? TRT_PEND_SLOTS * 4 * TRT_TRACE_BLOCK : (NK == 1 ? 2 : 1) * DEPTH * TRT_TRACE_BLOCK];
+    const LightBox nobox = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+    constexpr bool OCC = QUERY == QUERY_OCCLUDED;
+    traceQueue<OCC, COUNT, DEPTH, SPILL, IMPL, 0, NK, HIT8, PIPE, QUERY>(sc, src, n, hit, nullptr, 0u, nullptr, spill, spill_stride, stats, smem, OCC, redo, nobox);
+}
+
 // The exact form of the traversal for the rays a traversal launch put on its redo list (see RedoList): a few blocks, launched
 // behind every launch of k_trace_closest / k_trace_shadow of a per-lane driver; it finds an empty list all but once in ~10^7 rays
 // on padded trees.  redo.count[0] = length of the list, redo.count[1] = blocks of this launch that are through: the last one adds
 // the length to DeviceStats::redo_rays (trt_stats.redo_rays: how often the slow path ran is visible to the caller) and empties the list.
 constexpr uint32_t TRT_FIX_BLOCKS = 32;
-template <bool SHADOW, int PRIMARY, int NK>
+template <bool SHADOW, int PRIMARY, int NK, int QUERY = QUERY_NONE>
 __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_trace_fix(SceneDev sc, RaySource src, f4* __restrict__ hit, const f4* __restrict__ sw, uint32_t light_mat,
                                                                f4* __restrict__ Lacc, uint32_t* __restrict__ spill, uint32_t spill_stride, RedoList redo, uint32_t any_flag,
                                                                DeviceStats* stats)
@@ -874,7 +903,7 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_trace_fix(SceneDev sc, RayS
         stk.lds = smem + threadIdx.x;
         stk.spill = spill + (size_t)blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x;
         stk.spill_stride = spill_stride;
-        const bool any = SHADOW && any_flag != 0u;
+        const bool any = SHADOW && (QUERY == QUERY_OCCLUDED || any_flag != 0u);
         for (uint32_t k = blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x; k < n; k += gridDim.x * TRT_TRACE_BLOCK) {
             const uint32_t i = redo.idx[k];
             f4 a, b;
@@ -882,10 +911,14 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_trace_fix(SceneDev sc, RayS
             const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
             uint32_t ni = 0, nt = 0;
             const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-            const Hit h = (raySpecial(inv) && rayOnABoxPlane(sc, o, inv))
-                              ? traceClosestBvh2Glm<LdsStack<TRT_LDS_STACK_MAX, true>, false>(sc, o, d, stk, ni, nt, SHADOW ? b.w : TRT_INF, any)
-                              : traceClosestPass<LdsStack<TRT_LDS_STACK_MAX, true>, false, NK, true>(sc, o, d, stk, ni, nt, SHADOW ? b.w : TRT_INF, any, SHADOW && !any);
-            storeResult<SHADOW>(sc, o, d, h.t, h.tri, h.flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
+            const float t_init = (SHADOW || QUERY != QUERY_NONE) ? b.w : TRT_INF;
+            Hit h = (raySpecial(inv) && rayOnABoxPlane(sc, o, inv))
+                        ? traceClosestBvh2Glm<LdsStack<TRT_LDS_STACK_MAX, true>, false>(sc, o, d, stk, ni, nt, t_init, any)
+                        : traceClosestPass<LdsStack<TRT_LDS_STACK_MAX, true>, false, NK, true>(sc, o, d, stk, ni, nt, t_init, any, SHADOW && !any);
+            // the literal walk ignores t_init in closest mode: its (unbounded) closest hit, clipped to the bound — at equal t every tied candidate
+            // lies on the same side of it, so this is the closest hit inside the bound
+            if (QUERY == QUERY_CLOSEST && !(h.t < b.w)) h.tri = -1;
+            storeResult<SHADOW, false, QUERY>(sc, o, d, h.t, h.tri, h.flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         }
     }
     __syncthreads();
@@ -1490,15 +1523,28 @@ __global__ __launch_bounds__(1024) void k_publish_counts(const uint32_t* __restr
     }
 }
 
-// ray-batch entry on a scene with 8-byte hit records (trt_handle::hit8): the 16-byte records the caller gets, (u, v) formed as k_shade forms them
-__global__ __launch_bounds__(256) void k_hit_uv(SceneDev sc, const f4* __restrict__ ra, const f4* __restrict__ rb, const f4* __restrict__ hit8, f4* __restrict__ out, uint32_t n)
+// ray-batch entries (trt_trace_closest*): the hit records into the caller's arrays t[n], tri[n], uv[n][2] (uv may be null).  HIT8: the 8-byte
+// records of a scene with trt_handle::hit8, (u, v) formed on the packed ray as k_shade forms them.
+template <bool HIT8>
+__global__ __launch_bounds__(256) void k_unpack_hits(SceneDev sc, const f4* __restrict__ ra, const f4* __restrict__ rb, const f4* __restrict__ hit, float* __restrict__ t,
+                                                     int32_t* __restrict__ tri, float* __restrict__ uv, uint32_t n)
 {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const trt_v2f h = reinterpret_cast<const trt_v2f*>(hit8)[i];
-        f4 hit4 = mk4(h.x, h.y, 0.0f, 0.0f);
-        hitBarycentrics(sc.tri_isect, ra[i], rb[i], hit4);
-        out[i] = hit4;
+        f4 hit4;
+        if constexpr (HIT8) {
+            const trt_v2f h = reinterpret_cast<const trt_v2f*>(hit)[i];
+            hit4 = mk4(h.x, h.y, 0.0f, 0.0f);
+            if (uv) hitBarycentrics(sc.tri_isect, ra[i], rb[i], hit4);
+        } else {
+            hit4 = hit[i];
+        }
+        t[i] = hit4.x;
+        tri[i] = (int32_t)f2u(hit4.y);
+        if (uv) {
+            const trt_v2f w = {hit4.z, hit4.w};
+            reinterpret_cast<trt_v2f*>(uv)[i] = w;
+        }
     }
 }
 
@@ -1509,6 +1555,18 @@ __global__ __launch_bounds__(256) void k_pack_rays(const float* __restrict__ org
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         ra[i] = mk4(org[(size_t)i * 3], org[(size_t)i * 3 + 1], org[(size_t)i * 3 + 2], dir[(size_t)i * 3]);
         rb[i] = mk4(dir[(size_t)i * 3 + 1], dir[(size_t)i * 3 + 2], u2f(i), 0.0f);
+    }
+}
+// the same for the ray queries, with each ray's bound in rb.w: t_max[i] > TRT_T_MIN ? min(t_max[i], TRT_INF) : TRT_T_MIN (NaN, negative values, 0
+// and TRT_T_MIN find nothing; +inf and anything beyond TRT_INF are TRT_INF, Q7); t_max null: TRT_INF for every ray
+__global__ __launch_bounds__(256) void k_pack_rays_bounded(const float* __restrict__ org, const float* __restrict__ dir, const float* __restrict__ t_max,
+                                                           f4* __restrict__ ra, f4* __restrict__ rb, uint32_t n)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float m = t_max ? t_max[i] : TRT_INF;
+        ra[i] = mk4(org[(size_t)i * 3], org[(size_t)i * 3 + 1], org[(size_t)i * 3 + 2], dir[(size_t)i * 3]);
+        rb[i] = mk4(dir[(size_t)i * 3 + 1], dir[(size_t)i * 3 + 2], u2f(i), m > TRT_T_MIN ? fminf(m, TRT_INF) : TRT_T_MIN);
     }
 }
 
