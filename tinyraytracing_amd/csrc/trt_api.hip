@@ -104,6 +104,8 @@ struct trt_handle {
     // The wave-uniform walk's faster kernels (trt_kernels.h traceQueueUniform PIPE / HIT8); TRT_SLIM_WALK=0 at trt_create keeps the earlier ones (A/B, tests):
     bool slim_walk = false;   // both walk kernels read the triangles' flag words from an LDS copy
     bool hit8 = false;        // and the render's hit records are 8 bytes (t, bits(tri)); k_shade forms (u, v) itself — needs k_shade<31> (every table in LDS)
+    bool bin_walk = false;    // and the closest-hit queue kernel sorts each wave's rays by the leaves they reach (trt_kernels.h traceQueueBinned; TRT_BIN_WALK=0 at
+                              // trt_create keeps traceQueueUniform's kernel: A/B, tests)
     int node_kind = 0;        // what the persistent traversal kernels walk: 0 exact 128-B 4-wide nodes, 1 compressed 80-B 8-wide nodes (trt_oct.h)
     uint32_t oct_levels = 0;  // nodes on the longest root path of the oct tree
     bool dbg = false;         // TRT_DEBUG at trt_create: every render prints which k_shade variant it runs
@@ -344,6 +346,7 @@ int traversalOf(const trt_handle* h) { return h->trace_impl == 0 ? 0 : (h->node_
 // primary: 0 the queue, 1 the camera rays of a tile, PRIMARY_LIST those of a pixel list.  With h->hit8 the kernel stores 8-byte hit records.
 ClosestKernel closestKernel(const trt_handle* h, bool count, int primary)
 {
+    if (h->bin_walk && primary == 0) return count ? k_trace_closest_binned<true> : k_trace_closest_binned<false>;
     if (h->trace_impl == 0 && h->hit8) {
         const ClosestKernel s[2][3] = {
             {k_trace_closest<false, 1, false, 0, 0, 0, true, true>, k_trace_closest<false, 1, false, 0, 1, 0, true, true>, k_trace_closest<false, 1, false, 0, PRIMARY_LIST, 0, true, true>},
@@ -709,7 +712,9 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->slim_walk = h->trace_impl == 0 && s->n_tris <= 64;  // (trace_impl 0 implies <= 64 triangles: the LDS copies of trt_kernels.h hold 64)
     if (const char* e = std::getenv("TRT_SLIM_WALK")) h->slim_walk = h->slim_walk && std::atoi(e) != 0;
     h->hit8 = h->slim_walk && h->shade_tabs == 31u;
-    if (im.dbg) std::fprintf(stderr, "trt_create: slim walk %d, 8-byte hit records %d\n", (int)h->slim_walk, (int)h->hit8);
+    h->bin_walk = h->hit8;  // (the flags in LDS and the 8-byte records: what traceQueueBinned's kernel is built for)
+    if (const char* e = std::getenv("TRT_BIN_WALK")) h->bin_walk = h->bin_walk && std::atoi(e) != 0;
+    if (im.dbg) std::fprintf(stderr, "trt_create: slim walk %d, 8-byte hit records %d, binned walk %d\n", (int)h->slim_walk, (int)h->hit8, (int)h->bin_walk);
 
     // traversal spill area: levels beyond the LDS stack, for the largest grid
     // (k_trace_fix / k_tail walk the caller's BVH2 itself for the rays of raySpecial(), trt_path.h: one entry per level of it)

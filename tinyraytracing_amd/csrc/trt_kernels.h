@@ -364,6 +364,56 @@ __device__ __forceinline__ bool checkedStore(const SceneDev& sc, f3 o, f3 d, f3 
 // emissive, one of ANOTHER leaf by "leftmost emissive, else rightmost" — what the leaf-local fold followed by
 // the between-leaves merge yields, since the leaves are disjoint index ranges.
 constexpr int TRT_PEND_SLOTS = 4;
+// Division + cut + fold of every parked candidate of the lane, slot by slot (= in the order they were found); empties the queue.
+template <int STRIDE, bool FLAGS_LDS>
+__device__ __forceinline__ void flushPending(const SceneDev& sc, const f4* __restrict__ my_pend, uint32_t& n_pend, float& best_t, int32_t& best_tri,
+                                             uint32_t& best_flags, const uint32_t* tri_flags)
+{
+    for (uint32_t s = 0; ballotb(s < n_pend) != 0ull; ++s) {
+        if (s < n_pend) {
+            const f4 e = my_pend[s * STRIDE];
+            const float t = e.x / e.y;
+            if (!(t < TRT_T_MIN) && !(t < e.w)) {  // bvh.cpp:189; and not in front of the box of its leaf (leafFloor(), trt_path.h)
+                const uint32_t pk = f2u(e.z);  // triangle index | first triangle of its leaf << 8 | triangles in the leaf << 16 (<= 64 triangles here)
+                const int32_t j = (int32_t)(pk & 0xFFu);
+                const uint32_t fl = FLAGS_LDS ? tri_flags[j] : f2u(sc.tri_isect[j].c.z);
+                bool take = t < best_t;
+                if (t == best_t && best_tri >= 0) {
+                    const bool em = (fl & 1u) != 0, bem = (best_flags & 1u) != 0;
+                    const uint32_t first = (pk >> 8) & 0xFFu, cnt = pk >> 16;
+                    const bool same_leaf = (uint32_t)best_tri >= first && (uint32_t)best_tri < first + cnt;
+                    take = same_leaf ? em : (em ? (!bem || j < best_tri) : (!bem && j > best_tri));
+                }
+                if (take) { best_t = t; best_tri = j; best_flags = fl; }
+            }
+        }
+    }
+    n_pend = 0;
+}
+// The triangles of one leaf (`ref`) for the lanes that reach it (`hc`; m_hc = the wave's vote on it, not empty), in index order (interactBVHNode,
+// bvh.cpp:211-229): every candidate is parked with `floor`, the floor of the leaf's box for this lane's ray (leaf-box rule).  uniformWalkImpl keeps its own
+// copy of this loop: calling this one from it changed the code of 24 kernels by a few instructions.
+template <bool COUNT, int STRIDE, bool FLAGS_LDS>
+__device__ __forceinline__ void walkLeaf(const SceneDev& sc, f3 o, f3 d, bool hc, unsigned long long m_hc, uint32_t ref, float floor, f4* __restrict__ my_pend,
+                                         uint32_t& n_pend, float& best_t, int32_t& best_tri, uint32_t& best_flags, uint32_t& n_tri, const uint32_t* tri_flags)
+{
+    const uint32_t first = TRT_LEAF_FIRST(ref), count = TRT_LEAF_COUNT(ref);
+    for (uint32_t k = 0; k < count; ++k) {
+        const TriIsect T = sc.tri_isect[first + k];  // wave-uniform address
+        if (COUNT && hc) n_tri++;
+        float tn, un, vn, det;
+        bool ok_det, ok_in;
+        triCandidateParts(T, o, d, tn, un, vn, det, ok_det, ok_in);
+        const bool cand = ok_det && ok_in && hc;
+        // a full queue among the candidates: empty all of them first (votes on the single compares: their own lane masks)
+        if ((ballotb(ok_det) & ballotb(ok_in) & m_hc & ballotb(n_pend == (uint32_t)TRT_PEND_SLOTS)) != 0ull)
+            flushPending<STRIDE, FLAGS_LDS>(sc, my_pend, n_pend, best_t, best_tri, best_flags, tri_flags);
+        if (cand) {
+            my_pend[n_pend * STRIDE] = mk4(tn, det, u2f((first + k) | (first << 8) | (count << 16)), floor);
+            n_pend++;
+        }
+    }
+}
 // The walk itself for the rays the active lanes of a wave hold (`valid`: this lane has one).  best_t comes in as the
 // bound of the search (TRT_INF, or an occlusion range) and goes out with best_tri / best_flags as the closest hit.
 // GLM: this wave holds a ray with a zero direction component (`special` lanes): those lanes take the literal slab test (trt_path.h boxTestGlm: a NaN from 0 * inf
@@ -377,29 +427,7 @@ __device__ __forceinline__ void uniformWalkImpl(const SceneDev& sc, f3 o, f3 d, 
     const uint32_t n_nodes = sc.n_nodes;
     uint32_t reach = valid ? 1u : 0u;  // bit k: the ray reaches inner node k
     uint32_t n_pend = 0;
-    // division + cut + fold of every parked candidate, slot by slot (= in the order they were found)
-    auto flush = [&]() {
-        for (uint32_t s = 0; ballotb(s < n_pend) != 0ull; ++s) {
-            if (s < n_pend) {
-                const f4 e = my_pend[s * STRIDE];
-                const float t = e.x / e.y;
-                if (!(t < TRT_T_MIN) && !(t < e.w)) {  // bvh.cpp:189; and not in front of the box of its leaf (leafFloor(), trt_path.h)
-                    const uint32_t pk = f2u(e.z);  // triangle index | first triangle of its leaf << 8 | triangles in the leaf << 16 (<= 64 triangles here)
-                    const int32_t j = (int32_t)(pk & 0xFFu);
-                    const uint32_t fl = FLAGS_LDS ? tri_flags[j] : f2u(sc.tri_isect[j].c.z);
-                    bool take = t < best_t;
-                    if (t == best_t && best_tri >= 0) {
-                        const bool em = (fl & 1u) != 0, bem = (best_flags & 1u) != 0;
-                        const uint32_t first = (pk >> 8) & 0xFFu, cnt = pk >> 16;
-                        const bool same_leaf = (uint32_t)best_tri >= first && (uint32_t)best_tri < first + cnt;
-                        take = same_leaf ? em : (em ? (!bem || j < best_tri) : (!bem && j > best_tri));
-                    }
-                    if (take) { best_t = t; best_tri = j; best_flags = fl; }
-                }
-            }
-        }
-        n_pend = 0;
-    };
+    auto flush = [&]() { flushPending<STRIDE, FLAGS_LDS>(sc, my_pend, n_pend, best_t, best_tri, best_flags, tri_flags); };
     for (uint32_t ni = 0; ni < n_nodes; ++ni) {
         const bool at = (reach >> ni) & 1u;
         if (ballotb(at) == 0ull) continue;
@@ -555,6 +583,235 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
     }
 }
 
+// BIN (trt_create: the closest-hit queue kernel of this walk, unless TRT_BIN_WALK=0): the walk above tests every triangle of a leaf as soon as ONE lane of
+// the wave reaches it, so a wave of incoherent rays pays for the union of its rays' leaves.  Which leaves a ray reaches depends on the box tests alone (the
+// walk is the reference's whole visit set: no culling by the best hit), so it is known before any triangle is tested.  A wave takes the rays of
+// TRT_BIN_GROUP of its batches at once (the queue positions traceQueueUniform gives it, so no ray changes wave):
+//   1. mask   per batch, the inner nodes walked as uniformWalkImpl walks them, box tests only: bit k of a ray's mask = it reaches the k-th leaf in walk
+//             order (node index, child 0 before child 1; <= 33 leaves under <= 32 inner nodes);
+//   2. bin    a counting sort of the wave's rays by mask (the low 8 bits; with more than 8 leaves, bit k stands for a run of consecutive leaves) in the
+//             wave's own part of the candidate queue's LDS (the masks wait there too): histogram, prefix sum, scatter of (queue index, mask); lane l
+//             then holds the rays of rank l, 64 + l, ... (registers);
+//   3. walk   per batch of 64 sorted rays, the ray fetched again by its index, the leaves of the wave's masks in the same order, with the triangles in
+//             the same order and walkLeaf's candidate queue and fold; a leaf's floor is formed again from its box (same test, same ray: same bits).
+// For every ray the candidates, their order and the rules are uniformWalkImpl's: the results are the same bits, stored at the ray's own queue index.
+// The counters are too (inner nodes by the lane that walked the mask, triangles where the lane's ray reaches the leaf).  Rays with a zero direction
+// component are parked and walked again exactly as in traceQueueUniform.  Measured and removed (profiles/r06_binned_walk.txt): a block-wide sort of
+// 256 rays with the rays exchanged through LDS (five barriers per batch: VALU -18 %, time +58 %); the same sort for the shadow rays (+11 %: the
+// bounce-0 shadow rays of the Cornell box all reach the same leaves) and for the camera rays (already coherent).
+// 8 waves per SIMD, as traceQueueUniform's kernels (64 VGPRs; left to the compiler: 68-72 VGPRs, 7 waves)
+#define TRT_BIN_WAVES __attribute__((amdgpu_waves_per_eu(8)))
+#ifndef TRT_BIN_GROUP
+#define TRT_BIN_GROUP 4
+#endif
+constexpr uint32_t TRT_BIN_KEYS = 256;
+__device__ __forceinline__ void waveSync()  // orders the LDS accesses of the wave's lanes (DS instructions of one wave complete in order)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <bool COUNT>
+__device__ __forceinline__ void traceQueueBinned(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit, DeviceStats* stats, f4* __restrict__ pend)
+{
+    constexpr uint32_t B = TRT_TRACE_BLOCK, G = TRT_BIN_GROUP;
+    static_assert(G * 64u == TRT_BIN_KEYS && TRT_PEND_SLOTS == 4, "one wave sorts 256 rays; its four 256-word pieces of the candidate queue hold the sort");
+    uint32_t n_inner = 0, n_tri = 0;
+    const uint32_t lb = xcdSwizzle(blockIdx.x, gridDim.x);
+    const uint32_t stride = gridDim.x * B;
+    f4* my_pend = pend + threadIdx.x;  // slot s of this lane: my_pend[s * B]
+    const uint32_t lane = threadIdx.x & 63u;
+    // the wave's pieces of the candidate queue (slot s: words [4 (s B + 64 w), + 256)): histogram, then the sorted queue indices and masks
+    uint32_t* piece = reinterpret_cast<uint32_t*>(pend) + 4u * 64u * (threadIdx.x >> 6);
+    uint32_t* s_hist = piece;
+    uint32_t* x_idx = piece + 4u * B;
+    uint32_t* x_lo = piece + 8u * B;
+    uint32_t* x_hi = piece + 12u * B;
+    __shared__ uint32_t s_flags[64];
+    __shared__ uint32_t s_parked[2 * B];
+    uint32_t* my_parked = s_parked + (threadIdx.x >> 6) * 128u;
+    const uint32_t n_nodes = sc.n_nodes;
+    // which children are leaves: bit ni of lf0 / lf1 for child 0 / 1 of inner node ni (wave-uniform).  Leaf (ni, c) is leaf number
+    // popc(lf0 & below(ni)) + popc(lf1 & below(ni)) + (c == 1 && child 0 of ni is a leaf) in walk order.
+    bool l0 = false, l1 = false;
+    if (lane < n_nodes) {
+        const f4 q3 = reinterpret_cast<const f4*>(sc.nodes + lane)[3];
+        l0 = (f2u(q3.x) & TRT_LEAF_BIT) != 0u;
+        l1 = (f2u(q3.y) & TRT_LEAF_BIT) != 0u;
+    }
+    const unsigned long long lf0 = ballotb(l0), lf1 = ballotb(l1);
+    const uint32_t run = ((uint32_t)(__popcll(lf0) + __popcll(lf1)) + 7u) >> 3;  // leaves per key bit
+    if (threadIdx.x < (sc.n_tris < 64u ? sc.n_tris : 64u)) s_flags[threadIdx.x] = f2u(sc.tri_isect[threadIdx.x].c.z);
+    __syncthreads();
+    uint32_t n_parked = 0;  // wave-uniform
+    for (uint32_t base0 = lb * B; base0 < n; base0 += G * stride) {
+        // 1. mask, and the rank of each ray in its bin
+        reinterpret_cast<uint4*>(s_hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
+        waveSync();
+#pragma unroll 1
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t i = base0 + j * stride + threadIdx.x;
+            const bool valid = i < n;
+            f4 a, b;
+            fetchRay<0>(sc, src, valid ? i : n - 1, a, b);
+            const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
+            const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+            uint32_t reach = valid ? 1u : 0u;
+            unsigned long long mask = 0ull;
+            for (uint32_t ni = 0; ni < n_nodes; ++ni) {
+                const bool at = (reach >> ni) & 1u;
+                if (ballotb(at) == 0ull) continue;
+                const f4* np4 = reinterpret_cast<const f4*>(sc.nodes + ni);  // wave-uniform address
+                const f4 q0 = np4[0], q1 = np4[1], q2 = np4[2], q3 = np4[3];
+                if (COUNT && at) n_inner++;
+                float e0, e1;
+                const bool h0 = at && boxTest(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, e0);
+                const bool h1 = at && boxTest(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, e1);
+                const unsigned long long below = (1ull << ni) - 1ull;
+                const uint32_t leaf0 = (uint32_t)(__popcll(lf0 & below) + __popcll(lf1 & below));
+                const uint32_t ref0 = f2u(q3.x), ref1 = f2u(q3.y);
+                if (ref0 & TRT_LEAF_BIT) mask |= h0 ? (1ull << leaf0) : 0ull;
+                else reach |= h0 ? (1u << ref0) : 0u;
+                if (ref1 & TRT_LEAF_BIT) mask |= h1 ? (1ull << (leaf0 + ((ref0 & TRT_LEAF_BIT) ? 1u : 0u))) : 0ull;
+                else reach |= h1 ? (1u << ref1) : 0u;
+            }
+            uint32_t key = (uint32_t)mask & (TRT_BIN_KEYS - 1u);
+            if (run > 1u) {
+                key = 0u;
+                for (uint32_t k = 0; k < 8u; ++k) key |= ((mask >> (k * run)) & ((1ull << run) - 1ull)) != 0ull ? (1u << k) : 0u;
+            }
+            x_idx[j * 64u + lane] = key | (atomicAdd(&s_hist[key], 1u) << 8);  // (unsorted until the scatter)
+            x_lo[j * 64u + lane] = (uint32_t)mask;
+            x_hi[j * 64u + lane] = (uint32_t)(mask >> 32);
+        }
+        // 2. bin: exclusive prefix sum over the bins (4 per lane), scatter, and lane l takes ranks l, 64 + l, ...
+        waveSync();
+        const uint4 h = reinterpret_cast<const uint4*>(s_hist)[lane];
+        const uint32_t own = h.x + h.y + h.z + h.w;
+        uint32_t incl = own;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = __shfl_up(incl, off);
+            if ((int)lane >= off) incl += up;
+        }
+        const uint32_t ex = incl - own;
+        reinterpret_cast<uint4*>(s_hist)[lane] = make_uint4(ex, ex + h.x, ex + h.x + h.y, ex + h.x + h.y + h.z);
+        uint32_t rk[G];
+        unsigned long long msk[G];
+#pragma unroll
+        for (uint32_t j = 0; j < G; ++j) {
+            rk[j] = x_idx[j * 64u + lane];
+            msk[j] = (unsigned long long)x_lo[j * 64u + lane] | ((unsigned long long)x_hi[j * 64u + lane] << 32);
+        }
+        waveSync();
+#pragma unroll
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t r = s_hist[rk[j] & 0xFFu] + (rk[j] >> 8);
+            x_idx[r] = base0 + j * stride + threadIdx.x;
+            x_lo[r] = (uint32_t)msk[j];
+            x_hi[r] = (uint32_t)(msk[j] >> 32);
+        }
+        waveSync();
+        uint32_t sidx[G];
+        unsigned long long smask[G];
+#pragma unroll
+        for (uint32_t j = 0; j < G; ++j) {
+            sidx[j] = x_idx[j * 64u + lane];
+            smask[j] = (unsigned long long)x_lo[j * 64u + lane] | ((unsigned long long)x_hi[j * 64u + lane] << 32);
+        }
+        waveSync();  // the sort is read: the candidate queue may be written
+        // 3. walk, 64 sorted rays at a time
+#pragma unroll 1
+        for (uint32_t j = 0; j < G; ++j) {
+            const uint32_t i = sidx[0];
+            const unsigned long long mask = smask[0];
+#pragma unroll
+            for (uint32_t k = 0; k + 1 < G; ++k) { sidx[k] = sidx[k + 1]; smask[k] = smask[k + 1]; }
+            const bool valid = i < n;
+            f4 a, b;
+            fetchRay<0>(sc, src, valid ? i : n - 1, a, b);
+            const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
+            const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+            float best_t = TRT_INF;
+            int32_t best_tri = -1;
+            uint32_t best_flags = 0u;
+            uint32_t n_pend = 0;
+            for (uint32_t ni = 0; ni < n_nodes; ++ni) {
+                const bool c0 = (lf0 >> ni) & 1ull, c1 = (lf1 >> ni) & 1ull;  // wave-uniform
+                if (!c0 && !c1) continue;
+                const unsigned long long below = (1ull << ni) - 1ull;
+                const uint32_t leaf0 = (uint32_t)(__popcll(lf0 & below) + __popcll(lf1 & below));
+                const bool hc0 = c0 && ((mask >> leaf0) & 1ull);
+                const bool hc1 = c1 && ((mask >> (leaf0 + (c0 ? 1u : 0u))) & 1ull);
+                const unsigned long long m0 = ballotb(hc0), m1 = ballotb(hc1);
+                if ((m0 | m1) == 0ull) continue;
+                const f4* np4 = reinterpret_cast<const f4*>(sc.nodes + ni);  // wave-uniform address
+                const f4 q0 = np4[0], q1 = np4[1], q2 = np4[2], q3 = np4[3];
+                if (m0 != 0ull) {
+                    float e = 0.0f;
+                    if (hc0) boxTest(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, e);
+                    walkLeaf<COUNT, B, true>(sc, o, d, hc0, m0, f2u(q3.x), trt_leaf_floor(e, sc.leaf_alpha), my_pend, n_pend, best_t, best_tri, best_flags, n_tri, s_flags);
+                }
+                if (m1 != 0ull) {
+                    float e = 0.0f;
+                    if (hc1) boxTest(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, e);
+                    walkLeaf<COUNT, B, true>(sc, o, d, hc1, m1, f2u(q3.y), trt_leaf_floor(e, sc.leaf_alpha), my_pend, n_pend, best_t, best_tri, best_flags, n_tri, s_flags);
+                }
+            }
+            flushPending<B, true>(sc, my_pend, n_pend, best_t, best_tri, best_flags, s_flags);
+            const bool special = valid && raySpecial(inv);
+            if (valid && !special) storeResult<false, true>(sc, o, d, best_t, best_tri, best_flags, i, 0u, hit, nullptr, 0u, nullptr, false);
+            const unsigned long long m_sp = ballotb(special);
+            if (m_sp != 0ull) {  // (wave-uniform, rare)
+                const uint32_t at = n_parked + (uint32_t)__popcll(m_sp & ((1ull << lane) - 1ull));
+                if (special && at < 128u) my_parked[at] = i;
+                n_parked += (uint32_t)__popcll(m_sp);
+            }
+        }
+        waveSync();  // the candidate queue is empty: the next histogram may be written
+    }
+    if (n_parked != 0u && n_parked <= 128u) {
+        for (uint32_t pb = 0; pb < n_parked; pb += 64u) {
+            const bool valid = pb + lane < n_parked;
+            const uint32_t i = my_parked[valid ? pb + lane : 0u];
+            f4 a, b;
+            fetchRay<0>(sc, src, i, a, b);
+            const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
+            float best_t = TRT_INF;
+            int32_t best_tri = -1;
+            uint32_t best_flags = 0u;
+            uint32_t ni = 0, nt = 0;
+            uniformWalkImpl<false, B, true, true>(sc, o, d, mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), valid, valid, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
+            if (valid) storeResult<false, true>(sc, o, d, best_t, best_tri, best_flags, i, 0u, hit, nullptr, 0u, nullptr, false);
+        }
+        if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
+    } else if (n_parked > 128u) {
+        // more than the list holds: this wave goes over its share of the queue once more (the rays never left it) and walks the batches that hold such rays
+        for (uint32_t base = lb * B; base < n; base += stride) {
+            const uint32_t i = base + threadIdx.x;
+            const bool valid = i < n;
+            f4 a, b;
+            fetchRay<0>(sc, src, valid ? i : n - 1, a, b);
+            const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
+            const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+            const bool special = valid && raySpecial(inv);
+            if (ballotb(special) == 0ull) continue;
+            float best_t = TRT_INF;
+            int32_t best_tri = -1;
+            uint32_t best_flags = 0u;
+            uint32_t ni = 0, nt = 0;
+            uniformWalkImpl<false, B, true, true>(sc, o, d, inv, special, special, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
+            if (special) storeResult<false, true>(sc, o, d, best_t, best_tri, best_flags, i, 0u, hit, nullptr, 0u, nullptr, false);
+        }
+        if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
+    }
+    if (COUNT) {
+        const unsigned long long si = waveSum(n_inner), st = waveSum(n_tri);
+        if (lane == 0) {
+            atomicAdd(&stats->inner_visits[0], si);
+            atomicAdd(&stats->tri_tests[0], st);
+        }
+    }
+}
 
 template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
@@ -870,6 +1127,15 @@ __global__ TRT_TRACE_BOUNDS void k_trace_shadow(SceneDev sc, ShadowQueue sq, uin
     src.rb = sq.sb;
     src.s0 = 0;
     traceQueue<true, COUNT, DEPTH, SPILL, IMPL, false, NK, false, PIPE>(sc, src, n, nullptr, sq.sw, light_mat, Lacc, spill, spill_stride, stats, smem, any != 0u, redo, lbox);
+}
+
+// The binned walk (traceQueueBinned) of the render's closest-hit queue: trt_create's bin_walk.
+template <bool COUNT>
+__global__ TRT_TRACE_BOUNDS TRT_BIN_WAVES void k_trace_closest_binned(SceneDev sc, RaySource src, f4* __restrict__ hit, uint32_t n,
+                                                                      uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, RedoList redo)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t smem[TRT_PEND_SLOTS * 4 * TRT_TRACE_BLOCK];  // the candidate queue, and each wave's sort
+    traceQueueBinned<COUNT>(sc, src, n, hit, stats, reinterpret_cast<f4*>(smem));
 }
 
 // The ray-batch queries (QUERY_CLOSEST, QUERY_OCCLUDED) on the packed rays of src (rb.w: the bound), on the driver the scene picked.  Same arguments
