@@ -29,8 +29,8 @@ HOST_HDR := $(wildcard $(PKG)/host/*.h) include/trt.h include/trt_host.h include
 HIP_SRC := $(PKG)/csrc/trt_api.hip
 HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include/trt_exact.h
 
-.PHONY: all host hip lbvh oracle cli hostsim variants probe exactcheck clean
-all: host hip lbvh oracle hostsim cli exactcheck
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu variants probe exactcheck clean
+all: host hip lbvh oracle hostsim denoisecpu cli exactcheck
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -42,6 +42,10 @@ oracle:
 hostsim: tests/hostsim/libhostsim.so
 tests/hostsim/libhostsim.so: tests/hostsim/hostsim.cpp $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/hostsim/hostsim.cpp
+# CPU compile of the a-trous filter's per-pixel code (trt_denoise.h), for tests only (tests/test_*denoise*.py)
+denoisecpu: tests/denoise/libdenoise_cpu.so
+tests/denoise/libdenoise_cpu.so: tests/denoise/denoise_cpu.cpp $(PKG)/csrc/trt_denoise.h include/trt.h include/trt_prims.h include/trt_exact.h
+	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/denoise/denoise_cpu.cpp
 
 $(OUT)/libtrt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(OUT)
@@ -72,7 +76,7 @@ variants: $(HIP_SRC) $(HIP_HDR)
 	  echo "variant $$name: $$defs"; $(HIPCC) $(HIPFLAGS) $$defs -shared -o $(OUT)/variants/libtrt_hip_$$name.so $(HIP_SRC) || exit 1; done
 
 clean:
-	rm -rf $(OUT) tests/hostsim/libhostsim.so
+	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/denoise/libdenoise_cpu.so
 	$(MAKE) -C oracle clean
 
 # exhaustive (2^32 inputs) proof that include/trt_exact.h returns the bits of sqrtf / 1.0f / sqrtf: run by tests/test_gpu_parity.py

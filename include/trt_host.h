@@ -85,7 +85,7 @@ int trth_decode_jpeg(const char* path, int* width, int* height, uint8_t* rgb, ui
 int trth_decode_png(const char* path, int* width, int* height, uint8_t* rgb, uint64_t rgb_capacity);
 
 /* sizeof() of the trt.h structs as the C compiler sees them, for binding self-checks:
- * bvh_node, material, light, light_tri, texture, camera, scene, params, stats, ABI version. */
+ * bvh_node, material, light, light_tri, texture, camera, scene, params, stats, ABI version, denoise_params, 0. */
 int trth_abi_sizes(int64_t out[12]);
 
 const char* trth_last_error(void);

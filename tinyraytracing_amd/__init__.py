@@ -14,7 +14,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _abi, adaptive
-from ._abi import Params, Stats, SceneFlat, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES  # noqa: F401
+from ._abi import Params, Stats, SceneFlat, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES, TRT_K_DENOISE  # noqa: F401
 
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES_DIR = os.path.join(REPO_ROOT, "scenes")
@@ -352,6 +352,42 @@ class Renderer:
         shape = (ys.size, xs.size)
         return AdaptiveResult(image.reshape(shape + (3,)), counts.reshape(shape), err.reshape(shape), total, rounds)
 
+    def render_denoised(self, params, aov_spp=None, iterations=5, sigma_normal=128, sigma_depth=1.0, sigma_luminance=4.0):
+        """A render of the tile of `params` and its denoised image (trt_denoise).  The beauty is rendered with trt_render_pixels over every
+        pixel of the tile in tile order, samples [0, params.spp) (params.spp >= 2), so `color` is exactly render(params)'s image, and its
+        moments give `variance`, the variance of each pixel's mean luminance (mean_luminance_variance).  The feature buffers are
+        render_aov at aov_spp samples (None = min(spp, 16)), same seed and flags.  The tile is filtered as one image: rows may not be
+        interleaved.  -> dict(color, variance, albedo, normal, depth, denoised) as float32 arrays [rows, tile_w(, 3)], and stats: the
+        Stats of the three calls summed."""
+        if params.spp < 2:
+            raise TrtError("render_denoised: spp must be >= 2 (the variance needs two samples)")
+        if params.row_mod > 1:
+            raise TrtError("render_denoised: the tile must not interleave rows (it is filtered as one image)")
+        ys = np.asarray(rows_selected(params), np.int64)
+        xs = np.arange(params.x0, params.x1, dtype=np.int64)
+        if ys.size == 0 or xs.size == 0:
+            raise TrtError("render_denoised: empty tile")
+        shape = (ys.size, xs.size)
+        pixels = (ys[:, None] * params.width + xs[None, :]).reshape(-1).astype(np.uint32)
+        total = Stats()
+        sums, sumsq, st = self.render_pixels(params, pixels, 0, params.spp)
+        _add_stats(total, st)
+        pa = make_params(params.width, params.height, params.spp if aov_spp is None else aov_spp, params.seed, tile=(params.x0, params.y0, params.x1, params.y1),
+                         max_depth=params.max_depth, flags=params.flags, mem_budget=params.mem_budget)
+        if aov_spp is None:
+            pa.spp = min(params.spp, 16)
+        aov, st = self.render_aov(pa, want_stats=True)
+        _add_stats(total, st)
+        out = {"color": sums.astype(np.float32).reshape(shape + (3,)),
+               "variance": mean_luminance_variance(sums, sumsq, params.spp).reshape(shape)}
+        out.update(aov)
+        out["denoised"], st = denoise(out["color"], out["variance"], aov["albedo"], aov["normal"], aov["depth"], iterations=iterations,
+                                      sigma_normal=sigma_normal, sigma_depth=sigma_depth, sigma_luminance=sigma_luminance, device=self.device,
+                                      want_stats=True)
+        _add_stats(total, st)
+        out["stats"] = total
+        return out
+
     def render_into(self, params, out_tensor, stream_ptr=0):
         """Renders into a CUDA/HIP torch tensor (float32, >= rows*tile_w*3 elements) on this device."""
         nrows = self._lib.trt_rows_selected(C.byref(params))
@@ -567,6 +603,76 @@ class GroupRenderer:
             self.close()
         except Exception:
             pass
+
+
+def mean_luminance_variance(sums, sumsq, spp):
+    """The variance of each pixel's mean luminance from trt_render_pixels' moments of samples [0, spp) (spp >= 2): per channel the unbiased
+    sample variance of the radiance divided by spp, no covariances, weighted by LUMA^2.  sums / sumsq: float64 [n, 3] of v = L / spp and
+    v * v.  -> float32 [n].  The CLI's --denoise computes it with the same float64 operations in the same order (host/render.cpp)."""
+    n = float(spp)
+    m = sums / n
+    vv = (sumsq / n - m * m) * (n / (n - 1.0))
+    vm = np.where(vv > 0.0, vv, 0.0) * n
+    L = adaptive.LUMA
+    return ((L[0] * L[0]) * vm[:, 0] + (L[1] * L[1]) * vm[:, 1] + (L[2] * L[2]) * vm[:, 2]).astype(np.float32)
+
+
+def _denoise_params(iterations, sigma_normal, sigma_depth, sigma_luminance):
+    dp = _abi.DenoiseParams()
+    dp.iterations, dp.sigma_normal = int(iterations), int(sigma_normal)
+    dp.sigma_depth, dp.sigma_luminance, dp.flags = float(sigma_depth), float(sigma_luminance), 0
+    return dp
+
+
+def _image_shape(color, what):
+    if color.ndim != 3 or color.shape[2] != 3 or color.shape[0] < 1 or color.shape[1] < 1:
+        raise TrtError(f"{what}: color must be [height, width, 3]")
+    return int(color.shape[0]), int(color.shape[1])
+
+
+def denoise(color, variance, albedo, normal, depth, iterations=5, sigma_normal=128, sigma_depth=1.0, sigma_luminance=4.0, device=0, want_stats=False):
+    """The edge-avoiding a-trous filter on `device` (trt_denoise, include/trt.h has the contract): color, albedo, normal [h, w, 3],
+    variance (of the pixel's mean luminance) and depth [h, w], all converted to float32.  -> denoised float32 [h, w, 3][, Stats]."""
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    h, w = _image_shape(color, "denoise")
+    bufs = [color]
+    for name, a, shape in (("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise TrtError(f"denoise: {name} must have shape {shape}, not {a.shape}")
+        bufs.append(a)
+    out = np.empty((h, w, 3), np.float32)
+    dp = _denoise_params(iterations, sigma_normal, sigma_depth, sigma_luminance)
+    st = Stats()
+    lib = _abi.load_hip()
+    fp = C.POINTER(C.c_float)
+    rc = lib.trt_denoise(int(device), C.byref(dp), w, h, *[b.ctypes.data_as(fp) for b in bufs], out.ctypes.data_as(fp), C.byref(st))
+    if rc != 0:
+        raise TrtError(f"trt_denoise failed ({rc}): {lib.trt_last_error().decode()}")
+    return (out, st) if want_stats else out
+
+
+def denoise_into(color, variance, albedo, normal, depth, out, iterations=5, sigma_normal=128, sigma_depth=1.0, sigma_luminance=4.0, stream_ptr=0):
+    """trt_denoise_device: the buffers of denoise() as contiguous float32 torch tensors on one device (color, albedo, normal and out
+    [h, w, 3]; variance and depth [h, w]), the work on stream `stream_ptr` (0 = default).  Writes out; -> Stats."""
+    if not _is_torch(color) or color.dim() != 3:
+        raise TrtError("denoise_into: color must be a float32 tensor [height, width, 3]")
+    h, w = _image_shape(color, "denoise_into")
+    dev = color.device
+    ptrs = []
+    for name, t, shape in (("color", color, (h, w, 3)), ("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)),
+                           ("depth", depth, (h, w)), ("out", out, (h, w, 3))):
+        if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape
+                or t.device != dev):
+            raise TrtError(f"denoise_into: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+        ptrs.append(C.c_void_p(t.data_ptr()))
+    dp = _denoise_params(iterations, sigma_normal, sigma_depth, sigma_luminance)
+    st = Stats()
+    lib = _abi.load_hip()
+    rc = lib.trt_denoise_device(int(dev.index or 0), C.byref(dp), w, h, *ptrs, C.c_void_p(stream_ptr), C.byref(st))
+    if rc != 0:
+        raise TrtError(f"trt_denoise_device failed ({rc}): {lib.trt_last_error().decode()}")
+    return st
 
 
 def tonemap(image):

@@ -21,6 +21,10 @@ TRT_FLAG_RAY_OFFSET = 32
 TRT_FLAG_SPECULAR_KS = 64
 TRT_MAX_KERNELS = 8
 KERNEL_NAMES = ["gen_primary", "trace_closest", "shade", "trace_shadow", "resolve", "tail"]
+# trt_denoise*'s slot of Stats.launches / kernel_ms: not in KERNEL_NAMES, whose last entry is the render's own last kernel
+TRT_K_DENOISE = 6
+TRT_DENOISE_MAX_ITERATIONS = 10
+TRT_DENOISE_MAX_PIXELS = 1 << 28
 
 c_float3 = C.c_float * 3
 
@@ -82,10 +86,15 @@ class Stats(C.Structure):
         return self.rays_camera + self.rays_shadow + self.rays_indirect
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("sigma_normal", C.c_int32), ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float),
+                ("flags", C.c_uint32)]
+
+
 # the symbols include/trt.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_aov",
                "trt_render_aov_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
-               "trt_trace_occluded_device",
+               "trt_trace_occluded_device", "trt_denoise", "trt_denoise_device",
                "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
 HOST_SYMBOLS = ["trth_scene_load", "trth_scene_load_opts", "trth_scene_drop_tris", "trth_scene_add_soup", "trth_scene_add_blob", "trth_scene_add_lamps",
@@ -209,6 +218,8 @@ def load_hip():
     lib.trt_trace_occluded.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.POINTER(C.c_uint8), C.POINTER(Stats)]
     lib.trt_trace_occluded_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.trt_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 6 + [C.POINTER(Stats)]
+    lib.trt_denoise_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.POINTER(Stats)]
     lib.trt_destroy.argtypes = [C.c_void_p]
     lib.trt_destroy.restype = None
     lib.trt_group_create.argtypes = [C.POINTER(SceneFlat), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]

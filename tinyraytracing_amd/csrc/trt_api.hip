@@ -23,6 +23,7 @@
 #include "trt_kernels.h"
 #include "trt_wide.h"
 #include "trt_oct_build.h"
+#include "trt_denoise_kernels.h"
 
 using namespace trtd;
 
@@ -594,9 +595,9 @@ int buildSceneImage(const trt_scene* s, SceneImage& im)
 
 // The device half of trt_create: a handle on `device` from the host image (thread-safe against other devices' calls: touches only
 // the handle, the image read-only and this thread's HIP device).
-int createOnDevice(const SceneImage& im, int device, trt_handle** out)
+// Makes `device` current after checking that it exists and is a gfx950 (TRT_ENODEV otherwise).
+int useDevice(int device)
 {
-    const trt_scene* s = im.s;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(TRT_ENODEV, "no HIP device");
     if (device < 0 || device >= ndev) return fail(TRT_ENODEV, "device ordinal out of range");
@@ -604,6 +605,13 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     hipDeviceProp_t prop;
     HIPC(hipGetDeviceProperties(&prop, device));
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(TRT_ENODEV, std::string("this library is built for gfx950 only, device is ") + prop.gcnArchName);
+    return TRT_OK;
+}
+
+int createOnDevice(const SceneImage& im, int device, trt_handle** out)
+{
+    const trt_scene* s = im.s;
+    if (int e = useDevice(device)) return e;
 
     Lap lap{im.dbg};
     std::unique_ptr<trt_handle> h(new trt_handle);
@@ -1858,6 +1866,135 @@ int trt_group_render(trt_group* g, const trt_params* p_in, float* out_host, trt_
     HIPC(hipSetDevice(g->devices[0]));
     HIPC(hipMemcpy(out_host, g->image.p, bytes, hipMemcpyDeviceToHost));
     return TRT_OK;
+}
+
+}  // extern "C"
+
+// ---- trt_denoise / trt_denoise_device ----------------------------------------------------------------------------------------------
+
+namespace {
+
+struct DenoiseIo {
+    const float *color, *variance, *albedo, *normal, *depth;
+    float* out;
+};
+
+// Scratch and events of one call, released on every way out of it.
+struct DenoiseScratch {
+    void* p = nullptr;
+    hipEvent_t ev[4] = {};
+    ~DenoiseScratch()
+    {
+        if (p) (void)hipFree(p);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// The checks of include/trt.h; fills the level arguments (step 1) and the number of levels.
+int denoiseArgs(const trt_denoise_params* prm, int width, int height, const DenoiseIo& io, trt_dn_args& a, int& levels, const char* what)
+{
+    if (!io.color || !io.variance || !io.albedo || !io.normal || !io.depth || !io.out) return fail(TRT_EINVAL, std::string(what) + ": null buffer");
+    if (width < 1 || height < 1) return fail(TRT_EINVAL, std::string(what) + ": width and height must be >= 1");
+    if ((uint64_t)width * (uint64_t)height > TRT_DENOISE_MAX_PIXELS) return fail(TRT_EINVAL, std::string(what) + ": image larger than 2^28 pixels");
+    trt_denoise_params d{};
+    if (prm) d = *prm;
+    if (d.iterations < 0 || d.iterations > TRT_DENOISE_MAX_ITERATIONS) return fail(TRT_EINVAL, std::string(what) + ": iterations must be 0..10");
+    if (d.sigma_normal < 0 || d.sigma_normal > 256) return fail(TRT_EINVAL, std::string(what) + ": sigma_normal must be 0..256");
+    if (!(d.sigma_depth >= 0.0f) || !(d.sigma_luminance >= 0.0f)) return fail(TRT_EINVAL, std::string(what) + ": sigmas must be >= 0");
+    if (d.flags != 0) return fail(TRT_EINVAL, std::string(what) + ": flags must be 0");
+    levels = d.iterations ? d.iterations : TRT_DN_ITERATIONS;
+    a.width = width;
+    a.height = height;
+    a.step = 1;
+    a.sigma_normal = d.sigma_normal ? d.sigma_normal : TRT_DN_SIGMA_NORMAL;
+    a.sigma_depth = d.sigma_depth != 0.0f ? d.sigma_depth : TRT_DN_SIGMA_DEPTH;
+    a.sigma_luminance = d.sigma_luminance != 0.0f ? d.sigma_luminance : TRT_DN_SIGMA_LUMINANCE;
+    return TRT_OK;
+}
+
+// One call: (host: upload) -> k_denoise_prepare -> k_denoise_level per level -> (host: download), all on `stream`.
+// TRT_DENOISE_LDS=0 in the environment sends levels 0 and 1 through the global-memory kernel as well (A/B of the LDS tiles; same bits).
+int denoise(int device, const trt_denoise_params* prm, int width, int height, const DenoiseIo& io, bool host, hipStream_t stream, trt_stats* stats,
+            const char* what)
+{
+    trt_dn_args a{};
+    int levels = 0;
+    if (int e = denoiseArgs(prm, width, height, io, a, levels, what)) return e;
+    if (int e = useDevice(device)) return e;
+    const size_t n = (size_t)width * (size_t)height, f1 = n * sizeof(float), f3 = 3 * f1, r16 = n * sizeof(trt_dn4);
+    Layout L;
+    const size_t o_cv0 = L.add(r16, 256), o_cv1 = L.add(r16, 256), o_gd = L.add(r16, 256), o_aux = L.add(r16, 256);
+    // host entries stage color, variance, albedo, normal, depth and out
+    const size_t o_c = L.add(host ? f3 : 0, 256), o_v = L.add(host ? f1 : 0, 256), o_a = L.add(host ? f3 : 0, 256), o_n = L.add(host ? f3 : 0, 256);
+    const size_t o_z = L.add(host ? f1 : 0, 256), o_o = L.add(host ? f3 : 0, 256);
+    DenoiseScratch S;
+    HIPC(hipMalloc(&S.p, L.bytes));
+    for (hipEvent_t& e : S.ev) HIPC(hipEventCreate(&e));
+    char* b = (char*)S.p;
+    trt_dn4* cv[2] = {(trt_dn4*)(b + o_cv0), (trt_dn4*)(b + o_cv1)};
+    trt_dn4* gd = (trt_dn4*)(b + o_gd);
+    trt_dn4* aux = (trt_dn4*)(b + o_aux);
+    DenoiseIo dev = io;
+    HIPC(hipEventRecord(S.ev[0], stream));
+    if (host) {
+        dev = DenoiseIo{(const float*)(b + o_c), (const float*)(b + o_v), (const float*)(b + o_a), (const float*)(b + o_n), (const float*)(b + o_z), (float*)(b + o_o)};
+        HIPC(hipMemcpyAsync((void*)dev.color, io.color, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.variance, io.variance, f1, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.albedo, io.albedo, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.normal, io.normal, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.depth, io.depth, f1, hipMemcpyHostToDevice, stream));
+    }
+    const char* lds_env = std::getenv("TRT_DENOISE_LDS");
+    const bool lds = !(lds_env && lds_env[0] == '0');
+    const dim3 grid((unsigned)((width + DN_BX - 1) / DN_BX), (unsigned)((height + DN_BY - 1) / DN_BY)), block(DN_BX, DN_BY);
+    HIPC(hipEventRecord(S.ev[1], stream));
+    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, stream, width, height, dev.color, dev.variance, dev.albedo, dev.normal, dev.depth, cv[0], gd, aux);
+    for (int k = 0; k < levels; ++k) {
+        a.step = 1 << k;
+        const trt_dn4* in = cv[k & 1];
+        trt_dn4* nxt = cv[(k + 1) & 1];
+        const bool last = k + 1 == levels;
+        const int lds_step = lds && a.step <= 2 ? a.step : 0;
+        using LevelKernel = void (*)(trt_dn_args, const trt_dn4*, const trt_dn4*, const trt_dn4*, trt_dn4*, float*);
+        static const LevelKernel table[3][2] = {{k_denoise_level<0, false>, k_denoise_level<0, true>},
+                                                {k_denoise_level<1, false>, k_denoise_level<1, true>},
+                                                {k_denoise_level<2, false>, k_denoise_level<2, true>}};
+        hipLaunchKernelGGL(table[lds_step][last ? 1 : 0], grid, block, 0, stream, a, in, (const trt_dn4*)gd, (const trt_dn4*)aux, nxt, dev.out);
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(S.ev[2], stream));
+    if (host) HIPC(hipMemcpyAsync(io.out, dev.out, f3, hipMemcpyDeviceToHost, stream));
+    HIPC(hipEventRecord(S.ev[3], stream));
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+    if (stats) {
+        float k_ms = 0.f, all_ms = 0.f;
+        HIPC(hipEventElapsedTime(&k_ms, S.ev[1], S.ev[2]));
+        HIPC(hipEventElapsedTime(&all_ms, S.ev[0], S.ev[3]));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->launches[TRT_K_DENOISE] = 1 + (uint64_t)levels;
+        stats->kernel_ms[TRT_K_DENOISE] = k_ms;
+        stats->render_ms = all_ms;
+    }
+    return TRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trt_denoise(int device, const trt_denoise_params* params, int width, int height, const float* color, const float* variance,
+                const float* albedo, const float* normal, const float* depth, float* out, trt_stats* stats)
+{
+    return denoise(device, params, width, height, DenoiseIo{color, variance, albedo, normal, depth, out}, true, nullptr, stats, "trt_denoise");
+}
+
+int trt_denoise_device(int device, const trt_denoise_params* params, int width, int height, const float* color, const float* variance,
+                       const float* albedo, const float* normal, const float* depth, float* out, void* hip_stream, trt_stats* stats)
+{
+    return denoise(device, params, width, height, DenoiseIo{color, variance, albedo, normal, depth, out}, false, (hipStream_t)hip_stream, stats,
+                   "trt_denoise_device");
 }
 
 }  // extern "C"

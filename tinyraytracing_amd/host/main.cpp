@@ -20,11 +20,13 @@ static void usage()
     std::fprintf(stderr,
                  "usage: tinyrt <basedir> <mtl> <xml> <obj> <spp> [--width W --height H] [--seed S] [--device D | --gpus N | --devices a,b,..]\n"
                  "              [--leaf N] [--gpu-bvh] [--max-depth D] [--out file.png] [--fixed | --fixed-nee | --fixed-pixels] [--ray-offset] [--specular-ks] [--polygons]\n"
-                 "              [--every N] [--checkpoint file.acc] [--stop-after M] [--aov PREFIX [--aov-spp N]]\n"
+                 "              [--every N] [--checkpoint file.acc] [--stop-after M] [--aov PREFIX [--aov-spp N]] [--denoise file.png]\n"
                  "                                                    progressive: N samples per step, image rewritten after\n"
                  "                                                    every step, accumulator kept in file.acc (resumes from it)\n"
                  "                                                    --aov: denoiser inputs PREFIX_{color,albedo,normal,depth}.pfm, the\n"
-                 "                                                    feature buffers averaged over N samples (default min(spp, 16))\n");
+                 "                                                    feature buffers averaged over N samples (default min(spp, 16))\n"
+                 "                                                    --denoise: also the image filtered by trt_denoise (a-trous, 5 levels),\n"
+                 "                                                    guided by those feature buffers; one device, spp >= 2\n");
 }
 
 int main(int argc, char** argv)
@@ -36,8 +38,9 @@ int main(int argc, char** argv)
     opts.timing = true;
     int width = 0, height = 0;
     bool polygons = false;  // fan-triangulate faces of more than three vertices (the reference keeps their first three only)
-    std::string out_path, aov_prefix;
+    std::string out_path, aov_prefix, denoise_path;
     int aov_spp = 0;
+    bool multi = false;  // --gpus / --devices given
     for (int i = 6; i < argc; ++i) {
         auto need = [&](const char* flag) -> const char* {
             if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", flag); std::exit(2); }
@@ -49,9 +52,11 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--device")) opts.device = std::atoi(need("--device"));
         else if (!std::strcmp(argv[i], "--gpus")) {  // devices 0..N-1 of this node: image tiled in row stripes, one RCCL gather
             const int n = std::atoi(need("--gpus"));
+            multi = true;
             opts.devices.clear();
             for (int d = 0; d < n; ++d) opts.devices.push_back(d);
         } else if (!std::strcmp(argv[i], "--devices")) {  // explicit list; one device may appear several times (rehearsal on one GPU)
+            multi = true;
             opts.devices.clear();
             const std::string list = need("--devices");
             size_t pos = 0;
@@ -78,13 +83,21 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--stop-after")) opts.stop_after = std::atoi(need("--stop-after"));
         else if (!std::strcmp(argv[i], "--aov")) aov_prefix = need("--aov");
         else if (!std::strcmp(argv[i], "--aov-spp")) aov_spp = std::atoi(need("--aov-spp"));
+        else if (!std::strcmp(argv[i], "--denoise")) denoise_path = need("--denoise");
         else { usage(); return 2; }
     }
-    if (!aov_prefix.empty()) {
+    if (!denoise_path.empty()) {
+        // one image on one device, rendered in one go: the filter sees the whole frame (no tile seams), and the variance needs the moments
+        if (multi) { std::fprintf(stderr, "--denoise runs on one device: it cannot be combined with --gpus or --devices\n"); return 2; }
+        if (opts.every > 0 || !opts.checkpoint.empty()) { std::fprintf(stderr, "--denoise cannot be combined with --every or --checkpoint\n"); return 2; }
+        if (opts.spp < 2) { std::fprintf(stderr, "--denoise needs spp >= 2\n"); return 2; }
+        opts.denoise = true;
+    }
+    if (!aov_prefix.empty() || opts.denoise) {
         opts.aov_spp = aov_spp > 0 ? aov_spp : std::min(opts.spp, 16);
         if (opts.aov_spp < 1) { std::fprintf(stderr, "--aov needs spp >= 1\n"); return 2; }
     } else if (aov_spp > 0) {
-        std::fprintf(stderr, "--aov-spp needs --aov PREFIX\n");
+        std::fprintf(stderr, "--aov-spp needs --aov PREFIX or --denoise\n");
         return 2;
     }
     try {
@@ -113,7 +126,7 @@ int main(int argc, char** argv)
             };
         }
         trt::AovImages aov;
-        trt::render(scene, opts, image.data(), &st, aov_prefix.empty() ? nullptr : &aov);
+        trt::render(scene, opts, image.data(), &st, opts.aov_spp > 0 ? &aov : nullptr);
         const uint64_t rays = st.rays_camera + st.rays_shadow + st.rays_indirect;
         std::printf("rays: %llu (camera %llu, shadow %llu, indirect %llu)  render %.3f ms  %.1f Mrays/s\n", (unsigned long long)rays,
                     (unsigned long long)st.rays_camera, (unsigned long long)st.rays_shadow, (unsigned long long)st.rays_indirect, st.render_ms,
@@ -134,6 +147,11 @@ int main(int argc, char** argv)
                 {"_color.pfm", 3, color.data()}, {"_albedo.pfm", 3, aov.albedo.data()}, {"_normal.pfm", 3, aov.normal.data()}, {"_depth.pfm", 1, aov.depth.data()}};
             for (const auto& f : files)
                 if (!trt::writePFM(aov_prefix + f.name, w, hgt, f.channels, f.data)) { std::fprintf(stderr, "cannot write %s%s\n", aov_prefix.c_str(), f.name); return 1; }
+        }
+        if (opts.denoise) {
+            std::vector<uint8_t> bytes;
+            trt::tonemap(aov.denoised.data(), scene.img_width, scene.img_height, bytes);
+            if (!trt::writePNG(denoise_path, scene.img_width, scene.img_height, bytes.data())) { std::fprintf(stderr, "cannot write %s\n", denoise_path.c_str()); return 1; }
         }
         std::fprintf(stderr, "\nDone.\n");
         std::printf("%f\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());

@@ -77,9 +77,27 @@ void writeCheckpoint(const std::string& path, const Checkpoint& head, const std:
     if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("cannot rename " + tmp + " to " + path);
 }
 
+void meanLuminanceVariance(const double* sum, const double* sumsq, size_t n, int spp, float* out)
+{
+    static const double luma[3] = {0.2126, 0.7152, 0.0722};
+    const double k = (double)spp;
+    for (size_t i = 0; i < n; ++i) {
+        double vm[3];
+        for (int c = 0; c < 3; ++c) {
+            const double m = sum[3 * i + c] / k;
+            const double vv = (sumsq[3 * i + c] / k - m * m) * (k / (k - 1.0));
+            vm[c] = (vv > 0.0 ? vv : 0.0) * k;
+        }
+        out[i] = (float)((luma[0] * luma[0]) * vm[0] + (luma[1] * luma[1]) * vm[1] + (luma[2] * luma[2]) * vm[2]);
+    }
+}
+
 void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stats, AovImages* aov)
 {
     const bool want_aov = aov && opts.aov_spp > 0;
+    const bool want_denoise = want_aov && opts.denoise;
+    if (opts.denoise && !want_aov) throw std::runtime_error("denoising needs the feature buffers (aov_spp > 0)");
+    if (want_denoise && opts.spp < 2) throw std::runtime_error("denoising needs spp >= 2 (the variance of a pixel needs two samples)");
     FlatBVH bvh;
     std::vector<uint32_t> gpu_order;
     if (opts.gpu_builder) {
@@ -143,7 +161,7 @@ void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stat
     if (opts.devices.size() > 1) {
         // several GPUs: one host thread and one replica of the scene per device, one gather (trt_group_render)
         if (progressive) throw std::runtime_error("progressive / check-pointed renders run on one device");
-        if (want_aov) throw std::runtime_error("feature buffers (--aov) are rendered on one device");
+        if (want_aov) throw std::runtime_error("feature buffers (--aov) and denoising (--denoise) run on one device");
         trt_group* g = nullptr;
         if (trt_group_create(flat.c_scene(), (int)opts.devices.size(), opts.devices.data(), &g) != TRT_OK) throw std::runtime_error(std::string("trt_group_create: ") + trt_last_error());
         p.row_block = opts.row_block > 0 ? opts.row_block : 8;
@@ -156,7 +174,20 @@ void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stat
     }
     trt_handle* h = nullptr;
     if (trt_create(flat.c_scene(), opts.devices.size() == 1 ? opts.devices[0] : opts.device, &h) != TRT_OK) throw std::runtime_error(std::string("trt_create: ") + trt_last_error());
-    if (!progressive) {
+    std::vector<double> sum, sumsq;  // the moments of a render to be denoised
+    if (want_denoise) {
+        // every pixel in image order, samples [0, spp): sum is trt_render's accumulator, so (float)sum is its image
+        if (progressive) { trt_destroy(h); throw std::runtime_error("a denoised render is not progressive or check-pointed"); }
+        const size_t n = (size_t)p.width * p.height;
+        std::vector<uint32_t> pixels(n);
+        for (size_t i = 0; i < n; ++i) pixels[i] = (uint32_t)i;
+        sum.assign(n * 3, 0.0);
+        sumsq.assign(n * 3, 0.0);
+        rc = trt_render_pixels(h, &p, (uint32_t)n, pixels.data(), 0, p.spp, sum.data(), sumsq.data(), stats);
+        if (rc) msg = trt_last_error();
+        else
+            for (size_t i = 0; i < out.size(); ++i) out[i] = (float)sum[i];
+    } else if (!progressive) {
         rc = trt_render(h, &p, out.data(), stats);
         if (rc) msg = trt_last_error();
     } else {
@@ -218,6 +249,14 @@ void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stat
         aov->depth.resize(n);
         rc = trt_render_aov(h, &pa, aov->albedo.data(), aov->normal.data(), aov->depth.data(), nullptr);
         if (rc) msg = std::string("trt_render_aov: ") + trt_last_error();
+        if (rc == TRT_OK && want_denoise) {
+            aov->variance.resize(n);
+            aov->denoised.resize(n * 3);
+            meanLuminanceVariance(sum.data(), sumsq.data(), n, p.spp, aov->variance.data());
+            rc = trt_denoise(opts.devices.size() == 1 ? opts.devices[0] : opts.device, &opts.denoise_params, p.width, p.height, out.data(),
+                             aov->variance.data(), aov->albedo.data(), aov->normal.data(), aov->depth.data(), aov->denoised.data(), nullptr);
+            if (rc) msg = std::string("trt_denoise: ") + trt_last_error();
+        }
     } else if (rc != TRT_OK) {
         msg = "trt_render: " + msg;
     }

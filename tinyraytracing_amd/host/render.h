@@ -38,12 +38,23 @@ struct RenderOpts {
     std::string checkpoint;
     std::function<void(int samples_done, const float* rgb)> on_progress;
     int aov_spp = 0;          // > 0: after the render, the first-hit albedo / normal / depth of samples [0, aov_spp) (trt_render_aov) into render()'s `aov`
+    // Denoise (one device, not progressive; needs spp >= 2 and aov_spp > 0): the beauty is rendered through trt_render_pixels over every pixel in
+    // image order — the same image as trt_render — whose moments give the variance of each pixel's mean luminance; then trt_denoise with
+    // these parameters filters it into aov->denoised (aov->variance holds the variance).
+    bool denoise = false;
+    trt_denoise_params denoise_params{};
 };
 
 // First-hit feature buffers of the whole image for a denoiser (trt_render_aov): albedo and normal width*height*3, depth width*height floats.
 struct AovImages {
     std::vector<float> albedo, normal, depth;
+    std::vector<float> variance, denoised;  // RenderOpts::denoise: width*height and width*height*3 floats
 };
+
+// The variance of each pixel's mean luminance from trt_render_pixels' moments of samples [0, spp) (spp >= 2): per channel the unbiased
+// sample variance of the radiance divided by spp, no covariances, weighted by the squared Rec. 709 luminance weights.  The float64
+// operations of tinyraytracing_amd.mean_luminance_variance, in its order.  sum / sumsq: n * 3 doubles; out: n floats.
+void meanLuminanceVariance(const double* sum, const double* sumsq, size_t n, int spp, float* out);
 
 // Accumulator file of a progressive render: header + width*height*3 doubles (the sums of trt_render_samples).
 struct Checkpoint {
