@@ -7,9 +7,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <limits>
 #include <vector>
 
+// range checks of the traversal (TRT_WALK_CHECK, trt_path.h): a walk that would leave the tree, the triangles or the stack the GPU
+// driver has ends its ray and is counted (g_breaches: the entry then returns 2) instead of reading out of range
+#define TRT_HOSTSIM_CHECKS 1
 #include "trt_path.h"
 #include "trt_wide.h"
 #include "trt_oct_build.h"
@@ -18,10 +22,20 @@ using namespace trtd;
 
 namespace {
 int g_node_kind = 0;  // hostsim_set_node_kind: 0 = exact 4-wide nodes; 1 = the 8-wide compressed nodes of trt_oct.h where the tree allows them
+std::atomic<uint64_t> g_breaches{0};  // walks TRT_WALK_CHECK ended: reset when an entry builds its HostScene; the entry returns 2 when it is not 0 at the end
 struct ArrayStack {
     uint32_t s[1024];
-    void push(int sp, uint32_t v) { s[sp] = v; }
-    uint32_t pop(int sp) const { return s[sp]; }
+    uint32_t cap = 1024;       // entries the 4-wide walk can need on this tree: the collapse's stack_need (HostScene::stack())
+    uint32_t bvh2_cap = 1024;  // entries the literal walk of the caller's BVH2 can need: its inner depth (k_trace_fix / k_tail size theirs from it)
+    void push(int sp, uint32_t v)
+    {
+        if (sp >= 0 && sp < 1024) s[sp] = v;
+        else g_breaches++;
+    }
+    uint32_t pop(int sp) const { return sp >= 0 && sp < 1024 ? s[sp] : TRT_WIDE_EMPTY; }
+    int capacity() const { return (int)cap; }
+    int bvh2Capacity() const { return (int)bvh2_cap; }
+    void breach() const { g_breaches++; }
 };
 
 struct OctArrayStack {
@@ -46,8 +60,32 @@ struct HostScene {
     std::vector<uint32_t> plane_bits;
     int nk = 0;  // node kind the traversal walks: 0 exact 4-wide nodes, 1 compressed 8-wide nodes (TRT_NODE_KIND)
     SceneDev sc{};
+    uint32_t bvh2_depth = 0;  // inner nodes on the longest root path of the caller's BVH2
+    // a reference stack with the bounds the GPU drivers' stacks are sized by: stack_need entries for the 4-wide walk, the BVH2's inner
+    // depth for the literal walk (it pushes at most one entry per inner node on its path)
+    ArrayStack stack() const
+    {
+        ArrayStack k;
+        k.cap = wide.stack_need;
+        k.bvh2_cap = bvh2_depth;
+        return k;
+    }
     explicit HostScene(const trt_scene* s)
     {
+        g_breaches = 0;  // every entry that walks rays builds its scene first: a breach is reported by the entry whose walk made it
+        {
+            struct Ref { uint32_t node, depth; };
+            std::vector<Ref> todo;
+            if (s->n_nodes) todo.push_back({0u, 1u});
+            while (!todo.empty()) {
+                const Ref r = todo.back();
+                todo.pop_back();
+                if (r.depth > bvh2_depth) bvh2_depth = r.depth;
+                if (r.node >= s->n_nodes || r.depth > s->n_nodes) continue;  // (trt_create rejects such a tree; the walk's checks report it here)
+                for (uint32_t c : {s->nodes[r.node].child0, s->nodes[r.node].child1})
+                    if (!(c & TRT_LEAF_BIT)) todo.push_back({c, r.depth + 1u});
+            }
+        }
         isect.resize(s->n_tris);
         shade.resize(s->n_tris);
         for (uint32_t i = 0; i < s->n_tris; ++i) {
@@ -184,7 +222,7 @@ extern "C" int hostsim_render(const trt_scene* s, const trt_params* p, float* ou
     const uint32_t S = (uint32_t)p->spp;  // one chunk: path id = s * npix + pixel
 #pragma omp parallel for schedule(dynamic, 64) reduction(+ : r_cam, r_sh, r_ind)
     for (long pl = 0; pl < (long)npix; ++pl) {
-        ArrayStack stk;
+        ArrayStack stk = hs.stack();
         OctArrayStack ostk;
         uint32_t ni = 0, nt = 0;
         double acc[3] = {0, 0, 0};
@@ -239,7 +277,7 @@ extern "C" int hostsim_render(const trt_scene* s, const trt_params* p, float* ou
         out_rgb[(size_t)pl * 3 + 2] = (float)acc[2];
     }
     if (rays) { rays[0] = r_cam; rays[1] = r_sh; rays[2] = r_ind; }
-    return 0;
+    return g_breaches.exchange(0) ? 2 : 0;
 }
 
 extern "C" int hostsim_trace(const trt_scene* s, uint64_t n, const float* org, const float* dir, float* t, int32_t* tri, float* uv, uint64_t counts[2])
@@ -249,7 +287,7 @@ extern "C" int hostsim_trace(const trt_scene* s, uint64_t n, const float* org, c
     uint64_t ci = 0, ct = 0;
 #pragma omp parallel for schedule(static) reduction(+ : ci, ct)
     for (long long i = 0; i < (long long)n; ++i) {
-        ArrayStack stk;
+        ArrayStack stk = hs.stack();
         OctArrayStack ostk;
         uint32_t ni = 0, nt = 0;
         const Hit h = hs.nk ? traceClosestOct<OctArrayStack, ArrayStack, true>(hs.sc, ld3(org + i * 3), ld3(dir + i * 3), ostk, stk, ni, nt)
@@ -261,7 +299,41 @@ extern "C" int hostsim_trace(const trt_scene* s, uint64_t n, const float* org, c
         ct += nt;
     }
     if (counts) { counts[0] = ci; counts[1] = ct; }
-    return 0;
+    return g_breaches.exchange(0) ? 2 : 0;
+}
+
+// The ray queries on the device code, per ray with bound[i] (null: none) as the search's t_init:
+//   form 0 — what the per-lane drivers run (k_trace_closest / k_trace_query): traceClosest, or traceClosestOct where the node kind is 1;
+//   form 1 — what k_trace_fix runs on the rays of a redo list: the literal walk for rays of raySpecial() whose origin may lie on a box plane,
+//            else the exact form (RULE) on the 4-wide nodes.
+// `any`: the occlusion query (stop at the first hit nearer than the bound).  Without `any` a hit at or beyond the bound is a miss: the literal
+// walk ignores the bound in closest mode, and k_trace_fix clips its result so for QUERY_CLOSEST (the per-lane drivers hand every ray of raySpecial()
+// to k_trace_fix).  A miss is (TRT_INF, -1, 0, 0), as storeResult writes it.  Returns 2 when a walk was ended by TRT_WALK_CHECK.
+extern "C" int hostsim_query(const trt_scene* s, int form, int any, uint64_t n, const float* org, const float* dir, const float* bound, float* t, int32_t* tri, float* uv)
+{
+    if (!s || !org || !dir || !t || !tri || form < 0 || form > 1) return 1;
+    HostScene hs(s);
+#pragma omp parallel for schedule(dynamic, 256)
+    for (long long i = 0; i < (long long)n; ++i) {
+        ArrayStack stk = hs.stack();
+        OctArrayStack ostk;
+        uint32_t ni = 0, nt = 0;
+        const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3), inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+        const float t_init = bound ? bound[i] : TRT_INF;
+        Hit h;
+        if (form == 0)
+            h = hs.nk ? traceClosestOct<OctArrayStack, ArrayStack, false>(hs.sc, o, d, ostk, stk, ni, nt, t_init, any != 0)
+                      : traceClosest<ArrayStack, false, 0>(hs.sc, o, d, stk, ni, nt, t_init, any != 0);
+        else
+            h = (raySpecial(inv) && rayOnABoxPlane(hs.sc, o, inv)) ? traceClosestBvh2Glm<ArrayStack, false>(hs.sc, o, d, stk, ni, nt, t_init, any != 0)
+                                                                    : traceClosestPass<ArrayStack, false, 0, true>(hs.sc, o, d, stk, ni, nt, t_init, any != 0);
+        if (!any && !(h.t < t_init)) h.tri = -1;
+        const bool hit = h.tri >= 0;
+        t[i] = hit ? h.t : TRT_INF;
+        tri[i] = hit ? h.tri : -1;
+        if (uv) { uv[i * 2] = hit ? h.u : 0.0f; uv[i * 2 + 1] = hit ? h.v : 0.0f; }
+    }
+    return g_breaches.exchange(0) ? 2 : 0;
 }
 
 // how many of the rays take the exact form behind the oct traversal (its result failed octResultCounts): tests/test_hostsim_parity.py
@@ -294,7 +366,7 @@ extern "C" int hostsim_trace_counts(const trt_scene* s, int nk, uint64_t n, cons
     if (nk && !hs.nk) return 1;
 #pragma omp parallel for schedule(dynamic, 256)
     for (long long i = 0; i < (long long)n; ++i) {
-        ArrayStack stk;
+        ArrayStack stk = hs.stack();
         OctArrayStack ostk;
         uint32_t ni = 0, nt = 0;
         const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3);
@@ -303,7 +375,7 @@ extern "C" int hostsim_trace_counts(const trt_scene* s, int nk, uint64_t n, cons
         visits[i] = ni;
         tests[i] = nt;
     }
-    return 0;
+    return g_breaches.exchange(0) ? 2 : 0;
 }
 
 // The sequence of steps the wave driver takes for one ray on the oct nodes (tools/pool_sim.py: what would grouping rays by phase across the waves

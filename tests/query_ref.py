@@ -23,6 +23,17 @@ def bound(t_max, n):
         return np.where(m > TRT_T_MIN, np.minimum(m, TRT_INF), TRT_T_MIN).astype(np.float32)
 
 
+def bounds_for(t0, seed=5):
+    """Per ray: a random fraction in [0, 1.5] of t0, exactly t0, nextafter(t0, inf), NaN, +-inf, 0, TRT_T_MIN, 1e30 (t0: the unbounded hit)."""
+    rng = np.random.default_rng(seed)
+    n = len(t0)
+    k = np.arange(n) % 12
+    frac = (rng.random(n) * 1.5).astype(np.float32) * t0
+    choices = [frac, frac, frac, t0, np.nextafter(t0, np.float32(np.inf)), np.full(n, np.nan, np.float32), np.full(n, np.inf, np.float32),
+               np.full(n, -np.inf, np.float32), np.zeros(n, np.float32), np.full(n, TRT_T_MIN, np.float32), np.full(n, 1e30, np.float32), frac]
+    return np.choose(k, choices).astype(np.float32)
+
+
 def inside(ref, t_max):
     t0, tri0, _ = ref
     with np.errstate(invalid="ignore"):

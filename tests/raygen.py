@@ -101,3 +101,40 @@ def grazing_rays(flat, n, seed=5):
     o = P - d * 10.0 ** rng.uniform(-1, 1.2, (n, 1))
     ok = np.isfinite(o).all(1) & np.isfinite(d).all(1) & (np.abs(d).sum(1) > 0)
     return np.ascontiguousarray(o[ok].astype(np.float32)), np.ascontiguousarray(d[ok].astype(np.float32))
+
+
+def box_planes(flat):
+    """Every coordinate of every box of the caller's BVH2, per axis: (3, 4 n_nodes) float32."""
+    import ctypes as C
+    f = flat.contents
+    raw = np.ctypeslib.as_array(C.cast(f.nodes, C.POINTER(C.c_float)), (f.n_nodes * 16,)).reshape(f.n_nodes, 16)
+    return np.ascontiguousarray(raw[:, :12].reshape(f.n_nodes, 4, 3).transpose(2, 0, 1).reshape(3, -1))
+
+
+def zero_direction_rays(scene, n, seed=13):
+    """Rays whose direction is the zero vector, in all eight combinations of signed zeros (1/d = +-inf on every axis: the slab test
+    passes, with entry +inf, every box that on each axis holds the origin or lies where that zero's sign points).  Origins, a quarter
+    each: inside the scene's box; outside it (up to its size again beyond each face); with one to three coordinates copied from the
+    planes of the tree's boxes (0 * inf = NaN there: the literal walk); with a NaN, +-inf or +-1e38 in one coordinate."""
+    rng = np.random.default_rng(seed)
+    lo, hi = scene_bounds(scene)
+    ext = np.maximum(hi - lo, np.float32(1e-3))
+    k = np.arange(n)
+    org = (rng.random((n, 3)) * (hi - lo) + lo).astype(np.float32)
+    out = (k % 4) == 1
+    side = rng.choice([-1.0, 1.0], (out.sum(), 3))
+    org[out] = np.where(side < 0, lo - rng.random((out.sum(), 3)) * ext, hi + rng.random((out.sum(), 3)) * ext).astype(np.float32)
+    planes = box_planes(scene.flat)
+    on = np.nonzero((k % 4) == 2)[0]
+    for j, i in enumerate(on):
+        axes = rng.permutation(3)[: 1 + j % 3]
+        for a in axes:
+            org[i, a] = planes[a, rng.integers(0, planes.shape[1])]
+    bad = np.nonzero((k % 4) == 3)[0]
+    vals = np.array([np.nan, np.inf, -np.inf, 1e38, -1e38], np.float32)
+    org[bad, rng.integers(0, 3, len(bad))] = vals[rng.integers(0, len(vals), len(bad))]
+    signs = (k // 4) % 8  # every origin kind meets every sign pattern
+    d = np.zeros((n, 3), np.float32)
+    for a in range(3):
+        d[(signs >> a) & 1 == 1, a] = np.float32(-0.0)
+    return org, d

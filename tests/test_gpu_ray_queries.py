@@ -50,28 +50,12 @@ def ray_sets(s):
             "axis": SU.axis_rays(s, 48)}
 
 
-def bounds_for(t0, seed=5):
-    """Per ray: a random fraction in [0, 1.5] of t0, exactly t0, nextafter(t0, inf), NaN, +-inf, 0, TRT_T_MIN, 1e30 (t0: the unbounded hit)."""
-    rng = np.random.default_rng(seed)
-    n = len(t0)
-    k = np.arange(n) % 12
-    frac = (rng.random(n) * 1.5).astype(np.float32) * t0
-    choices = [frac, frac, frac, t0, np.nextafter(t0, np.float32(np.inf)), np.full(n, np.nan, np.float32), np.full(n, np.inf, np.float32),
-               np.full(n, -np.inf, np.float32), np.zeros(n, np.float32), np.full(n, Q.TRT_T_MIN, np.float32), np.full(n, 1e30, np.float32), frac]
-    return np.choose(k, choices).astype(np.float32)
-
-
 _refs = {}
 
 
 def reference(name, s):
     if name not in _refs:
         sets = ray_sets(s)
-        if name == "non-nesting":
-            # The zero vector as a direction on a tree whose boxes do not nest: trt_trace_closest of the parent commit already leaves the records of
-            # some of these rays unwritten (8 of the 40 of non_finite_rays, on the 4-wide nodes), a fault of the traversal that the queries share
-            # and do not change; they are left out here, every other ray of the sets is compared.
-            sets = {k: (o[np.abs(d).sum(1) != 0], d[np.abs(d).sum(1) != 0]) for k, (o, d) in sets.items()}
         _refs[name] = {k: (o, d, O.trace(s.flat, o, d)) for k, (o, d) in sets.items()}
     return _refs[name]
 
@@ -90,7 +74,7 @@ def renderer_with(s, env, monkeypatch):
 def check_queries(r, refs, what):
     for set_name, (o, d, ref) in refs.items():
         tag = f"{what} / {set_name}"
-        tm = bounds_for(ref[0])
+        tm = Q.bounds_for(ref[0])
         t, tri, uv = r.trace_closest(o, d, t_max=tm)
         et, etri, euv = Q.closest(ref, tm)
         assert np.array_equal(tri, etri), f"{tag}: {int((tri != etri).sum())} tri differ"
@@ -145,7 +129,7 @@ def test_device_entries_equal_the_host_entries(name, renderer_factory):
     for n in (1, 63, 65, 4096, (1 << 20) + 17):
         o, d = raygen.random_rays(n, lo, hi, seed=n)
         base_t = r.trace_closest(o, d)[0]
-        tm = bounds_for(base_t, seed=n)
+        tm = Q.bounds_for(base_t, seed=n)
         want = r.trace_closest(o, d, t_max=tm)
         want_occ = r.trace_occluded(o, d, t_max=tm)
         want_none = r.trace_closest(o, d)

@@ -22,6 +22,23 @@
 #define TRT_PREFETCH 1
 #endif
 
+// Range checks of the traversal, compiled into the CPU test build only (tests/hostsim defines TRT_HOSTSIM_CHECKS): a walk that is about to
+// follow a reference out of range ends the ray with `ret` and tells its stack (stk.breach()), which the test counts.  Everywhere else the
+// macro is empty and the arguments are never evaluated, so the device code is the same with or without the checks.
+#ifdef TRT_HOSTSIM_CHECKS
+#define TRT_WALK_CHECK(ok, stk, ret) \
+    do {                             \
+        if (!(ok)) {                 \
+            (stk).breach();          \
+            return ret;              \
+        }                            \
+    } while (0)
+#else
+#define TRT_WALK_CHECK(ok, stk, ret) \
+    do {                             \
+    } while (0)
+#endif
+
 namespace trtd {
 
 // ------------------------------------------------------------------ types ----
@@ -415,11 +432,14 @@ TRT_HD inline bool innerStep(const SceneDev& sc, uint32_t& cur, int& sp, Stack& 
     r0 = f2u(rf.x); r1 = f2u(rf.y); r2 = f2u(rf.z); r3 = f2u(rf.w);
     const int n = (int)h0 + (int)h1 + (int)h2 + (int)h3;
     if (n == 0) return false;
-    // sort by entry distance; children that are not visited get a key no visited one can reach (a visited
-    // entry is <= cull_t, a finite bound or +inf when nothing bounds the search: then nothing is skipped by distance and the
-    // only keys of 3e38 belong to children whose box the ray misses) and so end up last
-    const float skip = 3.0e38f;
-    float k0 = h0 ? e0 : skip, k1 = h1 ? e1 : skip, k2 = h2 ? e2 : skip, k3 = h3 ? e3 : skip;
+    // sort by entry distance; children that are not visited get the key +inf, which no visited one can reach, and so end up last.
+    // A visited entry is <= cull_t, and where nothing bounds the search (cull_t = +inf: trees whose boxes do not nest) it can be
+    // beyond any finite key, +inf included: a ray whose direction is the zero vector passes, with entry +inf, every box that on each
+    // axis either holds its origin or lies on the side the sign of that zero points to.  A visited key is therefore clamped to the
+    // largest finite float (the visiting order is free; only the set matters).  Under a finite `skip` such a child would sort behind
+    // the ones not visited, and the walk would follow an unused slot's TRT_WIDE_EMPTY as a leaf.
+    const float skip = __builtin_inff(), kmax = 3.4028235e38f;
+    float k0 = h0 ? fminf(e0, kmax) : skip, k1 = h1 ? fminf(e1, kmax) : skip, k2 = h2 ? fminf(e2, kmax) : skip, k3 = h3 ? fminf(e3, kmax) : skip;
     TRT_CSWAP(k0, r0, k1, r1)
     TRT_CSWAP(k2, r2, k3, r3)
     TRT_CSWAP(k0, r0, k2, r2)
@@ -467,6 +487,7 @@ TRT_HD inline Hit traceClosestPass(const SceneDev& sc, f3 o, f3 d, Stack& stk, u
     for (;;) {
         if (cur & TRT_LEAF_BIT) {
             const uint32_t first = TRT_LEAF_FIRST(cur), count = TRT_LEAF_COUNT(cur);
+            TRT_WALK_CHECK((uint64_t)first + count <= sc.n_tris, stk, best);
             float lt = TRT_INF, lun = 0.f, lvn = 0.f, ldet = 1.0f;
             int32_t li = -1;
             uint32_t lflags = 0u;
@@ -506,10 +527,12 @@ TRT_HD inline Hit traceClosestPass(const SceneDev& sc, f3 o, f3 d, Stack& stk, u
             continue;
         }
         if (COUNT) n_inner++;
+        TRT_WALK_CHECK(cur < sc.n_wnodes, stk, best);
         if (!innerStep(sc, cur, sp, stk, o, inv, trt_cull_bound(best.t, sc.cull_alpha))) {
             if (sp == 0) break;
             cur = stk.pop(--sp);
         }
+        TRT_WALK_CHECK(sp <= stk.capacity(), stk, best);
     }
     if (!redo || best.tri >= 0 || !(best.t < TRT_INF)) break;
     best.t = TRT_INF;
@@ -539,6 +562,7 @@ TRT_HD inline Hit traceClosestBvh2Glm(const SceneDev& sc, f3 o, f3 d, Stack& stk
             float lt = TRT_INF, lun = 0.f, lvn = 0.f, ldet = 1.0f;
             int32_t li = -1;
             uint32_t lflags = 0u;
+            TRT_WALK_CHECK((uint64_t)first + count <= sc.n_tris, stk, best);
             if (count) {
                 const f4 ba = sc.leaf_box[2 * (size_t)first], bb = sc.leaf_box[2 * (size_t)first + 1];  // the box this leaf was entered through
                 float e;
@@ -568,6 +592,7 @@ TRT_HD inline Hit traceClosestBvh2Glm(const SceneDev& sc, f3 o, f3 d, Stack& stk
             continue;
         }
         if (COUNT) n_inner++;
+        TRT_WALK_CHECK(cur < sc.n_nodes, stk, best);
         const trt_bvh_node& nd = sc.nodes[cur];
         float e0, e1;
         const bool h0 = boxTestGlm(nd.lo0[0], nd.lo0[1], nd.lo0[2], nd.hi0[0], nd.hi0[1], nd.hi0[2], o, inv, e0);
@@ -580,6 +605,7 @@ TRT_HD inline Hit traceClosestBvh2Glm(const SceneDev& sc, f3 o, f3 d, Stack& stk
             if (sp == 0) break;
             cur = stk.pop(--sp);
         }
+        TRT_WALK_CHECK(sp <= stk.bvh2Capacity(), stk, best);
     }
     if (best.tri >= 0) {
         best.u = best.u / best_det;
