@@ -25,12 +25,12 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fa
             -Wall -Wextra -Wno-unused-parameter -Iinclude -I$(PKG)/csrc
 
 HOST_SRC := $(PKG)/host/scene.cpp $(PKG)/host/bvh.cpp $(PKG)/host/synth.cpp $(PKG)/host/image_out.cpp $(PKG)/host/jpeg.cpp $(PKG)/host/png.cpp $(PKG)/host/capi.cpp
-HOST_HDR := $(wildcard $(PKG)/host/*.h) include/trt.h include/trt_host.h include/trt_prims.h
+HOST_HDR := $(wildcard $(PKG)/host/*.h) $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_host.h include/trt_prims.h include/trt_exact.h
 HIP_SRC := $(PKG)/csrc/trt_api.hip
 HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include/trt_exact.h
 
-.PHONY: all host hip lbvh oracle cli hostsim denoisecpu variants probe exactcheck clean
-all: host hip lbvh oracle hostsim denoisecpu cli exactcheck
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu refitcpu variants probe exactcheck clean
+all: host hip lbvh oracle hostsim denoisecpu refitcpu cli exactcheck
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -46,10 +46,14 @@ tests/hostsim/libhostsim.so: tests/hostsim/hostsim.cpp $(HIP_HDR)
 denoisecpu: tests/denoise/libdenoise_cpu.so
 tests/denoise/libdenoise_cpu.so: tests/denoise/denoise_cpu.cpp $(PKG)/csrc/trt_denoise.h include/trt.h include/trt_prims.h include/trt_exact.h
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/denoise/denoise_cpu.cpp
+# CPU compile of the geometry update's per-node functions (trt_refit.h) over collapseBvh / buildOct output, for tests only (tests/test_refit_cpu.py)
+refitcpu: tests/refit/librefit_cpu.so
+tests/refit/librefit_cpu.so: tests/refit/refit_cpu.cpp $(HIP_HDR)
+	$(CXX) $(CXXFLAGS) -pthread -I$(PKG)/csrc -shared -o $@ tests/refit/refit_cpu.cpp
 
 $(OUT)/libtrt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(OUT)
-	$(CXX) $(CXXFLAGS) -fopenmp -shared -o $@ $(HOST_SRC)
+	$(CXX) $(CXXFLAGS) -I$(PKG)/csrc -fopenmp -shared -o $@ $(HOST_SRC)
 
 $(OUT)/libtrt_hip.so: $(HIP_SRC) $(HIP_HDR)
 	@mkdir -p $(OUT)
@@ -76,7 +80,7 @@ variants: $(HIP_SRC) $(HIP_HDR)
 	  echo "variant $$name: $$defs"; $(HIPCC) $(HIPFLAGS) $$defs -shared -o $(OUT)/variants/libtrt_hip_$$name.so $(HIP_SRC) || exit 1; done
 
 clean:
-	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/denoise/libdenoise_cpu.so
+	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/denoise/libdenoise_cpu.so tests/refit/librefit_cpu.so
 	$(MAKE) -C oracle clean
 
 # exhaustive (2^32 inputs) proof that include/trt_exact.h returns the bits of sqrtf / 1.0f / sqrtf: run by tests/test_gpu_parity.py

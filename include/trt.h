@@ -193,7 +193,8 @@ enum {
     TRT_K_TRACE_SHADOW = 3,
     TRT_K_RESOLVE = 4,
     TRT_K_TAIL = 5,       /* the last, short-queue bounces of a pass fused into one launch */
-    TRT_K_DENOISE = 6     /* trt_denoise*: the prepare kernel and every level of the a-trous filter */
+    TRT_K_DENOISE = 6,    /* trt_denoise*: the prepare kernel and every level of the a-trous filter */
+    TRT_K_REFIT = 7       /* trt_update_geometry*: every kernel of an update */
 };
 
 typedef struct trt_stats {
@@ -342,6 +343,48 @@ int trt_trace_occluded_device(trt_handle* h, uint64_t n, const float* org, const
                               uint8_t* occluded, void* hip_stream, trt_stats* stats);
 
 void trt_destroy(trt_handle* h);
+
+/* ---- geometry that moves: keep the tree, recompute its boxes ("refit") ----------------------------------------------------------
+ * trt_update_geometry gives the triangles of a handle new coordinates.  Topology, triangle order, materials, texture coordinates, textures,
+ * camera and every tuning decision of trt_create (trace_impl, the k_shade tables, slim / binned walk, grids, spill sizes) stay; only
+ * coordinates change.  The cost is a pass over the triangles and the nodes on the device instead of trt_create's host work.
+ *   Boxes.  A leaf's box becomes, per axis, min(coordinates of its triangles) - 0.001f / max + 0.001f (what the reference pads every node by,
+ *   bvh.cpp:31-40, and what the builders of this repository emit); an inner child's box becomes the union of that child's two boxes.  Both are
+ *   exact in fp32 (min / max and one rounded add; rounding is monotone, so the union of padded boxes is the padded union).  A leaf of 0 triangles
+ *   keeps the box it has; so does a node no root path reaches.
+ *   Result.  After the call the handle answers every entry point exactly as a fresh handle would that was created from the same trt_scene with
+ *   tri_v (tri_vn, lights, light_tris) replaced and `nodes` carrying the boxes above — bit for bit: hits depend on the tree only through the
+ *   stored boxes and the leaf order (trt_bvh_node above), refit boxes nest, and every node kind gives the same results.  All derived device
+ *   state follows: the intersection and shading records (geometry rewritten, material and flags kept), the caller's nodes, the per-triangle leaf
+ *   boxes, the 4-wide nodes and, on a handle that walks them, the 8-wide compressed nodes with their triangle records (each refitted
+ *   in its own tree: the collapses chosen at trt_create only dropped boxes and stay valid; the 8-wide bytes come from the quantiser trt_create
+ *   uses, so a stored box contains the exact one), the box-plane filter, the leaf-box tolerance, the light boxes, and the tables k_shade stages.
+ *   A handle that walks the 8-wide nodes and whose new boxes reach 2^40 (the premise of that node kind) walks the exact 4-wide nodes from then
+ *   on, for good; results do not change (trt_stats::inner_node_bytes then says 128).  A tree whose boxes did not nest at trt_create nests
+ *   afterwards but stays without distance culling (correct, slower).
+ *   Lights.  lights / light_tris (both or neither, HOST memory in both entries) replace the sampling tables; counts, every light's material and
+ *   the ranges must fit the handle's (TRT_EINVAL otherwise).  A handle that bisects the packed CDF (every handle whose CDFs were non-decreasing
+ *   at trt_create) refuses tables whose cumulative areas decrease or are NaN with TRT_EINVAL; one that scans keeps scanning.  With lights NULL
+ *   the tables are not touched: correct iff no emissive triangle moved — the library does not check.  The light boxes are recomputed either way.
+ *   Checks, all before anything is written: a null handle, u or tri_v, n_tris other than the handle's, the light checks above -> TRT_EINVAL on
+ *   the host; a vertex coordinate that is NaN or infinite -> TRT_EINVAL from a reduction over the new vertices that runs first.  After any
+ *   TRT_EINVAL the handle is unchanged and usable.  Normals may hold anything, as at trt_create.
+ *   Calls on one handle are the caller's to serialise.  Both entries return after the stream has been synchronised.  Device memory: the first
+ *   update allocates one 4-byte index per BVH2 node and per 4-wide node, and 28 bytes per 8-wide node (index + the exact union of its slots) on
+ *   a handle that walks them (about 5 bytes per triangle on a leaf-2 tree, 16 at most), plus a few words per light and material, kept until trt_destroy; a handle that is never updated costs nothing.  The host entry also stages the
+ *   vertices (36 bytes per triangle, 72 with normals) for the duration of the call.
+ *   stats (optional): launches / kernel_ms[TRT_K_REFIT] = every kernel of the update, render_ms = the call's device time (copies included);
+ *   every other field 0.  trt_group handles are not updated (re-create the group). */
+typedef struct trt_geometry_update {
+    const float* tri_v;               /* [n_tris][3][3], post-BVH order as in trt_scene; required */
+    const float* tri_vn;              /* [n_tris][3][3] or NULL = normals stay */
+    const trt_light* lights;          /* HOST in both entries; NULL = light tables stay */
+    const trt_light_tri* light_tris;  /* HOST in both entries; NULL iff lights is NULL */
+    uint32_t n_lights, n_light_tris;  /* must equal the handle's when lights != NULL */
+} trt_geometry_update;
+int trt_update_geometry(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris, trt_stats* stats);
+/* The same with tri_v / tri_vn in DEVICE memory of the handle's device, all work on hip_stream (NULL = default stream). */
+int trt_update_geometry_device(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris, void* hip_stream, trt_stats* stats);
 
 /* ---- denoising: the edge-avoiding a-trous wavelet filter (Dammertz et al. 2010, the spatial part of SVGF) ------------------------
  * A feature-guided spatial filter of one W x H image.  It needs no scene handle: any image with these buffers can be filtered, one read

@@ -60,6 +60,14 @@ int trth_scene_adopt_bvh(trth_scene* s, const trt_bvh_node* nodes, uint32_t n_no
 /* Valid after trth_scene_build / trth_scene_adopt_bvh; owned by the scene. */
 const trt_scene* trth_scene_flat(const trth_scene* s);
 
+/* Moves the vertices of a built scene: tri_v (and tri_vn, or NULL = normals stay) are [n_triangles][3][3] in the order of the flat
+ * description (post-BVH order, trt_scene::tri_v).  Topology and tree stay; the flat `nodes` are refitted by the box rule of
+ * trt_update_geometry (trt.h; the same functions, tinyraytracing_amd/csrc/trt_refit.h), and lights / light_tris / areas are rebuilt from the
+ * moved emissive triangles the way the loader builds them (running totals in file order, scene.cpp:199-205).  The pointers inside the flat
+ * description stay valid.  What a caller then hands to trt_update_geometry, or to trt_create for a fresh handle.  Non-finite coordinates and a
+ * malformed tree are refused before anything is written. */
+int trth_scene_set_vertices(trth_scene* s, const float* tri_v, const float* tri_vn);
+
 /* info[0..7] = width, height, n_vertices, n_vn, n_vt, n_triangles, n_materials, n_lights */
 int trth_scene_info(const trth_scene* s, int64_t info[8]);
 /* total area of light i (Material::area) in double */

@@ -14,7 +14,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _abi, adaptive
-from ._abi import Params, Stats, SceneFlat, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES, TRT_K_DENOISE  # noqa: F401
+from ._abi import Params, Stats, SceneFlat, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES, TRT_K_DENOISE, TRT_K_REFIT  # noqa: F401
 
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES_DIR = os.path.join(REPO_ROOT, "scenes")
@@ -162,6 +162,26 @@ class Scene:
             "bvh_depth": int(f.bvh_depth),
         }
         return out
+
+    def set_vertices(self, tri_v, tri_vn=None):
+        """Moves the triangles of a built scene (trth_scene_set_vertices): tri_v, and tri_vn unless None, are float32 [n_triangles, 3, 3] in
+        the order of the flat description (arrays()["tri_v"]).  The tree keeps its topology and gets the boxes of the moved triangles, the
+        light tables are rebuilt; `flat` then describes the moved scene — for Renderer.update_geometry, or for a fresh Renderer."""
+        n = self.flat.contents.n_tris
+        fp = C.POINTER(C.c_float)
+        arrs = []
+        for name, a in (("tri_v", tri_v), ("tri_vn", tri_vn)):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.size != n * 9:
+                raise TrtError(f"set_vertices: {name} must hold {n} x 3 x 3 floats")
+            arrs.append(a)
+        if arrs[0] is None:
+            raise TrtError("set_vertices: tri_v is needed")
+        self._check(self._lib.trth_scene_set_vertices(self._h, arrs[0].ctypes.data_as(fp), None if arrs[1] is None else arrs[1].ctypes.data_as(fp)))
+        return self
 
     def close(self):
         if self._h:
@@ -539,6 +559,60 @@ class Renderer:
         rc = self._lib.trt_trace_occluded_device(self._h, n, *p, C.c_void_p(stream_ptr), C.byref(st))
         if rc != 0:
             raise TrtError(f"trt_trace_occluded_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return st
+
+    def _light_tables(self, upd, lights_from):
+        if lights_from is None:
+            return
+        f = lights_from.flat.contents
+        upd.lights, upd.light_tris, upd.n_lights, upd.n_light_tris = f.lights, f.light_tris, f.n_lights, f.n_light_tris
+
+    def update_geometry(self, scene_or_tri_v, tri_vn=None, lights_from=None, want_stats=False):
+        """trt_update_geometry: new coordinates for the triangles of this handle, tree topology kept, boxes refitted on the GPU; afterwards the
+        handle answers exactly as a fresh Renderer of the moved scene would (include/trt.h).  Given a Scene (after Scene.set_vertices) its flat
+        vertices, normals and light tables are taken; given a float32 array [n, 3, 3] (host), tri_vn likewise or None = normals stay, and
+        lights_from = a Scene whose light tables to take, or None = they stay (right iff no emissive triangle moved).  -> None or Stats."""
+        upd = _abi.GeometryUpdate()
+        keep = []
+        if isinstance(scene_or_tri_v, Scene):
+            f = scene_or_tri_v.flat.contents
+            n = f.n_tris
+            upd.tri_v, upd.tri_vn = C.cast(f.tri_v, C.c_void_p), C.cast(f.tri_vn, C.c_void_p)
+            self._light_tables(upd, scene_or_tri_v)
+        else:
+            v = np.ascontiguousarray(scene_or_tri_v, dtype=np.float32)
+            if v.ndim != 3 or v.shape[1:] != (3, 3):
+                raise TrtError("update_geometry: tri_v must be a float32 array of shape (n, 3, 3)")
+            n = v.shape[0]
+            keep.append(v)
+            upd.tri_v = v.ctypes.data
+            if tri_vn is not None:
+                vn = np.ascontiguousarray(tri_vn, dtype=np.float32)
+                if vn.shape != v.shape:
+                    raise TrtError("update_geometry: tri_vn must have tri_v's shape")
+                keep.append(vn)
+                upd.tri_vn = vn.ctypes.data
+            self._light_tables(upd, lights_from)
+        st = Stats()
+        rc = self._lib.trt_update_geometry(self._h, C.byref(upd), n, C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_update_geometry failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return st if want_stats else None
+
+    def update_geometry_from(self, tri_v, tri_vn=None, lights_from=None, stream_ptr=0):
+        """trt_update_geometry_device: tri_v (float32 [n, 3, 3]) and tri_vn (the same, or None = normals stay) are torch tensors on this device;
+        lights_from as for update_geometry (host tables); the work runs on stream `stream_ptr` (0 = default).  -> Stats."""
+        if not _is_torch(tri_v) or tri_v.dim() != 3 or tuple(tri_v.shape[1:]) != (3, 3):
+            raise TrtError("update_geometry_from: tri_v must be a float32 tensor of shape (n, 3, 3)")
+        n = tri_v.shape[0]
+        p = self._device_arrays("update_geometry_from", n, [("tri_v", tri_v, ("torch.float32",), 9 * n), ("tri_vn", tri_vn, ("torch.float32",), 9 * n)])
+        upd = _abi.GeometryUpdate()
+        upd.tri_v, upd.tri_vn = p[0], p[1]
+        self._light_tables(upd, lights_from)
+        st = Stats()
+        rc = self._lib.trt_update_geometry_device(self._h, C.byref(upd), n, C.c_void_p(stream_ptr), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_update_geometry_device failed ({rc}): {self._lib.trt_last_error().decode()}")
         return st
 
     def close(self):

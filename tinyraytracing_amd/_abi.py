@@ -23,6 +23,8 @@ TRT_MAX_KERNELS = 8
 KERNEL_NAMES = ["gen_primary", "trace_closest", "shade", "trace_shadow", "resolve", "tail"]
 # trt_denoise*'s slot of Stats.launches / kernel_ms: not in KERNEL_NAMES, whose last entry is the render's own last kernel
 TRT_K_DENOISE = 6
+# trt_update_geometry*'s slot
+TRT_K_REFIT = 7
 TRT_DENOISE_MAX_ITERATIONS = 10
 TRT_DENOISE_MAX_PIXELS = 1 << 28
 
@@ -91,14 +93,19 @@ class DenoiseParams(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class GeometryUpdate(C.Structure):
+    _fields_ = [("tri_v", C.c_void_p), ("tri_vn", C.c_void_p), ("lights", C.POINTER(Light)), ("light_tris", C.POINTER(LightTri)),
+                ("n_lights", C.c_uint32), ("n_light_tris", C.c_uint32)]
+
+
 # the symbols include/trt.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_aov",
                "trt_render_aov_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
                "trt_trace_occluded_device", "trt_denoise", "trt_denoise_device",
-               "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
+               "trt_update_geometry", "trt_update_geometry_device", "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
 HOST_SYMBOLS = ["trth_scene_load", "trth_scene_load_opts", "trth_scene_drop_tris", "trth_scene_add_soup", "trth_scene_add_blob", "trth_scene_add_lamps",
-                "trth_scene_build", "trth_scene_vertices", "trth_scene_adopt_bvh", "trth_scene_flat", "trth_scene_info", "trth_scene_light_area",
+                "trth_scene_build", "trth_scene_vertices", "trth_scene_adopt_bvh", "trth_scene_set_vertices", "trth_scene_flat", "trth_scene_info", "trth_scene_light_area",
                 "trth_scene_material_name", "trth_scene_free", "trth_tonemap", "trth_write_png", "trth_write_pfm",
                 "trth_write_png_bytes", "trth_decode_jpeg", "trth_decode_png", "trth_abi_sizes", "trth_last_error"]
 
@@ -144,6 +151,7 @@ def load_host():
     lib.trth_scene_build.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.trth_scene_vertices.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint64]
     lib.trth_scene_adopt_bvh.argtypes = [C.c_void_p, C.POINTER(BvhNode), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
+    lib.trth_scene_set_vertices.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.trth_scene_flat.restype = C.POINTER(SceneFlat)
     lib.trth_scene_flat.argtypes = [C.c_void_p]
     lib.trth_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
@@ -220,6 +228,8 @@ def load_hip():
     lib.trt_trace_occluded_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 6 + [C.POINTER(Stats)]
     lib.trt_denoise_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.POINTER(Stats)]
+    lib.trt_update_geometry.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_uint32, C.POINTER(Stats)]
+    lib.trt_update_geometry_device.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
     lib.trt_destroy.argtypes = [C.c_void_p]
     lib.trt_destroy.restype = None
     lib.trt_group_create.argtypes = [C.POINTER(SceneFlat), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]

@@ -24,6 +24,7 @@
 #include "trt_wide.h"
 #include "trt_oct_build.h"
 #include "trt_denoise_kernels.h"
+#include "trt_refit_kernels.h"
 
 using namespace trtd;
 
@@ -138,8 +139,27 @@ struct trt_handle {
     int fail_at_bounce = -1;                           // TRT_TEST_FAIL_AT_BOUNCE at trt_create: the next render reports an injected failure
                                                        // after issuing that bounce (exercises the error path; consumed once)
     std::vector<hipEvent_t> events;
+    // trt_update_geometry: what trt_create leaves behind for it costs no device memory; the rest is made at the first update and kept
+    uint32_t n_materials = 0, n_light_tris = 0, n_tri_trav = 0;
+    bool light_boxes_fixed = false;                    // TRT_SHADOW_STOP=0 at trt_create: every light's box is all of space and stays so
+    struct Refit {
+        bool ready = false;
+        DevBuf order2, order4, order8, exact8, small;  // breadth-first node lists of the BVH2, the 4-wide and the 8-wide tree; per 8-wide node the exact union
+                                                       // of its slots; cursor + flags + light boxes
+        std::vector<uint32_t> level2, level4, level8;  // level l = order[level[l] .. level[l + 1])
+        DevBuf light_of_mat;
+        hipEvent_t ev[4] = {};
+    } refit;
     ~trt_handle()
     {
+        refit.order2.release();
+        refit.order4.release();
+        refit.order8.release();
+        refit.exact8.release();
+        refit.small.release();
+        refit.light_of_mat.release();
+        for (hipEvent_t e : refit.ev)
+            if (e) (void)hipEventDestroy(e);
         for (void* p : scene_allocs) (void)hipFree(p);
         arena.release();
         spill.release();
@@ -608,6 +628,21 @@ int useDevice(int device)
     return TRT_OK;
 }
 
+// The tables k_shade stages, copied into the handle's packed image in LDS layout (trt_create; again after trt_update_geometry rewrote them).
+int packLdsImage(trt_handle* h, hipStream_t stream)
+{
+    const void* src[5] = {h->sc.materials, h->sc.lights, h->sc.light_cum, h->sc.light_tris, h->sc.tri_shade};
+    size_t off = 0;
+    for (int k = 0; k < 5; ++k)
+        if (h->shade_tabs >> k & 1u) {
+            const size_t padded = (h->lds_tab[k] + 15u) & ~15u;  // upload() padded the source the same way
+            HIPC(hipMemcpyAsync((char*)h->lds_image + off, src[k], padded, hipMemcpyDeviceToDevice, stream));
+            off += padded;
+        }
+    HIPC(hipStreamSynchronize(stream));
+    return TRT_OK;
+}
+
 int createOnDevice(const SceneImage& im, int device, trt_handle** out)
 {
     const trt_scene* s = im.s;
@@ -658,6 +693,7 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
         h->sc.n_onodes = (uint32_t)im.oct.nodes.size();
         if (int e = upload(h.get(), im.oct.nodes.data(), im.oct.nodes.size(), &h->sc.onodes)) return e;
         if (int e = upload(h.get(), im.oct.tri_trav.data(), im.oct.tri_trav.size(), &h->sc.tri_trav)) return e;
+        h->n_tri_trav = (uint32_t)im.oct.tri_trav.size();
     }
     if (int e = upload(h.get(), im.mats.data(), im.mats.size(), &h->sc.materials)) return e;
     if (int e = upload(h.get(), im.lights.data(), im.lights.size(), &h->sc.lights)) return e;
@@ -671,6 +707,9 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->sc.n_tris = s->n_tris;
     h->sc.n_nodes = s->n_nodes;
     h->sc.n_lights = s->n_lights;
+    h->n_materials = s->n_materials;
+    h->n_light_tris = s->n_light_tris;
+    if (const char* e = std::getenv("TRT_SHADOW_STOP")) h->light_boxes_fixed = std::atoi(e) == 0;
     h->sc.light0_area = s->n_lights ? s->lights[0].area : 0.0f;
     h->sc.leaf_alpha = im.leaf_alpha;
     h->sc.cull_alpha = im.cull_alpha;
@@ -698,7 +737,6 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
             std::fprintf(stderr, "trt_create: k_shade tables %u (lds bytes: materials %u, lights %u, cdf %u, light tris %u, shading tris %u)\n", h->shade_tabs,
                          h->lds_tab[0], h->lds_tab[1], h->lds_tab[2], h->lds_tab[3], h->lds_tab[4]);
         // the staged tables once more, packed in LDS layout: a block fetches them with one coalesced pass
-        const void* src[5] = {h->sc.materials, h->sc.lights, h->sc.light_cum, h->sc.light_tris, h->sc.tri_shade};
         size_t total = 0;
         for (int k = 0; k < 5; ++k)
             if (h->shade_tabs >> k & 1u) total += (h->lds_tab[k] + 15u) & ~15u;
@@ -706,15 +744,9 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
             void* img = nullptr;
             HIPC(hipMalloc(&img, total));
             h->scene_allocs.push_back(img);
-            size_t off = 0;
-            for (int k = 0; k < 5; ++k)
-                if (h->shade_tabs >> k & 1u) {
-                    const size_t padded = (h->lds_tab[k] + 15u) & ~15u;  // upload() padded the source the same way
-                    HIPC(hipMemcpy((char*)img + off, src[k], padded, hipMemcpyDeviceToDevice));
-                    off += padded;
-                }
             h->lds_image = img;
             h->lds_image_bytes = (uint32_t)total;
+            if (int e = packLdsImage(h.get(), nullptr)) return e;
         }
     }
     h->slim_walk = h->trace_impl == 0 && s->n_tris <= 64;  // (trace_impl 0 implies <= 64 triangles: the LDS copies of trt_kernels.h hold 64)
@@ -1995,6 +2027,255 @@ int trt_denoise_device(int device, const trt_denoise_params* params, int width, 
 {
     return denoise(device, params, width, height, DenoiseIo{color, variance, albedo, normal, depth, out}, false, (hipStream_t)hip_stream, stats,
                    "trt_denoise_device");
+}
+
+}  // extern "C"
+
+// ---- geometry update (include/trt.h trt_update_geometry; per-element code trt_refit.h) ------------------------------------------------
+namespace {
+
+inline dim3 refitGrid(uint64_t n) { return dim3((unsigned)std::max<uint64_t>(1, (n + REFIT_BLOCK - 1) / REFIT_BLOCK)); }
+
+// First update of a handle: the breadth-first node lists of both trees (one launch and one 4-byte read-back per level), the
+// material-to-light table and the events.  Nothing a render reads is written.
+template <class Bfs>
+int refitNumber(Bfs launch, uint32_t n_nodes, uint32_t* d_order, uint32_t* d_cursor, hipStream_t stream, std::vector<uint32_t>& level)
+{
+    const uint32_t root[2] = {0u, 1u};  // order[0] = node 0; cursor = 1
+    HIPC(hipMemcpyAsync(d_order, &root[0], sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIPC(hipMemcpyAsync(d_cursor, &root[1], sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    level.assign(1, 0u);
+    uint32_t begin = 0, end = 1;
+    while (begin < end) {
+        level.push_back(end);
+        launch(begin, end);
+        uint32_t cur = 0;
+        HIPC(hipMemcpyAsync(&cur, d_cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIPC(hipStreamSynchronize(stream));
+        if (cur > n_nodes || level.size() > (size_t)MAX_BVH_DEPTH * 2 + 4) return fail(TRT_EHIP, "trt_update_geometry: the handle's tree does not number (internal error)");
+        begin = end;
+        end = cur;
+    }
+    return TRT_OK;
+}
+
+int refitPrepare(trt_handle* h, hipStream_t stream)
+{
+    trt_handle::Refit& R = h->refit;
+    if (R.ready) return TRT_OK;
+    const uint32_t nn = h->sc.n_nodes, nw = h->sc.n_wnodes;
+    if (int e = R.order2.ensure((size_t)nn * sizeof(uint32_t))) return e;
+    if (int e = R.order4.ensure((size_t)std::max(nw, 1u) * sizeof(uint32_t))) return e;
+    if (int e = R.small.ensure((size_t)(16 + 6 * (size_t)std::max(h->sc.n_lights, 1u)) * sizeof(uint32_t))) return e;
+    if (int e = R.light_of_mat.ensure((size_t)std::max(h->n_materials, 1u) * sizeof(int32_t))) return e;
+    for (hipEvent_t& e : R.ev)
+        if (!e) HIPC(hipEventCreate(&e));
+    uint32_t* cursor = (uint32_t*)R.small.p;
+    uint32_t* o2 = (uint32_t*)R.order2.p;
+    uint32_t* o4 = (uint32_t*)R.order4.p;
+    if (int e = refitNumber([&](uint32_t b, uint32_t en) { hipLaunchKernelGGL(k_refit_bfs2, refitGrid(en - b), dim3(REFIT_BLOCK), 0, stream, h->sc.nodes, o2, b, en, cursor, nn); },
+                            nn, o2, cursor, stream, R.level2)) return e;
+    if (nw)
+        if (int e = refitNumber([&](uint32_t b, uint32_t en) { hipLaunchKernelGGL(k_refit_bfs4, refitGrid(en - b), dim3(REFIT_BLOCK), 0, stream, h->sc.wnodes, o4, b, en, cursor, nw); },
+                                nw, o4, cursor, stream, R.level4)) return e;
+    if (h->node_kind == 1 && h->sc.onodes) {
+        const uint32_t no = h->sc.n_onodes;
+        if (int e = R.order8.ensure((size_t)std::max(no, 1u) * sizeof(uint32_t))) return e;
+        if (int e = R.exact8.ensure((size_t)std::max(no, 1u) * sizeof(RefitBox))) return e;
+        uint32_t* o8 = (uint32_t*)R.order8.p;
+        if (int e = refitNumber([&](uint32_t b, uint32_t en) { hipLaunchKernelGGL(k_refit_bfs8, refitGrid(en - b), dim3(REFIT_BLOCK), 0, stream, h->sc.onodes, o8, b, en, cursor, no); },
+                                no, o8, cursor, stream, R.level8)) return e;
+    }
+    std::vector<int32_t> lom(std::max(h->n_materials, 1u), -1);
+    for (size_t l = h->light_mats.size(); l-- > 0;)
+        if (h->light_mats[l] < h->n_materials) lom[h->light_mats[l]] = (int32_t)l;  // the first light of a material stands for all of them
+    HIPC(hipMemcpyAsync(R.light_of_mat.p, lom.data(), lom.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+    R.ready = true;
+    return TRT_OK;
+}
+
+struct RefitStage {  // the host entry's copy of the vertices, released on every way out
+    void* v = nullptr;
+    void* vn = nullptr;
+    ~RefitStage()
+    {
+        if (v) (void)hipFree(v);
+        if (vn) (void)hipFree(vn);
+    }
+};
+
+int updateGeometry(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris, bool host, hipStream_t stream, trt_stats* stats, const char* what)
+{
+    const std::string w(what);
+    if (!h || !u) return fail(TRT_EINVAL, w + ": null handle / update");
+    if (!u->tri_v && h->sc.n_tris) return fail(TRT_EINVAL, w + ": tri_v is null");
+    if (n_tris != h->sc.n_tris) return fail(TRT_EINVAL, w + ": n_tris differs from the handle's (topology cannot change)");
+    if ((u->lights == nullptr) != (u->light_tris == nullptr) && (u->lights || h->n_light_tris)) return fail(TRT_EINVAL, w + ": lights and light_tris come together");
+    std::vector<LightDev> lights;
+    std::vector<LightTriDev> ltris;
+    std::vector<float> cum;
+    const bool new_lights = u->lights != nullptr;
+    if (new_lights) {
+        if (u->n_lights != h->sc.n_lights || u->n_light_tris != h->n_light_tris) return fail(TRT_EINVAL, w + ": light counts differ from the handle's");
+        for (uint32_t l = 0; l < u->n_lights; ++l) {
+            const trt_light& L = u->lights[l];
+            if (L.mat < 0 || (uint32_t)L.mat >= h->n_materials) return fail(TRT_EINVAL, w + ": light material id out of range");
+            if ((uint32_t)L.mat != h->light_mats[l]) return fail(TRT_EINVAL, w + ": a light's material differs from the handle's");
+            if ((uint64_t)L.tri_first + L.tri_count > u->n_light_tris) return fail(TRT_EINVAL, w + ": light triangle range out of bounds");
+        }
+        std::vector<MaterialDev> mats(h->n_materials);  // radiance comes from the materials (makeLightDev); they live on the device only
+        HIPC(hipSetDevice(h->device));
+        HIPC(hipMemcpy(mats.data(), h->sc.materials, mats.size() * sizeof(MaterialDev), hipMemcpyDeviceToHost));
+        lights.resize(u->n_lights);
+        for (uint32_t l = 0; l < u->n_lights; ++l) lights[l] = makeLightDevFrom(u->lights[l], mats[(size_t)u->lights[l].mat].radiance);
+        ltris.resize(u->n_light_tris);
+        cum.resize(u->n_light_tris);
+        for (uint32_t k = 0; k < u->n_light_tris; ++k) { ltris[k] = makeLightTriDev(u->light_tris[k]); cum[k] = u->light_tris[k].cum_area; }
+        bool monotone = true;
+        for (uint32_t l = 0; l < u->n_lights; ++l)
+            for (uint32_t k = 0; k < u->lights[l].tri_count; ++k) {
+                const float c = cum[u->lights[l].tri_first + k];
+                if (!(c == c) || (k && c < cum[u->lights[l].tri_first + k - 1])) monotone = false;
+            }
+        // a handle that bisects the packed CDF keeps doing so (k_shade's LDS layout is fixed at trt_create): a CDF it cannot bisect is refused
+        if (h->sc.light_cum && !monotone) return fail(TRT_EINVAL, w + ": a light's cumulative areas decrease or are NaN (this handle bisects them)");
+    }
+    HIPC(hipSetDevice(h->device));
+    trt_handle::Refit& R = h->refit;
+    for (hipEvent_t& e : R.ev)
+        if (!e) HIPC(hipEventCreate(&e));
+    HIPC(hipEventRecord(R.ev[0], stream));  // render_ms of a handle's first update holds the numbering of its trees
+    if (int e = refitPrepare(h, stream)) return e;
+    const uint32_t n = h->sc.n_tris, nn = h->sc.n_nodes, nw = h->sc.n_wnodes, nl = h->sc.n_lights;
+    uint32_t* flag = (uint32_t*)R.small.p + 1;
+    uint32_t* oct_fail = (uint32_t*)R.small.p + 2;
+    uint32_t* lbox = (uint32_t*)R.small.p + 16;
+
+    RefitStage S;
+    const float* d_v = u->tri_v;
+    const float* d_vn = u->tri_vn;
+    if (host && n) {
+        const size_t bytes = (size_t)n * 9 * sizeof(float);
+        HIPC(hipMalloc(&S.v, bytes));
+        HIPC(hipMemcpyAsync(S.v, u->tri_v, bytes, hipMemcpyHostToDevice, stream));
+        d_v = (const float*)S.v;
+        if (u->tri_vn) {
+            HIPC(hipMalloc(&S.vn, bytes));
+            HIPC(hipMemcpyAsync(S.vn, u->tri_vn, bytes, hipMemcpyHostToDevice, stream));
+            d_vn = (const float*)S.vn;
+        }
+    }
+    uint64_t launches = 0;
+    HIPC(hipEventRecord(R.ev[1], stream));
+    {   // nothing is written before the vertices have passed
+        HIPC(hipMemsetAsync(flag, 0, sizeof(uint32_t), stream));
+        const uint64_t nf = (uint64_t)n * 9;
+        hipLaunchKernelGGL(k_refit_check, dim3((unsigned)std::min<uint64_t>(4096, std::max<uint64_t>(1, (nf + REFIT_BLOCK - 1) / REFIT_BLOCK))), dim3(REFIT_BLOCK), 0, stream, d_v, nf, flag);
+        ++launches;
+        uint32_t bad = 0;
+        HIPC(hipMemcpyAsync(&bad, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIPC(hipStreamSynchronize(stream));
+        HIPC(hipGetLastError());
+        if (bad) return fail(TRT_EINVAL, w + ": a vertex coordinate is NaN or infinite");
+    }
+    if (n) {
+        hipLaunchKernelGGL(k_refit_tris, refitGrid(n), dim3(REFIT_BLOCK), 0, stream, n, d_v, d_vn, (TriIsect*)h->sc.tri_isect, (TriShade*)h->sc.tri_shade);
+        ++launches;
+    }
+    for (size_t l = R.level2.size() - 1; l-- > 0;) {
+        const uint32_t b = R.level2[l], e = R.level2[l + 1];
+        hipLaunchKernelGGL(k_refit_level2, refitGrid(e - b), dim3(REFIT_BLOCK), 0, stream, (trt_bvh_node*)h->sc.nodes, nn, (const uint32_t*)R.order2.p, b, e, d_v, (f4*)h->sc.leaf_box);
+        ++launches;
+    }
+    for (size_t l = R.level4.empty() ? 0 : R.level4.size() - 1; l-- > 0;) {
+        const uint32_t b = R.level4[l], e = R.level4[l + 1];
+        hipLaunchKernelGGL(k_refit_level4, refitGrid(e - b), dim3(REFIT_BLOCK), 0, stream, (WideNode*)h->sc.wnodes, nw, (const uint32_t*)R.order4.p, b, e, h->sc.leaf_box);
+        ++launches;
+    }
+    const bool oct = h->node_kind == 1 && !R.level8.empty();
+    if (oct) {   // the 8-wide nodes: triangle records in node order, then the nodes level by level with their children's exact boxes in scratch
+        HIPC(hipMemsetAsync(oct_fail, 0, sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(k_refit_tri_trav, refitGrid(h->n_tri_trav), dim3(REFIT_BLOCK), 0, stream, h->n_tri_trav, h->sc.tri_isect, (TriIsect*)h->sc.tri_trav);
+        ++launches;
+        for (size_t l = R.level8.size() - 1; l-- > 0;) {
+            const uint32_t b = R.level8[l], e = R.level8[l + 1];
+            hipLaunchKernelGGL(k_refit_level8, refitGrid(e - b), dim3(REFIT_BLOCK), 0, stream, (OctNode*)h->sc.onodes, h->sc.n_onodes, (const uint32_t*)R.order8.p, b, e,
+                               h->sc.tri_trav, h->sc.leaf_box, (RefitBox*)R.exact8.p, oct_fail);
+            ++launches;
+        }
+    }
+    if (h->sc.plane_bits) {
+        const size_t words = (size_t)((1ull << (32u - h->sc.plane_shift)) / 32);
+        HIPC(hipMemsetAsync((void*)h->sc.plane_bits, 0, words * sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(k_refit_planes, refitGrid(nn), dim3(REFIT_BLOCK), 0, stream, h->sc.nodes, nn, (uint32_t*)h->sc.plane_bits, h->sc.plane_shift);
+        ++launches;
+    }
+    std::vector<uint32_t> lb_host((size_t)6 * nl);
+    const bool light_boxes = nl && !h->light_boxes_fixed;
+    if (light_boxes) {
+        for (uint32_t l = 0; l < nl; ++l)
+            for (int a = 0; a < 3; ++a) { lb_host[6 * l + a] = refitOrdered(3.0e38f); lb_host[6 * l + 3 + a] = refitOrdered(-3.0e38f); }
+        HIPC(hipMemcpyAsync(lbox, lb_host.data(), lb_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_refit_light_boxes, refitGrid(n), dim3(REFIT_BLOCK), 0, stream, n, h->sc.tri_isect, h->sc.leaf_box, (const int32_t*)R.light_of_mat.p, h->n_materials, lbox);
+        ++launches;
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(R.ev[2], stream));
+    trt_bvh_node root{};
+    HIPC(hipMemcpyAsync(&root, h->sc.nodes, sizeof(root), hipMemcpyDeviceToHost, stream));
+    uint32_t oct_failed = 0;
+    if (oct) HIPC(hipMemcpyAsync(&oct_failed, oct_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (light_boxes) HIPC(hipMemcpyAsync(lb_host.data(), lbox, lb_host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (new_lights) {
+        if (!lights.empty()) HIPC(hipMemcpyAsync((void*)h->sc.lights, lights.data(), lights.size() * sizeof(LightDev), hipMemcpyHostToDevice, stream));
+        if (!ltris.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_tris, ltris.data(), ltris.size() * sizeof(LightTriDev), hipMemcpyHostToDevice, stream));
+        if (h->sc.light_cum && !cum.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_cum, cum.data(), cum.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
+    if (h->lds_image)
+        if (int e = packLdsImage(h, stream)) return e;
+    HIPC(hipEventRecord(R.ev[3], stream));
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+
+    h->sc.leaf_alpha = sceneLeafAlpha(&root, 1);
+    if (h->sc.cull_alpha != std::numeric_limits<float>::infinity()) h->sc.cull_alpha = h->sc.leaf_alpha;  // a tree that did not nest at trt_create stays without distance culling
+    if (light_boxes)
+        for (uint32_t l = 0; l < nl; ++l) {
+            const uint32_t m = h->light_mats[l];
+            uint32_t from = l;  // lights of one material share the box of the first of them
+            for (uint32_t k = 0; k < l; ++k)
+                if (h->light_mats[k] == m) { from = k; break; }
+            for (int a = 0; a < 3; ++a) { h->light_boxes[l].lo[a] = refitUnordered(lb_host[6 * from + a]); h->light_boxes[l].hi[a] = refitUnordered(lb_host[6 * from + 3 + a]); }
+        }
+    if (new_lights) h->sc.light0_area = nl ? u->lights[0].area : 0.0f;
+    // boxes that reach 2^40 (or an extent the bytes cannot hold): the tree no longer qualifies for the 8-wide nodes — the exact 4-wide ones from here on, for good
+    if (oct && oct_failed) h->node_kind = 0;
+    if (stats) {
+        float k_ms = 0.f, all_ms = 0.f;
+        HIPC(hipEventElapsedTime(&k_ms, R.ev[1], R.ev[2]));
+        HIPC(hipEventElapsedTime(&all_ms, R.ev[0], R.ev[3]));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->launches[TRT_K_REFIT] = launches;
+        stats->kernel_ms[TRT_K_REFIT] = k_ms;
+        stats->render_ms = all_ms;
+    }
+    return TRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trt_update_geometry(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris, trt_stats* stats)
+{
+    return updateGeometry(h, u, n_tris, true, nullptr, stats, "trt_update_geometry");
+}
+
+int trt_update_geometry_device(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris, void* hip_stream, trt_stats* stats)
+{
+    return updateGeometry(h, u, n_tris, false, (hipStream_t)hip_stream, stats, "trt_update_geometry_device");
 }
 
 }  // extern "C"

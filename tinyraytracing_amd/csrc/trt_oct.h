@@ -58,6 +58,62 @@ static_assert(sizeof(OctNode) == 80, "OctNode is five 16-byte words");
 
 #define TRT_OCT_MAX_LEAF_TRIS 3u
 
+// The quantiser of the 8-wide nodes, the ONE piece of code that decides "stored box contains exact box": trt_oct_build.h's buildOct calls it when it lays a
+// node out, trt_refit.h's refitOct when the boxes of a resident tree move.  blo / bhi: the exact boxes by slot, valid where bit `slot` of mask is set (>= 1
+// slot).  Frame origin p = the per-axis minimum, scale 2^(e-127) the smallest power of two that fits the extent into 0..255, every byte moved outward until
+// p + q * scale contains the exact bound IN BINARY64 (exact arithmetic: a 24-bit and an 8-bit significand).  Empty slots get qlo = 255, qhi = 0.
+// false: the extent is not representable (e would pass 254).
+TRT_HD inline bool octQuantise(const float blo[8][3], const float bhi[8][3], uint32_t mask, float p_out[3], uint32_t ebits[3], uint32_t qlo[3][8], uint32_t qhi[3][8])
+{
+    for (int a = 0; a < 3; ++a) {
+        double lo = 0, hi = 0;
+        bool first = true;
+        for (int sl = 0; sl < 8; ++sl) {
+            if (!((mask >> sl) & 1u)) continue;
+            if (first || blo[sl][a] < lo) lo = blo[sl][a];
+            if (first || bhi[sl][a] > hi) hi = bhi[sl][a];
+            first = false;
+        }
+        const double p = lo, ext = hi - lo;
+        int eb = 1;
+        if (ext > 0.0) {
+            int ex = 0;
+            (void)frexp(ext / 255.0, &ex);  // ext / 255 = m * 2^ex, m in [0.5, 1): 2^ex >= ext / 255
+            eb = ex + 127 > 1 ? ex + 127 : 1;
+        }
+        for (;; ++eb) {
+            if (eb > 254) return false;
+            const double s = ldexp(1.0, eb - 127);
+            bool fits = true;
+            for (int sl = 0; sl < 8 && fits; ++sl) {
+                if (!((mask >> sl) & 1u)) { qlo[a][sl] = 255u; qhi[a][sl] = 0u; continue; }
+                const double el = (double)blo[sl][a], eh = (double)bhi[sl][a];
+                long ql = (long)floor((el - p) / s);
+                ql = ql < 0L ? 0L : (ql > 255L ? 255L : ql);
+                while (ql > 0 && p + (double)ql * s > el) --ql;
+                long qh = (long)ceil((eh - p) / s);
+                qh = qh < 0L ? 0L : qh;
+                while (qh < 256 && p + (double)qh * s < eh) ++qh;
+                if (qh > 255 || p + (double)ql * s > el) { fits = false; break; }
+                qlo[a][sl] = (uint32_t)ql;
+                qhi[a][sl] = (uint32_t)qh;
+            }
+            if (fits) break;
+        }
+        ebits[a] = (uint32_t)eb;
+        p_out[a] = (float)lo;
+    }
+    return true;
+}
+TRT_HD inline uint32_t octPack4(const uint32_t* v) { return v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24); }
+// q2..q4 of a node from the bytes
+TRT_HD inline void octStoreBounds(OctNode& on, const uint32_t qlo[3][8], const uint32_t qhi[3][8])
+{
+    on.q[2] = mk4(u2f(octPack4(qlo[0])), u2f(octPack4(qlo[0] + 4)), u2f(octPack4(qlo[1])), u2f(octPack4(qlo[1] + 4)));
+    on.q[3] = mk4(u2f(octPack4(qlo[2])), u2f(octPack4(qlo[2] + 4)), u2f(octPack4(qhi[0])), u2f(octPack4(qhi[0] + 4)));
+    on.q[4] = mk4(u2f(octPack4(qhi[1])), u2f(octPack4(qhi[1] + 4)), u2f(octPack4(qhi[2])), u2f(octPack4(qhi[2] + 4)));
+}
+
 // Per-ray constants of the quantised-frame test.
 struct OctRay {
     f3 o, inv;         // inv: 1 / d, an infinite one (d = +-0) replaced by TRT_OCT_DEAD_K

@@ -260,38 +260,21 @@ inline OctTree buildOct(const trt_bvh_node* caller_nodes2, uint32_t caller_n_nod
                 child_in[bs] = bk;
             }
         }
-        // quantisation
+        // quantisation (trt_oct.h octQuantise: the same function refits a resident tree)
         uint32_t ebits[3];
         uint32_t qlo[3][W], qhi[3][W];
-        d.ok = true;
-        for (int a = 0; a < 3; ++a) {
-            const double p = lo[a], ext = hi[a] - lo[a];
-            int eb = 1;
-            if (ext > 0.0) {
-                int ex = 0;
-                (void)std::frexp(ext / 255.0, &ex);  // ext / 255 = m * 2^ex, m in [0.5, 1): 2^ex >= ext / 255
-                eb = std::max(ex + 127, 1);
+        float pf[3];
+        {
+            float blo[W][3], bhi[W][3];
+            uint32_t mask = 0u;
+            for (int sl = 0; sl < W; ++sl) {
+                const int k = child_in[sl];
+                if (k < 0) continue;
+                mask |= 1u << sl;
+                for (int a = 0; a < 3; ++a) { blo[sl][a] = e[k].b.lo[a]; bhi[sl][a] = e[k].b.hi[a]; }
             }
-            for (;; ++eb) {
-                if (eb > 254) { d.ok = false; return; }
-                const double s = std::ldexp(1.0, eb - 127);
-                bool fits = true;
-                for (int sl = 0; sl < W && fits; ++sl) {
-                    const int k = child_in[sl];
-                    if (k < 0) { qlo[a][sl] = 255u; qhi[a][sl] = 0u; continue; }
-                    long ql = (long)std::floor(((double)e[k].b.lo[a] - p) / s);
-                    ql = std::min(std::max(ql, 0L), 255L);
-                    while (ql > 0 && p + (double)ql * s > (double)e[k].b.lo[a]) --ql;
-                    long qh = (long)std::ceil(((double)e[k].b.hi[a] - p) / s);
-                    qh = std::max(qh, 0L);
-                    while (qh < 256 && p + (double)qh * s < (double)e[k].b.hi[a]) ++qh;
-                    if (qh > 255 || p + (double)ql * s > (double)e[k].b.lo[a]) { fits = false; break; }
-                    qlo[a][sl] = (uint32_t)ql;
-                    qhi[a][sl] = (uint32_t)qh;
-                }
-                if (fits) break;
-            }
-            ebits[a] = (uint32_t)eb;
+            d.ok = octQuantise(blo, bhi, mask, pf, ebits, qlo, qhi);
+            if (!d.ok) return;
         }
         // children: inner ones get consecutive node indices in slot order, leaf triangles consecutive records in slot order
         uint32_t imask = 0u, tri_off = 0u, n_inner = 0u;
@@ -315,13 +298,10 @@ inline OctTree buildOct(const trt_bvh_node* caller_nodes2, uint32_t caller_n_nod
         }
         d.n_inner = n_inner;
         d.n_tri = tri_off;
-        auto pack4 = [](const uint32_t* v) { return v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24); };
         auto packm = [](const uint8_t* v) { return (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24); };
-        d.on.q[0] = mk4((float)lo[0], (float)lo[1], (float)lo[2], u2f(ebits[0] | (ebits[1] << 8) | (ebits[2] << 16) | (imask << 24)));
+        d.on.q[0] = mk4(pf[0], pf[1], pf[2], u2f(ebits[0] | (ebits[1] << 8) | (ebits[2] << 16) | (imask << 24)));
         d.on.q[1] = mk4(0.f, 0.f, u2f(packm(meta)), u2f(packm(meta + 4)));
-        d.on.q[2] = mk4(u2f(pack4(qlo[0])), u2f(pack4(qlo[0] + 4)), u2f(pack4(qlo[1])), u2f(pack4(qlo[1] + 4)));
-        d.on.q[3] = mk4(u2f(pack4(qlo[2])), u2f(pack4(qlo[2] + 4)), u2f(pack4(qhi[0])), u2f(pack4(qhi[0] + 4)));
-        d.on.q[4] = mk4(u2f(pack4(qhi[1])), u2f(pack4(qhi[1] + 4)), u2f(pack4(qhi[2])), u2f(pack4(qhi[2] + 4)));
+        octStoreBounds(d.on, qlo, qhi);
     };
     std::vector<Job> cur{{0u, 0u}}, next;
     std::vector<Draft> drafts;

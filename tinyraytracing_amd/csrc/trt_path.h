@@ -222,14 +222,15 @@ TRT_HD inline LightTriDev makeLightTriDev(const trt_light_tri& t)
 }
 // The radiance of the direct term is the light MATERIAL's (pathTracing.cpp:65 reads scene.materials[light_triangle.mtl_name].radiance), not trt_light::radiance:
 // the loaders write the same three numbers into both (scene.cpp:50-52), a caller of the C-ABI who does not gets what the reference would compute.
-TRT_HD inline LightDev makeLightDev(const trt_light& l, const trt_material* materials)
+TRT_HD inline LightDev makeLightDevFrom(const trt_light& l, const float* mat_radiance)
 {
     LightDev d;
     d.mat = l.mat;
-    for (int k = 0; k < 3; ++k) d.radiance[k] = materials[l.mat].radiance[k];
+    for (int k = 0; k < 3; ++k) d.radiance[k] = mat_radiance[k];
     d.area = l.area; d.tri_first = l.tri_first; d.tri_count = l.tri_count; d.pdf = 1.0f / l.area;
     return d;
 }
+TRT_HD inline LightDev makeLightDev(const trt_light& l, const trt_material* materials) { return makeLightDevFrom(l, materials[l.mat].radiance); }
 
 // Build-time helper shared by trt_create and the hostsim: the 48-B record of one triangle.
 TRT_HD inline TriIsect makeTriIsect(const float* v9, int32_t mat, bool emissive)

@@ -15,6 +15,7 @@
 #include <omp.h>
 
 #include "scene.h"
+#include "trt_refit.h"  // csrc: the box rule of a geometry update, shared with the HIP kernels
 
 namespace trt {
 
@@ -463,6 +464,7 @@ void FlatScene::build(const Scene& scene, const FlatBVH& bvh, const uint32_t* or
     tri_vn.resize(n * 9);
     tri_vt.resize(n * 6);
     tri_mat.resize(n);
+    tri_src.resize(n);
     int bad_material = 0;
     const int threads = builderThreads();
 #pragma omp parallel for schedule(static) num_threads(threads) if (n >= 100000)
@@ -478,6 +480,7 @@ void FlatScene::build(const Scene& scene, const FlatBVH& bvh, const uint32_t* or
             bad_material = 1;  // (no exception out of a parallel loop)
         }
         tri_mat[i] = t.mtl_id;
+        tri_src[i] = (uint32_t)(order ? order[i] : i);
     }
     if (bad_material) throw std::runtime_error("flatten: triangle without material");
     nodes = bvh.nodes;
@@ -558,6 +561,76 @@ void FlatScene::build(const Scene& scene, const FlatBVH& bvh, const uint32_t* or
     flat.camera.lower_left_corner[0] = c.lower_left_corner.x; flat.camera.lower_left_corner[1] = c.lower_left_corner.y; flat.camera.lower_left_corner[2] = c.lower_left_corner.z;
     flat.camera.horizontal[0] = c.horizontal.x; flat.camera.horizontal[1] = c.horizontal.y; flat.camera.horizontal[2] = c.horizontal.z;
     flat.camera.vertical[0] = c.vertical.x; flat.camera.vertical[1] = c.vertical.y; flat.camera.vertical[2] = c.vertical.z;
+}
+
+void FlatScene::setVertices(Scene& scene, const float* new_v, const float* new_vn)
+{
+    const size_t n = tri_mat.size();
+    if (tri_src.size() != n || scene.triangles.size() != n) throw std::runtime_error("set_vertices: scene not built");
+    for (size_t k = 0; k < n * 9; ++k)
+        if (!trtd::refitFinite(new_v[k])) throw std::runtime_error("set_vertices: a vertex coordinate is NaN or infinite");
+    // every check before the first write: the tree (children before parents — a depth-first list from the root, walked backwards at the end)
+    std::vector<uint32_t> order, st{0u};
+    order.reserve(nodes.size());
+    if (nodes.empty()) st.clear();
+    while (!st.empty()) {
+        const uint32_t i = st.back();
+        st.pop_back();
+        if (i >= nodes.size() || order.size() >= nodes.size()) throw std::runtime_error("set_vertices: malformed tree");
+        order.push_back(i);
+        if (!(nodes[i].child0 & TRT_LEAF_BIT)) st.push_back(nodes[i].child0);
+        if (!(nodes[i].child1 & TRT_LEAF_BIT)) st.push_back(nodes[i].child1);
+    }
+    for (uint32_t i : order)
+        for (uint32_t ref : {nodes[i].child0, nodes[i].child1})
+            if ((ref & TRT_LEAF_BIT) && (uint64_t)TRT_LEAF_FIRST(ref) + TRT_LEAF_COUNT(ref) > n) throw std::runtime_error("set_vertices: leaf range out of bounds");
+    for (size_t i = 0; i < n; ++i) {
+        const Triangle& t = scene.triangles[tri_src[i]];
+        if (t.is_emissive && t.light_slot >= 0 && (size_t)t.light_slot >= scene.materials[(size_t)t.mtl_id].triangles.size()) throw std::runtime_error("set_vertices: light triangle without a slot");
+    }
+    std::memcpy(tri_v.data(), new_v, n * 9 * sizeof(float));
+    if (new_vn) std::memcpy(tri_vn.data(), new_vn, n * 9 * sizeof(float));
+    // the scene's own triangles, and the light copies their materials keep (Material::triangles, file order)
+    for (size_t i = 0; i < n; ++i) {
+        Triangle& t = scene.triangles[tri_src[i]];
+        for (int k = 0; k < 3; ++k) {
+            t.v[k] = vec3(tri_v[i * 9 + k * 3], tri_v[i * 9 + k * 3 + 1], tri_v[i * 9 + k * 3 + 2]);
+            t.vn[k] = vec3(tri_vn[i * 9 + k * 3], tri_vn[i * 9 + k * 3 + 1], tri_vn[i * 9 + k * 3 + 2]);
+        }
+        t.normal = normalize(cross(t.v[1] - t.v[0], t.v[2] - t.v[0]));
+        t.center = (t.v[0] + t.v[1] + t.v[2]) / 3.0f;
+        if (!t.is_emissive || t.light_slot < 0) continue;
+        Material& m = scene.materials[(size_t)t.mtl_id];
+        Triangle& c = m.triangles[(size_t)t.light_slot];
+        for (int k = 0; k < 3; ++k) { c.v[k] = t.v[k]; c.vn[k] = t.vn[k]; }
+        c.normal = t.normal;
+        c.center = t.center;
+    }
+    // readobj's accumulation once more (scene.cpp:199-205): the running total is the light's CDF
+    for (Material& m : scene.materials) {
+        if (!m.is_emissive) continue;
+        m.area = 0.0;
+        for (Triangle& c : m.triangles) {
+            m.area += c.calAera();
+            c.area = m.area;
+        }
+    }
+    for (Triangle& t : scene.triangles)
+        if (t.is_emissive && t.light_slot >= 0) t.area = scene.materials[(size_t)t.mtl_id].triangles[(size_t)t.light_slot].area;
+    for (size_t l = 0; l < lights.size(); ++l) {
+        const Material& m = scene.materials[(size_t)lights[l].mat];
+        lights[l].area = (float)m.area;
+        for (size_t j = 0; j < m.triangles.size(); ++j) {
+            const Triangle& t = m.triangles[j];
+            trt_light_tri& lt = light_tris[lights[l].tri_first + j];
+            for (int k = 0; k < 3; ++k) {
+                lt.v[k][0] = t.v[k].x; lt.v[k][1] = t.v[k].y; lt.v[k][2] = t.v[k].z;
+                lt.vn[k][0] = t.vn[k].x; lt.vn[k][1] = t.vn[k].y; lt.vn[k][2] = t.vn[k].z;
+            }
+            lt.cum_area = (float)t.area;
+        }
+    }
+    for (size_t k = order.size(); k-- > 0;) trtd::refitNode2(nodes.data(), order[k], tri_v.data(), nullptr);
 }
 
 }  // namespace trt

@@ -144,6 +144,14 @@ int trth_scene_adopt_bvh(trth_scene* s, const trt_bvh_node* nodes, uint32_t n_no
     return 0;
 }
 
+int trth_scene_set_vertices(trth_scene* s, const float* tri_v, const float* tri_vn)
+{
+    if (!s || !tri_v) return fail("trth_scene_set_vertices: null argument");
+    if (!s->flat) return fail("scene not built");
+    try { s->flat->setVertices(s->scene, tri_v, tri_vn); } catch (const std::exception& e) { return fail(e); }
+    return 0;
+}
+
 const trt_scene* trth_scene_flat(const trth_scene* s)
 {
     if (!s || !s->flat) { fail("scene not built"); return nullptr; }

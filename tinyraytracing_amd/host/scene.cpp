@@ -403,6 +403,7 @@ void Scene::readobj(const std::string& obj_path)
                 tri.is_emissive = true;
                 m.area += tri.calAera();
                 tri.area = m.area;
+                tri.light_slot = (int)m.triangles.size();
                 m.triangles.push_back(tri);
             }
             triangles.push_back(std::move(tri));

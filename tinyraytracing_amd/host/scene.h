@@ -77,9 +77,15 @@ public:
     // objects of a big scene stay where they are).
     void build(const Scene& scene, const FlatBVH& bvh, const uint32_t* order = nullptr);
     const trt_scene* c_scene() const { return &flat; }
+    // New coordinates for a built scene (trth_scene_set_vertices, include/trt_host.h): tri_v / tri_vn in flat order (tri_vn may be null).
+    // Refits `nodes` (csrc/trt_refit.h), rebuilds lights / light_tris as the loader accumulates them, and writes the moved triangles back
+    // into `scene` (its triangle list and its materials' light copies: what trth_scene_vertices and a later build read).  Every check is made
+    // before the first write: a refused call leaves the scene as it was.
+    void setVertices(Scene& scene, const float* new_v, const float* new_vn);
 
     std::vector<float> tri_v, tri_vn, tri_vt;
     std::vector<int32_t> tri_mat;
+    std::vector<uint32_t> tri_src;     // flat position i holds scene.triangles[tri_src[i]]
     std::vector<trt_bvh_node> nodes;
     std::vector<trt_material> materials;
     std::vector<trt_light> lights;

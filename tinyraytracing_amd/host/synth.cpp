@@ -211,6 +211,7 @@ void makeLampsScene(Scene& scene, uint32_t seed, uint32_t n_lamps)
             t.is_emissive = true;
             m.area += t.calAera();
             t.area = m.area;
+            t.light_slot = (int)m.triangles.size();
             m.triangles.push_back(t);
             scene.triangles.push_back(std::move(t));
         }

@@ -53,6 +53,7 @@ public:
     std::string mtl_name;
     int mtl_id = -1;
     bool is_emissive = false;
+    int light_slot = -1;     // emissive triangles: position of this triangle's copy in its material's `triangles`
 };
 
 class Light {
