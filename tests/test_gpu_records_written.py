@@ -17,6 +17,7 @@ import raygen
 import scene_util as SU
 import tinyraytracing_amd as T
 from conftest import get_scene
+from sched_cases import parked_per_wave
 
 pytestmark = pytest.mark.gpu
 
@@ -117,32 +118,45 @@ def bits_equal(got, want):
     return all(np.array_equal(np.ascontiguousarray(x).view(np.uint32), np.ascontiguousarray(y).view(np.uint32)) for x, y in zip(got, want))
 
 
-def check_host_entries(r, s, o, d, ref, tag):
+def check_host_entries(r, s, o, d, ref, tag, decoys=None, unbounded=False):
+    """The host entries on the batch (o, d), each after a decoy batch.  decoys: two (o, d, records) batches of the same size to use instead of
+    fresh ones; unbounded: trace_occluded without t_max is checked as well.  -> redo_rays of the batch."""
     n = len(o)
     tm = Q.bounds_for(ref[0])
     want_b = Q.closest(ref, tm)
     want_occ = Q.occluded(ref, tm)
-    decoys = [decoy(s.flat, [ref, want_b], 101), decoy(s.flat, [ref, want_b], 202)]
+    if decoys is None:
+        decoys = [decoy(s.flat, [ref, want_b], 101), decoy(s.flat, [ref, want_b], 202)]
+    redo = None
     for k, (do, dd, drec) in enumerate(decoys):
         assert not records_equal(drec, ref).any() and not records_equal(drec, want_b).any(), tag
         # the decoy's own records come back right: it really did fill the staging buffer
         assert bits_equal(r.trace_closest(do, dd), drec), f"{tag}: decoy {k}"
-        assert bits_equal(r.trace_closest(o, d), ref), f"{tag}: trace_closest after decoy {k}"
+        t, tri, uv, st = r.trace_closest(o, d, want_stats=True)
+        assert bits_equal((t, tri, uv), ref), f"{tag}: trace_closest after decoy {k}: {int((~records_equal((t, tri, uv), ref)).sum())} records differ"
+        assert redo in (None, st.redo_rays), f"{tag}: redo_rays {redo}, then {st.redo_rays} on the same batch"
+        redo = st.redo_rays
         assert bits_equal(r.trace_closest(do, dd, t_max=np.full(n, 1e30, np.float32)), drec), f"{tag}: decoy {k}"
-        assert bits_equal(r.trace_closest(o, d, t_max=tm), want_b), f"{tag}: trace_closest(t_max=) after decoy {k}"
+        got = r.trace_closest(o, d, t_max=tm)
+        assert bits_equal(got, want_b), f"{tag}: trace_closest(t_max=) after decoy {k}: {int((~records_equal(got, want_b)).sum())} records differ"
     # occlusion: decoy 0 leaves a 1 at every index (all its rays hit), decoy 1 a 0 (the same rays bounded below TRT_T_MIN); between them every
     # expected byte is contradicted at some point
     do, dd, _ = decoys[0]
+    bounds = [(tm, want_occ)] + ([(None, Q.occluded(ref, None))] if unbounded else [])
     for k, (dm, want_dec) in enumerate(((None, np.ones(n, bool)), (np.zeros(n, np.float32), np.zeros(n, bool)))):
-        got = r.trace_occluded(do, dd, t_max=dm)
-        assert np.array_equal(got.view(np.uint8), want_dec.view(np.uint8)), f"{tag}: occlusion decoy {k}"
-        got = r.trace_occluded(o, d, t_max=tm)
-        raw = got.view(np.uint8)
-        assert raw.max() <= 1, f"{tag}: occlusion bytes other than 0 / 1 after decoy {k}"
-        assert np.array_equal(raw.astype(bool), want_occ), f"{tag}: {int((raw.astype(bool) != want_occ).sum())} occlusions differ after decoy {k}"
+        for bound, want in bounds:
+            got = r.trace_occluded(do, dd, t_max=dm)
+            assert np.array_equal(got.view(np.uint8), want_dec.view(np.uint8)), f"{tag}: occlusion decoy {k}"
+            got = r.trace_occluded(o, d, t_max=bound)
+            raw = got.view(np.uint8)
+            assert raw.max() <= 1, f"{tag}: occlusion bytes other than 0 / 1 after decoy {k}"
+            assert np.array_equal(raw.astype(bool), want), \
+                f"{tag}: {int((raw.astype(bool) != want).sum())} occlusions differ after decoy {k} (bounded: {bound is not None})"
+    return redo
 
 
-def check_device_entries(r, s, o, d, ref, tag):
+def check_device_entries(r, s, o, d, ref, tag, decoys=None):
+    """The device entries, which write into the very tensors the decoy filled.  decoys: as for check_host_entries."""
     import torch
     dev = torch.device("cuda", 0)
     n = len(o)
@@ -154,8 +168,9 @@ def check_device_entries(r, s, o, d, ref, tag):
     tri = torch.empty(n, dtype=torch.int32, device=dev)
     uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
     occ = torch.empty(n, dtype=torch.uint8, device=dev)
-    for k, seed in enumerate((303, 404)):
-        do, dd, drec = decoy(s.flat, [ref, want_b], seed)
+    if decoys is None:
+        decoys = [decoy(s.flat, [ref, want_b], seed) for seed in (303, 404)]
+    for k, (do, dd, drec) in enumerate(decoys):
         assert not records_equal(drec, ref).any(), tag
         dog, ddg = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (do, dd))
         for bound, want in ((None, ref), (tg, want_b)):
@@ -199,21 +214,6 @@ def test_every_record_is_written_after_a_decoy(name, env, monkeypatch):
         check_device_entries(r, s, o, d, ref, f"{name} {env}")
     finally:
         r.close()
-
-
-def parked_per_wave(n, fill_blocks, rays_per_wave=256, block=256):
-    """Rays of a batch of n each wave of the wave-uniform walk meets, when every one of them is parked (a zero direction): the grid of
-    trt_handle::traceGrid (trt_api.hip) for those settings, each wave taking 64 queue positions of its block per grid-wide stride."""
-    b = (n + block - 1) // block
-    b = min(b, max(fill_blocks, (n + 4 * rays_per_wave - 1) // (4 * rays_per_wave)))
-    b = (min(max(b, 8), 8192) + 7) & ~7
-    stride = b * block
-    counts = []
-    for lb in range(b):
-        for w in range(block // 64):
-            first = lb * block + 64 * w
-            counts.append(sum(max(0, min(64, n - base)) for base in range(first, n, stride)))
-    return np.array(counts)
 
 
 # (name, environment at trt_create, n): the default grid of 300 000 rays gives every wave one batch, i.e. at most 64 parked rays (the

@@ -3,7 +3,11 @@
 scenes (and a 50 k-triangle soup) rendered by the HIP path through the C-ABI — default handles, handles on trees of the GPU builder, on the reference's own leaf size, on hostile
 trees (boxes that do not nest, +-inf, inverted; non-finite vertices and normals), and handles on the optional code paths
 (quantised nodes, speculative scheduler, per-lane traversal of the tiny scene) — and by the oracle; every image and every ray count
-must be identical.  usage: tools/fuzz_parity.py [seconds] [seed]"""
+must be identical.  usage: tools/fuzz_parity.py [seconds] [seed] [--schedule]
+
+--schedule: every trial also draws one of the scheduling knob sets and one of the edge batch sizes of tests/sched_cases.py (for that
+knob set's grid), creates a handle of a random scene under it and compares a ray batch of that size, cut from a random place of a
+hostile ray pool, with the oracle's records (tests/test_gpu_schedule_invariance.py has the fixed matrix; this is the soak)."""
 import os
 import sys
 import time
@@ -14,13 +18,53 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle_lib as O  # noqa: E402
+import raygen  # noqa: E402
+import sched_cases as SC  # noqa: E402
 import scene_util as SU  # noqa: E402
 import tinyraytracing_amd as T  # noqa: E402
 
 
+def schedule_trial(rng, name, scene, pools):
+    """One knob set, one edge size: a ray batch on a fresh handle against the oracle.  -> a description of the mismatch, or None."""
+    knobs = SC.PERSISTENT_KNOBS[int(rng.integers(0, len(SC.PERSISTENT_KNOBS)))]
+    sizes = SC.edge_sizes(knobs)
+    n, labels = sizes[int(rng.integers(0, len(sizes)))]
+    env = dict(knobs, TRT_NODE_KIND=str(int(rng.integers(0, 2))))
+    if name != "back" or rng.random() < 0.5:
+        env["TRT_TRACE_IMPL"] = "3"  # the tiny scene: per lane half of the time, else (unset) its wave-uniform walk
+    if name not in pools:
+        lo, hi = raygen.scene_bounds(scene)
+        o1, d1 = raygen.random_rays(SC.LONG_N // 2, lo - 5, hi + 5, seed=int(rng.integers(0, 1 << 30)))
+        o2, d2 = raygen.adversarial_rays(scene, SC.LONG_N // 2, seed=int(rng.integers(0, 1 << 30)))
+        o, d = np.concatenate([o1, o2]), np.concatenate([d1, d2])
+        order = rng.permutation(len(o))
+        pools[name] = (o[order], d[order], O.trace(scene.flat, o[order], d[order]))
+    o, d, ref = pools[name]
+    idx = (int(rng.integers(0, len(o))) + np.arange(n)) % len(o)
+    before = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        r = T.Renderer(scene, 0)
+    finally:
+        for k, v in before.items():  # what the caller had exported for the soak comes back
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
+    try:
+        t, tri, uv = r.trace_closest(o[idx], d[idx])
+    finally:
+        r.close()
+    same = np.array_equal(tri, ref[1][idx]) and np.array_equal(t.view(np.uint32), ref[0][idx].view(np.uint32)) and np.array_equal(uv.view(np.uint32), ref[2][idx].view(np.uint32))
+    return None if same else dict(env=env, n=n, labels=labels, first=int(idx[0]))
+
+
 def main():
-    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-    rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    schedule = "--schedule" in sys.argv[1:]
+    budget = float(args[0]) if len(args) > 0 else 120.0
+    rng = np.random.default_rng(int(args[1]) if len(args) > 1 else 1)
+    pools = {}
     sizes = {"back": (257, 131), "veach-mis": (320, 180), "staircase": (192, 108), "soup": (160, 90)}
     scenes, renderers, alt, scenes_gpu_tree, on_gpu_tree, scenes_leaf8, on_leaf8, scenes_foreign, on_foreign, on_default_no_tail = {}, {}, {}, {}, {}, {}, {}, {}, {}, {}
     for name, (w, h) in sizes.items():
@@ -62,6 +106,11 @@ def main():
             t_print = time.time()
         name = list(sizes)[int(rng.integers(0, len(sizes)))]
         w, h = sizes[name]
+        if schedule:
+            bad = schedule_trial(rng, name, scenes[name], pools)
+            if bad:
+                print("MISMATCH", name, "schedule", bad, flush=True)
+                sys.exit(1)
         x0 = int(rng.integers(0, w - 1)); x1 = int(rng.integers(x0 + 1, min(w, x0 + 40) + 1))
         y0 = int(rng.integers(0, h - 1)); y1 = int(rng.integers(y0 + 1, min(h, y0 + 24) + 1))
         spp = int(rng.choice([1, 2, 3, 5, 8, 17, 33]))
