@@ -1,7 +1,7 @@
 """How the traversal kernels deal a queue of n rays out to waves, restated in plain Python, and the batch sizes at which that can go wrong.
 
-trace_grid is trt_handle::traceGrid (trt_api.hip); wave_slices is the slice arithmetic at the top of traceQueuePersistent and
-traceQueuePersistentOct (trt_kernels.h): per = ceil(n / n_waves), wave w walks [min(w * per, n), min(w * per + per, n)).  The knob sets are
+trace_grid is trt_handle::traceGrid (trt_api.hip); wave_slices is the slice arithmetic of waveSlice(), which traceQueuePersistent and
+traceQueuePersistentOct share (trt_kernels.h): per = ceil(n / n_waves), wave w walks [min(w * per, n), min(w * per + per, n)).  The knob sets are
 environments read at trt_create that may change only WHEN a ray is walked and by which lane, never what is computed for it;
 tests/test_gpu_schedule_invariance.py holds them to that, tests/test_sched_cases_cpu.py holds this file to the edges it claims to reach."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The slim kernels of the wave-uniform walk (trt_kernels.h traceQueueUniform PIPE / HIT8: 8-byte hit records, (u, v) formed in k_shade,
+"""The slim kernels of the wave-uniform walk (trt_kernels.h WalkUniformFlags / WalkUniformHit8: 8-byte hit records, (u, v) formed in k_shade,
 the triangles' flag words read from LDS) against the kernels TRT_SLIM_WALK=0 keeps — MI355X only.
 
 Every render, pixel list and ray batch must come out bit-identical with the switch on and off, and equal to the CPU oracle.  Which

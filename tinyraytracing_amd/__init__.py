@@ -90,7 +90,7 @@ class Scene:
         else:
             raise TrtError(f"unknown scene {name!r}")
         if leaf_num is None:
-            # tiny scenes are walked wave-uniformly (every node, every triangle: trt_kernels.h IMPL 0), where fewer,
+            # tiny scenes are walked wave-uniformly (every node, every triangle: trt_kernels.h WalkUniform), where fewer,
             # fuller leaves are cheaper; everything else is traversed per ray, where 2 measured best
             leaf_num = default_leaf(name, s.info["n_triangles"])
         s.build_bvh(leaf_num, builder, device)

@@ -357,67 +357,66 @@ using FixKernel = void (*)(SceneDev, RaySource, f4*, const f4*, uint32_t, f4*, u
 using ShadeKernel = void (*)(SceneDev, ShadeArgs);
 using TailKernel = void (*)(SceneDev, TailArgs);
 
-// Traversal kernels: one per (driver, LDS depth, node kind), the combination the scene picked in trt_create.  The LDS stack holds 16 levels
-// without spill code when the verified BVH depth fits, else TRT_LDS_STACK_MAX levels + a global spill area (16 KiB per block keeps 8 waves per
-// SIMD resident); the wave-uniform walk (trt_kernels.h) serves tiny trees.  The oct tree needs one 8-byte entry per level below the root:
-// OCT_LDS_LEVELS of them in LDS (20 KiB per block: eight blocks per CU), deeper ones — staircase has 10 levels, the 10 M-triangle mesh 11 —
-// in the spill area.  One instantiation serves every tree.  traversalOf: the row of the tables below.
-constexpr uint32_t OCT_LDS_LEVELS = 10;
-int traversalOf(const trt_handle* h) { return h->trace_impl == 0 ? 0 : (h->node_kind == 1 ? 1 : (h->depth <= 16 ? 2 : 3)); }
+// Traversal kernels: one set per driver tag (trt_kernels.h: WalkUniform ... WalkOct), the one the scene picked in trt_create.  A kernel family's row
+// of a tag is built by one function template, so a new driver is one entry per table and a new family one template.
+enum Walk { WALK_UNIFORM, WALK_UNIFORM_FLAGS, WALK_UNIFORM_HIT8, WALK_OCT, WALK_WIDE16, WALK_WIDE_SPILL, N_WALKS };
+// traversalOf: the rows of the tables below that a handle runs — `closest` for the kernels that store hit records, `occlusion` for the shadow rays and
+// the occlusion query — and whether the closest-hit kernel of its queue is the binned one.  The wave-uniform walk as trt_create set it up: 8-byte
+// records with hit8, flags in LDS for the shadow walk with slim_walk.
+struct Traversal {
+    Walk closest, occlusion;
+    bool binned;
+};
+Traversal traversalOf(const trt_handle* h)
+{
+    if (h->trace_impl == 0) return {h->hit8 ? WALK_UNIFORM_HIT8 : WALK_UNIFORM, h->slim_walk ? WALK_UNIFORM_FLAGS : WALK_UNIFORM, h->bin_walk};
+    const Walk w = h->node_kind == 1 ? WALK_OCT : (h->depth <= 16 ? WALK_WIDE16 : WALK_WIDE_SPILL);
+    return {w, w, h->bin_walk};
+}
+struct ClosestRow { ClosestKernel k[2][3], query; bool redo; };  // [count][primary]; QUERY_CLOSEST; the tag's REDO: k_trace_fix runs behind every launch
+struct ShadowRow { ShadowKernel k[2]; ClosestKernel query; bool redo; };  // [count]; QUERY_OCCLUDED
+template <class D>
+ClosestRow closestRow()
+{
+    return {{{k_trace_closest<false, D, 0>, k_trace_closest<false, D, 1>, k_trace_closest<false, D, PRIMARY_LIST>},
+             {k_trace_closest<true, D, 0>, k_trace_closest<true, D, 1>, k_trace_closest<true, D, PRIMARY_LIST>}},
+            k_trace_query<D, QUERY_CLOSEST>, D::REDO};
+}
+template <class D>
+ShadowRow shadowRow()
+{
+    return {{k_trace_shadow<false, D>, k_trace_shadow<true, D>}, k_trace_query<D, QUERY_OCCLUDED>, D::REDO};
+}
+// (a form of the wave-uniform walk serves hit records or occlusion, not both: the other table has no row for it)
+const ClosestRow closest_rows[N_WALKS] = {closestRow<WalkUniform>(), {}, closestRow<WalkUniformHit8>(), closestRow<WalkOct>(), closestRow<WalkWide16>(), closestRow<WalkWideSpill>()};
+const ShadowRow shadow_rows[N_WALKS] = {shadowRow<WalkUniform>(), shadowRow<WalkUniformFlags>(), {}, shadowRow<WalkOct>(), shadowRow<WalkWide16>(), shadowRow<WalkWideSpill>()};
 // primary: 0 the queue, 1 the camera rays of a tile, PRIMARY_LIST those of a pixel list.  With h->hit8 the kernel stores 8-byte hit records.
 ClosestKernel closestKernel(const trt_handle* h, bool count, int primary)
 {
-    if (h->bin_walk && primary == 0) return count ? k_trace_closest_binned<true> : k_trace_closest_binned<false>;
-    if (h->trace_impl == 0 && h->hit8) {
-        const ClosestKernel s[2][3] = {
-            {k_trace_closest<false, 1, false, 0, 0, 0, true, true>, k_trace_closest<false, 1, false, 0, 1, 0, true, true>, k_trace_closest<false, 1, false, 0, PRIMARY_LIST, 0, true, true>},
-            {k_trace_closest<true, 1, false, 0, 0, 0, true, true>, k_trace_closest<true, 1, false, 0, 1, 0, true, true>, k_trace_closest<true, 1, false, 0, PRIMARY_LIST, 0, true, true>}};
-        return s[count][primary];
-    }
-    const ClosestKernel k[4][2][3] = {
-        {{k_trace_closest<false, 1, false, 0, 0, 0>, k_trace_closest<false, 1, false, 0, 1, 0>, k_trace_closest<false, 1, false, 0, PRIMARY_LIST, 0>},
-         {k_trace_closest<true, 1, false, 0, 0, 0>, k_trace_closest<true, 1, false, 0, 1, 0>, k_trace_closest<true, 1, false, 0, PRIMARY_LIST, 0>}},
-        {{k_trace_closest<false, OCT_LDS_LEVELS, true, 3, 0, 1>, k_trace_closest<false, OCT_LDS_LEVELS, true, 3, 1, 1>, k_trace_closest<false, OCT_LDS_LEVELS, true, 3, PRIMARY_LIST, 1>},
-         {k_trace_closest<true, OCT_LDS_LEVELS, true, 3, 0, 1>, k_trace_closest<true, OCT_LDS_LEVELS, true, 3, 1, 1>, k_trace_closest<true, OCT_LDS_LEVELS, true, 3, PRIMARY_LIST, 1>}},
-        {{k_trace_closest<false, 16, false, 3, 0, 0>, k_trace_closest<false, 16, false, 3, 1, 0>, k_trace_closest<false, 16, false, 3, PRIMARY_LIST, 0>},
-         {k_trace_closest<true, 16, false, 3, 0, 0>, k_trace_closest<true, 16, false, 3, 1, 0>, k_trace_closest<true, 16, false, 3, PRIMARY_LIST, 0>}},
-        {{k_trace_closest<false, TRT_LDS_STACK_MAX, true, 3, 0, 0>, k_trace_closest<false, TRT_LDS_STACK_MAX, true, 3, 1, 0>, k_trace_closest<false, TRT_LDS_STACK_MAX, true, 3, PRIMARY_LIST, 0>},
-         {k_trace_closest<true, TRT_LDS_STACK_MAX, true, 3, 0, 0>, k_trace_closest<true, TRT_LDS_STACK_MAX, true, 3, 1, 0>, k_trace_closest<true, TRT_LDS_STACK_MAX, true, 3, PRIMARY_LIST, 0>}}};
-    return k[traversalOf(h)][count][primary];
+    const Traversal t = traversalOf(h);
+    if (t.binned && primary == 0) return count ? k_trace_closest_binned<true> : k_trace_closest_binned<false>;
+    return closest_rows[t.closest].k[count][primary];
 }
-ShadowKernel shadowKernel(const trt_handle* h, bool count)
-{
-    if (h->trace_impl == 0 && h->slim_walk) return count ? k_trace_shadow<true, 1, false, 0, 0, true> : k_trace_shadow<false, 1, false, 0, 0, true>;
-    const ShadowKernel k[4][2] = {{k_trace_shadow<false, 1, false, 0, 0>, k_trace_shadow<true, 1, false, 0, 0>},
-                                  {k_trace_shadow<false, OCT_LDS_LEVELS, true, 3, 1>, k_trace_shadow<true, OCT_LDS_LEVELS, true, 3, 1>},
-                                  {k_trace_shadow<false, 16, false, 3, 0>, k_trace_shadow<true, 16, false, 3, 0>},
-                                  {k_trace_shadow<false, TRT_LDS_STACK_MAX, true, 3, 0>, k_trace_shadow<true, TRT_LDS_STACK_MAX, true, 3, 0>}};
-    return k[traversalOf(h)][count];
-}
+ShadowKernel shadowKernel(const trt_handle* h, bool count) { return shadow_rows[traversalOf(h).occlusion].k[count]; }
 // Behind every traversal launch of a per-lane driver: k_trace_fix (a few blocks) traces the rays of the launch's redo list again in the
 // exact form (trt_kernels.h, RedoList).  The wave-uniform walk applies the rule on the spot and has no list: nullptr.
 FixKernel fixKernel(const trt_handle* h, bool shadow, int primary)
 {
-    const FixKernel k[4] = {k_trace_fix<false, 0, 0>, k_trace_fix<false, 1, 0>, k_trace_fix<false, PRIMARY_LIST, 0>, k_trace_fix<true, false, 0>};
-    return h->trace_impl == 0 ? nullptr : k[shadow ? 3 : primary];
+    const FixKernel k[4] = {k_trace_fix<false, 0>, k_trace_fix<false, 1>, k_trace_fix<false, PRIMARY_LIST>, k_trace_fix<true, 0>};
+    const Traversal t = traversalOf(h);
+    return (shadow ? shadow_rows[t.occlusion].redo : closest_rows[t.closest].redo) ? k[shadow ? 3 : primary] : nullptr;
 }
-// The ray queries (QUERY_CLOSEST, QUERY_OCCLUDED) on the rows of closestKernel / shadowKernel: the same driver, LDS depth and node kind, with
-// the counters on (as trt_trace_closest); the wave-uniform walk as the render runs it (8-byte records with hit8, flags in LDS with slim_walk).
+// The ray queries (QUERY_CLOSEST, QUERY_OCCLUDED) on the rows of closestKernel / shadowKernel: the same driver, with the counters on (as
+// trt_trace_closest); the wave-uniform walk as the render runs it.
 ClosestKernel queryKernel(const trt_handle* h, int query)
 {
-    const bool occ = query == QUERY_OCCLUDED;
-    if (h->trace_impl == 0 && h->hit8 && !occ) return k_trace_query<QUERY_CLOSEST, true, 1, false, 0, 0, true, true>;
-    if (h->trace_impl == 0 && h->slim_walk && occ) return k_trace_query<QUERY_OCCLUDED, true, 1, false, 0, 0, false, true>;
-    const ClosestKernel k[4][2] = {{k_trace_query<QUERY_CLOSEST, true, 1, false, 0, 0>, k_trace_query<QUERY_OCCLUDED, true, 1, false, 0, 0>},
-                                   {k_trace_query<QUERY_CLOSEST, true, OCT_LDS_LEVELS, true, 3, 1>, k_trace_query<QUERY_OCCLUDED, true, OCT_LDS_LEVELS, true, 3, 1>},
-                                   {k_trace_query<QUERY_CLOSEST, true, 16, false, 3, 0>, k_trace_query<QUERY_OCCLUDED, true, 16, false, 3, 0>},
-                                   {k_trace_query<QUERY_CLOSEST, true, TRT_LDS_STACK_MAX, true, 3, 0>, k_trace_query<QUERY_OCCLUDED, true, TRT_LDS_STACK_MAX, true, 3, 0>}};
-    return k[traversalOf(h)][occ];
+    const Traversal t = traversalOf(h);
+    return query == QUERY_OCCLUDED ? shadow_rows[t.occlusion].query : closest_rows[t.closest].query;
 }
 FixKernel queryFixKernel(const trt_handle* h, int query)
 {
-    if (h->trace_impl == 0) return nullptr;
-    return query == QUERY_OCCLUDED ? k_trace_fix<true, 0, 0, QUERY_OCCLUDED> : k_trace_fix<false, 0, 0, QUERY_CLOSEST>;
+    if (!fixKernel(h, query == QUERY_OCCLUDED, 0)) return nullptr;
+    return query == QUERY_OCCLUDED ? k_trace_fix<true, 0, QUERY_OCCLUDED> : k_trace_fix<false, 0, QUERY_CLOSEST>;
 }
 ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list, bool hit8)
 {
@@ -437,11 +436,11 @@ ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list, bool hit8)
         {{k_shade<0u, SHADE_ONE>, k_shade<0u, SHADE_FEW>, k_shade<0u, SHADE_MANY>}, {k_shade<0u, SHADE_ONE, true>, k_shade<0u, SHADE_FEW, true>, k_shade<0u, SHADE_MANY, true>}}};
     return k[tabs == 31u ? 0 : (tabs == 15u ? 1 : (tabs == 7u ? 2 : (tabs == 3u ? 3 : 4)))][list][lights];
 }
-// (named in this order: named the other way round, k_tail<true, 0, true> / <false, 0, false> build 1 instruction shorter / longer, tools/isa_diff.py)
+// (named in this order: named the other way round, k_tail<true, true> / <false, false> build 1 instruction shorter / longer, tools/isa_diff.py)
 TailKernel tailKernel(bool count, bool list)
 {
-    if (list) return count ? k_tail<true, 0, true> : k_tail<false, 0, true>;
-    return count ? k_tail<true, 0> : k_tail<false, 0>;
+    if (list) return count ? k_tail<true, true> : k_tail<false, true>;
+    return count ? k_tail<true> : k_tail<false>;
 }
 
 void launchTraceClosest(const trt_handle* h, ClosestKernel k, FixKernel fix, hipStream_t stream, uint32_t* spill, const RaySource& src, f4* hit, uint32_t n,

@@ -159,6 +159,13 @@ struct OctLdsStack {
     }
 };
 
+// This thread's stack of a traversal kernel: its column of the block's LDS array and of the launch's spill area.
+template <class Stack>
+__device__ __forceinline__ Stack makeStack(uint32_t* smem, uint32_t* spill, uint32_t spill_stride)
+{
+    return Stack{smem + threadIdx.x, spill + (size_t)blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x, spill_stride};
+}
+
 // Blocks b and b+8 share an XCD (round-robin dispatch): give each XCD a
 // contiguous range of the queue so rays that are neighbours in the queue
 // (spatially coherent) meet in one L2.  Speed only, never correctness.
@@ -170,6 +177,18 @@ __device__ inline uint32_t xcdSwizzle(uint32_t bid, uint32_t nblocks)
 // __ballot() takes an int: the predicate is widened to 0 / 1 (v_cndmask) and compared again (v_cmp_ne), two VALU instructions
 // per vote that the compiler does not always fold away; the builtin takes the lane mask as it is.
 __device__ __forceinline__ unsigned long long ballotb(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
+// The contiguous slice [first, end) of a queue of n rays that this wave of a persistent driver works through (XCD-aware: neighbouring slices
+// share an L2); wave-uniform values.  tests/sched_cases.py restates the arithmetic.
+struct WaveSlice { uint32_t first, end; };
+__device__ __forceinline__ WaveSlice waveSlice(uint32_t n)
+{
+    const uint32_t n_waves = gridDim.x * (TRT_TRACE_BLOCK / 64);
+    const uint32_t wave = xcdSwizzle(blockIdx.x, gridDim.x) * (TRT_TRACE_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint32_t per = (n + n_waves - 1) / n_waves;
+    const unsigned long long w0 = (unsigned long long)wave * per;
+    return {(uint32_t)__builtin_amdgcn_readfirstlane((int)(w0 < n ? w0 : n)), (uint32_t)__builtin_amdgcn_readfirstlane((int)((w0 + per) < n ? (w0 + per) : n))};
+}
 
 __device__ inline unsigned long long waveSum(unsigned long long v)
 {
@@ -188,9 +207,9 @@ __device__ inline unsigned long long waveSum(unsigned long long v)
 // visiting order, the culling rule and the tie rules are exactly
 // traceClosest()'s (trt_path.h), whichever driver below runs it.
 //
-// IMPL selects the wave-level driver (trt_create picks it per scene):
-//   0  wave-uniform walk of a tiny tree (<= 32 inner nodes, <= 64 triangles): scalar loads, no stack
-//   3  persistent wave with a per-step scheduler: each wave owns a contiguous queue slice and refills finished lanes from
+// The driver tag (WalkUniform ... WalkOct, below the drivers) selects the wave-level driver (trt_create picks it per scene):
+//   WalkUniform*           wave-uniform walk of a tiny tree (<= 32 inner nodes, <= 64 triangles): scalar loads, no stack
+//   WalkWide*, WalkOct     persistent wave with a per-step scheduler: each wave owns a contiguous queue slice and refills finished lanes from
 //      it (__ballot of free lanes, rank = popcount of the lower free lanes); each iteration runs the step kind (inner
 //      node / one triangle) that more lanes are waiting for
 // (Round 2 also carried a static driver, a while-while driver and a scheduler with a postponed leaf; they lost on every
@@ -261,6 +280,19 @@ struct TraceProbe {  // COUNT builds only: work and SIMD utilisation of the two 
     uint32_t wave_inner = 0, wave_tri = 0;      // counted by the first participating lane: wave-level steps
     uint32_t c_in = 0, c_lf = 0, c_done = 0, c_it = 0;  // lane 0: the census of DeviceStats
 };
+// The COUNT epilogue of a driver: the wave's sums of the lanes' counters, one atomic each, into the closest-hit or the SHADOW slot of DeviceStats.
+// STEPS: the wave-level steps of a persistent driver too (the wave-uniform walks have none).
+template <bool SHADOW, bool STEPS = false>
+__device__ __forceinline__ void addProbe(DeviceStats* stats, uint32_t n_inner, uint32_t n_tri, uint32_t wave_inner = 0u, uint32_t wave_tri = 0u)
+{
+    const unsigned long long si = waveSum(n_inner), st = waveSum(n_tri), wi = STEPS ? waveSum(wave_inner) : 0ull, wt = STEPS ? waveSum(wave_tri) : 0ull;
+    if ((threadIdx.x & 63u) == 0) {
+        atomicAdd(&stats->inner_visits[SHADOW ? 1 : 0], si);
+        atomicAdd(&stats->tri_tests[SHADOW ? 1 : 0], st);
+        if (STEPS) atomicAdd(&stats->wave_inner_steps, wi);
+        if (STEPS) atomicAdd(&stats->wave_leaf_steps, wt);
+    }
+}
 
 // The ray queries of trt_trace_closest_range / trt_trace_occluded (include/trt.h): a third store mode of the traversal drivers, the QUERY
 // template parameter.  Both read the ray's bound from rb.w (k_pack_rays_bounded): the walk starts with best_t = bound, so only hits STRICTLY
@@ -346,7 +378,7 @@ __device__ __forceinline__ bool checkedStore(const SceneDev& sc, f3 o, f3 d, f3 
     return false;
 }
 
-// IMPL 0 — wave-uniform evaluation of a tiny BVH (<= 32 inner nodes): no stack, no divergent control
+// WalkUniform* — wave-uniform evaluation of a tiny BVH (<= 32 inner nodes): no stack, no divergent control
 // flow, no per-lane addresses.  The tree is walked in node-index order (the builders emit parents
 // before children) by the whole wave at once; a per-lane bit mask records which inner nodes the lane's
 // ray reaches (parent reached AND child box hit, bvh.cpp:162-166), node and triangle records are
@@ -510,6 +542,9 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
     // calls it from inside the loop (a wave-uniform branch in the walk cost 4 %, a call of the second walk from the loop 50 %: the compiler's doing), and no other
     // wave waits for it (handed to the last block of the launch, that block walked alone, latency-bound: +60 %).  What remains is +4 % on k_trace_closest of the
     // Cornell box for three compares, a vote and a predicated store (profiles/r04_hardening.txt).
+    // traceQueueBinned carries this list and the two re-walks below as its own copy (the <SHADOW = false, PRIMARY = 0, HIT8, PIPE, QUERY_NONE> case).  One struct
+    // with a park() step and one function for the re-walks, used by both, was built and taken out again: by reference or by value, with the wave's share
+    // handed in or formed again, all 22 kernels of the wave-uniform walk came out 8 to 27 instructions longer (tools/isa_diff.py; profiles/trace_driver_refactor.txt).
     __shared__ uint32_t s_parked[2 * TRT_TRACE_BLOCK];
     uint32_t* my_parked = s_parked + (threadIdx.x >> 6) * 128u;
     const uint32_t lane = threadIdx.x & 63u;
@@ -574,13 +609,7 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
         }
         if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
     }
-    if (COUNT) {
-        const unsigned long long si = waveSum(n_inner), st = waveSum(n_tri);
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&stats->inner_visits[SHADOW ? 1 : 0], si);
-            atomicAdd(&stats->tri_tests[SHADOW ? 1 : 0], st);
-        }
-    }
+    if (COUNT) addProbe<SHADOW>(stats, n_inner, n_tri);
 }
 
 // BIN (trt_create: the closest-hit queue kernel of this walk, unless TRT_BIN_WALK=0): the walk above tests every triangle of a leaf as soon as ONE lane of
@@ -804,34 +833,20 @@ __device__ __forceinline__ void traceQueueBinned(const SceneDev& sc, const RaySo
         }
         if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
     }
-    if (COUNT) {
-        const unsigned long long si = waveSum(n_inner), st = waveSum(n_tri);
-        if (lane == 0) {
-            atomicAdd(&stats->inner_visits[0], si);
-            atomicAdd(&stats->tri_tests[0], st);
-        }
-    }
+    if (COUNT) addProbe<false>(stats, n_inner, n_tri);
 }
 
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, int QUERY = QUERY_NONE>
+template <bool SHADOW, bool COUNT, class Stack, int PRIMARY, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo)
 {
-    LdsStack<DEPTH, SPILL> stk;
-    stk.lds = smem + threadIdx.x;
-    stk.spill = spill + (size_t)blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x;
-    stk.spill_stride = spill_stride;
+    Stack stk = makeStack<Stack>(smem, spill, spill_stride);
     const bool any = SHADOW && (QUERY == QUERY_OCCLUDED || any_flag);  // occlusion test (TRT_FLAG_FIXED_NEE): the ray carries its own t_max in rb.w
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long lower = (1ull << lane) - 1ull;
-    // contiguous queue slice of this wave (XCD-aware: neighbouring slices share an L2)
-    const uint32_t n_waves = gridDim.x * (TRT_TRACE_BLOCK / 64);
-    const uint32_t wave = xcdSwizzle(blockIdx.x, gridDim.x) * (TRT_TRACE_BLOCK / 64) + (threadIdx.x >> 6);
-    const uint32_t per = (n + n_waves - 1) / n_waves;
-    const unsigned long long w0 = (unsigned long long)wave * per;
-    uint32_t next = (uint32_t)__builtin_amdgcn_readfirstlane((int)(w0 < n ? w0 : n));
-    const uint32_t end = (uint32_t)__builtin_amdgcn_readfirstlane((int)((w0 + per) < n ? (w0 + per) : n));
+    const auto [first, end] = waveSlice(n);
+    uint32_t next = first;
 
     uint32_t cur = TRT_REF_IDLE, idx = 0, pid = 0;
     int sp = 0;
@@ -839,7 +854,7 @@ __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const R
     float best_t = TRT_INF;
     int32_t best_tri = -1;
     uint32_t best_flags = 0;
-    // IMPL 3: fold state of the leaf the lane is in (interactBVHNode's local `res`, bvh.cpp:213)
+    // fold state of the leaf the lane is in (interactBVHNode's local `res`, bvh.cpp:213)
     uint32_t lk = 0;  // next triangle of the leaf, relative to its first
     float lt = TRT_INF;
     int32_t li = -1;
@@ -930,18 +945,10 @@ __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const R
         }
         }
     }
-    if (COUNT) {
-        const unsigned long long si = waveSum(pr.n_inner), st = waveSum(pr.n_tri), wi = waveSum(pr.wave_inner), wt = waveSum(pr.wave_tri);
-        if (lane == 0) {
-            atomicAdd(&stats->inner_visits[SHADOW ? 1 : 0], si);
-            atomicAdd(&stats->tri_tests[SHADOW ? 1 : 0], st);
-            atomicAdd(&stats->wave_inner_steps, wi);
-            atomicAdd(&stats->wave_leaf_steps, wt);
-        }
-    }
+    if (COUNT) addProbe<SHADOW, true>(stats, pr.n_inner, pr.n_tri, pr.wave_inner, pr.wave_tri);
 }
 
-// The same persistent-wave scheduler over the 8-wide compressed nodes (NK = 1, trt_oct.h).  Lane state: the node group it is
+// The same persistent-wave scheduler over the 8-wide compressed nodes (WalkOct, trt_oct.h).  Lane state: the node group it is
 // descending (`ng`: first-child index, hit byte, imask), the triangles it still has to test (`tg`: first record, one bit each), an
 // 8-byte stack entry per level.  A lane with triangle bits waits for a leaf step, one without them for a node step; a wave runs the
 // kind more of its lanes wait for (same weights).  idx == ~0: the lane holds no ray; no work bits and idx != ~0: ray finished, not
@@ -960,24 +967,17 @@ __device__ __forceinline__ void traceQueuePersistent(const SceneDev& sc, const R
 // brings a group of up to 24 triangles per node and gets a longer loop (trt_create; TRT_LEAF_LOOP in the environment overrides).
 // (Also measured: the root and its children read from an LDS copy — a fifth of all node fetches on veach-mis —: +-0.3 %.  These kernels
 // are bound by VALU issue, profiles/r03_roofs_stair.txt, not by the texture addresser.  Removed.)
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int PRIMARY, int QUERY = QUERY_NONE>
+template <bool SHADOW, bool COUNT, class Stack, int PRIMARY, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo, const LightBox& lbox)
 {
-    OctLdsStack<DEPTH, SPILL> stk;
-    stk.lds = smem + threadIdx.x;
-    stk.spill = spill + (size_t)blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x;
-    stk.spill_stride = spill_stride;
+    Stack stk = makeStack<Stack>(smem, spill, spill_stride);
     const bool any = SHADOW && (QUERY == QUERY_OCCLUDED || any_flag);
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long lower = (1ull << lane) - 1ull;
-    const uint32_t n_waves = gridDim.x * (TRT_TRACE_BLOCK / 64);
-    const uint32_t wave = xcdSwizzle(blockIdx.x, gridDim.x) * (TRT_TRACE_BLOCK / 64) + (threadIdx.x >> 6);
-    const uint32_t per = (n + n_waves - 1) / n_waves;
-    const unsigned long long w0 = (unsigned long long)wave * per;
-    uint32_t next = (uint32_t)__builtin_amdgcn_readfirstlane((int)(w0 < n ? w0 : n));
-    const uint32_t end = (uint32_t)__builtin_amdgcn_readfirstlane((int)((w0 + per) < n ? (w0 + per) : n));
+    const auto [first, end] = waveSlice(n);
+    uint32_t next = first;
 
     constexpr uint32_t NO_RAY = 0xFFFFFFFFu;
     uint32_t idx = NO_RAY;
@@ -1076,7 +1076,7 @@ __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, cons
             else ng.y = 0u;  // finished
         }
     }
-    if (COUNT) {
+    if (COUNT) {  // (not addProbe() and the census behind it: that moves three instructions of the ten COUNT kernels of this driver)
         const unsigned long long si = waveSum(pr.n_inner), st = waveSum(pr.n_tri), wi = waveSum(pr.wave_inner), wt = waveSum(pr.wave_tri);
         if (lane == 0) {
             atomicAdd(&stats->inner_visits[SHADOW ? 1 : 0], si);
@@ -1091,42 +1091,64 @@ __device__ __forceinline__ void traceQueuePersistentOct(const SceneDev& sc, cons
     }
 }
 
-template <bool SHADOW, bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, bool HIT8 = false, bool PIPE = false, int QUERY = QUERY_NONE>
+// One type per driver: what a traversal kernel is instantiated with.  Stack: the per-lane stack (void: the walk has none); LDS_WORDS: the kernel's
+// LDS array — the stack (8-byte entries on the oct tree), or (uniform walk) the candidate queue; REDO: the driver checks its results when it stores
+// them and puts the rays that fail on a RedoList, so k_trace_fix runs behind it; LIGHT_BOX: its shadow walk ends early by the light's box.
+// The wave-uniform walk in the three forms trt_create picks from (FLAGS_LDS, HIT8: traceQueueUniform's PIPE and HIT8):
+struct WalkUniformBase { using Stack = void; static constexpr int LDS_WORDS = TRT_PEND_SLOTS * 4 * TRT_TRACE_BLOCK; static constexpr bool REDO = false, LIGHT_BOX = false; };
+struct WalkUniform : WalkUniformBase { static constexpr bool FLAGS_LDS = false, HIT8 = false; };       // flags from global memory, 16-byte hit records
+struct WalkUniformFlags : WalkUniformBase { static constexpr bool FLAGS_LDS = true, HIT8 = false; };   // the shadow / occlusion walk of a slim scene
+struct WalkUniformHit8 : WalkUniformBase { static constexpr bool FLAGS_LDS = true, HIT8 = true; };     // the closest hits of a hit8 scene
+// The per-lane walk of the exact 4-wide nodes: 16 levels in LDS without spill code when the verified BVH depth fits, else TRT_LDS_STACK_MAX levels
+// and a global spill area (16 KiB per block keeps 8 waves per SIMD resident).
+template <int DEPTH, bool SPILL>
+struct WalkWideBase { using Stack = LdsStack<DEPTH, SPILL>; static constexpr int LDS_WORDS = DEPTH * TRT_TRACE_BLOCK; static constexpr bool REDO = true, LIGHT_BOX = false; };
+struct WalkWide16 : WalkWideBase<16, false> {};
+struct WalkWideSpill : WalkWideBase<TRT_LDS_STACK_MAX, true> {};
+// The per-lane walk of the 8-wide nodes: one 8-byte entry per level below the root, OCT_LDS_LEVELS of them in LDS (20 KiB per block: eight blocks
+// per CU), deeper ones — staircase has 10 levels, the 10 M-triangle mesh 11 — in the spill area.  One instantiation serves every tree.
+constexpr uint32_t OCT_LDS_LEVELS = 10;
+struct WalkOct { using Stack = OctLdsStack<OCT_LDS_LEVELS, true>; static constexpr int LDS_WORDS = 2 * OCT_LDS_LEVELS * TRT_TRACE_BLOCK; static constexpr bool REDO = true, LIGHT_BOX = true; };
+
+template <class Driver, bool SHADOW, bool COUNT, int PRIMARY, int QUERY = QUERY_NONE>
 __device__ __forceinline__ void traceQueue(const SceneDev& sc, const RaySource& src, uint32_t n, f4* __restrict__ hit,
                                            const f4* __restrict__ sw, uint32_t light_mat, f4* __restrict__ Lacc, uint32_t* __restrict__ spill,
                                            uint32_t spill_stride, DeviceStats* stats, uint32_t* smem, bool any_flag, RedoList redo, const LightBox& lbox)
 {
-    static_assert(IMPL == 0 || !(HIT8 || PIPE), "8-byte hit records and the flags in LDS belong to the wave-uniform walk");
-    if constexpr (IMPL == 0) traceQueueUniform<SHADOW, COUNT, PRIMARY, HIT8, PIPE, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, stats, any_flag, reinterpret_cast<f4*>(smem));
-    else if constexpr (NK == 1) traceQueuePersistentOct<SHADOW, COUNT, DEPTH, SPILL, PRIMARY, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo, lbox);
-    else traceQueuePersistent<SHADOW, COUNT, DEPTH, SPILL, IMPL, PRIMARY, NK, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo);
+    // (each driver forms its `any` from any_flag itself: formed here and handed down, or in a function they share, k_trace_query<WalkOct, QUERY_OCCLUDED>
+    // comes out with two pairs of SGPRs exchanged)
+    using Stack = typename Driver::Stack;
+    if constexpr (std::is_void_v<Stack>) traceQueueUniform<SHADOW, COUNT, PRIMARY, Driver::HIT8, Driver::FLAGS_LDS, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, stats, any_flag, reinterpret_cast<f4*>(smem));
+    else if constexpr (Driver::LIGHT_BOX) traceQueuePersistentOct<SHADOW, COUNT, Stack, PRIMARY, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo, lbox);
+    else traceQueuePersistent<SHADOW, COUNT, Stack, PRIMARY, QUERY>(sc, src, n, hit, sw, light_mat, Lacc, spill, spill_stride, stats, smem, any_flag, redo);
 }
 
+// COUNT stays the kernels' first template argument: the profiling tools tell the counting build by a kernel name that begins "<true".
 // PRIMARY: bounce 0 — ray i is the camera ray of path i, generated in registers (K1 of SURVEY.md §7 fused
-// into K2: no primary-ray queue is ever written or read).  HIT8, PIPE: traceQueueUniform.
-template <bool COUNT, int DEPTH, bool SPILL, int IMPL, int PRIMARY, int NK, bool HIT8 = false, bool PIPE = false>
+// into K2: no primary-ray queue is ever written or read).
+template <bool COUNT, class Driver, int PRIMARY>
 __global__ TRT_TRACE_BOUNDS void k_trace_closest(SceneDev sc, RaySource src, f4* __restrict__ hit, uint32_t n,
                                                  uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, RedoList redo)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t smem[IMPL == 0 ? TRT_PEND_SLOTS * 4 * TRT_TRACE_BLOCK : (NK == 1 ? 2 : 1) * DEPTH * TRT_TRACE_BLOCK];  // stack (8-byte entries on the oct tree), or (uniform walk) the candidate queue
+    __shared__ __attribute__((aligned(16))) uint32_t smem[Driver::LDS_WORDS];
     const LightBox nobox = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-    traceQueue<false, COUNT, DEPTH, SPILL, IMPL, PRIMARY, NK, HIT8, PIPE>(sc, src, n, hit, nullptr, 0u, nullptr, spill, spill_stride, stats, smem, false, redo, nobox);
+    traceQueue<Driver, false, COUNT, PRIMARY>(sc, src, n, hit, nullptr, 0u, nullptr, spill, spill_stride, stats, smem, false, redo, nobox);
 }
 
 // Shadow test of shade() (pathTracing.cpp:51-58): CLOSEST hit, visible iff
 // its material is the light's (Q5); then L += w.  One launch per light, in
 // light order; each path has at most one ray per launch, so the read-modify-
 // write of Lacc needs no atomic and the sum order is fixed.
-template <bool COUNT, int DEPTH, bool SPILL, int IMPL, int NK, bool PIPE = false>
+template <bool COUNT, class Driver>
 __global__ TRT_TRACE_BOUNDS void k_trace_shadow(SceneDev sc, ShadowQueue sq, uint32_t n, uint32_t light_mat, f4* __restrict__ Lacc,
                                                 uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, uint32_t any, RedoList redo, LightBox lbox)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t smem[IMPL == 0 ? TRT_PEND_SLOTS * 4 * TRT_TRACE_BLOCK : (NK == 1 ? 2 : 1) * DEPTH * TRT_TRACE_BLOCK];
+    __shared__ __attribute__((aligned(16))) uint32_t smem[Driver::LDS_WORDS];
     RaySource src;
     src.ra = sq.sa;
     src.rb = sq.sb;
     src.s0 = 0;
-    traceQueue<true, COUNT, DEPTH, SPILL, IMPL, false, NK, false, PIPE>(sc, src, n, nullptr, sq.sw, light_mat, Lacc, spill, spill_stride, stats, smem, any != 0u, redo, lbox);
+    traceQueue<Driver, true, COUNT, 0>(sc, src, n, nullptr, sq.sw, light_mat, Lacc, spill, spill_stride, stats, smem, any != 0u, redo, lbox);
 }
 
 // The binned walk (traceQueueBinned) of the render's closest-hit queue: trt_create's bin_walk.
@@ -1134,21 +1156,21 @@ template <bool COUNT>
 __global__ TRT_TRACE_BOUNDS TRT_BIN_WAVES void k_trace_closest_binned(SceneDev sc, RaySource src, f4* __restrict__ hit, uint32_t n,
                                                                       uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, RedoList redo)
 {
-    __shared__ __attribute__((aligned(16))) uint32_t smem[TRT_PEND_SLOTS * 4 * TRT_TRACE_BLOCK];  // the candidate queue, and each wave's sort
+    __shared__ __attribute__((aligned(16))) uint32_t smem[WalkUniformHit8::LDS_WORDS];  // the candidate queue, and each wave's sort
     traceQueueBinned<COUNT>(sc, src, n, hit, stats, reinterpret_cast<f4*>(smem));
 }
 
-// The ray-batch queries (QUERY_CLOSEST, QUERY_OCCLUDED) on the packed rays of src (rb.w: the bound), on the driver the scene picked.  Same arguments
-// as k_trace_closest; QUERY_OCCLUDED takes `hit` as its byte array and counts as a shadow walk (DeviceStats slot 1).  HIT8, PIPE: traceQueueUniform.
-template <int QUERY, bool COUNT, int DEPTH, bool SPILL, int IMPL, int NK, bool HIT8 = false, bool PIPE = false>
+// The ray-batch queries (QUERY_CLOSEST, QUERY_OCCLUDED) on the packed rays of src (rb.w: the bound), on the driver the scene picked, with the counters
+// on (as trt_trace_closest).  Same arguments as k_trace_closest; QUERY_OCCLUDED takes `hit` as its byte array and counts as a shadow walk (DeviceStats slot 1).
+template <class Driver, int QUERY>
 __global__ TRT_TRACE_BOUNDS void k_trace_query(SceneDev sc, RaySource src, f4* __restrict__ hit, uint32_t n,
                                                uint32_t* __restrict__ spill, uint32_t spill_stride, DeviceStats* stats, RedoList redo)
 {
     static_assert(QUERY == QUERY_CLOSEST || QUERY == QUERY_OCCLUDED, "k_trace_closest serves the unbounded closest hit");
-    __shared__ __attribute__((aligned(16))) uint32_t smem[IMPL == 0 ? TRT_PEND_SLOTS * 4 * TRT_TRACE_BLOCK : (NK == 1 ? 2 : 1) * DEPTH * TRT_TRACE_BLOCK];
+    __shared__ __attribute__((aligned(16))) uint32_t smem[Driver::LDS_WORDS];
     const LightBox nobox = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
     constexpr bool OCC = QUERY == QUERY_OCCLUDED;
-    traceQueue<OCC, COUNT, DEPTH, SPILL, IMPL, 0, NK, HIT8, PIPE, QUERY>(sc, src, n, hit, nullptr, 0u, nullptr, spill, spill_stride, stats, smem, OCC, redo, nobox);
+    traceQueue<Driver, OCC, true, 0, QUERY>(sc, src, n, hit, nullptr, 0u, nullptr, spill, spill_stride, stats, smem, OCC, redo, nobox);
 }
 
 // The exact form of the traversal for the rays a traversal launch put on its redo list (see RedoList): a few blocks, launched
@@ -1156,7 +1178,7 @@ __global__ TRT_TRACE_BOUNDS void k_trace_query(SceneDev sc, RaySource src, f4* _
 // on padded trees.  redo.count[0] = length of the list, redo.count[1] = blocks of this launch that are through: the last one adds
 // the length to DeviceStats::redo_rays (trt_stats.redo_rays: how often the slow path ran is visible to the caller) and empties the list.
 constexpr uint32_t TRT_FIX_BLOCKS = 32;
-template <bool SHADOW, int PRIMARY, int NK, int QUERY = QUERY_NONE>
+template <bool SHADOW, int PRIMARY, int QUERY = QUERY_NONE>
 __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_trace_fix(SceneDev sc, RaySource src, f4* __restrict__ hit, const f4* __restrict__ sw, uint32_t light_mat,
                                                                f4* __restrict__ Lacc, uint32_t* __restrict__ spill, uint32_t spill_stride, RedoList redo, uint32_t any_flag,
                                                                DeviceStats* stats)
@@ -1165,10 +1187,7 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_trace_fix(SceneDev sc, RayS
     const uint32_t n = *redo.count;  // complete: the traversal launch precedes this one on the stream; stable until the last block resets it
     if (n == 0u) return;             // every block sees the same n: all leave here, or none
     {
-        LdsStack<TRT_LDS_STACK_MAX, true> stk;
-        stk.lds = smem + threadIdx.x;
-        stk.spill = spill + (size_t)blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x;
-        stk.spill_stride = spill_stride;
+        LdsStack<TRT_LDS_STACK_MAX, true> stk = makeStack<LdsStack<TRT_LDS_STACK_MAX, true>>(smem, spill, spill_stride);
         const bool any = SHADOW && (QUERY == QUERY_OCCLUDED || any_flag != 0u);
         for (uint32_t k = blockIdx.x * TRT_TRACE_BLOCK + threadIdx.x; k < n; k += gridDim.x * TRT_TRACE_BLOCK) {
             const uint32_t i = redo.idx[k];
@@ -1180,7 +1199,7 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_trace_fix(SceneDev sc, RayS
             const float t_init = (SHADOW || QUERY != QUERY_NONE) ? b.w : TRT_INF;
             Hit h = (raySpecial(inv) && rayOnABoxPlane(sc, o, inv))
                         ? traceClosestBvh2Glm<LdsStack<TRT_LDS_STACK_MAX, true>, false>(sc, o, d, stk, ni, nt, t_init, any)
-                        : traceClosestPass<LdsStack<TRT_LDS_STACK_MAX, true>, false, NK, true>(sc, o, d, stk, ni, nt, t_init, any, SHADOW && !any);
+                        : traceClosestPass<LdsStack<TRT_LDS_STACK_MAX, true>, false, 0, true>(sc, o, d, stk, ni, nt, t_init, any, SHADOW && !any);
             // the literal walk ignores t_init in closest mode: its (unbounded) closest hit, clipped to the bound — at equal t every tied candidate
             // lies on the same side of it, so this is the closest hit inside the bound
             if (QUERY == QUERY_CLOSEST && !(h.t < b.w)) h.tri = -1;
@@ -1575,7 +1594,7 @@ struct TailArgs {
 };
 
 // LIST: the paths of a pixel list (trt_render_pixels)
-template <bool COUNT, int NK, bool LIST = false>
+template <bool COUNT, bool LIST = false>
 __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_tail(SceneDev sc, TailArgs A)
 {
     __shared__ __attribute__((aligned(16))) uint32_t smem[TRT_LDS_STACK_MAX * TRT_TRACE_BLOCK];  // the stacks, or (uniform) the candidate queues
@@ -1604,7 +1623,7 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_tail(SceneDev sc, TailArgs 
                     if (triTest(sc.tri_isect[h.tri], o, d, t, un, vn, det)) { h.u = un / det; h.v = vn / det; }
                 }
             } else {
-                h = traceClosest<LdsStack<TRT_LDS_STACK_MAX, true>, COUNT, NK>(sc, mk3(ra.x, ra.y, ra.z), mk3(ra.w, rb.x, rb.y), stk, ni[0], nt[0]);
+                h = traceClosest<LdsStack<TRT_LDS_STACK_MAX, true>, COUNT>(sc, mk3(ra.x, ra.y, ra.z), mk3(ra.w, rb.x, rb.y), stk, ni[0], nt[0]);
             }
             ShadeCtx c;
             if constexpr (LIST) shadeBegin(sc, A.td, A.s0, ra, rb, bt, mk4(h.t, u2f((uint32_t)h.tri), h.u, h.v), c, PixelList());
@@ -1624,7 +1643,7 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_tail(SceneDev sc, TailArgs 
                     sh.t = fixed ? t_max : TRT_INF; sh.tri = -1; sh.flags = 0u; sh.u = 0.f; sh.v = 0.f;
                     uniformWalk<COUNT>(sc, rayOrigin(c, wo), wo, true, reinterpret_cast<f4*>(smem) + threadIdx.x, sh.t, sh.tri, sh.flags, ni[1], nt[1]);
                 } else {
-                    sh = traceClosest<LdsStack<TRT_LDS_STACK_MAX, true>, COUNT, NK>(sc, rayOrigin(c, wo), wo, stk, ni[1], nt[1], t_max, fixed, !fixed);
+                    sh = traceClosest<LdsStack<TRT_LDS_STACK_MAX, true>, COUNT>(sc, rayOrigin(c, wo), wo, stk, ni[1], nt[1], t_max, fixed, !fixed);
                 }
                 if (fixed ? sh.tri < 0 : (sh.tri >= 0 && (sh.flags >> 8) == (uint32_t)sc.lights[li].mat)) { L.x = L.x + w.x; L.y = L.y + w.y; L.z = L.z + w.z; }
             }

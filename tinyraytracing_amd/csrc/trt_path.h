@@ -144,10 +144,10 @@ struct WideNode {
 
 struct OctNode;  // trt_oct.h
 struct SceneDev {
-    const trt_bvh_node* nodes;   // the caller's BVH2: the wave-uniform walk of tiny trees (trt_kernels.h, IMPL 0)
-    const WideNode* wnodes;      // its 4-wide collapse, exact boxes (NK = 0; always present: the exact form of k_trace_fix / k_tail walks it)
-    const OctNode* onodes;       // its 8-wide collapse, quantised conservative boxes (NK = 1, trt_oct.h); null when the tree does not qualify
-    const TriIsect* tri_trav;    // NK = 1: the triangle records in the order the oct nodes address them
+    const trt_bvh_node* nodes;   // the caller's BVH2: the wave-uniform walk of tiny trees (trt_kernels.h, WalkUniform)
+    const WideNode* wnodes;      // its 4-wide collapse, exact boxes (WalkWide16 / WalkWideSpill; always present: the exact form of k_trace_fix / k_tail walks it)
+    const OctNode* onodes;       // its 8-wide collapse, quantised conservative boxes (WalkOct, trt_oct.h); null when the tree does not qualify
+    const TriIsect* tri_trav;    // WalkOct: the triangle records in the order the oct nodes address them
     const f4* leaf_box;          // for every triangle i the caller's box of its leaf at [2 i] = (lo.xyz, hi.x), [2 i + 1] = (hi.y, hi.z, -, -): leafEntry()
     const TriIsect* tri_isect;
     const TriShade* tri_shade;
