@@ -29,8 +29,8 @@ HOST_HDR := $(wildcard $(PKG)/host/*.h) $(wildcard $(PKG)/csrc/*.h) include/trt.
 HIP_SRC := $(PKG)/csrc/trt_api.hip
 HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include/trt_exact.h
 
-.PHONY: all host hip lbvh oracle cli hostsim denoisecpu refitcpu variants probe exactcheck clean
-all: host hip lbvh oracle hostsim denoisecpu refitcpu cli exactcheck
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu refitcpu rayscpu variants probe exactcheck clean
+all: host hip lbvh oracle hostsim denoisecpu refitcpu rayscpu cli exactcheck
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -50,6 +50,10 @@ tests/denoise/libdenoise_cpu.so: tests/denoise/denoise_cpu.cpp $(PKG)/csrc/trt_d
 refitcpu: tests/refit/librefit_cpu.so
 tests/refit/librefit_cpu.so: tests/refit/refit_cpu.cpp $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -pthread -I$(PKG)/csrc -shared -o $@ tests/refit/refit_cpu.cpp
+# CPU compile of the per-ray functions of trt_render_rays (trt_path.h: rayRecord, rayValid, cameraRecord), for tests only (tests/test_render_rays_cpu.py)
+rayscpu: tests/render_rays/librays_cpu.so
+tests/render_rays/librays_cpu.so: tests/render_rays/rays_cpu.cpp $(HIP_HDR)
+	$(CXX) $(CXXFLAGS) -I$(PKG)/csrc -shared -o $@ tests/render_rays/rays_cpu.cpp
 
 $(OUT)/libtrt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(OUT)
@@ -80,7 +84,7 @@ variants: $(HIP_SRC) $(HIP_HDR)
 	  echo "variant $$name: $$defs"; $(HIPCC) $(HIPFLAGS) $$defs -shared -o $(OUT)/variants/libtrt_hip_$$name.so $(HIP_SRC) || exit 1; done
 
 clean:
-	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/denoise/libdenoise_cpu.so tests/refit/librefit_cpu.so
+	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/denoise/libdenoise_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so
 	$(MAKE) -C oracle clean
 
 # exhaustive (2^32 inputs) proof that include/trt_exact.h returns the bits of sqrtf / 1.0f / sqrtf: run by tests/test_gpu_parity.py

@@ -187,7 +187,7 @@ typedef struct trt_params {
 
 #define TRT_MAX_KERNELS 8
 enum {
-    TRT_K_GEN_PRIMARY = 0,  /* unused since primary-ray generation is fused into bounce 0 (always 0 launches) */
+    TRT_K_GEN_PRIMARY = 0,  /* trt_render_rays*: the kernel that queues the caller's rays; 0 launches everywhere else (the camera's rays are generated inside bounce 0) */
     TRT_K_TRACE_CLOSEST = 1,
     TRT_K_SHADE = 2,
     TRT_K_TRACE_SHADOW = 3,
@@ -278,6 +278,55 @@ int trt_render_pixels(trt_handle* h, const trt_params* p, uint32_t n_pixels, con
 int trt_render_pixels_device(trt_handle* h, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels_dev,
                              int32_t sample_begin, int32_t sample_end, double* sum_dev, double* sumsq_dev,
                              void* hip_stream, trt_stats* stats);
+
+/* ---- full paths along rays the caller chose ----------------------------------------------------------------------------------
+ * trt_render_rays is trt_render_pixels with the built-in ray generator replaced by the caller's arrays: n entries ("slots", each with its own
+ * random stream and its own sums), samples [sample_begin, sample_end), one ray per entry and sample.  It serves a camera that moves while the
+ * handle stays resident, any camera that is not the reference's pinhole (thin lens, fisheye, orthographic, stereo), and rays that start on
+ * surfaces (light probes, irradiance samples, lightmap texels).  The handle keeps no state of it.
+ *   Rays.  org / dir: [n_samples][n][3] floats, sample-major, n_samples = sample_end - sample_begin; the ray of (entry i, sample s) sits at
+ *   index (s - sample_begin) * n + i.  stream[n] (uint32, may be NULL = i): the "pixel" word of the entry's random stream; any 32 bits.
+ *   One path.  The path of (entry i, sample s) is exactly what trt_render traces from its bounce-0 ray on: the ray's type is camera, so a light
+ *   hit directly is kept (pathTracing.cpp:9-12); depth 0, throughput 1; the random stream is (p->seed, stream[i], s), and THE FIRST DRAW INDEX
+ *   IS 2: draws 0 and 1 of that stream belong to whoever generated the ray — the built-in camera spends them on its jitter (main.cpp:92-93),
+ *   and a caller's generator may use them too (trt_prims.h trt_rng_uniform(key, 0 / 1)).
+ *   Sums.  sum / sumsq: n * 3 doubles, in/out, the terms of trt_render_pixels in its order: v = (double)(L / (float)p->spp), sum += v,
+ *   sumsq += v * v, in increasing s.  sumsq may be NULL.  sample_end may exceed p->spp (p->spp only scales v).
+ *   The built-in camera.  trt_camera_rays(the handle's camera, p, pixels, ...) fed into trt_render_rays with stream = pixels leaves, bit for
+ *   bit, what trt_render_pixels leaves for that pixel list — and with another trt_camera what a handle created with THAT camera would leave.
+ *   Parameters.  max_depth, mem_budget (132 + 48 * n_lights bytes per path, as trt_render_pixels; TRT_ENOMEM when one sample of every entry
+ *   does not fit) and the flags FIXED_NEE, RAY_OFFSET, SPECULAR_KS, TIMING, COUNT and OVERLAP mean what they mean for trt_render_pixels.
+ *   trt_render_rays ignores width, height, the tile fields and TRT_FLAG_FIXED_PIXELS; trt_camera_rays honours width, height and
+ *   TRT_FLAG_FIXED_PIXELS (and ignores the tile fields, spp, max_depth, mem_budget and every other flag).
+ *   Directions are used as given.  Radiance is meaningful for unit directions only; a non-unit direction is not an error.
+ *   Invalid entries.  An entry whose six components are not all finite (a NaN, an infinity), or whose direction is (0, 0, 0), is not traced:
+ *   it adds exactly 0 to sum and sumsq for that sample, is not counted in stats.rays_camera, and never disturbs another entry.  A single zero
+ *   component and denormals are valid.
+ *   TRT_EINVAL, checked on the host before anything is written, the handle stays usable: a null handle or p; a null org, dir or sum while
+ *   n > 0; n > 0x7FFF0000 (the path ids of one pass); sample_begin < 0 or > sample_end; p->spp < 1; max_depth < 0.  n == 0 or an empty sample
+ *   range: nothing to do, TRT_OK.
+ *   stats: as for trt_render_pixels; rays_camera counts the valid entries, rows_rendered = 0, and the kernels that bring the caller's rays into
+ *   the queue are counted under TRT_K_GEN_PRIMARY.
+ *   Cost.  Bounce 0 goes through HBM here (a 48-byte queue record written and read per path besides the 24 bytes of the ray) where the
+ *   built-in camera forms its rays in registers; the host entry stages the rays pass by pass, never all at once. */
+int trt_render_rays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, const float* dir, const uint32_t* stream,
+                    int32_t sample_begin, int32_t sample_end, double* sum_host, double* sumsq_host, trt_stats* stats);
+/* The same with org, dir, stream, sum and sumsq in DEVICE memory of the handle's device, all work on hip_stream (NULL = default);
+ * returns after the stream has been synchronised. */
+int trt_render_rays_device(trt_handle* h, const trt_params* p, uint32_t n, const float* org_dev, const float* dir_dev, const uint32_t* stream_dev,
+                           int32_t sample_begin, int32_t sample_end, double* sum_dev, double* sumsq_dev, void* hip_stream, trt_stats* stats);
+/* The rays trt_render traces for the listed pixels (pixels[i] = y * p->width + x), samples [sample_begin, sample_end), of ANY camera: the
+ * stream (p->seed, pixels[i], s), its draws 0 and 1 as the jitter, Camera::getRay (camera.cpp:19-28) — in the layout trt_render_rays reads,
+ * org / dir [n_samples][n_pixels][3].  Host only: needs no handle and no GPU.  width and height >= 1 (a side of 1 gives what the reference's
+ * x = j / (W - 1) gives: NaN, unless TRT_FLAG_FIXED_PIXELS).  TRT_EINVAL, before anything is written: a null cam or p, a null array while
+ * n_pixels > 0, width or height < 1, width * height > 2^32 (a pixel is a 32-bit index), sample_begin < 0 or > sample_end, an entry >= width * height. */
+int trt_camera_rays(const trt_camera* cam, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels,
+                    int32_t sample_begin, int32_t sample_end, float* org_host, float* dir_host);
+/* The same bits on `device` (HIP ordinal; a gfx950, else TRT_ENODEV) with pixels, org and dir in DEVICE memory, the work on hip_stream
+ * (NULL = default); returns after the stream has been synchronised.  An entry >= width * height is found by the kernel: TRT_EINVAL after
+ * the fact, with org / dir written for the other entries.  A few bytes of device memory are allocated and freed per call. */
+int trt_camera_rays_device(int device, const trt_camera* cam, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels_dev,
+                           int32_t sample_begin, int32_t sample_end, float* org_dev, float* dir_dev, void* hip_stream);
 
 /* First-hit feature buffers ("AOVs") for denoisers: per-pixel albedo, shading normal and depth, the inputs OIDN / OptiX / SVGF-style
  * filters take beside a low-spp render.  For every selected pixel (x, y) of the tile (tile and row interleave exactly as trt_render)

@@ -14,7 +14,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _abi, adaptive
-from ._abi import Params, Stats, SceneFlat, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES, TRT_K_DENOISE, TRT_K_REFIT  # noqa: F401
+from ._abi import Params, Stats, SceneFlat, Camera, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES, TRT_K_DENOISE, TRT_K_REFIT  # noqa: F401
 
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES_DIR = os.path.join(REPO_ROOT, "scenes")
@@ -561,6 +561,83 @@ class Renderer:
             raise TrtError(f"trt_trace_occluded_device failed ({rc}): {self._lib.trt_last_error().decode()}")
         return st
 
+    def render_rays(self, params, org, dir, streams=None, sample_begin=0, sums=None, sumsq=None):
+        """Full paths along caller-supplied rays (trt_render_rays, include/trt.h): org / dir are float32 [S, n, 3] — sample-major, the rays of
+        samples [sample_begin, sample_begin + S) of n entries ([n, 3] = one sample); streams: uint32 [n], the "pixel" word of each entry's
+        random stream (None = 0..n-1).  The path of (entry i, sample s) is what trt_render traces from its bounce-0 ray on, with the stream
+        (seed, streams[i], s) from draw 2.  Adds v = (double)(L / params.spp) and v * v onto sums / sumsq (float64 [n, 3]; None = zeros)
+        and returns (sums, sumsq, Stats).  Entries with a NaN, an infinity or a zero direction are not traced and add nothing."""
+        org = np.ascontiguousarray(org, dtype=np.float32)
+        dir = np.ascontiguousarray(dir, dtype=np.float32)
+        if org.ndim == 2:
+            org, dir = org[None], dir[None] if dir.ndim == 2 else dir
+        if org.ndim != 3 or org.shape[2] != 3 or dir.shape != org.shape:
+            raise TrtError("render_rays: org and dir must both be float32 arrays of shape (S, n, 3)")
+        n_samples, n = org.shape[0], org.shape[1]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
+            if streams.size != n:
+                raise TrtError(f"render_rays: streams must hold {n} ids")
+        sums = self._moments(sums, n, "sums")
+        sumsq = self._moments(sumsq, n, "sumsq")
+        st = Stats()
+        fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+        rc = self._lib.trt_render_rays(self._h, C.byref(params), n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp),
+                                       None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint32)), int(sample_begin),
+                                       int(sample_begin) + n_samples, sums.ctypes.data_as(dp), sumsq.ctypes.data_as(dp), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_render_rays failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return sums, sumsq, st
+
+    def render_rays_into(self, params, org, dir, sums, sumsq=None, streams=None, sample_begin=0, stream_ptr=0):
+        """trt_render_rays_device: org / dir (float32 [S, n, 3]), streams (int32 or uint32 [n], None = 0..n-1), sums and sumsq (float64 [n, 3],
+        in/out; sumsq may be None) are contiguous torch tensors on this device; the work runs on stream `stream_ptr` (0 = default).  -> Stats."""
+        if not _is_torch(org) or org.dim() != 3 or org.shape[2] != 3:
+            raise TrtError("render_rays_into: org must be a float32 tensor of shape (S, n, 3)")
+        n_samples, n = int(org.shape[0]), int(org.shape[1])
+        f32, f64 = ("torch.float32",), ("torch.float64",)
+        p = self._device_arrays("render_rays_into", n, [("org", org, f32, 3 * n * n_samples), ("dir", dir, f32, 3 * n * n_samples),
+                                                        ("streams", streams, ("torch.int32", "torch.uint32"), n), ("sums", sums, f64, 3 * n),
+                                                        ("sumsq", sumsq, f64, 3 * n)])
+        if dir is None or sums is None:
+            raise TrtError("render_rays_into: dir and sums are needed")
+        st = Stats()
+        rc = self._lib.trt_render_rays_device(self._h, C.byref(params), n, p[0], p[1], p[2], int(sample_begin), int(sample_begin) + n_samples,
+                                              p[3], p[4], C.c_void_p(stream_ptr), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_render_rays_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return st
+
+    def render_camera(self, params, camera, samples_per_call=1, want_stats=False, on_device=False):
+        """The tile of `params` as seen by `camera` (a Camera, e.g. from look_at) — on THIS handle, whatever camera its scene was created with:
+        rays are generated on the device (camera_rays_into) and rendered on the device (render_rays_into), samples_per_call samples at a
+        time, accumulated in sample order.  -> float32 image [rows, tile_w, 3], bit-identical to Renderer(scene with that camera).render(params)
+        [, Stats summed over the calls].  on_device: the image stays a torch tensor on this device (nothing but the stats crosses to the host)."""
+        import torch
+        ys = np.asarray(rows_selected(params), np.int64)
+        xs = np.arange(params.x0, params.x1, dtype=np.int64)
+        if ys.size == 0 or xs.size == 0:
+            raise TrtError("render_camera: empty tile")
+        if params.width * params.height > 0x7FFFFFFF:
+            raise TrtError("render_camera: needs width * height < 2^31 (int32 pixel tensors)")
+        k = max(1, min(int(samples_per_call), params.spp))
+        dev = torch.device("cuda", self.device)
+        pix = torch.from_numpy((ys[:, None] * params.width + xs[None, :]).reshape(-1).astype(np.int32)).to(dev)
+        n = pix.numel()
+        org = torch.empty((k, n, 3), dtype=torch.float32, device=dev)
+        dirs = torch.empty_like(org)
+        sums = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        total = Stats()
+        for s0 in range(0, params.spp, k):
+            s1 = min(s0 + k, params.spp)
+            camera_rays_into(camera, params, pix, s0, s1, org[:s1 - s0], dirs[:s1 - s0], device=self.device, stream_ptr=stream)
+            _add_stats(total, self.render_rays_into(params, org[:s1 - s0], dirs[:s1 - s0], sums, streams=pix, sample_begin=s0, stream_ptr=stream))
+        image = sums.to(torch.float32).reshape(ys.size, xs.size, 3)
+        if not on_device:
+            image = image.cpu().numpy()
+        return (image, total) if want_stats else image
+
     def _light_tables(self, upd, lights_from):
         if lights_from is None:
             return
@@ -677,6 +754,66 @@ class GroupRenderer:
             self.close()
         except Exception:
             pass
+
+
+def look_at(eye, target, up, fovy_deg, width, height):
+    """The pinhole Camera of Camera::setCamera (camera.cpp:3-17) for an eye point, a target, an up vector, a vertical field of view in
+    degrees and an image of width x height pixels: the half-height tan(fovy / 2) in double, the viewport extents narrowed to float, the
+    basis w = normalize(eye - target), u = normalize(up x w), v = w x u in float32."""
+    f = np.float32
+    eye, target, up = (np.asarray(a, f).reshape(3) for a in (eye, target, up))
+
+    def normalize(a):
+        return a * (f(1.0) / np.sqrt(f((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2])))
+
+    vh = f(2.0 * np.tan(float(fovy_deg) * 0.01745329251994329576923690768489 / 2.0))
+    vw = f((float(width) / float(height)) * float(vh))
+    w = normalize(eye - target)
+    u = normalize(np.cross(up, w).astype(f))
+    v = np.cross(w, u).astype(f)
+    cam = _abi.Camera()
+    hor, ver = vw * u, vh * v
+    llc = eye - hor / f(2.0) - ver / f(2.0) - w
+    for name, a in (("eye", eye), ("lower_left_corner", llc), ("horizontal", hor), ("vertical", ver)):
+        setattr(cam, name, _abi.c_float3(*[float(x) for x in a]))
+    return cam
+
+
+def camera_rays(camera, params, pixels, sample_begin, sample_end):
+    """trt_camera_rays (host only, no GPU): the rays trt_render traces for the listed pixels (y * width + x), samples [sample_begin,
+    sample_end), of any Camera -> (org, dir), float32 [S, n, 3] in the layout Renderer.render_rays reads."""
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+    n, n_samples = pixels.size, max(int(sample_end) - int(sample_begin), 0)
+    org = np.empty((n_samples, n, 3), np.float32)
+    dirs = np.empty_like(org)
+    lib = _abi.load_hip()
+    fp = C.POINTER(C.c_float)
+    rc = lib.trt_camera_rays(C.byref(camera), C.byref(params), n, pixels.ctypes.data_as(C.POINTER(C.c_uint32)), int(sample_begin), int(sample_end),
+                             org.ctypes.data_as(fp), dirs.ctypes.data_as(fp))
+    if rc != 0:
+        raise TrtError(f"trt_camera_rays failed ({rc}): {lib.trt_last_error().decode()}")
+    return org, dirs
+
+
+def camera_rays_into(camera, params, pixels, sample_begin, sample_end, org, dir, device=0, stream_ptr=0):
+    """trt_camera_rays_device: the same rays on `device`; pixels (int32 or uint32 [n]), org and dir (float32 [S, n, 3], S = sample_end -
+    sample_begin) are contiguous torch tensors there, the work runs on stream `stream_ptr` (0 = default)."""
+    n_samples = int(sample_end) - int(sample_begin)
+    if not _is_torch(pixels) or pixels.dim() != 1:
+        raise TrtError("camera_rays_into: pixels must be a 1-D int32 / uint32 tensor")
+    n = pixels.numel()
+    ptrs = []
+    for name, t, dtypes, need in (("pixels", pixels, ("torch.int32", "torch.uint32"), n), ("org", org, ("torch.float32",), 3 * n * n_samples),
+                                  ("dir", dir, ("torch.float32",), 3 * n * n_samples)):
+        if (not _is_torch(t) or str(t.dtype) not in dtypes or not t.is_cuda or not t.is_contiguous() or t.numel() != need
+                or (t.device.index is not None and t.device.index != int(device))):
+            raise TrtError(f"camera_rays_into: {name} must be a contiguous {' or '.join(d[6:] for d in dtypes)} tensor on cuda:{int(device)} with {need} elements")
+        ptrs.append(C.c_void_p(t.data_ptr()))
+    lib = _abi.load_hip()
+    rc = lib.trt_camera_rays_device(int(device), C.byref(camera), C.byref(params), n, ptrs[0], int(sample_begin), int(sample_end), ptrs[1], ptrs[2],
+                                    C.c_void_p(stream_ptr))
+    if rc != 0:
+        raise TrtError(f"trt_camera_rays_device failed ({rc}): {lib.trt_last_error().decode()}")
 
 
 def mean_luminance_variance(sums, sumsq, spp):

@@ -99,7 +99,8 @@ class GeometryUpdate(C.Structure):
 
 
 # the symbols include/trt.h declares (checked by tests/test_abi.py)
-HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_aov",
+HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_rays", "trt_render_rays_device",
+               "trt_camera_rays", "trt_camera_rays_device", "trt_render_aov",
                "trt_render_aov_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
                "trt_trace_occluded_device", "trt_denoise", "trt_denoise_device",
                "trt_update_geometry", "trt_update_geometry_device", "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
@@ -215,6 +216,14 @@ def load_hip():
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
     lib.trt_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_int32, C.c_int32,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.trt_render_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
+    lib.trt_render_rays_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.trt_camera_rays.argtypes = [C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.POINTER(C.c_uint32), C.c_int32, C.c_int32,
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.trt_camera_rays_device.argtypes = [C.c_int, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
     lib.trt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Stats)]
     lib.trt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_trace_closest.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float),

@@ -832,7 +832,7 @@ struct PassSlot {
     uint32_t seq = 0;                 // last sequence number asked for
     uint32_t* spill = nullptr;
     RedoList redo{nullptr, nullptr};  // rays the traversal kernels hand to k_trace_fix (trt_kernels.h)
-    enum State { IDLE, ISSUE, WAIT, RESOLVE } state = IDLE;
+    enum State { IDLE, PACK, PACKWAIT, ISSUE, WAIT, RESOLVE } state = IDLE;  // PACK / PACKWAIT: trt_render_rays only (the caller's rays into the queue)
     uint32_t chunk = 0, s0 = 0, sc_count = 0, n_active = 0, b = 0;
     int cur = 0;
 };
@@ -912,8 +912,12 @@ struct Layout {
 // What one render call traces, and where its per-pixel sums come from and go.  A tile (trt_render*): its selected rows; the sums are the
 // caller's host accumulator (in/out) or, without one, start at zero and are dropped; out_dev receives them rounded to float.  A pixel list
 // (trt_render_pixels*) of the whole image: pixels, sum and sumsq (may be null) are host arrays (`host`, staged) or device arrays used in place.
+// Caller-supplied rays (trt_render_rays*): a list whose entries are the stream ids (`pixels`; null = 0..npix-1, filled on the device) and whose
+// bounce-0 rays come from org / dir [samples of the call][npix][3] instead of the camera (host arrays are staged pass by pass).
 struct RenderInput {
-    bool list = false, host = true;
+    bool list = false, host = true, rays = false;
+    const float* org = nullptr;
+    const float* dir = nullptr;
     std::vector<int32_t> rows;
     const uint32_t* pixels = nullptr;
     uint32_t npix = 0;
@@ -1040,13 +1044,14 @@ int planArena(trt_handle* h, const trt_params* p, uint32_t npix, uint32_t n_samp
 int stageInput(const RenderInput& in, const trt_params* p, void* d_table, size_t table_bytes, double* d_sum, double* d_sq, uint32_t* d_list_max, hipStream_t stream)
 {
     const size_t acc_bytes = (size_t)in.npix * 3 * sizeof(double);
+    if (in.rays && !in.pixels) hipLaunchKernelGGL(k_iota, dim3(std::min<uint32_t>((in.npix + 255) / 256, 1024u)), dim3(256), 0, stream, (uint32_t*)d_table, in.npix);
+    else if (in.host) HIPC(hipMemcpyAsync(d_table, in.list ? (const void*)in.pixels : (const void*)in.rows.data(), table_bytes, hipMemcpyHostToDevice, stream));
     if (in.host) {
-        HIPC(hipMemcpyAsync(d_table, in.list ? (const void*)in.pixels : (const void*)in.rows.data(), table_bytes, hipMemcpyHostToDevice, stream));
         if (in.sum) HIPC(hipMemcpyAsync(d_sum, in.sum, acc_bytes, hipMemcpyHostToDevice, stream));
         else HIPC(hipMemsetAsync(d_sum, 0, acc_bytes, stream));
         if (d_sq) HIPC(hipMemcpyAsync(d_sq, in.sumsq, acc_bytes, hipMemcpyHostToDevice, stream));
     }
-    if (!in.list) return TRT_OK;
+    if (!in.list || in.rays) return TRT_OK;  // stream ids are any 32 bits
     uint32_t list_max = 0;
     hipLaunchKernelGGL(k_list_max, dim3(std::min<uint32_t>((in.npix + 255) / 256, 1024u)), dim3(256), 0, stream, in.host ? (const uint32_t*)d_table : in.pixels, in.npix, d_list_max);
     HIPC(hipMemcpyAsync(&list_max, d_list_max, sizeof(list_max), hipMemcpyDeviceToHost, stream));
@@ -1065,15 +1070,17 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     // ---- small_buf: the row table or the staged pixel list, the counters of each slot, the block cleared first (DeviceStats; per slot the
     // length of its redo list and the blocks of k_trace_fix that are through; the list's maximum), the staged sums and sums of squares
     const size_t counts_bytes = (size_t)COUNT_STRIDE * count_rows * sizeof(uint32_t), acc_bytes = (size_t)npix * 3 * sizeof(double);
-    const size_t table_bytes = !in.host ? 0 : (in.list ? (size_t)npix * sizeof(uint32_t) : in.rows.size() * sizeof(int32_t));
+    const bool own_table = in.host || (in.rays && !in.pixels);  // the table is staged, or (rays without stream ids) filled here
+    const size_t table_bytes = !own_table ? 0 : (in.list ? (size_t)npix * sizeof(uint32_t) : in.rows.size() * sizeof(int32_t));
     Layout L;
     const size_t o_table = L.add(table_bytes, 256), o_counts = L.add(counts_bytes * N_SLOTS, 256);
     const size_t o_stats = L.add(sizeof(DeviceStats), 256), o_redo = L.add(2 * N_SLOTS * sizeof(uint32_t), 64), o_list_max = L.add(sizeof(uint32_t), 64);
+    const size_t o_pack = L.add(N_SLOTS * sizeof(unsigned long long), 64);  // per slot: the rays k_rays_pack queued (low word; read as k_shade's pair word)
     const size_t o_sum = L.add(in.host ? acc_bytes : 0, 256), o_sumsq = L.add(in.host && in.sumsq ? acc_bytes : 0, sizeof(double));
     if (int e = h->small_buf.ensure(L.bytes)) return e;
     char* sb = (char*)h->small_buf.p;
     DeviceStats* d_stats = (DeviceStats*)(sb + o_stats);
-    const void* d_table = in.host ? (const void*)(sb + o_table) : (const void*)in.pixels;
+    const void* d_table = own_table ? (const void*)(sb + o_table) : (const void*)in.pixels;
     double* d_sum = in.host ? (double*)(sb + o_sum) : in.sum;
     double* d_sq = !in.sumsq ? nullptr : (in.host ? (double*)(sb + o_sumsq) : in.sumsq);
     HIPC(hipMemsetAsync(d_stats, 0, o_sum - o_stats, stream));
@@ -1105,7 +1112,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const ShadeArgs shade_args = shadeArgsOf(h, p, in, d_table, rows_lds, d_stats);
     const TileDesc& td = shade_args.td;
     if (h->dbg)
-        std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.list ? "trt_render_pixels" : "trt_render",
+        std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"),
                      lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds, td.grid_ok);
 
     Timer tm{h, (p->flags & TRT_FLAG_TIMING) != 0};
@@ -1128,15 +1135,50 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         S.b = 0;
         S.cur = 0;
         HIPC(hipMemsetAsync(S.d_counts, 0, counts_bytes, S.stream));
-        st.rays_camera += S.n_active;  // bounce 0 generates its camera rays inside the traversal and shade kernels
-        S.state = PassSlot::ISSUE;
+        if (!in.rays) st.rays_camera += S.n_active;  // bounce 0 generates its camera rays inside the traversal and shade kernels
+        S.state = in.rays ? PassSlot::PACK : PassSlot::ISSUE;
+        return TRT_OK;
+    };
+    // trt_render_rays: the pass's slice of the caller's arrays -> the slot's queue (k_rays_pack), then the number of valid rays on its way to
+    // the host.  Host arrays are staged in the slot's OTHER queue, which nothing uses before bounce 0's k_shade writes it: Q[1].ra / rb / bt
+    // are carved one behind the other (SlotLayout), 48 bytes per path for the 24 a ray takes.
+    auto issuePack = [&](PassSlot& S) -> int {
+        const size_t at = (size_t)(S.s0 - s_begin) * npix * 3, comps = (size_t)S.n_active * 3;
+        const float* org = in.org + at;
+        const float* dir = in.dir + at;
+        if (in.host) {
+            float* stage = (float*)S.Q[1].ra;
+            HIPC(hipMemcpyAsync(stage, org, comps * sizeof(float), hipMemcpyHostToDevice, S.stream));
+            HIPC(hipMemcpyAsync(stage + comps, dir, comps * sizeof(float), hipMemcpyHostToDevice, S.stream));
+            org = stage;
+            dir = stage + comps;
+        }
+        unsigned long long* packed = (unsigned long long*)(sb + o_pack) + (&S - slots);
+        HIPC(hipMemsetAsync(packed, 0, sizeof(*packed), S.stream));
+        tm.launch(TRT_K_GEN_PRIMARY, S.stream, st, [&] {
+            hipLaunchKernelGGL(k_rays_pack, dim3(std::min<uint32_t>((S.n_active + 255) / 256, 65536u)), dim3(256), 0, S.stream, org, dir, S.n_active, S.Q[0], S.Lacc,
+                               (uint32_t*)packed);
+        });
+        S.seq++;
+        hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(64), 0, S.stream, S.d_counts, COUNT_STRIDE, 0u, 1u, packed, (volatile uint32_t*)S.host_counts, 2u * count_rows, S.seq);
+        S.state = PassSlot::PACKWAIT;
+        return TRT_OK;
+    };
+    auto completePack = [&](PassSlot& S) -> int {
+        if (int e = awaitCounts(S, count_rows)) return e;
+        const uint32_t n_valid = S.host_counts[1];
+        if (n_valid > S.n_active) return fail(TRT_EHIP, "internal error: more rays queued than given");
+        st.rays_camera += n_valid;
+        S.n_active = n_valid;
+        S.state = n_valid ? PassSlot::ISSUE : PassSlot::RESOLVE;  // no valid entry: the zeroed Lacc is all there is to resolve
         return TRT_OK;
     };
     // trace + shade of the slot's current bounce, then the queue lengths on their way to the host
     auto issueFront = [&](PassSlot& S) -> int {
         const RaySource src{S.Q[S.cur].ra, S.Q[S.cur].rb, td, S.s0};
         tm.launch(TRT_K_TRACE_CLOSEST, S.stream, st, [&] {
-            launchTraceClosest(h, S.b == 0 ? camera_k : queue_k, S.b == 0 ? camera_fix : queue_fix, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
+            const bool generated = S.b == 0 && !in.rays;  // the rays of bounce 0 come from the camera, not from the queue
+            launchTraceClosest(h, generated ? camera_k : queue_k, generated ? camera_fix : queue_fix, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
         });
         ShadeArgs A = shade_args;
         A.qin = S.Q[S.cur];
@@ -1150,7 +1192,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         A.shadow_counts = S.d_counts + (size_t)COUNT_STRIDE + S.b;  // light l: + l * COUNT_STRIDE
         A.Lacc = S.Lacc;
         A.s0 = S.s0;
-        A.primary = S.b == 0 ? 1u : 0u;
+        A.primary = (S.b == 0 && !in.rays) ? 1u : 0u;
         tm.launch(TRT_K_SHADE, S.stream, st, [&] {
             hipLaunchKernelGGL(shade_k, dim3(std::min<uint32_t>((S.n_active + shade_block - 1) / shade_block, 65536u)), dim3(shade_block), h->shade_pad_lds, S.stream, h->sc, A);
         });
@@ -1211,6 +1253,10 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         if (int e = startPass(slots[k])) return e;
     for (;;) {
         bool any = false;
+        for (int k = 0; k < plan.slots; ++k)
+            if (slots[k].state == PassSlot::PACK) { if (int e = issuePack(slots[k])) return e; }
+        for (int k = 0; k < plan.slots; ++k)
+            if (slots[k].state == PassSlot::PACKWAIT) { if (int e = completePack(slots[k])) return e; }
         for (int k = 0; k < plan.slots; ++k)
             if (slots[k].state == PassSlot::ISSUE) { if (int e = issueFront(slots[k])) return e; }
         for (int k = 0; k < plan.slots; ++k) {
@@ -1447,6 +1493,119 @@ int trt_render_pixels_device(trt_handle* h, const trt_params* p, uint32_t n_pixe
                              double* sum_dev, double* sumsq_dev, void* hip_stream, trt_stats* stats)
 {
     return renderPixels(h, p, n_pixels, pixels_dev, sample_begin, sample_end, sum_dev, sumsq_dev, hip_stream, stats, false);
+}
+
+namespace {
+// trt_render_rays / _device: the checks of include/trt.h, then the render loop on the list of stream ids with the caller's rays as bounce 0.
+// width, height, the tile fields and TRT_FLAG_FIXED_PIXELS of p have no meaning here: the loop gets a 2 x 2 image that is never looked at.
+int renderRays(trt_handle* h, const trt_params* p_in, uint32_t n, const float* org, const float* dir, const uint32_t* stream_ids, int32_t sample_begin,
+               int32_t sample_end, double* sum, double* sumsq, void* hip_stream, trt_stats* stats, bool host)
+{
+    if (!h || !p_in) return fail(TRT_EINVAL, "null handle/params");
+    if (p_in->spp < 1) return fail(TRT_EINVAL, "spp must be >= 1");
+    if (p_in->max_depth < 0) return fail(TRT_EINVAL, "max_depth must be >= 0");
+    if (sample_begin < 0 || sample_begin > sample_end) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin <= end");
+    if (n > 0 && (!org || !dir || !sum)) return fail(TRT_EINVAL, "null ray arrays or sums");
+    if (n > MAX_PASS_PATHS) return fail(TRT_EINVAL, "more rays per sample than the path ids of one pass can number (0x7FFF0000)");
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (n == 0 || sample_begin == sample_end) return TRT_OK;
+    trt_params p = *p_in;
+    p.width = p.height = 2;
+    p.x0 = 0; p.y0 = 0; p.x1 = p.width; p.y1 = p.height;
+    p.row_block = 1; p.row_mod = 1; p.row_rem = 0;
+    HIPC(hipSetDevice(h->device));
+    RenderInput in;
+    in.list = true;
+    in.rays = true;
+    in.host = host;
+    in.org = org;
+    in.dir = dir;
+    in.pixels = stream_ids;
+    in.npix = n;
+    in.tile_w = p.width;
+    in.sum = sum;
+    in.sumsq = sumsq;
+    return renderCore(h, &p, (uint32_t)sample_begin, (uint32_t)sample_end, in, (hipStream_t)hip_stream, stats);
+}
+
+// What trt_camera_rays* takes of p, checked; the grid reciprocals as shadeArgsOf forms them
+int cameraRaysArgs(const trt_camera* cam, const trt_params* p, uint32_t n_pixels, const void* pixels, int32_t sample_begin, int32_t sample_end, const void* org,
+                   const void* dir, CameraRaysArgs& A)
+{
+    if (!cam || !p) return fail(TRT_EINVAL, "null camera/params");
+    if (p->width < 1 || p->height < 1) return fail(TRT_EINVAL, "width and height must be >= 1");
+    if ((uint64_t)p->width * (uint64_t)p->height > 0x100000000ull) return fail(TRT_EINVAL, "image too large (pixels are 32-bit indices)");
+    if (sample_begin < 0 || sample_begin > sample_end) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin <= end");
+    if (n_pixels > 0 && (!pixels || !org || !dir)) return fail(TRT_EINVAL, "null pixel list or ray arrays");
+    A.cam = *cam;
+    A.width = p->width;
+    A.height = p->height;
+    A.seed = p->seed;
+    A.fixed_pixels = (p->flags & TRT_FLAG_FIXED_PIXELS) ? 1u : 0u;
+    A.grid_ok = (p->width >= 2 && p->height >= 2 && p->width <= 65536 && p->height <= 65536) ? 1u : 0u;
+    A.grid_rcp[0] = 1.0 / double(p->width - 1.0);
+    A.grid_rcp[1] = 1.0 / double(p->height - 1.0);
+    A.grid_rcp[2] = 1.0 / double(p->width);
+    A.grid_rcp[3] = 1.0 / double(p->height);
+    return TRT_OK;
+}
+}  // namespace
+
+int trt_render_rays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, const float* dir, const uint32_t* stream, int32_t sample_begin,
+                    int32_t sample_end, double* sum_host, double* sumsq_host, trt_stats* stats)
+{
+    return renderRays(h, p, n, org, dir, stream, sample_begin, sample_end, sum_host, sumsq_host, nullptr, stats, true);
+}
+
+int trt_render_rays_device(trt_handle* h, const trt_params* p, uint32_t n, const float* org_dev, const float* dir_dev, const uint32_t* stream_dev,
+                           int32_t sample_begin, int32_t sample_end, double* sum_dev, double* sumsq_dev, void* hip_stream, trt_stats* stats)
+{
+    return renderRays(h, p, n, org_dev, dir_dev, stream_dev, sample_begin, sample_end, sum_dev, sumsq_dev, hip_stream, stats, false);
+}
+
+int trt_camera_rays(const trt_camera* cam, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels, int32_t sample_begin, int32_t sample_end,
+                    float* org_host, float* dir_host)
+{
+    CameraRaysArgs A;
+    if (int e = cameraRaysArgs(cam, p, n_pixels, pixels, sample_begin, sample_end, org_host, dir_host, A)) return e;
+    const uint64_t n_image = (uint64_t)p->width * (uint64_t)p->height;
+    for (uint32_t i = 0; i < n_pixels; ++i)
+        if (pixels[i] >= n_image) return fail(TRT_EINVAL, "pixel list holds an entry >= width * height");
+    for (int32_t s = sample_begin; s < sample_end; ++s)
+        for (uint32_t i = 0; i < n_pixels; ++i) {
+            f3 o, d;
+            cameraRayOf(A.cam, A.width, A.height, A.seed, pixels[i], (uint32_t)s, A.fixed_pixels != 0u, A.grid_ok ? A.grid_rcp : nullptr, o, d);
+            const size_t at = ((size_t)(s - sample_begin) * n_pixels + i) * 3;
+            org_host[at] = o.x; org_host[at + 1] = o.y; org_host[at + 2] = o.z;
+            dir_host[at] = d.x; dir_host[at + 1] = d.y; dir_host[at + 2] = d.z;
+        }
+    return TRT_OK;
+}
+
+int trt_camera_rays_device(int device, const trt_camera* cam, const trt_params* p, uint32_t n_pixels, const uint32_t* pixels_dev, int32_t sample_begin,
+                           int32_t sample_end, float* org_dev, float* dir_dev, void* hip_stream)
+{
+    CameraRaysArgs A;
+    if (int e = cameraRaysArgs(cam, p, n_pixels, pixels_dev, sample_begin, sample_end, org_dev, dir_dev, A)) return e;
+    if (n_pixels == 0 || sample_begin == sample_end) return TRT_OK;
+    if (int e = useDevice(device)) return e;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    uint32_t* d_bad = nullptr;
+    HIPC(hipMalloc((void**)&d_bad, sizeof(uint32_t)));
+    const uint32_t n_samples = (uint32_t)(sample_end - sample_begin);
+    uint32_t bad = 0;
+    hipError_t err = hipMemsetAsync(d_bad, 0, sizeof(uint32_t), stream);
+    if (err == hipSuccess) {
+        const dim3 grid(std::min<uint32_t>((n_pixels + 255) / 256, 8192u), std::min<uint32_t>(n_samples, 64u));
+        hipLaunchKernelGGL(k_camera_rays, grid, dim3(256), 0, stream, A, pixels_dev, n_pixels, (uint32_t)sample_begin, n_samples, org_dev, dir_dev, d_bad);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess) err = hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);
+    (void)hipFree(d_bad);
+    if (err != hipSuccess) return fail(TRT_EHIP, std::string("trt_camera_rays_device: ") + hipGetErrorString(err));
+    if (bad) return fail(TRT_EINVAL, "pixel list holds an entry >= width * height");
+    return TRT_OK;
 }
 
 int trt_render(trt_handle* h, const trt_params* p, float* out_host, trt_stats* stats)

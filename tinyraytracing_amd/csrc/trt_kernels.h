@@ -1855,4 +1855,82 @@ __global__ __launch_bounds__(256) void k_pack_rays_bounded(const float* __restri
     }
 }
 
+// ---- caller-supplied rays (trt_render_rays, include/trt.h) ----
+// One pass's slice of the caller's arrays (org / dir [n][3], entry i = path i of the pass) becomes the queue bounce 0 reads: the record
+// rayRecord() writes, throughput (1, 1, 1), and a zeroed Lacc for EVERY path of the pass — k_shade with primary = 0 adds onto Lacc, and a path
+// whose entry is invalid (rayValid) is never queued.  Valid entries are compacted as k_shade compacts its rays: ballot / popcount ranks, wave
+// totals through LDS, one atomic per block on *count (zeroed before the launch), so the queue holds *count rays and `pid` keeps addressing Lacc.
+// Streaming: the 12-byte components are read as three dwords each, the records stored as k_shade stores them (TRT_NT bit 2).
+__global__ __launch_bounds__(256) void k_rays_pack(const float* __restrict__ org, const float* __restrict__ dir, uint32_t n, RayQueue q, f4* __restrict__ Lacc,
+                                                   uint32_t* __restrict__ count)
+{
+    constexpr uint32_t NW = 256 / 64;
+    __shared__ uint32_t s_w[NW + 1];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t per_grid = gridDim.x * 256u;  // <= 2^24; n <= 0x7FFF0000: base never wraps
+    for (uint32_t base = blockIdx.x * 256u; base < n; base += per_grid) {  // uniform trip count per block: every thread reaches every barrier
+        const uint32_t i = base + threadIdx.x;
+        f3 o = mk3(0, 0, 0), d = o;
+        bool ok = false;
+        if (i < n) {
+            o = ld3(org + (size_t)i * 3);
+            d = ld3(dir + (size_t)i * 3);
+            ok = rayValid(o, d);
+            Lacc[i] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        const unsigned long long ballot = ballotb(ok);
+        const uint32_t rank = (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+        if (lane == 0) s_w[wave] = (uint32_t)__popcll(ballot);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t tot = 0;
+            for (uint32_t w = 0; w < NW; ++w) { const uint32_t c = s_w[w]; s_w[w] = tot; tot += c; }
+            s_w[NW] = tot ? atomicAdd(count, tot) : 0u;
+        }
+        __syncthreads();
+        if (ok) {
+            const uint32_t slot = s_w[NW] + s_w[wave] + rank;  // < *count <= n
+            f4 ra, rb;
+            rayRecord(o, d, i, ra, rb);
+            TRT_STQ(2, q.ra + slot, ra);
+            TRT_STQ(2, q.rb + slot, rb);
+            TRT_STQ(2, q.bt + slot, mk4(1.0f, 1.0f, 1.0f, 0.0f));
+        }
+        __syncthreads();  // s_w is rewritten by the next tile
+    }
+}
+// its sibling: the stream ids 0..n-1 of a call that gives none (the "pixel list" pathKey(..., PixelList) keys the random streams by)
+__global__ __launch_bounds__(256) void k_iota(uint32_t* __restrict__ list, uint32_t n)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) list[i] = i;
+}
+
+// trt_camera_rays_device: the rays trt_render traces for the listed pixels, samples [s_begin, s_begin + n_samples), of the camera in the
+// arguments, as plain arrays org / dir [n_samples][n][3] (cameraRayOf: what cameraRecord forms).  blockIdx.y strides the samples, x the
+// list; the array index (s * n + i) * 3 is formed in 64 bits.  A pixel >= width * height sets *bad and writes nothing.
+struct CameraRaysArgs {
+    trt_camera cam;
+    int32_t width, height;
+    uint32_t seed, fixed_pixels, grid_ok;
+    double grid_rcp[4];  // TileDesc::grid_rcp
+};
+__global__ __launch_bounds__(256) void k_camera_rays(CameraRaysArgs A, const uint32_t* __restrict__ pixels, uint32_t n, uint32_t s_begin, uint32_t n_samples,
+                                                     float* __restrict__ org, float* __restrict__ dir, uint32_t* __restrict__ bad)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const unsigned long long n_image = (unsigned long long)(uint32_t)A.width * (uint32_t)A.height;
+    for (uint32_t s = blockIdx.y; s < n_samples; s += gridDim.y) {
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+            const uint32_t q = pixels[i];
+            if (q >= n_image) { *bad = 1u; continue; }
+            f3 o, d;
+            cameraRayOf(A.cam, A.width, A.height, A.seed, q, s_begin + s, A.fixed_pixels != 0u, A.grid_ok ? A.grid_rcp : nullptr, o, d);
+            const size_t at = ((size_t)s * n + i) * 3;
+            org[at] = o.x; org[at + 1] = o.y; org[at + 2] = o.z;
+            dir[at] = d.x; dir[at + 1] = d.y; dir[at + 2] = d.z;
+        }
+    }
+}
+
 }  // namespace trtd

@@ -959,6 +959,36 @@ TRT_HD inline void primaryRay(const SceneDev& sc, const TileDesc& td, uint32_t s
     cameraRecord(sc, td, (int)y, (int)(q - y * (uint32_t)td.tile_w), s0 + s_local, pid, ra, rb);
 }
 
+// ---- caller-supplied rays (trt_render_rays, include/trt.h) ----
+// The queue record of a ray the caller chose, as path `pid`'s bounce-0 ray: what cameraRecord writes for a camera ray — type camera (a light
+// hit directly is kept), depth 0, and the next draw of the path's stream is draw 2: draws 0 and 1 belong to whoever generated the ray (the
+// built-in camera spends them on its jitter).
+#define TRT_RAYS_FIRST_DRAW 2u
+TRT_HD inline void rayRecord(f3 o, f3 d, uint32_t pid, f4& ra, f4& rb)
+{
+    ra = mk4(o.x, o.y, o.z, d.x);
+    rb = mk4(d.y, d.z, u2f(pid), u2f(packMeta(TRT_RAYS_FIRST_DRAW, TRT_META_CAMERA, 0)));
+}
+// An entry of trt_render_rays is traced iff all six components are finite and the direction is not (0, 0, 0); a single zero component and
+// denormals are fine.  (Finite <=> the exponent field is not all ones: no floating-point compare, so no flag or mode can bend it.)
+TRT_HD inline bool rayValid(f3 o, f3 d)
+{
+    const uint32_t e = 0x7F800000u;
+    const bool finite = (f2u(o.x) & e) != e && (f2u(o.y) & e) != e && (f2u(o.z) & e) != e && (f2u(d.x) & e) != e && (f2u(d.y) & e) != e && (f2u(d.z) & e) != e;
+    return finite && (((f2u(d.x) | f2u(d.y) | f2u(d.z)) & 0x7FFFFFFFu) != 0u);
+}
+// The ray cameraRecord forms for (pixel q = y * width + x, sample) — the same stream, the same two jitter draws, the same cameraRay call — for
+// ANY camera, as plain vectors (trt_camera_rays: k_camera_rays on the device, the same function on the host).  `grid`: TileDesc::grid_rcp or null.
+TRT_HD inline void cameraRayOf(const trt_camera& cam, int W, int H, uint32_t seed, uint32_t q, uint32_t sample, bool fixed, const double* grid, f3& o, f3& d)
+{
+    const uint32_t y = q / (uint32_t)W, x = q - y * (uint32_t)W;
+    Stream rng;
+    rng.key = trt_rng_make_key(seed, q, sample);
+    rng.ctr = 0;
+    const float u1 = rng.next(), u2 = rng.next();  // jitter x, then y (main.cpp:92-93)
+    cameraRay(cam, W, H, (int)y, (int)x, u1, u2, o, d, fixed, grid);
+}
+
 struct ShadeCtx {
     bool had_hit;   // the traced ray hit something
     bool shade_ok;  // ... a non-emissive surface: NEE + continuation follow
