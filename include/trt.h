@@ -187,7 +187,7 @@ typedef struct trt_params {
 
 #define TRT_MAX_KERNELS 8
 enum {
-    TRT_K_GEN_PRIMARY = 0,  /* trt_render_rays*: the kernel that queues the caller's rays; 0 launches everywhere else (the camera's rays are generated inside bounce 0) */
+    TRT_K_GEN_PRIMARY = 0,  /* trt_render_rays*, trt_aov_rays*: the kernel that queues the caller's rays; 0 launches everywhere else (the camera's rays are generated inside bounce 0) */
     TRT_K_TRACE_CLOSEST = 1,
     TRT_K_SHADE = 2,
     TRT_K_TRACE_SHADOW = 3,
@@ -352,6 +352,47 @@ int trt_render_aov(trt_handle* h, const trt_params* p, float* albedo_host, float
  * after the stream has been synchronised. */
 int trt_render_aov_device(trt_handle* h, const trt_params* p, float* albedo_dev, float* normal_dev, float* depth_dev,
                           void* hip_stream, trt_stats* stats);
+
+/* ---- first-hit feature buffers along rays the caller chose ---------------------------------------------------------------------
+ * trt_aov_rays is trt_render_aov with the built-in ray generator replaced by the caller's arrays, as trt_render_rays is to trt_render_pixels:
+ * the albedo, normal and depth of a camera that moves while the handle stays resident, of a thin lens, a fisheye, or of probe rays.  The
+ * handle keeps no state of it.
+ *   Rays.  Exactly trt_render_rays' arrays: org / dir [n_samples][n][3] floats, sample-major, n_samples = sample_end - sample_begin; the ray of
+ *   (entry i, sample s) sits at index (s - sample_begin) * n + i.  There are no stream ids: a first hit draws nothing.
+ *   Per ray.  The closest hit (t, tri, u, v) as trt_trace_closest defines it (the same leaf-box rule, the same tie rules, bound TRT_INF), then
+ *   the features as trt_render_aov defines them: a hit, on any material, gives albedo = the texel or Kd, normal = the normalised interpolated
+ *   vertex normal, depth = t — in units of the direction's length: directions are used as given; a miss gives (0, 0, 0), (0, 0, 0), TRT_INF.
+ *   Invalid entries.  An entry whose six components are not all finite, or whose direction is (0, 0, 0) (trt_render_rays' rule), counts as a
+ *   MISS for that sample, is not counted in stats.rays_camera and never disturbs another entry.  It is not traced as given: a fixed finite
+ *   ray takes its place in the queue and its record is marked, so no result depends on what a walk does with a NaN.  A single zero
+ *   component and denormals are valid.
+ *   Sums.  albedo_sum[3n], normal_sum[3n], depth_sum[n] doubles, in/out: per channel v = value / (float)p->spp (a float division), and
+ *   sum += (double)v in increasing s.  Nothing is zeroed and nothing is rounded to float.  Any of the three may be NULL, not all three.
+ *   sample_end may exceed p->spp (p->spp only scales v).
+ *   The built-in camera.  With the rays of trt_camera_rays(the handle's camera, p, the pixels of a tile in tile order, 0, p->spp) and sums
+ *   that start at zero, (float)sum is trt_render_aov's output for that tile, bit for bit — and with another trt_camera it is what a handle
+ *   created with THAT camera would return.
+ *   Parameters.  spp (the scale), mem_budget, TRT_FLAG_TIMING and TRT_FLAG_COUNT are honoured; width, height, the tile fields, seed,
+ *   max_depth and every other flag are ignored.  mem_budget counts this call's path state, TRT_AOV_RAYS_BYTES_PER_PATH = 52 bytes per path
+ *   and sample in a pass (a 32-byte packed ray, a 16-byte hit record, a 4-byte entry of the redo list); 0 = three quarters of what is free;
+ *   TRT_ENOMEM when one sample of every entry does not fit.  The host entry stages the rays pass by pass, never all at once (24 bytes per
+ *   path of a pass, beside the budget) and keeps a device copy of the given sums for the call.
+ *   TRT_EINVAL, checked on the host before anything is written, the handle stays usable: a null handle or p; a null org or dir while n > 0;
+ *   all three sums null; n > 0x7FFF0000; sample_begin < 0 or > sample_end; p->spp < 1.  Otherwise n == 0 or an empty sample range: nothing
+ *   to do, TRT_OK.
+ *   stats: rays_camera = the valid entries traced; the packing under TRT_K_GEN_PRIMARY, the traversal under TRT_K_TRACE_CLOSEST, the
+ *   accumulation under TRT_K_RESOLVE, one launch of each per pass; passes, redo_rays and the TRT_FLAG_COUNT counters as for trt_render_aov
+ *   (a placeholder ray is walked and counted like any ray that misses the root); rows_rendered = 0.
+ *   Cost.  Every ray goes through HBM three times here (24 bytes read and a 32-byte record written by the packing, the record read by the
+ *   traversal) where trt_render_aov forms its rays in registers.  Not yet measured on a GPU against trt_render_aov_device
+ *   (tools/aov_rays_cost.py measures it; profiles/aov_rays_cost.txt will hold the figures). */
+#define TRT_AOV_RAYS_BYTES_PER_PATH 52u
+int trt_aov_rays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, const float* dir, int32_t sample_begin, int32_t sample_end,
+                 double* albedo_sum_host, double* normal_sum_host, double* depth_sum_host, trt_stats* stats);
+/* The same with org, dir and the three sums in DEVICE memory of the handle's device (the sums are added onto in place), all work on hip_stream
+ * (NULL = default); returns after the stream has been synchronised. */
+int trt_aov_rays_device(trt_handle* h, const trt_params* p, uint32_t n, const float* org_dev, const float* dir_dev, int32_t sample_begin,
+                        int32_t sample_end, double* albedo_sum_dev, double* normal_sum_dev, double* depth_sum_dev, void* hip_stream, trt_stats* stats);
 
 /* traverseBVH (bvh.cpp:146-175) on a batch of n rays given as HOST arrays
  * org[n][3], dir[n][3].  Outputs (host): t[n] (TRT_INF on miss), tri[n]

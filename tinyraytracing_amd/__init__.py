@@ -14,7 +14,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _abi, adaptive
-from ._abi import Params, Stats, SceneFlat, Camera, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES, TRT_K_DENOISE, TRT_K_REFIT  # noqa: F401
+from ._abi import Params, Stats, SceneFlat, Camera, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, KERNEL_NAMES, TRT_K_DENOISE, TRT_K_REFIT, AOV_RAYS_BYTES_PER_PATH  # noqa: F401
 
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES_DIR = os.path.join(REPO_ROOT, "scenes")
@@ -638,6 +638,141 @@ class Renderer:
             image = image.cpu().numpy()
         return (image, total) if want_stats else image
 
+    def render_aov_rays(self, params, org, dir, sample_begin=0, sums=None, want_stats=False):
+        """First-hit feature sums along caller-supplied rays (trt_aov_rays, include/trt.h): org / dir are float32 [S, n, 3] — sample-major, the
+        rays of samples [sample_begin, sample_begin + S) of n entries ([n, 3] = one sample), as for render_rays.  Per ray the closest hit's
+        albedo (texel or Kd), shading normal and distance (a miss, or an entry with a NaN, an infinity or a zero direction: 0, 0, TRT_INF),
+        each divided by params.spp as a float and added as a double, in sample order, onto sums: a dict of contiguous float64 arrays
+        albedo [n, 3], normal [n, 3], depth [n] (None = all three from zeros; a key left out or None = not wanted, at least one given).
+        -> the dict of sums[, Stats]."""
+        org = np.ascontiguousarray(org, dtype=np.float32)
+        dir = np.ascontiguousarray(dir, dtype=np.float32)
+        if org.ndim == 2 and dir.ndim == 2:
+            org, dir = org[None], dir[None]
+        if org.ndim != 3 or org.shape[2] != 3 or dir.shape != org.shape:
+            raise TrtError("render_aov_rays: org and dir must both be float32 arrays of shape (S, n, 3)")
+        n_samples, n = org.shape[0], org.shape[1]
+        shapes = {"albedo": (n, 3), "normal": (n, 3), "depth": (n,)}
+        if sums is None:
+            sums = {k: np.zeros(shape, np.float64) for k, shape in shapes.items()}
+        if not isinstance(sums, dict) or any(k not in shapes for k in sums):
+            raise TrtError("render_aov_rays: sums must be a dict with the keys albedo, normal, depth")
+        out = {k: a for k, a in sums.items() if a is not None}
+        if not out:
+            raise TrtError("render_aov_rays: at least one of albedo, normal, depth is needed")
+        for k, a in out.items():
+            if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.shape != shapes[k] or not a.flags["C_CONTIGUOUS"]:
+                raise TrtError(f"render_aov_rays: {k} must be a contiguous float64 array of shape {shapes[k]}")
+        st = Stats()
+        fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
+        ptrs = [out[k].ctypes.data_as(dp) if k in out else None for k in ("albedo", "normal", "depth")]
+        rc = self._lib.trt_aov_rays(self._h, C.byref(params), n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp), int(sample_begin),
+                                    int(sample_begin) + n_samples, ptrs[0], ptrs[1], ptrs[2], C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_aov_rays failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return (out, st) if want_stats else out
+
+    def render_aov_rays_into(self, params, org, dir, albedo=None, normal=None, depth=None, sample_begin=0, stream_ptr=0):
+        """trt_aov_rays_device: org / dir (float32 [S, n, 3]) and the sums albedo, normal (float64 [n, 3]) and depth (float64 [n]; in/out, None =
+        not wanted, at least one given) are contiguous torch tensors on this device; the work runs on stream `stream_ptr` (0 = default).  -> Stats."""
+        if not _is_torch(org) or org.dim() != 3 or org.shape[2] != 3:
+            raise TrtError("render_aov_rays_into: org must be a float32 tensor of shape (S, n, 3)")
+        n_samples, n = int(org.shape[0]), int(org.shape[1])
+        if albedo is None and normal is None and depth is None:
+            raise TrtError("render_aov_rays_into: at least one of albedo, normal, depth is needed")
+        f32, f64 = ("torch.float32",), ("torch.float64",)
+        p = self._device_arrays("render_aov_rays_into", n, [("org", org, f32, 3 * n * n_samples), ("dir", dir, f32, 3 * n * n_samples),
+                                                            ("albedo", albedo, f64, 3 * n), ("normal", normal, f64, 3 * n), ("depth", depth, f64, n)])
+        if dir is None:
+            raise TrtError("render_aov_rays_into: dir is needed")
+        st = Stats()
+        rc = self._lib.trt_aov_rays_device(self._h, C.byref(params), n, p[0], p[1], int(sample_begin), int(sample_begin) + n_samples,
+                                           p[2], p[3], p[4], C.c_void_p(stream_ptr), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_aov_rays_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return st
+
+    def _camera_tile(self, params, what):
+        """The pixels of the tile of `params` in tile order as an int32 tensor on this device, and the tile's (rows, width)."""
+        import torch
+        ys = np.asarray(rows_selected(params), np.int64)
+        xs = np.arange(params.x0, params.x1, dtype=np.int64)
+        if ys.size == 0 or xs.size == 0:
+            raise TrtError(f"{what}: empty tile")
+        if params.width * params.height > 0x7FFFFFFF:
+            raise TrtError(f"{what}: needs width * height < 2^31 (int32 pixel tensors)")
+        dev = torch.device("cuda", self.device)
+        return torch.from_numpy((ys[:, None] * params.width + xs[None, :]).reshape(-1).astype(np.int32)).to(dev), (int(ys.size), int(xs.size))
+
+    def render_camera_aov(self, params, camera, samples_per_call=16, want_stats=False, on_device=False):
+        """The feature buffers of the tile of `params` as seen by `camera` — on THIS handle, whatever camera its scene was created with, as
+        render_camera gives the beauty: rays generated on the device (camera_rays_into) and traced on the device (render_aov_rays_into),
+        samples_per_call samples at a time, samples [0, params.spp) accumulated in order.  -> dict(albedo=float32 [rows, tile_w, 3],
+        normal=float32 [rows, tile_w, 3], depth=float32 [rows, tile_w]), bit-identical to Renderer(scene with that camera).render_aov(params)
+        [, Stats summed over the calls].  on_device: the buffers stay torch tensors on this device."""
+        import torch
+        pix, (rows, tw) = self._camera_tile(params, "render_camera_aov")
+        k = max(1, min(int(samples_per_call), params.spp))
+        dev = pix.device
+        n = pix.numel()
+        org = torch.empty((k, n, 3), dtype=torch.float32, device=dev)
+        dirs = torch.empty_like(org)
+        sums = {"albedo": torch.zeros((n, 3), dtype=torch.float64, device=dev), "normal": torch.zeros((n, 3), dtype=torch.float64, device=dev),
+                "depth": torch.zeros(n, dtype=torch.float64, device=dev)}
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        total = Stats()
+        for s0 in range(0, params.spp, k):
+            s1 = min(s0 + k, params.spp)
+            camera_rays_into(camera, params, pix, s0, s1, org[:s1 - s0], dirs[:s1 - s0], device=self.device, stream_ptr=stream)
+            _add_stats(total, self.render_aov_rays_into(params, org[:s1 - s0], dirs[:s1 - s0], sample_begin=s0, stream_ptr=stream, **sums))
+        out = {"albedo": sums["albedo"].to(torch.float32).reshape(rows, tw, 3), "normal": sums["normal"].to(torch.float32).reshape(rows, tw, 3),
+               "depth": sums["depth"].to(torch.float32).reshape(rows, tw)}
+        if not on_device:
+            out = {k_: v.cpu().numpy() for k_, v in out.items()}
+        return (out, total) if want_stats else out
+
+    def render_camera_denoised(self, params, camera, aov_spp=None, samples_per_call=16, iterations=5, sigma_normal=128, sigma_depth=1.0,
+                               sigma_luminance=4.0):
+        """render_denoised for the tile of `params` as seen by `camera`, on this handle: the same dict (color, variance, albedo, normal, depth,
+        denoised as float32 arrays, and stats) under the same rules (params.spp >= 2, no row interleave, aov_spp None = min(spp, 16)).  The
+        beauty and its moments come from render_rays_into on the camera's rays, the variance from mean_luminance_variance's operations on the
+        device, the features from render_camera_aov, the filter is denoise_into: nothing but stats crosses to the host until the final copy.
+        With the handle's own camera the dict is render_denoised(params)'s, bit for bit."""
+        import torch
+        if params.spp < 2:
+            raise TrtError("render_camera_denoised: spp must be >= 2 (the variance needs two samples)")
+        if params.row_mod > 1:
+            raise TrtError("render_camera_denoised: the tile must not interleave rows (it is filtered as one image)")
+        pix, (rows, tw) = self._camera_tile(params, "render_camera_denoised")
+        k = max(1, min(int(samples_per_call), params.spp))
+        dev = pix.device
+        n = pix.numel()
+        org = torch.empty((k, n, 3), dtype=torch.float32, device=dev)
+        dirs = torch.empty_like(org)
+        sums = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        sumsq = torch.zeros_like(sums)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        total = Stats()
+        for s0 in range(0, params.spp, k):
+            s1 = min(s0 + k, params.spp)
+            camera_rays_into(camera, params, pix, s0, s1, org[:s1 - s0], dirs[:s1 - s0], device=self.device, stream_ptr=stream)
+            _add_stats(total, self.render_rays_into(params, org[:s1 - s0], dirs[:s1 - s0], sums, sumsq, streams=pix, sample_begin=s0, stream_ptr=stream))
+        del org, dirs
+        pa = make_params(params.width, params.height, min(params.spp, 16) if aov_spp is None else aov_spp, params.seed,
+                         tile=(params.x0, params.y0, params.x1, params.y1), max_depth=params.max_depth, flags=params.flags, mem_budget=params.mem_budget)
+        aov, st = self.render_camera_aov(pa, camera, samples_per_call=samples_per_call, want_stats=True, on_device=True)
+        _add_stats(total, st)
+        color = sums.to(torch.float32).reshape(rows, tw, 3)
+        variance = mean_luminance_variance(sums, sumsq, params.spp).reshape(rows, tw)
+        denoised = torch.empty_like(color)
+        _add_stats(total, denoise_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], denoised, iterations=iterations,
+                                       sigma_normal=sigma_normal, sigma_depth=sigma_depth, sigma_luminance=sigma_luminance, stream_ptr=stream))
+        out = {"color": color, "variance": variance, "denoised": denoised}
+        out.update(aov)
+        out = {k_: v.cpu().numpy() for k_, v in out.items()}
+        out["stats"] = total
+        return out
+
     def _light_tables(self, upd, lights_from):
         if lights_from is None:
             return
@@ -821,10 +956,17 @@ def mean_luminance_variance(sums, sumsq, spp):
     sample variance of the radiance divided by spp, no covariances, weighted by LUMA^2.  sums / sumsq: float64 [n, 3] of v = L / spp and
     v * v.  -> float32 [n].  The CLI's --denoise computes it with the same float64 operations in the same order (host/render.cpp)."""
     n = float(spp)
+    L = adaptive.LUMA
+    if _is_torch(sums):  # float64 tensors: the same operations in the same order on their device -> a float32 tensor there
+        import torch
+        n_t = torch.full((), n, dtype=sums.dtype, device=sums.device)  # a tensor: torch divides by a Python number through its reciprocal
+        m = sums / n_t
+        vv = (sumsq / n_t - m * m) * (n / (n - 1.0))
+        vm = torch.where(vv > 0.0, vv, torch.zeros_like(vv)) * n
+        return ((L[0] * L[0]) * vm[:, 0] + (L[1] * L[1]) * vm[:, 1] + (L[2] * L[2]) * vm[:, 2]).to(torch.float32)
     m = sums / n
     vv = (sumsq / n - m * m) * (n / (n - 1.0))
     vm = np.where(vv > 0.0, vv, 0.0) * n
-    L = adaptive.LUMA
     return ((L[0] * L[0]) * vm[:, 0] + (L[1] * L[1]) * vm[:, 1] + (L[2] * L[2]) * vm[:, 2]).astype(np.float32)
 
 

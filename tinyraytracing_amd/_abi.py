@@ -20,6 +20,8 @@ TRT_FLAG_FIXED_PIXELS = 16
 TRT_FLAG_RAY_OFFSET = 32
 TRT_FLAG_SPECULAR_KS = 64
 TRT_MAX_KERNELS = 8
+# trt_aov_rays: bytes of mem_budget per path and sample in a pass (include/trt.h TRT_AOV_RAYS_BYTES_PER_PATH)
+AOV_RAYS_BYTES_PER_PATH = 52
 KERNEL_NAMES = ["gen_primary", "trace_closest", "shade", "trace_shadow", "resolve", "tail"]
 # trt_denoise*'s slot of Stats.launches / kernel_ms: not in KERNEL_NAMES, whose last entry is the render's own last kernel
 TRT_K_DENOISE = 6
@@ -101,7 +103,7 @@ class GeometryUpdate(C.Structure):
 # the symbols include/trt.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_rays", "trt_render_rays_device",
                "trt_camera_rays", "trt_camera_rays_device", "trt_render_aov",
-               "trt_render_aov_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
+               "trt_render_aov_device", "trt_aov_rays", "trt_aov_rays_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
                "trt_trace_occluded_device", "trt_denoise", "trt_denoise_device",
                "trt_update_geometry", "trt_update_geometry_device", "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
@@ -226,6 +228,10 @@ def load_hip():
                                            C.c_void_p, C.c_void_p, C.c_void_p]
     lib.trt_render_aov.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(Stats)]
     lib.trt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.trt_aov_rays.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32,
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
+    lib.trt_aov_rays_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_trace_closest.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                       C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(Stats)]
     lib.trt_trace_closest_range.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),

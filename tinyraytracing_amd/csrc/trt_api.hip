@@ -868,6 +868,21 @@ struct AovLayout {
     }
 };
 
+// A trt_aov_rays pass's share of the arena: the packed rays (ra, rb: 32 B), the hit records (16 B; the wave-uniform walk writes 8-byte ones
+// into the first half), then the redo list, one index per path: TRT_AOV_RAYS_BYTES_PER_PATH.  One pass at a time.
+struct AovRaysLayout {
+    static constexpr uint64_t bytes_per_path = 3 * sizeof(f4) + sizeof(uint32_t);
+    static_assert(bytes_per_path == TRT_AOV_RAYS_BYTES_PER_PATH, "include/trt.h states the figure");
+    static size_t bytes(uint64_t N, uint32_t) { return (size_t)(3 * N + (N + 3) / 4) * sizeof(f4); }
+    static void carve(f4* base, uint64_t N, f4*& ra, f4*& rb, f4*& hit, uint32_t*& redo_idx)
+    {
+        ra = base;
+        rb = base + N;
+        hit = base + 2 * N;
+        redo_idx = (uint32_t*)(base + 3 * N);
+    }
+};
+
 // How a render call splits its samples into passes: `slots` passes in flight at once, each of `chunk` samples of every pixel (the last one
 // may hold fewer), N paths and slot_bytes of arena.  Passes are as large as the budget allows: every pass ends in a tail of few, long paths,
 // so fewer and larger passes are faster (back 1080p x 256 spp: 3 passes in 32 GiB 101.4 ms, 1 pass in 93 GB 96.8 ms); >= slots_wanted
@@ -881,6 +896,7 @@ struct Footprint {
 };
 Footprint renderFootprint(uint32_t nl) { return Footprint{N_SLOTS, SlotLayout::bytesPerPath(nl), SlotLayout::bytes}; }
 Footprint aovFootprint() { return Footprint{1, AovLayout::bytes_per_path, AovLayout::bytes}; }
+Footprint aovRaysFootprint() { return Footprint{1, AovRaysLayout::bytes_per_path, AovRaysLayout::bytes}; }
 bool planPasses(uint32_t npix, uint32_t n_samples, uint32_t nl, uint64_t budget, int slots_wanted, const Footprint& fp, PassPlan& pl)
 {
     const uint64_t cap_paths = std::min<uint64_t>(budget / fp.per_path, MAX_PASS_PATHS);
@@ -1437,6 +1453,117 @@ int renderAov(trt_handle* h, const trt_params* p, float* albedo, float* normal, 
             if (user[k]) HIPC(hipMemcpy(user[k], out[k], floats[k] * sizeof(float), hipMemcpyDeviceToHost));
     return TRT_OK;
 }
+
+// trt_aov_rays / _device: the checks of include/trt.h, then pass by pass: k_aov_rays_pack turns the pass's slice of the caller's rays into queue
+// records in the arena (host arrays are staged in io_buf first, one pass's slice at a time), the queue flavour of the handle's closest-hit kernel
+// walks them with k_trace_fix behind it — what trt_trace_closest launches —, and k_aov_rays adds the first hits onto the caller's sums (device
+// entry: in place; host entry: copies of the given ones in small_buf, copied back at the end).  Everything runs on one stream, one pass at a time.
+int aovRays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, const float* dir, int32_t sample_begin, int32_t sample_end, double* albedo,
+            double* normal, double* depth, bool host, void* hip_stream, trt_stats* stats_out)
+{
+    if (!h || !p) return fail(TRT_EINVAL, "null handle/params");
+    if (p->spp < 1) return fail(TRT_EINVAL, "spp must be >= 1");
+    if (sample_begin < 0 || sample_begin > sample_end) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin <= end");
+    if (n > 0 && (!org || !dir)) return fail(TRT_EINVAL, "null ray arrays");
+    if (!albedo && !normal && !depth) return fail(TRT_EINVAL, "trt_aov_rays: every sum is null");
+    if (n > MAX_PASS_PATHS) return fail(TRT_EINVAL, "more rays per sample than the path ids of one pass can number (0x7FFF0000)");
+    if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
+    if (n == 0 || sample_begin == sample_end) return TRT_OK;
+    HIPC(hipSetDevice(h->device));
+    hipStream_t stream = host ? nullptr : (hipStream_t)hip_stream;
+    const uint32_t n_samples = (uint32_t)(sample_end - sample_begin);
+    PassPlan plan;
+    if (int e = planArena(h, p, n, n_samples, true, aovRaysFootprint(), plan)) return e;
+    // small_buf: the block cleared first (DeviceStats, the redo list's length and the blocks of k_trace_fix that are through, the number of valid
+    // entries), then the host entry's sums (albedo, normal: 3 per entry; depth: 1 per entry)
+    double* const user[3] = {albedo, normal, depth};
+    const size_t doubles[3] = {(size_t)n * 3, (size_t)n * 3, (size_t)n};
+    Layout L;
+    const size_t o_stats = L.add(sizeof(DeviceStats), 256), o_redo = L.add(2 * sizeof(uint32_t), 64), o_valid = L.add(sizeof(unsigned long long), 64);
+    const size_t o_sum = L.add(host ? (size_t)n * 7 * sizeof(double) : 0, 256);
+    if (int e = h->small_buf.ensure(L.bytes)) return e;
+    const size_t slice_floats = (size_t)plan.N * 3;  // one pass's org (and dir)
+    if (host)
+        if (int e = h->io_buf.ensure(2 * slice_floats * sizeof(float))) return e;
+    char* sb = (char*)h->small_buf.p;
+    DeviceStats* d_stats = (DeviceStats*)(sb + o_stats);
+    unsigned long long* d_valid = (unsigned long long*)(sb + o_valid);
+    double* sum[3] = {albedo, normal, depth};
+    HIPC(hipMemsetAsync(d_stats, 0, o_sum - o_stats, stream));
+    if (host) {
+        double* q = (double*)(sb + o_sum);
+        for (int k = 0; k < 3; ++k) {
+            sum[k] = user[k] ? q : nullptr;
+            if (user[k]) HIPC(hipMemcpyAsync(q, user[k], doubles[k] * sizeof(double), hipMemcpyHostToDevice, stream));
+            q += doubles[k];
+        }
+    }
+    f4 *ra = nullptr, *rb = nullptr, *hit = nullptr;
+    RedoList redo{(uint32_t*)(sb + o_redo), nullptr};
+    AovRaysLayout::carve((f4*)h->arena.p, plan.N, ra, rb, hit, redo.idx);
+    uint32_t* spill = (uint32_t*)h->spill.p;
+    const bool count = (p->flags & TRT_FLAG_COUNT) != 0;
+    const ClosestKernel queue_k = closestKernel(h, count, 0);
+    const FixKernel queue_fix = fixKernel(h, false, 0);
+    RaySource src{};
+    src.ra = ra;
+    src.rb = rb;
+
+    Timer tm{h, (p->flags & TRT_FLAG_TIMING) != 0};
+    trt_stats st;
+    std::memset(&st, 0, sizeof(st));
+    hipEvent_t ev_begin = tm.get(0), ev_end = tm.get(1);
+    if (!ev_begin || !ev_end) return fail(TRT_EHIP, "hipEventCreate failed");
+    HIPC(hipEventRecord(ev_begin, stream));
+    Drain drain{h, nullptr, 0, stream};
+    const dim3 block(256);
+    for (uint32_t c = 0; c < plan.n_chunks; ++c) {
+        const uint32_t s0 = c * plan.chunk, sc_count = std::min(plan.chunk, n_samples - s0), cnt = n * sc_count;
+        const size_t at = (size_t)s0 * n * 3, comps = (size_t)cnt * 3;
+        const float* d_org = org + at;
+        const float* d_dir = dir + at;
+        if (host) {  // the stream orders this pass's copies behind the last pass's packing
+            float* stage = (float*)h->io_buf.p;
+            HIPC(hipMemcpyAsync(stage, org + at, comps * sizeof(float), hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync(stage + slice_floats, dir + at, comps * sizeof(float), hipMemcpyHostToDevice, stream));
+            d_org = stage;
+            d_dir = stage + slice_floats;
+        }
+        tm.launch(TRT_K_GEN_PRIMARY, stream, st, [&] {
+            hipLaunchKernelGGL(k_aov_rays_pack, dim3(std::min<uint32_t>((cnt + 255) / 256, 65536u)), block, 0, stream, d_org, d_dir, cnt, ra, rb, d_valid);
+        });
+        tm.launch(TRT_K_TRACE_CLOSEST, stream, st, [&] { launchTraceClosest(h, queue_k, queue_fix, stream, spill, src, hit, cnt, d_stats, redo); });
+        tm.launch(TRT_K_RESOLVE, stream, st, [&] {
+            const dim3 grid(std::min<uint32_t>((n + 255) / 256, 65536u));
+            if (h->hit8) hipLaunchKernelGGL(k_aov_rays<true>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, sum[0], sum[1], sum[2], n, sc_count, (float)p->spp);
+            else hipLaunchKernelGGL(k_aov_rays<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, sum[0], sum[1], sum[2], n, sc_count, (float)p->spp);
+        });
+    }
+    HIPC(hipEventRecord(ev_end, stream));
+    DeviceStats ds;
+    unsigned long long n_valid = 0;
+    HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
+    HIPC(hipMemcpyAsync(&n_valid, d_valid, sizeof(n_valid), hipMemcpyDeviceToHost, stream));
+    if (host)
+        for (int k = 0; k < 3; ++k)
+            if (user[k]) HIPC(hipMemcpyAsync(user[k], sum[k], doubles[k] * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+    drain.armed = false;
+
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, ev_begin, ev_end));
+    st.render_ms = ms;
+    for (const auto& span : tm.spans) {
+        float k_ms = 0.f;
+        if (hipEventElapsedTime(&k_ms, h->events[span.e0], h->events[span.e1]) == hipSuccess) st.kernel_ms[span.k] += k_ms;
+    }
+    addDeviceStats(st, ds, h);
+    st.rays_camera = n_valid;
+    st.passes = plan.n_chunks;
+    if (stats_out) *stats_out = st;
+    return TRT_OK;
+}
 }  // namespace
 
 int trt_render_device(trt_handle* h, const trt_params* p, float* out_dev, void* hip_stream, trt_stats* stats_out)
@@ -1623,6 +1750,18 @@ int trt_render_aov(trt_handle* h, const trt_params* p, float* albedo_host, float
 int trt_render_aov_device(trt_handle* h, const trt_params* p, float* albedo_dev, float* normal_dev, float* depth_dev, void* hip_stream, trt_stats* stats)
 {
     return renderAov(h, p, albedo_dev, normal_dev, depth_dev, false, hip_stream, stats);
+}
+
+int trt_aov_rays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, const float* dir, int32_t sample_begin, int32_t sample_end,
+                 double* albedo_sum_host, double* normal_sum_host, double* depth_sum_host, trt_stats* stats)
+{
+    return aovRays(h, p, n, org, dir, sample_begin, sample_end, albedo_sum_host, normal_sum_host, depth_sum_host, true, nullptr, stats);
+}
+
+int trt_aov_rays_device(trt_handle* h, const trt_params* p, uint32_t n, const float* org_dev, const float* dir_dev, int32_t sample_begin, int32_t sample_end,
+                        double* albedo_sum_dev, double* normal_sum_dev, double* depth_sum_dev, void* hip_stream, trt_stats* stats)
+{
+    return aovRays(h, p, n, org_dev, dir_dev, sample_begin, sample_end, albedo_sum_dev, normal_sum_dev, depth_sum_dev, false, hip_stream, stats);
 }
 
 namespace {

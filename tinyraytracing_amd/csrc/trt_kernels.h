@@ -1933,4 +1933,85 @@ __global__ __launch_bounds__(256) void k_camera_rays(CameraRaysArgs A, const uin
     }
 }
 
+// ---- first-hit features along caller-supplied rays (trt_aov_rays, include/trt.h) ----
+// One pass's slice of the caller's arrays (org / dir [n][3], entry i = path i of the pass; the host forms the slice's address in 64 bits, and
+// so is i * 3 here) becomes the records the queue flavour of the traversal kernels reads: aovRayRecord (trt_path.h), entry i at index i — no
+// compaction, k_aov_rays finds the hit of (sample s, entry e) at s * n_entries + e.  The 12-byte components are not read per thread: a block
+// takes the 768 consecutive floats of its 256 entries with consecutive lanes on consecutive dwords, through LDS (read back at a stride of 3
+// words: no bank conflict), and stores the two 16-byte records coalesced.  The valid entries are counted for trt_stats::rays_camera: a ballot
+// per wave and tile, summed by the wave's lane 0, one atomic per wave at the end (*n_valid is zeroed by the host before the first pass).
+__global__ __launch_bounds__(256) void k_aov_rays_pack(const float* __restrict__ org, const float* __restrict__ dir, uint32_t n, f4* __restrict__ ra,
+                                                       f4* __restrict__ rb, unsigned long long* __restrict__ n_valid)
+{
+    __shared__ float s_o[768], s_d[768];
+    const uint32_t per_grid = gridDim.x * 256u;  // <= 2^24; n <= 0x7FFF0000: base never wraps
+    uint32_t seen = 0;
+    for (uint32_t base = blockIdx.x * 256u; base < n; base += per_grid) {  // uniform trip count per block: every thread reaches every barrier
+        const uint32_t left = n - base, cnt = left < 256u ? left : 256u;
+        const size_t at = (size_t)base * 3;
+        for (uint32_t k = threadIdx.x; k < cnt * 3u; k += 256u) { s_o[k] = org[at + k]; s_d[k] = dir[at + k]; }
+        __syncthreads();
+        bool ok = false;
+        if (threadIdx.x < cnt) {
+            f4 a, b;
+            ok = aovRayRecord(ld3(s_o + threadIdx.x * 3u), ld3(s_d + threadIdx.x * 3u), base + threadIdx.x, a, b);
+            TRT_STQ(2, ra + base + threadIdx.x, a);
+            TRT_STQ(2, rb + base + threadIdx.x, b);
+        }
+        seen += (uint32_t)__popcll(ballotb(ok));
+        __syncthreads();  // s_o / s_d are rewritten by the next tile
+    }
+    if ((threadIdx.x & 63u) == 0 && seen) atomicAdd(n_valid, (unsigned long long)seen);
+}
+
+// The counterpart of k_aov for those records: one thread per entry, the pass's samples in order, the seven sums in registers for the pass.
+// Hit s * n + e is read coalesced across e.  An entry whose record carries the bound of an invalid entry (aovRayTraced) is a miss whatever
+// the walk stored for it; rb.w is looked at only behind a hit.  HIT8: the 8-byte records of the wave-uniform walk, (u, v) formed on the packed
+// ray as k_unpack_hits forms them.  The sums are the caller's: albedo / normal [n][3], depth [n] doubles, in/out, any of them null = not wanted;
+// they are added onto, neither zeroed nor rounded.
+template <bool HIT8>
+__global__ __launch_bounds__(256) void k_aov_rays(SceneDev sc, const f4* __restrict__ ra, const f4* __restrict__ rb, const f4* __restrict__ hit,
+                                                  double* __restrict__ albedo, double* __restrict__ normal, double* __restrict__ depth, uint32_t n,
+                                                  uint32_t s_count, float spp)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
+        double a[3] = {0.0, 0.0, 0.0}, nr[3] = {0.0, 0.0, 0.0}, z = 0.0;
+        if (albedo) for (int k = 0; k < 3; ++k) a[k] = albedo[(size_t)e * 3 + k];
+        if (normal) for (int k = 0; k < 3; ++k) nr[k] = normal[(size_t)e * 3 + k];
+        if (depth) z = depth[e];
+        for (uint32_t s = 0; s < s_count; ++s) {
+            const uint32_t i = s * n + e;  // < n * s_count <= 0x7FFF0000 (MAX_PASS_PATHS)
+            f4 hit4;
+            if constexpr (HIT8) {
+                const trt_v2f r = reinterpret_cast<const trt_v2f*>(hit)[i];
+                hit4 = mk4(r.x, r.y, 0.0f, 0.0f);
+            } else {
+                hit4 = hit[i];
+            }
+            Hit h;
+            h.t = hit4.x; h.tri = (int32_t)f2u(hit4.y); h.u = hit4.z; h.v = hit4.w; h.flags = 0;
+            f3 alb = mk3(0.0f, 0.0f, 0.0f), nrm = alb;
+            float t = TRT_INF;
+            if (h.tri >= 0 && aovRayTraced(rb[i].w)) {
+                if constexpr (HIT8) {
+                    hitBarycentrics(sc.tri_isect, ra[i], rb[i], hit4);
+                    h.u = hit4.z; h.v = hit4.w;
+                }
+                const TriShade ts = sc.tri_shade[h.tri];
+                const Vertex vx = makeVertex(sc, h, alb, alb, ts, sc.materials[ts.mat]);  // the ray only gives the hit point, which is not used here
+                alb = vx.Kd;
+                nrm = vx.pn;
+                t = h.t;
+            }
+            a[0] += (double)(alb.x / spp); a[1] += (double)(alb.y / spp); a[2] += (double)(alb.z / spp);
+            nr[0] += (double)(nrm.x / spp); nr[1] += (double)(nrm.y / spp); nr[2] += (double)(nrm.z / spp);
+            z += (double)(t / spp);
+        }
+        if (albedo) for (int k = 0; k < 3; ++k) albedo[(size_t)e * 3 + k] = a[k];
+        if (normal) for (int k = 0; k < 3; ++k) normal[(size_t)e * 3 + k] = nr[k];
+        if (depth) depth[e] = z;
+    }
+}
+
 }  // namespace trtd

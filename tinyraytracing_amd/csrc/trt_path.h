@@ -977,6 +977,22 @@ TRT_HD inline bool rayValid(f3 o, f3 d)
     const bool finite = (f2u(o.x) & e) != e && (f2u(o.y) & e) != e && (f2u(o.z) & e) != e && (f2u(d.x) & e) != e && (f2u(d.y) & e) != e && (f2u(d.z) & e) != e;
     return finite && (((f2u(d.x) | f2u(d.y) | f2u(d.z)) & 0x7FFFFFFFu) != 0u);
 }
+// ---- first-hit features along caller-supplied rays (trt_aov_rays, include/trt.h) ----
+// The traversal record of entry `idx` of a pass: the record of the bounded ray query (k_pack_rays_bounded) with the bound TRT_INF in rb.w.  An
+// entry that is not valid (rayValid) never reaches a walk as given: its record is one fixed finite ray — far outside any scene, pointing away,
+// no zero component, so a walk leaves it at the root — with the bound TRT_T_MIN, the record of a query that can find nothing.  The bound, not
+// the walk's answer, is the entry's verdict (aovRayTraced): whichever kernel walks the record, and whether or not it reads rb.w, the entry is
+// a miss.  -> the entry is valid.
+TRT_HD inline bool aovRayRecord(f3 o, f3 d, uint32_t idx, f4& ra, f4& rb)
+{
+    const bool ok = rayValid(o, d);
+    if (!ok) { o = mk3(1.0e18f, 1.0e18f, 1.0e18f); d = mk3(1.0f, 1.0f, 1.0f); }
+    ra = mk4(o.x, o.y, o.z, d.x);
+    rb = mk4(d.y, d.z, u2f(idx), ok ? TRT_INF : TRT_T_MIN);
+    return ok;
+}
+TRT_HD inline bool aovRayTraced(float bound) { return bound > TRT_T_MIN; }
+
 // The ray cameraRecord forms for (pixel q = y * width + x, sample) — the same stream, the same two jitter draws, the same cameraRay call — for
 // ANY camera, as plain vectors (trt_camera_rays: k_camera_rays on the device, the same function on the host).  `grid`: TileDesc::grid_rcp or null.
 TRT_HD inline void cameraRayOf(const trt_camera& cam, int W, int H, uint32_t seed, uint32_t q, uint32_t sample, bool fixed, const double* grid, f3& o, f3& d)
