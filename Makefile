@@ -29,8 +29,8 @@ HOST_HDR := $(wildcard $(PKG)/host/*.h) $(wildcard $(PKG)/csrc/*.h) include/trt.
 HIP_SRC := $(PKG)/csrc/trt_api.hip
 HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include/trt_exact.h
 
-.PHONY: all host hip lbvh oracle cli hostsim denoisecpu refitcpu rayscpu variants probe exactcheck clean
-all: host hip lbvh oracle hostsim denoisecpu refitcpu rayscpu cli exactcheck
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu refitcpu rayscpu variants probe exactcheck nodecheck clean
+all: host hip lbvh oracle hostsim denoisecpu refitcpu rayscpu cli exactcheck nodecheck
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -91,6 +91,11 @@ clean:
 exactcheck: tools/exact_unary_check
 tools/exact_unary_check: tools/exact_unary_check.hip include/trt_exact.h include/trt_prims.h
 	$(HIPCC) -O3 --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Iinclude -o $@ tools/exact_unary_check.hip
+
+# octVisit, innerStep and the box tests as gfx950 compiles them (the flags of the library), one thread per case: run by tests/test_gpu_node_claims.py
+nodecheck: tools/node_visit_check
+tools/node_visit_check: tools/node_visit_check.hip $(HIP_HDR)
+	$(HIPCC) $(HIPFLAGS) -o $@ tools/node_visit_check.hip
 
 # chip-ceiling probe + TCC counter calibration workload (tools/calibrate_counters.sh runs it on the GPU box)
 probe: tools/gather_probe

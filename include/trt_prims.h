@@ -50,6 +50,18 @@ static inline uint32_t trt_popc32(uint32_t x) { return (uint32_t)__builtin_popco
 static inline TRT_HD uint32_t trt_f2u(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 static inline TRT_HD float trt_u2f(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
 
+/* Minimum and maximum of the slab test's entry and exit distances.  v_min_f32 / v_max_f32 order the zeros (-0 below +0); C leaves fminf / fmaxf free to return
+ * either zero of a pair of opposite sign, and the host's returns one by operand position.  No decision reads the sign of a zero distance, but the CPU build of the
+ * device code is to return gfx950's BITS (tests/test_gpu_node_claims.py compares box entries word for word), so on the host equal
+ * operands are merged by their bits: "or" keeps a minus sign (the minimum), "and" drops it (the maximum); for equal operands that are not zeros both are the identity. */
+#if defined(__HIP_DEVICE_COMPILE__)
+static inline __device__ float trt_fminf(float a, float b) { return fminf(a, b); }
+static inline __device__ float trt_fmaxf(float a, float b) { return fmaxf(a, b); }
+#else
+static inline float trt_fminf(float a, float b) { return a == b ? trt_u2f(trt_f2u(a) | trt_f2u(b)) : fminf(a, b); }
+static inline float trt_fmaxf(float a, float b) { return a == b ? trt_u2f(trt_f2u(a) & trt_f2u(b)) : fmaxf(a, b); }
+#endif
+
 /* ---- counter-based RNG ------------------------------------------------------ */
 
 /* 32-bit finaliser (full-avalanche integer hash). */

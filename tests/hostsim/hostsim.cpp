@@ -17,6 +17,7 @@
 #include "trt_path.h"
 #include "trt_wide.h"
 #include "trt_oct_build.h"
+#include "trt_refit.h"
 
 using namespace trtd;
 
@@ -37,6 +38,15 @@ struct ArrayStack {
     int bvh2Capacity() const { return (int)bvh2_cap; }
     void breach() const { g_breaches++; }
 };
+
+// a recorder of the parity-mode shadow rays hostsim_render traces (hostsim_shadow_rays)
+struct ShadowRec {
+    uint64_t cap;
+    std::atomic<uint64_t> n{0};
+    float *org, *dir;
+    int32_t* light;
+};
+ShadowRec* g_shadow_rec = nullptr;
 
 struct OctArrayStack {
     OctGroup s[256];
@@ -256,6 +266,16 @@ extern "C" int hostsim_render(const trt_scene* s, const trt_params* p, float* ou
                     if (!cx.shade_ok || !lightSample(hs.sc, cx.vx, *cx.m, li, cx.rng, wo, contrib, fixed, t_max)) continue;
                     const f3 w = cx.beta * contrib;
                     r_sh++;
+                    if (g_shadow_rec && !fixed) {
+                        const uint64_t k = g_shadow_rec->n.fetch_add(1);
+                        if (k < g_shadow_rec->cap) {
+                            const f3 so = rayOrigin(cx, wo);
+                            const float o3[3] = {so.x, so.y, so.z}, d3[3] = {wo.x, wo.y, wo.z};
+                            std::memcpy(g_shadow_rec->org + k * 3, o3, 12);
+                            std::memcpy(g_shadow_rec->dir + k * 3, d3, 12);
+                            g_shadow_rec->light[k] = (int32_t)li;
+                        }
+                    }
                     // k_trace_shadow
                     const Hit sh = hs.nk ? traceClosestOct<OctArrayStack, ArrayStack, false>(hs.sc, rayOrigin(cx, wo), wo, ostk, stk, ni, nt, t_max, fixed, !fixed, &hs.light_boxes[li])
                                          : traceClosest<ArrayStack, false, 0>(hs.sc, rayOrigin(cx, wo), wo, stk, ni, nt, t_max, fixed, !fixed);
@@ -457,4 +477,261 @@ extern "C" uint64_t hostsim_div_magic_mismatches(uint32_t d, const uint32_t* n, 
     uint64_t bad = 0;
     for (uint64_t i = 0; i < count; ++i) bad += divMagic(n[i], d, m) != n[i] / d ? 1u : 0u;
     return bad;
+}
+
+// ---- node by node: the decisions behind the results (tests/test_hostsim_node_claims.py; tests/test_gpu_node_claims.py compares the words of
+// tools/node_visit_check.hip, the same functions as gfx950 compiles them, with what these entries return).  The entries work on arrays the test owns
+// (nodes, boxes, filter words), so a negative control is a changed copy of the data, never a switch in the headers.
+namespace {
+inline uint32_t canonBits(float f) { return f != f ? 0x7FC00000u : f2u(f); }  // one NaN: the payload of a NaN is not part of any claim
+inline f3 invOf(f3 d) { return mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z); }
+
+}  // namespace
+
+// Synthetic 8-wide nodes straight from octQuantise.  kind[i][slot]: 0 empty, 1 an inner child, 2..4 a leaf slot of 1..3 triangles (offsets in slot order).
+// ok[i] = 0 where the extent is not representable (the node is left zeroed).
+extern "C" int hostsim_oct_quantise_nodes(uint64_t n, const float* blo, const float* bhi, const uint8_t* kind, OctNode* out, uint8_t* ok)
+{
+    for (uint64_t i = 0; i < n; ++i) {
+        float lo[8][3], hi[8][3], p[3];
+        uint32_t mask = 0u, imask = 0u, eb[3], qlo[3][8], qhi[3][8], meta[8], off = 0u;
+        for (int sl = 0; sl < 8; ++sl) {
+            for (int a = 0; a < 3; ++a) { lo[sl][a] = blo[(i * 8 + sl) * 3 + a]; hi[sl][a] = bhi[(i * 8 + sl) * 3 + a]; }
+            const uint32_t k = kind[i * 8 + sl];
+            meta[sl] = 0u;
+            if (!k) continue;
+            mask |= 1u << sl;
+            if (k == 1u) { imask |= 1u << sl; meta[sl] = 0x20u | (24u + (uint32_t)sl); }
+            else { const uint32_t c = k - 1u; meta[sl] = (((1u << c) - 1u) << 5) | off; off += c; }
+        }
+        std::memset(&out[i], 0, sizeof(OctNode));
+        ok[i] = (mask && octQuantise(lo, hi, mask, p, eb, qlo, qhi)) ? 1 : 0;
+        if (!ok[i]) continue;
+        out[i].q[0] = mk4(p[0], p[1], p[2], u2f(eb[0] | (eb[1] << 8) | (eb[2] << 16) | (imask << 24)));
+        out[i].q[1] = mk4(u2f(0u), u2f(0u), u2f(octPack4(meta)), u2f(octPack4(meta + 4)));
+        octStoreBounds(out[i], qlo, qhi);
+    }
+    return 0;
+}
+
+// octVisit per (node, ray, cull): words[2 i] = the node group's hit word (bits 24..31 by octant-permuted slot | imask), words[2 i + 1] = the triangle bits
+extern "C" int hostsim_oct_visit_cases(const OctNode* nodes, uint64_t n, const uint32_t* node, const float* org, const float* dir, const float* cull, uint32_t* words)
+{
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)n; ++i) {
+        const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3);
+        const OctRay R = makeOctRay(o, d, invOf(d));
+        OctGroup ng, tg;
+        octVisit(nodes, node[i], R, cull[i], ng, tg);
+        words[2 * i] = ng.y;
+        words[2 * i + 1] = tg.y;
+    }
+    return 0;
+}
+
+// the reference's test (boxTest) of the EXACT box of each of the eight slots of node[i] (slot_box[node][slot] = lo.xyz, hi.xyz: what octQuantise was fed)
+extern "C" int hostsim_slot_ref(const float* slot_box, uint64_t n, const uint32_t* node, const float* org, const float* dir, uint8_t* pass, float* entry)
+{
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)n; ++i) {
+        const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3), inv = invOf(d);
+        for (int sl = 0; sl < 8; ++sl) {
+            const float* b = slot_box + ((size_t)node[i] * 8 + sl) * 6;
+            float e;
+            pass[i * 8 + sl] = boxTest(b[0], b[1], b[2], b[3], b[4], b[5], o, inv, e) ? 1 : 0;
+            entry[i * 8 + sl] = e;
+        }
+    }
+    return 0;
+}
+
+// The nodes of an oct tree the REFERENCE's descent reaches: from the root, into an inner slot iff boxTest passes the slot's exact box.  Per ray up to
+// `cap` node indices in pair_node[ray][..], count[ray] = how many were reached (more than cap: the rest are dropped).  Rays of raySpecial() reach none:
+// traceClosestOct does not send them to these nodes.
+extern "C" int hostsim_oct_descent(const OctNode* nodes, const float* slot_box, uint32_t n_nodes, uint64_t n, const float* org, const float* dir, uint32_t cap,
+                                   uint32_t* pair_node, uint32_t* count)
+{
+    int bad = 0;
+#pragma omp parallel for schedule(dynamic, 64) reduction(| : bad)
+    for (long long i = 0; i < (long long)n; ++i) {
+        const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3), inv = invOf(d);
+        uint32_t m = 0;
+        std::vector<uint32_t> todo;
+        if (!raySpecial(inv) && n_nodes) todo.push_back(0u);
+        while (!todo.empty()) {
+            const uint32_t ni = todo.back();
+            todo.pop_back();
+            if (ni >= n_nodes || m > 4u * n_nodes) { bad = 1; break; }
+            if (m < cap) pair_node[(size_t)i * cap + m] = ni;
+            ++m;
+            for (int sl = 0; sl < 8; ++sl) {
+                const uint32_t mt = octMeta(nodes[ni], sl);
+                if (!mt || !octMetaInner(mt)) continue;
+                const float* b = slot_box + ((size_t)ni * 8 + sl) * 6;
+                float e;
+                if (boxTest(b[0], b[1], b[2], b[3], b[4], b[5], o, inv, e)) todo.push_back(octChildIndex(nodes[ni], sl));
+            }
+        }
+        count[i] = m;
+    }
+    return bad;
+}
+
+// boxTest and boxTestGlm per (box, ray): out[3 i] = verdicts (bit 0 boxTest, bit 1 boxTestGlm), out[3 i + 1] / [3 i + 2] = the bits of their entries
+extern "C" int hostsim_box_cases(uint64_t n, const float* box, const float* org, const float* dir, uint32_t* out)
+{
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)n; ++i) {
+        const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3), inv = invOf(d);
+        const float* b = box + i * 6;
+        float e0, e1;
+        const bool p0 = boxTest(b[0], b[1], b[2], b[3], b[4], b[5], o, inv, e0), p1 = boxTestGlm(b[0], b[1], b[2], b[3], b[4], b[5], o, inv, e1);
+        out[3 * i] = (p0 ? 1u : 0u) | (p1 ? 2u : 0u);
+        out[3 * i + 1] = canonBits(e0);
+        out[3 * i + 2] = canonBits(e1);
+    }
+    return 0;
+}
+
+// innerStep on 4-wide node node[i] with an empty private stack: out[6 i ..] = cur, the returned flag, entries pushed, the pushed references in order
+extern "C" int hostsim_inner_step_cases(const WideNode* wnodes, uint64_t n, const uint32_t* node, const float* org, const float* dir, const float* cull, uint32_t* out)
+{
+    SceneDev sc{};
+    sc.wnodes = wnodes;
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)n; ++i) {
+        const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3);
+        ArrayStack stk;
+        stk.s[0] = stk.s[1] = stk.s[2] = 0u;
+        uint32_t cur = node[i];
+        int sp = 0;
+        const bool go = innerStep(sc, cur, sp, stk, o, invOf(d), cull[i]);
+        out[6 * i] = cur; out[6 * i + 1] = go ? 1u : 0u; out[6 * i + 2] = (uint32_t)sp;
+        out[6 * i + 3] = stk.s[0]; out[6 * i + 4] = stk.s[1]; out[6 * i + 5] = stk.s[2];
+    }
+    return 0;
+}
+
+// trt_leaf_floor / trt_cull_bound element by element
+extern "C" void hostsim_leaf_floor_v(uint64_t n, const float* e, const float* alpha, float* out)
+{
+    for (uint64_t i = 0; i < n; ++i) out[i] = trt_leaf_floor(e[i], alpha[i]);
+}
+extern "C" void hostsim_cull_bound_v(uint64_t n, const float* b, const float* alpha, float* out)
+{
+    for (uint64_t i = 0; i < n; ++i) out[i] = trt_cull_bound(b[i], alpha[i]);
+}
+
+// what a handle derives from the tree: info[0] = leaf_alpha, info[1] = 1 when the boxes nest; light_box[l][6] (may be null)
+extern "C" int hostsim_scene_info(const trt_scene* s, float info[2], float* light_box)
+{
+    HostScene hs(s);
+    info[0] = hs.sc.leaf_alpha;
+    info[1] = wide_detail::boxesNested(s->nodes, s->n_nodes) ? 1.0f : 0.0f;
+    for (size_t l = 0; light_box && l < hs.light_boxes.size(); ++l)
+        for (int a = 0; a < 3; ++a) { light_box[l * 6 + a] = hs.light_boxes[l].lo[a]; light_box[l * 6 + 3 + a] = hs.light_boxes[l].hi[a]; }
+    return 0;
+}
+
+// The culling chain on results: for the hit (t[i], tri[i]) of ray i every box on tri's root path, in the caller's BVH2 (tree 2) and in its 4-wide collapse
+// (tree 4), root first: (0) boxTest passes, (1) the entry is not below the one above it, (2) NOT t < trt_leaf_floor(entry), (3) NOT entry >
+// trt_cull_bound(t).  Rays traceClosest does not walk with culling (a zero direction
+// component AND an origin the plane filter cannot clear) and misses are left out.  counts: [0] rays checked, [1] boxes checked, [2 + k] violations of (k);
+// viol[j][8] = kind, tree, node, slot, ray, entry, t, bound of the first 16.  3: the boxes do not nest (nothing is claimed for such a tree).
+extern "C" int hostsim_cull_chain(const trt_scene* s, uint64_t n, const float* org, const float* dir, const float* t, const int32_t* tri, uint64_t counts[6],
+                                  double* viol)
+{
+    HostScene hs(s);
+    for (int k = 0; k < 6; ++k) counts[k] = 0;
+    if (!wide_detail::boxesNested(s->nodes, s->n_nodes)) return 3;
+    struct Up { uint32_t node, slot; };
+    const Up none{~0u, 0u};
+    // tree 2: where each node hangs, which child box holds each triangle
+    std::vector<Up> up2(s->n_nodes, none), leaf2(s->n_tris, none), upw(hs.wide.nodes.size(), none), leafw(s->n_tris, none);
+    for (uint32_t i = 0; i < s->n_nodes; ++i)
+        for (uint32_t k = 0; k < 2; ++k) {
+            const uint32_t ref = k ? s->nodes[i].child1 : s->nodes[i].child0;
+            if (!(ref & TRT_LEAF_BIT)) { if (ref < s->n_nodes) up2[ref] = Up{i, k}; continue; }
+            for (uint32_t j = 0; j < TRT_LEAF_COUNT(ref); ++j)
+                if (TRT_LEAF_FIRST(ref) + j < s->n_tris) leaf2[TRT_LEAF_FIRST(ref) + j] = Up{i, k};
+        }
+    for (uint32_t i = 0; i < hs.wide.nodes.size(); ++i)
+        for (uint32_t k = 0; k < TRT_WIDE; ++k) {
+            const uint32_t ref = f2u((&hs.wide.nodes[i].q[6].x)[k]);
+            if (ref == TRT_WIDE_EMPTY) continue;
+            if (!(ref & TRT_LEAF_BIT)) { if (ref < hs.wide.nodes.size()) upw[ref] = Up{i, k}; continue; }
+            for (uint32_t j = 0; j < TRT_LEAF_COUNT(ref); ++j)
+                if (TRT_LEAF_FIRST(ref) + j < s->n_tris) leafw[TRT_LEAF_FIRST(ref) + j] = Up{i, k};
+        }
+    const float alpha = hs.sc.leaf_alpha;
+    uint64_t n_viol = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3), inv = invOf(d);
+        if (tri[i] < 0 || (uint32_t)tri[i] >= s->n_tris || (raySpecial(inv) && rayOnABoxPlane(hs.sc, o, inv))) continue;
+        counts[0]++;
+        const float bound = trt_cull_bound(t[i], alpha);
+        for (int tree = 2; tree <= 4; tree += 2) {
+            std::vector<Up> path;
+            for (Up u = (tree == 2 ? leaf2 : leafw)[(size_t)tri[i]]; u.node != ~0u && path.size() <= s->n_nodes; u = (tree == 2 ? up2 : upw)[u.node]) {
+                path.push_back(u);
+                if (u.node == 0u) break;
+            }
+            float above = -__builtin_inff();
+            for (size_t k = path.size(); k-- > 0;) {
+                const Up u = path[k];
+                float lo[3], hi[3], e;
+                if (tree == 2) {
+                    const trt_bvh_node& nd = s->nodes[u.node];
+                    for (int a = 0; a < 3; ++a) { lo[a] = u.slot ? nd.lo1[a] : nd.lo0[a]; hi[a] = u.slot ? nd.hi1[a] : nd.hi0[a]; }
+                } else {
+                    const f4* q = hs.wide.nodes[u.node].q;
+                    for (int a = 0; a < 3; ++a) { lo[a] = (&q[a].x)[u.slot]; hi[a] = (&q[3 + a].x)[u.slot]; }
+                }
+                const bool pass = boxTest(lo[0], lo[1], lo[2], hi[0], hi[1], hi[2], o, inv, e);
+                const bool bad[4] = {!pass, e < above, t[i] < trt_leaf_floor(e, alpha), e > bound};
+                counts[1]++;
+                for (int c = 0; c < 4; ++c) {
+                    if (!bad[c]) continue;
+                    counts[2 + c]++;
+                    if (n_viol < 16 && viol) {
+                        const double row[8] = {(double)c, (double)tree, (double)u.node, (double)u.slot, (double)i, (double)e, (double)t[i], (double)bound};
+                        std::memcpy(viol + n_viol * 8, row, sizeof row);
+                    }
+                    n_viol++;
+                }
+                above = e;
+            }
+        }
+    }
+    return 0;
+}
+
+// the parity-mode shadow rays of a render (origin, direction, the light each was drawn for), up to cap; returns how many there were (or ~0 on an error)
+extern "C" uint64_t hostsim_shadow_rays(const trt_scene* s, const trt_params* p, uint64_t cap, float* org, float* dir, int32_t* light)
+{
+    ShadowRec rec;
+    rec.cap = cap; rec.org = org; rec.dir = dir; rec.light = light;
+    std::vector<float> img((size_t)p->width * p->height * 3);
+    g_shadow_rec = &rec;
+    const int rc = hostsim_render(s, p, img.data(), nullptr);
+    g_shadow_rec = nullptr;
+    return rc ? ~0ull : rec.n.load();
+}
+
+// the plane filter a handle builds over the tree of `s`: the words (up to cap_words) and log2 of its bits (0: cap_words is too small)
+extern "C" uint32_t hostsim_plane_filter(const trt_scene* s, uint32_t* bits, uint64_t cap_words)
+{
+    std::vector<uint32_t> b;
+    const uint32_t lg = wide_detail::planeFilterBuild(s->nodes, s->n_nodes, b);
+    if (b.size() > cap_words) return 0u;
+    std::memcpy(bits, b.data(), b.size() * 4);
+    return lg;
+}
+// planeMaybe(axis[i], x[i]) on a filter of 2^lg bits
+extern "C" void hostsim_plane_maybe(const uint32_t* bits, uint32_t lg, uint64_t n, const int32_t* axis, const float* x, uint8_t* out)
+{
+    SceneDev sc{};
+    sc.plane_bits = bits;
+    sc.plane_shift = 32u - lg;
+    for (uint64_t i = 0; i < n; ++i) out[i] = planeMaybe(sc, axis[i], x[i]) ? 1 : 0;
 }

@@ -119,3 +119,158 @@ def tree_hashes(flat, threads):
     out = (C.c_uint64 * 8)()
     assert lib().hostsim_tree_hashes(flat, int(threads), out) == 0
     return [int(x) for x in out]
+
+
+# ---- node by node (tests/test_hostsim_node_claims.py, tests/test_gpu_node_claims.py): the entries work on arrays the caller owns ----------------------
+OCT_DT = np.dtype([("p", "<f4", 3), ("ew", "<u4"), ("child_base", "<u4"), ("tri_base", "<u4"), ("meta", "u1", 8), ("q", "u1", (6, 8))])
+assert OCT_DT.itemsize == 80
+_vp = C.c_void_p
+
+
+def _rays(org, direction):
+    org = np.ascontiguousarray(org, np.float32).reshape(-1, 3)
+    direction = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+    assert org.shape == direction.shape
+    return org, direction
+
+
+def _call(name, *args):
+    f = getattr(lib(), name)
+    f.restype = C.c_int
+    f.argtypes = [(_vp if isinstance(a, np.ndarray) or a is None else (C.c_uint64 if isinstance(a, int) else type(a))) for a in args]
+    return f(*[(a.ctypes.data if isinstance(a, np.ndarray) else a) for a in args])
+
+
+def oct_quantise_nodes(blo, bhi, kind):
+    """Synthetic 8-wide nodes from octQuantise: blo / bhi [n, 8, 3] exact boxes, kind [n, 8] (0 empty, 1 inner, 2..4 a leaf slot of 1..3 triangles).
+    -> (nodes [n] of OCT_DT, ok [n])."""
+    blo, bhi = np.ascontiguousarray(blo, np.float32), np.ascontiguousarray(bhi, np.float32)
+    kind = np.ascontiguousarray(kind, np.uint8)
+    n = kind.shape[0]
+    nodes, ok = np.zeros(n, OCT_DT), np.zeros(n, np.uint8)
+    assert _call("hostsim_oct_quantise_nodes", n, blo, bhi, kind, nodes, ok) == 0
+    return nodes, ok.astype(bool)
+
+
+def oct_visit_cases(nodes, node, org, direction, cull):
+    """octVisit per case -> words [n, 2] (node group word, triangle bits)."""
+    org, direction = _rays(org, direction)
+    node, cull = np.ascontiguousarray(node, np.uint32), np.ascontiguousarray(cull, np.float32)
+    assert len(node) == len(cull) == len(org) and (len(node) == 0 or int(node.max()) < len(nodes))
+    words = np.zeros((len(node), 2), np.uint32)
+    assert _call("hostsim_oct_visit_cases", np.ascontiguousarray(nodes), len(node), node, org, direction, cull, words) == 0
+    return words
+
+
+def slot_ref(slot_box, node, org, direction):
+    """boxTest of the exact box of every slot of node[i] -> (passes [n, 8] bool, entry [n, 8] float32)."""
+    org, direction = _rays(org, direction)
+    node = np.ascontiguousarray(node, np.uint32)
+    slot_box = np.ascontiguousarray(slot_box, np.float32)
+    assert len(node) == 0 or int(node.max()) < len(slot_box)
+    ok, e = np.zeros((len(node), 8), np.uint8), np.zeros((len(node), 8), np.float32)
+    assert _call("hostsim_slot_ref", slot_box, len(node), node, org, direction, ok, e) == 0
+    return ok.astype(bool), e
+
+
+def oct_descent(nodes, slot_box, org, direction, cap=256):
+    """(node, ray) pairs the reference's descent of the oct tree reaches (a child iff boxTest passes its exact box) -> (node [m], ray [m])."""
+    org, direction = _rays(org, direction)
+    n = len(org)
+    pair, cnt = np.zeros((n, cap), np.uint32), np.zeros(n, np.uint32)
+    assert _call("hostsim_oct_descent", np.ascontiguousarray(nodes), np.ascontiguousarray(slot_box, np.float32), C.c_uint32(len(nodes)), n, org, direction,
+                 C.c_uint32(cap), pair, cnt) == 0
+    keep = np.arange(cap)[None, :] < np.minimum(cnt, cap)[:, None]
+    return pair[keep], np.broadcast_to(np.arange(n, dtype=np.int64)[:, None], (n, cap))[keep]
+
+
+def box_cases(box, org, direction):
+    """boxTest / boxTestGlm per (box [n, 6] lo hi, ray) -> words [n, 3]: verdict bits, entry bits of each (one NaN)."""
+    org, direction = _rays(org, direction)
+    box = np.ascontiguousarray(box, np.float32).reshape(-1, 6)
+    out = np.zeros((len(box), 3), np.uint32)
+    assert _call("hostsim_box_cases", len(box), box, org, direction, out) == 0
+    return out
+
+
+def inner_step_cases(wnodes, node, org, direction, cull):
+    """innerStep on 4-wide node node[i], empty stack -> words [n, 6]: cur, flag, pushes, the pushed references."""
+    org, direction = _rays(org, direction)
+    node, cull = np.ascontiguousarray(node, np.uint32), np.ascontiguousarray(cull, np.float32)
+    assert len(node) == 0 or int(node.max()) < len(wnodes)
+    out = np.zeros((len(node), 6), np.uint32)
+    assert _call("hostsim_inner_step_cases", np.ascontiguousarray(wnodes), len(node), node, org, direction, cull, out) == 0
+    return out
+
+
+def leaf_floor(e, alpha):
+    e, alpha = np.ascontiguousarray(e, np.float32), np.ascontiguousarray(np.broadcast_to(np.float32(alpha), np.shape(e)), np.float32)
+    out = np.zeros(e.shape, np.float32)
+    _call("hostsim_leaf_floor_v", e.size, e, alpha, out)
+    return out
+
+
+def cull_bound(b, alpha):
+    b, alpha = np.ascontiguousarray(b, np.float32), np.ascontiguousarray(np.broadcast_to(np.float32(alpha), np.shape(b)), np.float32)
+    out = np.zeros(b.shape, np.float32)
+    _call("hostsim_cull_bound_v", b.size, b, alpha, out)
+    return out
+
+
+def scene_info(flat):
+    """(leaf_alpha, nested, light boxes [n_lights, 6]) as a handle derives them."""
+    n = flat.contents.n_lights
+    info, lb = np.zeros(2, np.float32), np.zeros((max(n, 1), 6), np.float32)
+    assert _call("hostsim_scene_info", flat, info, lb) == 0
+    return np.float32(info[0]), bool(info[1]), lb[:n]
+
+
+CHAIN_KINDS = ("boxTest fails", "entry below the box above", "t < floor(entry)", "entry > cull bound")
+
+
+def cull_chain(flat, org, direction, t, tri):
+    """The culling chain on results -> (counts dict, text of the first violations).  None for a tree whose boxes do not nest."""
+    org, direction = _rays(org, direction)
+    t, tri = np.ascontiguousarray(t, np.float32), np.ascontiguousarray(tri, np.int32)
+    counts, viol = np.zeros(6, np.uint64), np.zeros((16, 8), np.float64)
+    rc = _call("hostsim_cull_chain", flat, len(t), org, direction, t, tri, counts, viol)
+    if rc == 3:
+        return None
+    assert rc == 0, rc
+    bad = [int(x) for x in counts[2:]]
+    text = "; ".join(f"{CHAIN_KINDS[int(v[0])]}: tree {int(v[1])} node {int(v[2])} slot {int(v[3])} ray {int(v[4])} o={org[int(v[4])]} d={direction[int(v[4])]} "
+                     f"entry={v[5]!r} t={v[6]!r} bound={v[7]!r}" for v in viol[:min(sum(bad), 16)])
+    return {"rays": int(counts[0]), "boxes": int(counts[1]), "bad": bad}, text
+
+
+def shadow_rays(flat, p, cap=1 << 22):
+    """The parity-mode shadow rays of a render -> (org, dir, light)."""
+    org, d, light = np.zeros((cap, 3), np.float32), np.zeros((cap, 3), np.float32), np.zeros(cap, np.int32)
+    f = lib().hostsim_shadow_rays
+    f.restype = C.c_uint64
+    f.argtypes = [C.POINTER(SceneFlat), C.POINTER(Params), C.c_uint64, _vp, _vp, _vp]
+    n = int(f(flat, C.byref(p), cap, org.ctypes.data, d.ctypes.data, light.ctypes.data))
+    assert n <= cap, n
+    return org[:n], d[:n], light[:n]
+
+
+def plane_filter(flat):
+    """(words, log2 bits) of the plane filter planeFilterBuild makes for the scene's tree."""
+    cap = max(1 << 5, (64 * flat.contents.n_nodes * 2) // 32 + 64)
+    bits = np.zeros(cap, np.uint32)
+    f = lib().hostsim_plane_filter
+    f.restype = C.c_uint32
+    f.argtypes = [C.POINTER(SceneFlat), _vp, C.c_uint64]
+    lg = int(f(flat, bits.ctypes.data, cap))
+    assert lg >= 10
+    return bits[: (1 << lg) // 32].copy(), lg
+
+
+def plane_maybe(bits, lg, axis, x):
+    axis, x = np.ascontiguousarray(axis, np.int32), np.ascontiguousarray(x, np.float32)
+    assert axis.shape == x.shape and len(bits) == (1 << lg) // 32
+    out = np.zeros(x.shape, np.uint8)
+    lib().hostsim_plane_maybe.restype = None
+    lib().hostsim_plane_maybe.argtypes = [_vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp]
+    lib().hostsim_plane_maybe(np.ascontiguousarray(bits, np.uint32).ctypes.data, lg, x.size, axis.ctypes.data, x.ctypes.data, out.ctypes.data)
+    return out.astype(bool)

@@ -246,3 +246,40 @@ def test_host_and_device_entries_agree_and_bad_arguments_leave_the_handle_alone(
         assert st.launches[T.TRT_K_REFIT] > 0 and st.kernel_ms[T.TRT_K_REFIT] > 0 and st.render_ms >= st.kernel_ms[T.TRT_K_REFIT]
         assert st.rays == 0 and st.shaded_hits == 0 and sum(st.inner_visits) == 0 and sum(st.tri_tests) == 0 and st.redo_rays == 0
         assert all(st.launches[k] == 0 for k in range(7))
+
+
+def _vertex_eye_scene_displaced(tmp_path):
+    """test_hostsim_parity's vertex-eye scene with its one triangle elsewhere, loaded from a file of its own: no box of this tree — the box of the root's empty
+    second leaf included, which an update leaves alone — has a plane of the fixture's."""
+    obj = ("v 54434.95 57506.86 -161.27\nv 55692.92 56346.13 857.39\nv 56527.36 57846.1 -2700.01\n"
+           "vn 0 0 1\nvt 0 0\nusemtl lamp\nf 1/1/1 2/1/1 3/1/1\n")
+    SU.write_scene(tmp_path, "eye_moved", obj, SU.MTL_BASIC, lights=[("lamp", (4, 8, 9.5))], w=24, h=5, fovy=20.0, eye=(74036.484375, 79794.8046875, -4266.68115234375),
+                   lookat=(72698.703125, 79148.5546875, -1440.929931640625))
+    return SU.load(tmp_path, "eye_moved", leaf_num=15)
+
+
+@pytest.mark.parametrize("impl,nk", [("0", "0"), ("3", "0"), ("3", "1")])
+def test_an_update_rebuilds_the_plane_filter_for_the_new_planes(impl, nk, tmp_path, monkeypatch):
+    """test_hostsim_parity's vertex-eye scene reached by an UPDATE: the handle is created with the triangle elsewhere and moved to the fixture's vertices.
+    The rays' origin then sits on a vertex of the (unpadded at 7e4) leaf box, and the rays with a zero direction component find the triangle only through the
+    literal slab test — which they get only if the filter of planeMaybe() knows the planes of the NEW boxes (k_refit_planes).  A filter left as trt_create made
+    it clears those origins, the clean slab test runs, and the hits are lost.  Hits equal the oracle's on the scene set_vertices left, bit for bit."""
+    from test_hostsim_parity import _vertex_eye_scene
+    fixture = _vertex_eye_scene(tmp_path)
+    f = fixture.flat.contents
+    rng = np.random.default_rng(3)
+    rays = [O.camera_ray(f.camera, 24, 5, 1, int(rng.integers(17, 22)), float(np.float32(rng.random())), float(np.float32(rng.random()))) for _ in range(20000)]
+    org, dirs = np.array([r[0] for r in rays], np.float32), np.array([r[1] for r in rays], np.float32)
+    v0, vn0 = fixture.arrays()["tri_v"].copy(), fixture.arrays()["tri_vn"].copy()
+    s = _vertex_eye_scene_displaced(tmp_path)
+    assert not np.isin(raygen.box_planes(s.flat), raygen.box_planes(fixture.flat)).any()
+    A = renderer(s, {"TRT_TRACE_IMPL": impl, "TRT_NODE_KIND": nk}, monkeypatch)
+    s.set_vertices(v0, vn0)
+    A.update_geometry(s)
+    t0, tri0, uv0 = O.trace(s.flat, org, dirs)
+    assert (tri0[(dirs == 0).any(1)] >= 0).sum() > 50
+    t1, tri1, uv1 = A.trace_closest(org, dirs)
+    assert np.array_equal(tri0, tri1) and np.array_equal(t0, t1) and np.array_equal(uv0, uv1)
+    A.close()
+    s.close()
+    fixture.close()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from hostsim_lib import OCT_DT
 import raygen
 import refit_ref as RR
 import scene_util as SU
@@ -154,7 +155,6 @@ def test_oracle_renders_a_moved_scene_and_a_moved_back_one_as_before():
 
 # ---- the per-node functions of the 4-wide and 8-wide passes on the host (tests/refit/librefit_cpu.so) ------------------------------------
 WIDE_DT = np.dtype([("box", "<f4", (6, 4)), ("ref", "<u4", 4), ("pad", "<u4", 4)])
-OCT_DT = np.dtype([("p", "<f4", 3), ("ew", "<u4"), ("child_base", "<u4"), ("tri_base", "<u4"), ("meta", "u1", 8), ("q", "u1", (6, 8))])
 assert WIDE_DT.itemsize == 128 and OCT_DT.itemsize == 80
 LEAF = RR.LEAF
 

@@ -306,12 +306,12 @@ TRT_HD inline bool triTest(const TriIsect& T, f3 o, f3 d, float& t_out, float& u
 
 // ---------------------------------------------------- interactAABB (a4) ----
 // bvh.cpp:231-245: slab test; `entry` receives t0 (used for ordering/culling).
-// fminf/fmaxf differ from glm's ternaries only for NaN operands (an axis with
-// d == 0 and the origin exactly on the padded plane).
+// trt_fminf / trt_fmaxf (trt_prims.h: fminf / fmaxf, with the zeros ordered on every build) differ
+// from glm's ternaries only for NaN operands (an axis with d == 0 and the origin exactly on the padded plane).
 TRT_HD inline bool slabResult(float inx, float iny, float inz, float outx, float outy, float outz, float& entry)
 {
-    const float t1 = fminf(fmaxf(inx, outx), fminf(fmaxf(iny, outy), fmaxf(inz, outz)));
-    const float t0 = fmaxf(fminf(inx, outx), fmaxf(fminf(iny, outy), fminf(inz, outz)));
+    const float t1 = trt_fminf(trt_fmaxf(inx, outx), trt_fminf(trt_fmaxf(iny, outy), trt_fmaxf(inz, outz)));
+    const float t0 = trt_fmaxf(trt_fminf(inx, outx), trt_fmaxf(trt_fminf(iny, outy), trt_fminf(inz, outz)));  // trt_prims.h: the hardware's order of the zeros on every build
     entry = t0;
     // bvh.cpp:243-244 returns r = (t1 >= t0) ? ((t0 > 0) ? t0 : t1) : -1 and the caller descends iff r > 0 (bvh.cpp:162-166).
     // With t1 >= t0 true (so neither is NaN): t0 > 0 gives r = t0 > 0, and then t1 >= t0 > 0 as well; otherwise r = t1.  Either
