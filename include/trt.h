@@ -193,7 +193,7 @@ enum {
     TRT_K_TRACE_SHADOW = 3,
     TRT_K_RESOLVE = 4,
     TRT_K_TAIL = 5,       /* the last, short-queue bounces of a pass fused into one launch */
-    TRT_K_DENOISE = 6,    /* trt_denoise*: the prepare kernel and every level of the a-trous filter */
+    TRT_K_DENOISE = 6,    /* trt_denoise*: the prepare kernel and every level of the a-trous filter; trt_reproject*: its one kernel */
     TRT_K_REFIT = 7       /* trt_update_geometry*: every kernel of an update */
 };
 
@@ -520,6 +520,73 @@ int trt_denoise(int device, const trt_denoise_params* params, int width, int hei
  * stream has been synchronised.  Nothing but the stats crosses PCIe; out is written at its first W*H*3 floats only. */
 int trt_denoise_device(int device, const trt_denoise_params* params, int width, int height, const float* color, const float* variance,
                        const float* albedo, const float* normal, const float* depth, float* out, void* hip_stream, trt_stats* stats);
+
+/* ---- temporal accumulation: reproject the previous frame's history (the temporal half of SVGF) --------------------------------------
+ * A stateless image-space operation shaped like trt_denoise: one W x H image, no scene handle, no state in the library.  The caller owns
+ * the history and hands it back frame after frame; what comes out goes on to trt_denoise.  All buffers float, rows top to bottom.
+ * Inputs of the current frame, exactly trt_denoise's five: color W*H*3, variance W*H, albedo W*H*3, normal W*H*3, depth W*H.
+ * History, all four or none (all NULL = a first frame):
+ *   prev_cv      W*H*4  demodulated colour and its variance, the cv record (c.r, c.g, c.b, var) of trt_denoise.h (an earlier call's out_cv);
+ *   prev_len     W*H    history length (an earlier call's out_len);
+ *   prev_normal  W*H*3  and prev_depth W*H: the previous frame's own feature buffers.
+ * Outputs, none of which may alias an input (not checked):
+ *   out_color W*H*3 and out_variance W*H   what the caller hands to trt_denoise in place of color and variance;
+ *   out_cv W*H*4 and out_len W*H           the next frame's history, together with this frame's normal and depth.
+ * Per pixel p = (x, y):
+ *  1. Demodulate as trt_denoise does (the same functions: history and filter share one domain): a_c = albedo_c > 0 ? albedo_c : 1,
+ *     c = color / a, var = variance / max(lum(a), 1e-6)^2.
+ *  2. A pixel with no history — a miss (depth >= TRT_INF, or a NaN), or any pixel when the history is NULL — gives out_color and
+ *     out_variance = the input's bits, out_cv = (c, var), out_len = 1.
+ *  3. World point P = cur.eye + depth d, d the unit direction through the pixel's centre: d = normalize(llc + s horizontal + t vertical - eye)
+ *     with, under TRT_FLAG_FIXED_PIXELS, s = (x + 0.5) / W, t = (H - 1 - y + 0.5) / H, otherwise the reference's grid (quirks Q1, Q2 with
+ *     both jitters at 0.5): s = x / (W - 1), t = (H - y) / (H - 1).  fp32 throughout (a render's binary64 grid is not needed here).
+ *  4. Into the previous image: P - prev.eye = k ((prev.llc - prev.eye) + s' prev.horizontal + t' prev.vertical), solved by Cramer's rule;
+ *     a zero determinant, k <= 0 or anything that is not a number: no history.  (s', t') gives continuous pixel coordinates (fx, fy) by the
+ *     inverse of the grid of step 3, and z' = |P - prev.eye| is the depth the previous frame would have stored.  If cur and prev are
+ *     byte-identical the geometry is skipped: fx = x, fy = y, z' = depth, so a still camera accumulates without resampling blur.
+ *  5. Taps: the four pixels around (fx, fy), x0 = floor(fx), y0 = floor(fy), in the order (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), with
+ *     their bilinear weights.  (fx, fy) outside (-1, W) x (-1, H): no history.  A tap q counts iff its weight is > 0, it is inside the
+ *     image, prev_depth_q < TRT_INF, |z' - prev_depth_q| <= depth_tolerance z', and n_p . n_q > 0 with
+ *     (n_p . n_q)^2 >= normal_threshold^2 |n_p|^2 |n_q|^2 (normals are means of unit vectors, not unit: this form needs no square root).
+ *     W_s = the sum of the weights of the counting taps; W_s < 0.01: no history.  Otherwise c_h, var_h and N_h are the weighted means of
+ *     prev_cv and prev_len over the counting taps.
+ *  6. Blend: N = min(N_h + 1, max_history), alpha' = max(alpha, 1 / N); c' = c_h + alpha' (c - c_h); var' = alpha'^2 var + (1 - alpha')^2 var_h;
+ *     out_cv = (c', var'), out_len = N, out_color = c' a, out_variance = var' max(lum(a), 1e-6)^2.  So the history is the running mean of the
+ *     frames until 1 / N falls below alpha, and an exponential average from then on.
+ *  7. A hit pixel that found no history gives the results of step 2.
+ * The variance formula takes the frames as independent estimates: the caller MUST change the seed every frame.
+ * Geometry that moved between the frames (trt_update_geometry) is not tracked — there are no motion vectors: the history of such a surface
+ * is used whenever it passes the tests of step 5, and the caller resets it by passing NULL history.
+ * Arithmetic: fp32 throughout, the two normalisations by trt_sqrt (include/trt_exact.h); the exact operation order is
+ * tinyraytracing_amd/csrc/trt_reproject.h, which a CPU build of the same code reproduces bit for bit.  Non-finite colours are the caller's
+ * business, as for trt_denoise: no fault, the result is unspecified nearby.  Non-finite depths or camera values index nothing out of bounds:
+ * such a pixel has no history. */
+typedef struct trt_reproject_params {
+    trt_camera cur, prev;     /* the cameras of this frame and of the history */
+    float alpha;              /* least weight of the new frame, (0, 1]; 0 = 0.2 */
+    float depth_tolerance;    /* relative, >= 0; 0 = 0.1 */
+    float normal_threshold;   /* cosine, [0, 1]; 0 = 0.9 */
+    float max_history;        /* cap of the history length, >= 1; 0 = 255 */
+    uint32_t flags;           /* TRT_FLAG_FIXED_PIXELS only: which pixel grid the cameras use; any other bit TRT_EINVAL */
+} trt_reproject_params;
+
+/* Reprojects HOST buffers on `device` (HIP ordinal; a gfx950, else TRT_ENODEV); the buffers are staged in device memory for the call (80
+ * bytes per pixel, 116 with a history).  TRT_EINVAL, checked in this order before any device work: null params or a null required buffer
+ * (the five inputs, the four outputs); a history given in part; width or height < 1; width * height > TRT_DENOISE_MAX_PIXELS; alpha outside
+ * [0, 1] or NaN; a negative or NaN depth_tolerance; normal_threshold outside [0, 1]; max_history neither 0 nor >= 1; a flag other than
+ * TRT_FLAG_FIXED_PIXELS.  stats (optional): launches / kernel_ms[TRT_K_DENOISE] = the one kernel, render_ms = the call's device time (copies
+ * included); every other field 0. */
+int trt_reproject(int device, const trt_reproject_params* params, int width, int height, const float* color, const float* variance,
+                  const float* albedo, const float* normal, const float* depth, const float* prev_cv, const float* prev_len,
+                  const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance, float* out_cv, float* out_len,
+                  trt_stats* stats);
+/* The same with every buffer in DEVICE memory of `device`, the work enqueued on hip_stream (NULL = default stream); returns after that
+ * stream has been synchronised.  Nothing but the stats crosses PCIe and no device memory is allocated.  prev_cv and out_cv are read and
+ * written as 16-byte records: an address that is not a multiple of 16 is TRT_EINVAL. */
+int trt_reproject_device(int device, const trt_reproject_params* params, int width, int height, const float* color, const float* variance,
+                         const float* albedo, const float* normal, const float* depth, const float* prev_cv, const float* prev_len,
+                         const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance, float* out_cv,
+                         float* out_len, void* hip_stream, trt_stats* stats);
 
 
 /* ---- one node, several GPUs -------------------------------------------------------------------------------------

@@ -731,19 +731,15 @@ class Renderer:
             out = {k_: v.cpu().numpy() for k_, v in out.items()}
         return (out, total) if want_stats else out
 
-    def render_camera_denoised(self, params, camera, aov_spp=None, samples_per_call=16, iterations=5, sigma_normal=128, sigma_depth=1.0,
-                               sigma_luminance=4.0):
-        """render_denoised for the tile of `params` as seen by `camera`, on this handle: the same dict (color, variance, albedo, normal, depth,
-        denoised as float32 arrays, and stats) under the same rules (params.spp >= 2, no row interleave, aov_spp None = min(spp, 16)).  The
-        beauty and its moments come from render_rays_into on the camera's rays, the variance from mean_luminance_variance's operations on the
-        device, the features from render_camera_aov, the filter is denoise_into: nothing but stats crosses to the host until the final copy.
-        With the handle's own camera the dict is render_denoised(params)'s, bit for bit."""
+    def _camera_denoiser_inputs(self, params, camera, aov_spp, samples_per_call, what):
+        """The device part of render_camera_denoised, shared with TemporalAccumulator: the denoiser's inputs of the tile of `params` as seen by
+        `camera`, as float32 tensors on this device.  -> (color [rows, tw, 3], variance [rows, tw], aov dict, Stats summed, stream pointer)."""
         import torch
         if params.spp < 2:
-            raise TrtError("render_camera_denoised: spp must be >= 2 (the variance needs two samples)")
+            raise TrtError(f"{what}: spp must be >= 2 (the variance needs two samples)")
         if params.row_mod > 1:
-            raise TrtError("render_camera_denoised: the tile must not interleave rows (it is filtered as one image)")
-        pix, (rows, tw) = self._camera_tile(params, "render_camera_denoised")
+            raise TrtError(f"{what}: the tile must not interleave rows (it is filtered as one image)")
+        pix, (rows, tw) = self._camera_tile(params, what)
         k = max(1, min(int(samples_per_call), params.spp))
         dev = pix.device
         n = pix.numel()
@@ -764,6 +760,17 @@ class Renderer:
         _add_stats(total, st)
         color = sums.to(torch.float32).reshape(rows, tw, 3)
         variance = mean_luminance_variance(sums, sumsq, params.spp).reshape(rows, tw)
+        return color, variance, aov, total, stream
+
+    def render_camera_denoised(self, params, camera, aov_spp=None, samples_per_call=16, iterations=5, sigma_normal=128, sigma_depth=1.0,
+                               sigma_luminance=4.0):
+        """render_denoised for the tile of `params` as seen by `camera`, on this handle: the same dict (color, variance, albedo, normal, depth,
+        denoised as float32 arrays, and stats) under the same rules (params.spp >= 2, no row interleave, aov_spp None = min(spp, 16)).  The
+        beauty and its moments come from render_rays_into on the camera's rays, the variance from mean_luminance_variance's operations on the
+        device, the features from render_camera_aov, the filter is denoise_into: nothing but stats crosses to the host until the final copy.
+        With the handle's own camera the dict is render_denoised(params)'s, bit for bit."""
+        import torch
+        color, variance, aov, total, stream = self._camera_denoiser_inputs(params, camera, aov_spp, samples_per_call, "render_camera_denoised")
         denoised = torch.empty_like(color)
         _add_stats(total, denoise_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], denoised, iterations=iterations,
                                        sigma_normal=sigma_normal, sigma_depth=sigma_depth, sigma_luminance=sigma_luminance, stream_ptr=stream))
@@ -1026,6 +1033,153 @@ def denoise_into(color, variance, albedo, normal, depth, out, iterations=5, sigm
     if rc != 0:
         raise TrtError(f"trt_denoise_device failed ({rc}): {lib.trt_last_error().decode()}")
     return st
+
+
+HISTORY_KEYS = ("cv", "length", "normal", "depth")
+
+
+def _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags):
+    rp = _abi.ReprojectParams()
+    rp.cur, rp.prev = cur, cur if prev is None else prev
+    rp.alpha, rp.depth_tolerance, rp.normal_threshold = float(alpha), float(depth_tolerance), float(normal_threshold)
+    rp.max_history, rp.flags = float(max_history), int(flags)
+    return rp
+
+
+def _history(history, what):
+    if history is None:
+        return [None] * 4
+    if not isinstance(history, dict) or any(history.get(k) is None for k in HISTORY_KEYS):
+        raise TrtError(f"{what}: history must be None or a dict with the keys cv, length, normal, depth")
+    return [history[k] for k in HISTORY_KEYS]
+
+
+def reproject(color, variance, albedo, normal, depth, cur, prev=None, history=None, alpha=0.2, depth_tolerance=0.1, normal_threshold=0.9,
+              max_history=255.0, flags=0, device=0, want_stats=False):
+    """Temporal accumulation on `device` (trt_reproject, include/trt.h has the contract): the current frame's color, albedo, normal [h, w, 3],
+    variance and depth [h, w] (denoise()'s inputs), the Cameras of this frame and of the history (prev None = cur: a still camera), and the
+    history: None on a first frame, else dict(cv [h, w, 4], length [h, w], normal [h, w, 3], depth [h, w]) — `cv` and `length` as an earlier
+    call returned them, `normal` and `depth` that frame's own.  flags: TRT_FLAG_FIXED_PIXELS if the frames were rendered with it.  The frames
+    must have been rendered with different seeds.  -> dict(color [h, w, 3], variance [h, w]: what goes on to denoise(); cv, length: the next
+    history, with this frame's normal and depth)[, Stats]."""
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    h, w = _image_shape(color, "reproject")
+    bufs = [color]
+    named = [("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))]
+    named += [("history " + k, a, shape) for k, a, shape in zip(HISTORY_KEYS, _history(history, "reproject"), ((h, w, 4), (h, w), (h, w, 3), (h, w)))]
+    for name, a, shape in named:
+        if a is None:
+            bufs.append(None)
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise TrtError(f"reproject: {name} must have shape {shape}, not {a.shape}")
+        bufs.append(a)
+    out = {"color": np.empty((h, w, 3), np.float32), "variance": np.empty((h, w), np.float32), "cv": np.empty((h, w, 4), np.float32),
+           "length": np.empty((h, w), np.float32)}
+    rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
+    st = Stats()
+    lib = _abi.load_hip()
+    fp = C.POINTER(C.c_float)
+    rc = lib.trt_reproject(int(device), C.byref(rp), w, h, *[None if b is None else b.ctypes.data_as(fp) for b in bufs],
+                           *[out[k].ctypes.data_as(fp) for k in ("color", "variance", "cv", "length")], C.byref(st))
+    if rc != 0:
+        raise TrtError(f"trt_reproject failed ({rc}): {lib.trt_last_error().decode()}")
+    return (out, st) if want_stats else out
+
+
+def reproject_into(color, variance, albedo, normal, depth, cur, prev, out_color, out_variance, out_cv, out_length, history=None, alpha=0.2,
+                   depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, flags=0, stream_ptr=0):
+    """trt_reproject_device: the buffers of reproject() as contiguous float32 torch tensors on one device (the history's too; out_color
+    [h, w, 3], out_variance [h, w], out_cv [h, w, 4], out_length [h, w]; no output may be an input), the work on stream `stream_ptr`
+    (0 = default).  Writes the four outputs; -> Stats."""
+    if not _is_torch(color) or color.dim() != 3:
+        raise TrtError("reproject_into: color must be a float32 tensor [height, width, 3]")
+    h, w = _image_shape(color, "reproject_into")
+    dev = color.device
+    named = [("color", color, (h, w, 3)), ("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))]
+    named += [("history " + k, t, shape) for k, t, shape in zip(HISTORY_KEYS, _history(history, "reproject_into"), ((h, w, 4), (h, w), (h, w, 3), (h, w)))]
+    named += [("out_color", out_color, (h, w, 3)), ("out_variance", out_variance, (h, w)), ("out_cv", out_cv, (h, w, 4)), ("out_length", out_length, (h, w))]
+    ptrs = []
+    for name, t, shape in named:
+        if t is None and name.startswith("history"):
+            ptrs.append(None)
+            continue
+        if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape
+                or t.device != dev):
+            raise TrtError(f"reproject_into: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+        ptrs.append(C.c_void_p(t.data_ptr()))
+    rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
+    st = Stats()
+    lib = _abi.load_hip()
+    rc = lib.trt_reproject_device(int(dev.index or 0), C.byref(rp), w, h, *ptrs, C.c_void_p(stream_ptr), C.byref(st))
+    if rc != 0:
+        raise TrtError(f"trt_reproject_device failed ({rc}): {lib.trt_last_error().decode()}")
+    return st
+
+
+class TemporalAccumulator:
+    """A frame loop over a moving camera: every frame is rendered, blended into the reprojected history of the frames before it
+    (reproject_into) and then filtered (denoise_into).  `params` names the image (its tile must be the whole image, spp >= 2, no row
+    interleave: render_camera_denoised's rules) and the first seed; alpha, depth_tolerance, normal_threshold and max_history are
+    trt_reproject's, aov_spp and samples_per_call render_camera_denoised's, denoise_kw (iterations, sigma_normal, sigma_depth,
+    sigma_luminance) denoise_into's.  The history lives in torch tensors on the renderer's device and belongs to this object alone: the
+    handle keeps nothing, and two accumulators on one renderer do not interact."""
+
+    def __init__(self, renderer, params, alpha=0.2, depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, aov_spp=None,
+                 samples_per_call=16, **denoise_kw):
+        unknown = set(denoise_kw) - {"iterations", "sigma_normal", "sigma_depth", "sigma_luminance"}
+        if unknown:
+            raise TrtError(f"TemporalAccumulator: unknown argument {sorted(unknown)[0]}")
+        if (params.x0, params.y0, params.x1, params.y1) != (0, 0, params.width, params.height):
+            raise TrtError("TemporalAccumulator: the tile must be the whole image (the cameras' pixel grid is the image's)")
+        if params.spp < 2:
+            raise TrtError("TemporalAccumulator: spp must be >= 2 (the variance needs two samples)")
+        if params.row_mod > 1:
+            raise TrtError("TemporalAccumulator: the tile must not interleave rows (it is filtered as one image)")
+        self.renderer = renderer
+        self.params = Params.from_buffer_copy(params)
+        self.reproject_kw = dict(alpha=alpha, depth_tolerance=depth_tolerance, normal_threshold=normal_threshold, max_history=max_history,
+                                 flags=params.flags & TRT_FLAG_FIXED_PIXELS)
+        self.render_kw = dict(aov_spp=aov_spp, samples_per_call=samples_per_call)
+        self.denoise_kw = denoise_kw
+        self.frame_index = 0  # frames rendered so far; reset() does not rewind it, so that no seed is used twice
+        self._history = None
+        self._camera = None
+
+    def reset(self):
+        """Drops the history: the next frame is a first frame (after a cut, or after trt_update_geometry moved the scene)."""
+        self._history = None
+        self._camera = None
+
+    def frame(self, camera, on_device=False):
+        """Renders the frame seen by `camera` with seed params.seed + frame_index (mod 2^32), accumulates and denoises it.  -> dict(color,
+        variance, albedo, normal, depth: the frame's own buffers; accumulated, accumulated_variance: the blend with the reprojected history;
+        history_length; denoised: the filtered accumulated image) as float32 arrays (on_device: torch tensors on the renderer's device), and
+        stats: the Stats of every call summed."""
+        import torch
+        p = Params.from_buffer_copy(self.params)
+        p.seed = (self.params.seed + self.frame_index) & 0xFFFFFFFF
+        color, variance, aov, total, stream = self.renderer._camera_denoiser_inputs(p, camera, self.render_kw["aov_spp"], self.render_kw["samples_per_call"],
+                                                                                   "TemporalAccumulator.frame")
+        h, w = color.shape[0], color.shape[1]
+        acc, acc_var = torch.empty_like(color), torch.empty_like(variance)
+        cv, length = torch.empty((h, w, 4), dtype=torch.float32, device=color.device), torch.empty_like(variance)
+        _add_stats(total, reproject_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], camera, self._camera, acc, acc_var, cv, length,
+                                         history=self._history, stream_ptr=stream, **self.reproject_kw))
+        denoised = torch.empty_like(color)
+        _add_stats(total, denoise_into(acc, acc_var, aov["albedo"], aov["normal"], aov["depth"], denoised, stream_ptr=stream, **self.denoise_kw))
+        self._history = {"cv": cv, "length": length, "normal": aov["normal"], "depth": aov["depth"]}
+        self._camera = Camera.from_buffer_copy(camera)
+        self.frame_index += 1
+        out = {"color": color, "variance": variance, "accumulated": acc, "accumulated_variance": acc_var, "history_length": length, "denoised": denoised}
+        out.update(aov)
+        if on_device:  # history_length, normal and depth are the next frame's history: the caller gets copies to do with as they please
+            out.update({k_: out[k_].clone() for k_ in ("history_length", "normal", "depth")})
+        else:
+            out = {k_: v.cpu().numpy() for k_, v in out.items()}
+        out["stats"] = total
+        return out
 
 
 def tonemap(image):

@@ -23,7 +23,7 @@ TRT_MAX_KERNELS = 8
 # trt_aov_rays: bytes of mem_budget per path and sample in a pass (include/trt.h TRT_AOV_RAYS_BYTES_PER_PATH)
 AOV_RAYS_BYTES_PER_PATH = 52
 KERNEL_NAMES = ["gen_primary", "trace_closest", "shade", "trace_shadow", "resolve", "tail"]
-# trt_denoise*'s slot of Stats.launches / kernel_ms: not in KERNEL_NAMES, whose last entry is the render's own last kernel
+# trt_denoise*'s and trt_reproject*'s slot of Stats.launches / kernel_ms: not in KERNEL_NAMES, whose last entry is the render's own last kernel
 TRT_K_DENOISE = 6
 # trt_update_geometry*'s slot
 TRT_K_REFIT = 7
@@ -95,6 +95,11 @@ class DenoiseParams(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class ReprojectParams(C.Structure):
+    _fields_ = [("cur", Camera), ("prev", Camera), ("alpha", C.c_float), ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float),
+                ("max_history", C.c_float), ("flags", C.c_uint32)]
+
+
 class GeometryUpdate(C.Structure):
     _fields_ = [("tri_v", C.c_void_p), ("tri_vn", C.c_void_p), ("lights", C.POINTER(Light)), ("light_tris", C.POINTER(LightTri)),
                 ("n_lights", C.c_uint32), ("n_light_tris", C.c_uint32)]
@@ -104,7 +109,7 @@ class GeometryUpdate(C.Structure):
 HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_rays", "trt_render_rays_device",
                "trt_camera_rays", "trt_camera_rays_device", "trt_render_aov",
                "trt_render_aov_device", "trt_aov_rays", "trt_aov_rays_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
-               "trt_trace_occluded_device", "trt_denoise", "trt_denoise_device",
+               "trt_trace_occluded_device", "trt_denoise", "trt_denoise_device", "trt_reproject", "trt_reproject_device",
                "trt_update_geometry", "trt_update_geometry_device", "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
 HOST_SYMBOLS = ["trth_scene_load", "trth_scene_load_opts", "trth_scene_drop_tris", "trth_scene_add_soup", "trth_scene_add_blob", "trth_scene_add_lamps",
@@ -243,6 +248,8 @@ def load_hip():
     lib.trt_trace_occluded_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 6 + [C.POINTER(Stats)]
     lib.trt_denoise_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.POINTER(Stats)]
+    lib.trt_reproject.argtypes = [C.c_int, C.POINTER(ReprojectParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 13 + [C.POINTER(Stats)]
+    lib.trt_reproject_device.argtypes = [C.c_int, C.POINTER(ReprojectParams), C.c_int, C.c_int] + [C.c_void_p] * 14 + [C.POINTER(Stats)]
     lib.trt_update_geometry.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_uint32, C.POINTER(Stats)]
     lib.trt_update_geometry_device.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
     lib.trt_destroy.argtypes = [C.c_void_p]

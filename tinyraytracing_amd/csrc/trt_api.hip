@@ -24,6 +24,7 @@
 #include "trt_wide.h"
 #include "trt_oct_build.h"
 #include "trt_denoise_kernels.h"
+#include "trt_reproject_kernels.h"
 #include "trt_refit_kernels.h"
 
 using namespace trtd;
@@ -2324,6 +2325,117 @@ int trt_denoise_device(int device, const trt_denoise_params* params, int width, 
 {
     return denoise(device, params, width, height, DenoiseIo{color, variance, albedo, normal, depth, out}, false, (hipStream_t)hip_stream, stats,
                    "trt_denoise_device");
+}
+
+}  // extern "C"
+
+// ---- trt_reproject / trt_reproject_device ---------------------------------------------------------------------------------------------
+
+namespace {
+
+struct ReprojectIo {
+    const float *color, *variance, *albedo, *normal, *depth;
+    const float *prev_cv, *prev_len, *prev_normal, *prev_depth;
+    float *out_color, *out_variance, *out_cv, *out_len;
+};
+
+// The checks of include/trt.h, in its order; fills the kernel's arguments.
+int reprojectArgs(const trt_reproject_params* prm, int width, int height, const ReprojectIo& io, bool host, trt_rp_args& a, const char* what)
+{
+    const bool required = io.color && io.variance && io.albedo && io.normal && io.depth && io.out_color && io.out_variance && io.out_cv && io.out_len;
+    const int given = (io.prev_cv ? 1 : 0) + (io.prev_len ? 1 : 0) + (io.prev_normal ? 1 : 0) + (io.prev_depth ? 1 : 0);
+    if (const char* msg = trt_rp_check(prm, width, height, required, given, a)) return fail(TRT_EINVAL, std::string(what) + ": " + msg);
+    if (!host && ((((uintptr_t)io.out_cv) | ((uintptr_t)io.prev_cv)) & 15u)) return fail(TRT_EINVAL, std::string(what) + ": prev_cv and out_cv must be 16-byte aligned");
+    return TRT_OK;
+}
+
+// One call: (host: upload) -> k_reproject -> (host: download), all on `stream`.
+int reproject(int device, const trt_reproject_params* prm, int width, int height, const ReprojectIo& io, bool host, hipStream_t stream, trt_stats* stats,
+              const char* what)
+{
+    trt_rp_args a{};
+    if (int e = reprojectArgs(prm, width, height, io, host, a, what)) return e;
+    if (int e = useDevice(device)) return e;
+    const size_t n = (size_t)width * (size_t)height, f1 = n * sizeof(float), f3 = 3 * f1, f4 = 4 * f1;
+    const bool hist = a.history != 0;
+    DenoiseScratch S;  // the staging of the host entry (none for the device entry) and the events
+    ReprojectIo dev = io;
+    for (hipEvent_t& e : S.ev) HIPC(hipEventCreate(&e));
+    if (host) {
+        Layout L;
+        const size_t o_c = L.add(f3, 256), o_v = L.add(f1, 256), o_a = L.add(f3, 256), o_n = L.add(f3, 256), o_z = L.add(f1, 256);
+        const size_t o_pc = L.add(hist ? f4 : 0, 256), o_pl = L.add(hist ? f1 : 0, 256), o_pn = L.add(hist ? f3 : 0, 256), o_pz = L.add(hist ? f1 : 0, 256);
+        const size_t o_oc = L.add(f3, 256), o_ov = L.add(f1, 256), o_ocv = L.add(f4, 256), o_ol = L.add(f1, 256);
+        HIPC(hipMalloc(&S.p, L.bytes));
+        char* b = (char*)S.p;
+        dev = ReprojectIo{(const float*)(b + o_c), (const float*)(b + o_v), (const float*)(b + o_a), (const float*)(b + o_n), (const float*)(b + o_z),
+                          hist ? (const float*)(b + o_pc) : nullptr, hist ? (const float*)(b + o_pl) : nullptr, hist ? (const float*)(b + o_pn) : nullptr,
+                          hist ? (const float*)(b + o_pz) : nullptr, (float*)(b + o_oc), (float*)(b + o_ov), (float*)(b + o_ocv), (float*)(b + o_ol)};
+    }
+    HIPC(hipEventRecord(S.ev[0], stream));
+    if (host) {
+        HIPC(hipMemcpyAsync((void*)dev.color, io.color, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.variance, io.variance, f1, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.albedo, io.albedo, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.normal, io.normal, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.depth, io.depth, f1, hipMemcpyHostToDevice, stream));
+        if (hist) {
+            HIPC(hipMemcpyAsync((void*)dev.prev_cv, io.prev_cv, f4, hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync((void*)dev.prev_len, io.prev_len, f1, hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync((void*)dev.prev_normal, io.prev_normal, f3, hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync((void*)dev.prev_depth, io.prev_depth, f1, hipMemcpyHostToDevice, stream));
+        }
+    }
+    const dim3 grid((unsigned)((width + RP_BX - 1) / RP_BX), (unsigned)((height + RP_BY - 1) / RP_BY)), block(RP_BX, RP_BY);
+    HIPC(hipEventRecord(S.ev[1], stream));
+    hipLaunchKernelGGL(k_reproject, grid, block, 0, stream, a, dev.color, dev.variance, dev.albedo, dev.normal, dev.depth,
+                       trt_rp_fetch{(const trt_dn4*)dev.prev_cv, dev.prev_len, dev.prev_normal, dev.prev_depth}, dev.out_color, dev.out_variance,
+                       (trt_dn4*)dev.out_cv, dev.out_len);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(S.ev[2], stream));
+    if (host) {
+        HIPC(hipMemcpyAsync(io.out_color, dev.out_color, f3, hipMemcpyDeviceToHost, stream));
+        HIPC(hipMemcpyAsync(io.out_variance, dev.out_variance, f1, hipMemcpyDeviceToHost, stream));
+        HIPC(hipMemcpyAsync(io.out_cv, dev.out_cv, f4, hipMemcpyDeviceToHost, stream));
+        HIPC(hipMemcpyAsync(io.out_len, dev.out_len, f1, hipMemcpyDeviceToHost, stream));
+    }
+    HIPC(hipEventRecord(S.ev[3], stream));
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+    if (stats) {
+        float k_ms = 0.f, all_ms = 0.f;
+        HIPC(hipEventElapsedTime(&k_ms, S.ev[1], S.ev[2]));
+        HIPC(hipEventElapsedTime(&all_ms, S.ev[0], S.ev[3]));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->launches[TRT_K_DENOISE] = 1;
+        stats->kernel_ms[TRT_K_DENOISE] = k_ms;
+        stats->render_ms = all_ms;
+    }
+    return TRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trt_reproject(int device, const trt_reproject_params* params, int width, int height, const float* color, const float* variance,
+                  const float* albedo, const float* normal, const float* depth, const float* prev_cv, const float* prev_len,
+                  const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance, float* out_cv, float* out_len,
+                  trt_stats* stats)
+{
+    return reproject(device, params, width, height,
+                     ReprojectIo{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len},
+                     true, nullptr, stats, "trt_reproject");
+}
+
+int trt_reproject_device(int device, const trt_reproject_params* params, int width, int height, const float* color, const float* variance,
+                         const float* albedo, const float* normal, const float* depth, const float* prev_cv, const float* prev_len,
+                         const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance, float* out_cv,
+                         float* out_len, void* hip_stream, trt_stats* stats)
+{
+    return reproject(device, params, width, height,
+                     ReprojectIo{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len},
+                     false, (hipStream_t)hip_stream, stats, "trt_reproject_device");
 }
 
 }  // extern "C"

@@ -226,7 +226,7 @@ int trth_abi_sizes(int64_t out[12])
     if (!out) return fail("null argument");
     out[0] = sizeof(trt_bvh_node); out[1] = sizeof(trt_material); out[2] = sizeof(trt_light); out[3] = sizeof(trt_light_tri);
     out[4] = sizeof(trt_texture); out[5] = sizeof(trt_camera); out[6] = sizeof(trt_scene); out[7] = sizeof(trt_params);
-    out[8] = sizeof(trt_stats); out[9] = TRT_ABI_VERSION; out[10] = sizeof(trt_denoise_params); out[11] = 0;
+    out[8] = sizeof(trt_stats); out[9] = TRT_ABI_VERSION; out[10] = sizeof(trt_denoise_params); out[11] = sizeof(trt_reproject_params);
     return 0;
 }
 
