@@ -561,6 +561,41 @@ class Renderer:
             raise TrtError(f"trt_trace_occluded_device failed ({rc}): {self._lib.trt_last_error().decode()}")
         return st
 
+    def trace_points(self, org, dir, tri_v_other, want_stats=False):
+        """trt_trace_points on host arrays: per ray the closest hit on this handle's current geometry, evaluated with its barycentrics on
+        the coordinates tri_v_other (float32 [n_tris, 3, 3], post-BVH order: Scene.arrays()["tri_v"]'s layout) — where the surface each ray
+        sees is, or was, on those vertices.  -> point float32 [n, 3], NaN (bits 0x7FC00000) for a miss[, Stats]."""
+        org, dir, _, n = self._rays(org, dir, None, "trace_points")
+        v = np.ascontiguousarray(tri_v_other, dtype=np.float32)
+        if v.ndim != 3 or v.shape[1:] != (3, 3):
+            raise TrtError("trace_points: tri_v_other must be a float32 array of shape (n_tris, 3, 3)")
+        point = np.empty((n, 3), np.float32)
+        st = Stats()
+        fp = C.POINTER(C.c_float)
+        rc = self._lib.trt_trace_points(self._h, n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp), v.ctypes.data_as(fp), v.shape[0],
+                                        point.ctypes.data_as(fp), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_trace_points failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return (point, st) if want_stats else point
+
+    def trace_points_into(self, org, dir, tri_v_other, point, stream_ptr=0):
+        """trt_trace_points_device: org / dir (float32 [n, 3]), tri_v_other (float32 [n_tris, 3, 3]) and point (float32 [n, 3], written) are
+        torch tensors on this device; the work runs on stream `stream_ptr` (0 = default).  -> Stats."""
+        n = self._ray_count(org, "trace_points_into")
+        if not _is_torch(tri_v_other) or tri_v_other.dim() != 3 or tuple(tri_v_other.shape[1:]) != (3, 3):
+            raise TrtError("trace_points_into: tri_v_other must be a float32 tensor of shape (n_tris, 3, 3)")
+        nt = tri_v_other.shape[0]
+        f32 = ("torch.float32",)
+        p = self._device_arrays("trace_points_into", n, [("org", org, f32, 3 * n), ("dir", dir, f32, 3 * n), ("tri_v_other", tri_v_other, f32, 9 * nt),
+                                                         ("point", point, f32, 3 * n)])
+        if any(x is None for x in p):
+            raise TrtError("trace_points_into: org, dir, tri_v_other and point are needed")
+        st = Stats()
+        rc = self._lib.trt_trace_points_device(self._h, n, p[0], p[1], p[2], nt, p[3], C.c_void_p(stream_ptr), C.byref(st))
+        if rc != 0:
+            raise TrtError(f"trt_trace_points_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        return st
+
     def render_rays(self, params, org, dir, streams=None, sample_begin=0, sums=None, sumsq=None):
         """Full paths along caller-supplied rays (trt_render_rays, include/trt.h): org / dir are float32 [S, n, 3] — sample-major, the rays of
         samples [sample_begin, sample_begin + S) of n entries ([n, 3] = one sample); streams: uint32 [n], the "pixel" word of each entry's
@@ -958,6 +993,35 @@ def camera_rays_into(camera, params, pixels, sample_begin, sample_end, org, dir,
         raise TrtError(f"trt_camera_rays_device failed ({rc}): {lib.trt_last_error().decode()}")
 
 
+def center_rays(camera, width, height, flags=0, device=None):
+    """The rays through the pixel centres of a width x height image of `camera`, on the grid trt_reproject's step 3 uses (flags:
+    TRT_FLAG_FIXED_PIXELS or 0 = the reference's grid): org = eye and dir = llc + horizontal * s + vertical * t - eye, NOT normalised, in
+    float32 in that order.  -> (org, dir), float32 [height * width, 3], pixel y * width + x.  device None: numpy arrays; a torch device (or
+    its index): torch tensors there, the per-pixel work done by torch operations on that device (on its current stream).  What
+    Renderer.trace_points makes of them does not depend on the direction's length."""
+    f = np.float32
+    w, h = int(width), int(height)
+    if w < 1 or h < 1:
+        raise TrtError("center_rays: width and height must be >= 1")
+    with np.errstate(all="ignore"):  # the reference's grid divides by W - 1 and H - 1
+        if int(flags) & TRT_FLAG_FIXED_PIXELS:
+            s = (np.arange(w).astype(f) + f(0.5)) / f(w)
+            t = (np.arange(h - 1, -1, -1).astype(f) + f(0.5)) / f(h)
+        else:
+            s = np.arange(w).astype(f) / (f(w) - f(1.0))
+            t = np.arange(h, 0, -1).astype(f) / (f(h) - f(1.0))
+    eye, llc, hor, ver = (np.array(list(getattr(camera, k)), f) for k in ("eye", "lower_left_corner", "horizontal", "vertical"))
+    if device is None:
+        with np.errstate(all="ignore"):
+            d = ((llc + hor * s[None, :, None]) + ver * t[:, None, None]) - eye
+        return np.ascontiguousarray(np.broadcast_to(eye, (h * w, 3))), np.ascontiguousarray(d.reshape(h * w, 3))
+    import torch
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    s, t, eye, llc, hor, ver = (torch.from_numpy(a).to(dev) for a in (s, t, eye, llc, hor, ver))
+    d = ((llc + hor * s[None, :, None]) + ver * t[:, None, None]) - eye  # separate multiplications and additions: nothing is contracted
+    return eye.expand(h * w, 3).contiguous(), d.reshape(h * w, 3).contiguous()
+
+
 def mean_luminance_variance(sums, sumsq, spp):
     """The variance of each pixel's mean luminance from trt_render_pixels' moments of samples [0, spp) (spp >= 2): per channel the unbiased
     sample variance of the radiance divided by spp, no covariances, weighted by LUMA^2.  sums / sumsq: float64 [n, 3] of v = L / spp and
@@ -1054,6 +1118,40 @@ def _history(history, what):
     return [history[k] for k in HISTORY_KEYS]
 
 
+def _reproject_host(what, color, variance, albedo, normal, depth, prev_point, cur, prev, history, alpha, depth_tolerance, normal_threshold,
+                    max_history, flags, device, want_stats):
+    """reproject() (prev_point None) and reproject_motion() on host arrays."""
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    h, w = _image_shape(color, what)
+    bufs = [color]
+    named = [("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))]
+    if what == "reproject_motion":
+        if prev_point is None:
+            raise TrtError("reproject_motion: prev_point is needed")
+        named.append(("prev_point", prev_point, (h, w, 3)))
+    named += [("history " + k, a, shape) for k, a, shape in zip(HISTORY_KEYS, _history(history, what), ((h, w, 4), (h, w), (h, w, 3), (h, w)))]
+    for name, a, shape in named:
+        if a is None:
+            bufs.append(None)
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise TrtError(f"{what}: {name} must have shape {shape}, not {a.shape}")
+        bufs.append(a)
+    out = {"color": np.empty((h, w, 3), np.float32), "variance": np.empty((h, w), np.float32), "cv": np.empty((h, w, 4), np.float32),
+           "length": np.empty((h, w), np.float32)}
+    rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
+    st = Stats()
+    lib = _abi.load_hip()
+    fp = C.POINTER(C.c_float)
+    entry = getattr(lib, "trt_" + what)
+    rc = entry(int(device), C.byref(rp), w, h, *[None if b is None else b.ctypes.data_as(fp) for b in bufs],
+               *[out[k].ctypes.data_as(fp) for k in ("color", "variance", "cv", "length")], C.byref(st))
+    if rc != 0:
+        raise TrtError(f"trt_{what} failed ({rc}): {lib.trt_last_error().decode()}")
+    return (out, st) if want_stats else out
+
+
 def reproject(color, variance, albedo, normal, depth, cur, prev=None, history=None, alpha=0.2, depth_tolerance=0.1, normal_threshold=0.9,
               max_history=255.0, flags=0, device=0, want_stats=False):
     """Temporal accumulation on `device` (trt_reproject, include/trt.h has the contract): the current frame's color, albedo, normal [h, w, 3],
@@ -1062,43 +1160,31 @@ def reproject(color, variance, albedo, normal, depth, cur, prev=None, history=No
     call returned them, `normal` and `depth` that frame's own.  flags: TRT_FLAG_FIXED_PIXELS if the frames were rendered with it.  The frames
     must have been rendered with different seeds.  -> dict(color [h, w, 3], variance [h, w]: what goes on to denoise(); cv, length: the next
     history, with this frame's normal and depth)[, Stats]."""
-    color = np.ascontiguousarray(color, dtype=np.float32)
-    h, w = _image_shape(color, "reproject")
-    bufs = [color]
-    named = [("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))]
-    named += [("history " + k, a, shape) for k, a, shape in zip(HISTORY_KEYS, _history(history, "reproject"), ((h, w, 4), (h, w), (h, w, 3), (h, w)))]
-    for name, a, shape in named:
-        if a is None:
-            bufs.append(None)
-            continue
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise TrtError(f"reproject: {name} must have shape {shape}, not {a.shape}")
-        bufs.append(a)
-    out = {"color": np.empty((h, w, 3), np.float32), "variance": np.empty((h, w), np.float32), "cv": np.empty((h, w, 4), np.float32),
-           "length": np.empty((h, w), np.float32)}
-    rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
-    st = Stats()
-    lib = _abi.load_hip()
-    fp = C.POINTER(C.c_float)
-    rc = lib.trt_reproject(int(device), C.byref(rp), w, h, *[None if b is None else b.ctypes.data_as(fp) for b in bufs],
-                           *[out[k].ctypes.data_as(fp) for k in ("color", "variance", "cv", "length")], C.byref(st))
-    if rc != 0:
-        raise TrtError(f"trt_reproject failed ({rc}): {lib.trt_last_error().decode()}")
-    return (out, st) if want_stats else out
+    return _reproject_host("reproject", color, variance, albedo, normal, depth, None, cur, prev, history, alpha, depth_tolerance, normal_threshold,
+                           max_history, flags, device, want_stats)
 
 
-def reproject_into(color, variance, albedo, normal, depth, cur, prev, out_color, out_variance, out_cv, out_length, history=None, alpha=0.2,
-                   depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, flags=0, stream_ptr=0):
-    """trt_reproject_device: the buffers of reproject() as contiguous float32 torch tensors on one device (the history's too; out_color
-    [h, w, 3], out_variance [h, w], out_cv [h, w, 4], out_length [h, w]; no output may be an input), the work on stream `stream_ptr`
-    (0 = default).  Writes the four outputs; -> Stats."""
+def reproject_motion(color, variance, albedo, normal, depth, prev_point, cur, prev=None, history=None, alpha=0.2, depth_tolerance=0.1,
+                     normal_threshold=0.9, max_history=255.0, flags=0, device=0, want_stats=False):
+    """reproject() for surfaces that move (trt_reproject_motion): one more input, prev_point [h, w, 3] — where the surface seen through each
+    pixel was when the history frame was rendered: Renderer.trace_points along center_rays(cur, w, h, flags) on the vertices of that time,
+    NaN where the ray misses.  The history is looked up where that point lay in `prev` (None = cur), with a still camera too.  Everything
+    else, and the result, as reproject()."""
+    return _reproject_host("reproject_motion", color, variance, albedo, normal, depth, prev_point, cur, prev, history, alpha, depth_tolerance,
+                           normal_threshold, max_history, flags, device, want_stats)
+
+
+def _reproject_device(what, color, variance, albedo, normal, depth, prev_point, cur, prev, out_color, out_variance, out_cv, out_length, history,
+                      alpha, depth_tolerance, normal_threshold, max_history, flags, stream_ptr):
+    """reproject_into() (prev_point None) and reproject_motion_into() on torch tensors."""
     if not _is_torch(color) or color.dim() != 3:
-        raise TrtError("reproject_into: color must be a float32 tensor [height, width, 3]")
-    h, w = _image_shape(color, "reproject_into")
+        raise TrtError(f"{what}: color must be a float32 tensor [height, width, 3]")
+    h, w = _image_shape(color, what)
     dev = color.device
     named = [("color", color, (h, w, 3)), ("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))]
-    named += [("history " + k, t, shape) for k, t, shape in zip(HISTORY_KEYS, _history(history, "reproject_into"), ((h, w, 4), (h, w), (h, w, 3), (h, w)))]
+    if what == "reproject_motion_into":
+        named.append(("prev_point", prev_point, (h, w, 3)))
+    named += [("history " + k, t, shape) for k, t, shape in zip(HISTORY_KEYS, _history(history, what), ((h, w, 4), (h, w), (h, w, 3), (h, w)))]
     named += [("out_color", out_color, (h, w, 3)), ("out_variance", out_variance, (h, w)), ("out_cv", out_cv, (h, w, 4)), ("out_length", out_length, (h, w))]
     ptrs = []
     for name, t, shape in named:
@@ -1107,15 +1193,33 @@ def reproject_into(color, variance, albedo, normal, depth, cur, prev, out_color,
             continue
         if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape
                 or t.device != dev):
-            raise TrtError(f"reproject_into: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+            raise TrtError(f"{what}: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
         ptrs.append(C.c_void_p(t.data_ptr()))
     rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
     st = Stats()
     lib = _abi.load_hip()
-    rc = lib.trt_reproject_device(int(dev.index or 0), C.byref(rp), w, h, *ptrs, C.c_void_p(stream_ptr), C.byref(st))
+    name = "trt_reproject_motion_device" if what == "reproject_motion_into" else "trt_reproject_device"
+    rc = getattr(lib, name)(int(dev.index or 0), C.byref(rp), w, h, *ptrs, C.c_void_p(stream_ptr), C.byref(st))
     if rc != 0:
-        raise TrtError(f"trt_reproject_device failed ({rc}): {lib.trt_last_error().decode()}")
+        raise TrtError(f"{name} failed ({rc}): {lib.trt_last_error().decode()}")
     return st
+
+
+def reproject_into(color, variance, albedo, normal, depth, cur, prev, out_color, out_variance, out_cv, out_length, history=None, alpha=0.2,
+                   depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, flags=0, stream_ptr=0):
+    """trt_reproject_device: the buffers of reproject() as contiguous float32 torch tensors on one device (the history's too; out_color
+    [h, w, 3], out_variance [h, w], out_cv [h, w, 4], out_length [h, w]; no output may be an input), the work on stream `stream_ptr`
+    (0 = default).  Writes the four outputs; -> Stats."""
+    return _reproject_device("reproject_into", color, variance, albedo, normal, depth, None, cur, prev, out_color, out_variance, out_cv, out_length,
+                             history, alpha, depth_tolerance, normal_threshold, max_history, flags, stream_ptr)
+
+
+def reproject_motion_into(color, variance, albedo, normal, depth, prev_point, cur, prev, out_color, out_variance, out_cv, out_length, history=None,
+                          alpha=0.2, depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, flags=0, stream_ptr=0):
+    """trt_reproject_motion_device: reproject_into() with prev_point (float32 [h, w, 3] on the same device, Renderer.trace_points_into's
+    output) after depth.  Writes the four outputs; -> Stats."""
+    return _reproject_device("reproject_motion_into", color, variance, albedo, normal, depth, prev_point, cur, prev, out_color, out_variance, out_cv,
+                             out_length, history, alpha, depth_tolerance, normal_threshold, max_history, flags, stream_ptr)
 
 
 class TemporalAccumulator:
@@ -1124,7 +1228,11 @@ class TemporalAccumulator:
     interleave: render_camera_denoised's rules) and the first seed; alpha, depth_tolerance, normal_threshold and max_history are
     trt_reproject's, aov_spp and samples_per_call render_camera_denoised's, denoise_kw (iterations, sigma_normal, sigma_depth,
     sigma_luminance) denoise_into's.  The history lives in torch tensors on the renderer's device and belongs to this object alone: the
-    handle keeps nothing, and two accumulators on one renderer do not interact."""
+    handle keeps nothing, and two accumulators on one renderer do not interact.
+    Geometry that moves keeps its history too: after Renderer.update_geometry_from(v1) (or update_geometry) pass the vertices the handle had
+    when the previous frame was rendered, frame(camera, moved_from=v0), and every pixel looks its history up where the surface it shows
+    was then.  The loop is `r.update_geometry_from(v1); acc.frame(cam, moved_from=v0)`; without moved_from a moved surface keeps or loses
+    its history by the depth and normal tests alone, as trt_reproject documents."""
 
     def __init__(self, renderer, params, alpha=0.2, depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, aov_spp=None,
                  samples_per_call=16, **denoise_kw):
@@ -1148,16 +1256,33 @@ class TemporalAccumulator:
         self._camera = None
 
     def reset(self):
-        """Drops the history: the next frame is a first frame (after a cut, or after trt_update_geometry moved the scene)."""
+        """Drops the history: the next frame is a first frame.  For a cut, or a change frame(moved_from=...) cannot follow (new topology,
+        a surface turned by more than the normal threshold allows); geometry moved by trt_update_geometry alone needs no reset: give
+        frame() the previous vertices."""
         self._history = None
         self._camera = None
 
-    def frame(self, camera, on_device=False):
+    def frame(self, camera, on_device=False, moved_from=None):
         """Renders the frame seen by `camera` with seed params.seed + frame_index (mod 2^32), accumulates and denoises it.  -> dict(color,
         variance, albedo, normal, depth: the frame's own buffers; accumulated, accumulated_variance: the blend with the reprojected history;
         history_length; denoised: the filtered accumulated image) as float32 arrays (on_device: torch tensors on the renderer's device), and
-        stats: the Stats of every call summed."""
+        stats: the Stats of every call summed.
+        moved_from: None, or the tri_v the handle's geometry had when the previous frame was rendered (float32 [n_tris, 3, 3], a torch tensor
+        on the renderer's device or a numpy array): the history is then found through center_rays -> Renderer.trace_points_into(...,
+        moved_from) -> reproject_motion_into, all on the frame's stream, in place of reproject_into.  Its shape is checked before anything
+        is rendered; on a first frame (or after reset()) there is no history to look up, and nothing is traced."""
         import torch
+        if moved_from is not None:
+            if _is_torch(moved_from):
+                ok = moved_from.dim() == 3 and tuple(moved_from.shape[1:]) == (3, 3) and str(moved_from.dtype) == "torch.float32"
+            else:
+                moved_from = np.ascontiguousarray(moved_from, dtype=np.float32)
+                ok = moved_from.ndim == 3 and moved_from.shape[1:] == (3, 3)
+            if not ok:
+                raise TrtError("TemporalAccumulator.frame: moved_from must be a float32 array or tensor of shape (n_tris, 3, 3)")
+            n_tris = self.renderer._scene.flat.contents.n_tris
+            if moved_from.shape[0] != n_tris:
+                raise TrtError(f"TemporalAccumulator.frame: moved_from holds {moved_from.shape[0]} triangles, the handle {n_tris}")
         p = Params.from_buffer_copy(self.params)
         p.seed = (self.params.seed + self.frame_index) & 0xFFFFFFFF
         color, variance, aov, total, stream = self.renderer._camera_denoiser_inputs(p, camera, self.render_kw["aov_spp"], self.render_kw["samples_per_call"],
@@ -1165,8 +1290,16 @@ class TemporalAccumulator:
         h, w = color.shape[0], color.shape[1]
         acc, acc_var = torch.empty_like(color), torch.empty_like(variance)
         cv, length = torch.empty((h, w, 4), dtype=torch.float32, device=color.device), torch.empty_like(variance)
-        _add_stats(total, reproject_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], camera, self._camera, acc, acc_var, cv, length,
-                                         history=self._history, stream_ptr=stream, **self.reproject_kw))
+        if moved_from is None or self._history is None:
+            _add_stats(total, reproject_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], camera, self._camera, acc, acc_var, cv, length,
+                                             history=self._history, stream_ptr=stream, **self.reproject_kw))
+        else:
+            v0 = moved_from if _is_torch(moved_from) else torch.from_numpy(moved_from).to(color.device)
+            org, dirs = center_rays(camera, w, h, flags=self.reproject_kw["flags"], device=color.device)
+            point = torch.empty((h * w, 3), dtype=torch.float32, device=color.device)
+            _add_stats(total, self.renderer.trace_points_into(org, dirs, v0.contiguous(), point, stream_ptr=stream))
+            _add_stats(total, reproject_motion_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], point.view(h, w, 3), camera, self._camera,
+                                                    acc, acc_var, cv, length, history=self._history, stream_ptr=stream, **self.reproject_kw))
         denoised = torch.empty_like(color)
         _add_stats(total, denoise_into(acc, acc_var, aov["albedo"], aov["normal"], aov["depth"], denoised, stream_ptr=stream, **self.denoise_kw))
         self._history = {"cv": cv, "length": length, "normal": aov["normal"], "depth": aov["depth"]}

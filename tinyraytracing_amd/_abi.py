@@ -109,7 +109,8 @@ class GeometryUpdate(C.Structure):
 HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_device", "trt_render_samples", "trt_render_pixels", "trt_render_pixels_device", "trt_render_rays", "trt_render_rays_device",
                "trt_camera_rays", "trt_camera_rays_device", "trt_render_aov",
                "trt_render_aov_device", "trt_aov_rays", "trt_aov_rays_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
-               "trt_trace_occluded_device", "trt_denoise", "trt_denoise_device", "trt_reproject", "trt_reproject_device",
+               "trt_trace_occluded_device", "trt_trace_points", "trt_trace_points_device", "trt_denoise", "trt_denoise_device", "trt_reproject", "trt_reproject_device",
+               "trt_reproject_motion", "trt_reproject_motion_device",
                "trt_update_geometry", "trt_update_geometry_device", "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
 HOST_SYMBOLS = ["trth_scene_load", "trth_scene_load_opts", "trth_scene_drop_tris", "trth_scene_add_soup", "trth_scene_add_blob", "trth_scene_add_lamps",
@@ -246,10 +247,15 @@ def load_hip():
     lib.trt_trace_occluded.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                        C.POINTER(C.c_uint8), C.POINTER(Stats)]
     lib.trt_trace_occluded_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.trt_trace_points.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32,
+                                     C.POINTER(C.c_float), C.POINTER(Stats)]
+    lib.trt_trace_points_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     lib.trt_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 6 + [C.POINTER(Stats)]
     lib.trt_denoise_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.POINTER(Stats)]
     lib.trt_reproject.argtypes = [C.c_int, C.POINTER(ReprojectParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 13 + [C.POINTER(Stats)]
     lib.trt_reproject_device.argtypes = [C.c_int, C.POINTER(ReprojectParams), C.c_int, C.c_int] + [C.c_void_p] * 14 + [C.POINTER(Stats)]
+    lib.trt_reproject_motion.argtypes = [C.c_int, C.POINTER(ReprojectParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 14 + [C.POINTER(Stats)]
+    lib.trt_reproject_motion_device.argtypes = [C.c_int, C.POINTER(ReprojectParams), C.c_int, C.c_int] + [C.c_void_p] * 15 + [C.POINTER(Stats)]
     lib.trt_update_geometry.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_uint32, C.POINTER(Stats)]
     lib.trt_update_geometry_device.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
     lib.trt_destroy.argtypes = [C.c_void_p]

@@ -1775,28 +1775,33 @@ struct RayBatch {
     int32_t* tri;
     float* uv;
     uint8_t* occluded;   // occlusion
+    // trt_trace_points*: other coordinates of the handle's triangles and the points on them; t, tri and uv are then null
+    const float* tri_v_other = nullptr;
+    float* point = nullptr;
 };
 
 // The ray-batch entries (trt_trace_closest*, trt_trace_occluded*): the checks of include/trt.h, the rays packed into io_buf (host arrays staged
-// there first), one traversal launch with k_trace_fix behind it, then for closest hits k_unpack_hits into the caller's arrays (device entries) or
-// into io_buf and from there to the host.  query: QUERY_NONE (no bound: trt_trace_closest's own kernels, k_trace_closest), QUERY_CLOSEST or
+// there first), one traversal launch with k_trace_fix behind it, then for closest hits k_unpack_hits (trt_trace_points*: k_hit_points) into the
+// caller's arrays (device entries) or into io_buf and from there to the host.  query: QUERY_NONE (no bound: trt_trace_closest's own kernels, k_trace_closest), QUERY_CLOSEST or
 // QUERY_OCCLUDED (k_trace_query, the bound in rb.w).  Host entries run on the null stream and copy after it is synchronised.
 int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool host, hipStream_t stream, trt_stats* stats_out, const char* what)
 {
-    const bool occ = query == QUERY_OCCLUDED;
-    if (!h || !io.org || !io.dir || (occ ? !io.occluded : (!io.t || !io.tri))) return fail(TRT_EINVAL, std::string(what) + ": null argument");
+    const bool occ = query == QUERY_OCCLUDED, pts = io.tri_v_other || io.point;
+    if (!h || !io.org || !io.dir || (occ ? !io.occluded : pts ? (!io.tri_v_other || !io.point) : (!io.t || !io.tri)))
+        return fail(TRT_EINVAL, std::string(what) + ": null argument");
     if (n == 0) return TRT_OK;
     if (n > 0x7FFF0000ull) return fail(TRT_EINVAL, "ray batch too large");
     HIPC(hipSetDevice(h->device));
     const uint32_t n32 = (uint32_t)n;
     const size_t in_bytes = (size_t)n * 3 * sizeof(float), q16 = (size_t)n * sizeof(f4), f_bytes = (size_t)n * sizeof(float);
     // host entries stage the caller's rays (org, dir, t_max) and, once they are packed, the results over them (t, tri, uv; or the bytes)
-    const size_t stage_in = 2 * in_bytes + (io.t_max ? f_bytes : 0), stage_out = occ ? (size_t)n : (io.uv ? 4 : 2) * f_bytes;
+    const size_t stage_in = 2 * in_bytes + (io.t_max ? f_bytes : 0), stage_out = occ ? (size_t)n : pts ? in_bytes : (io.uv ? 4 : 2) * f_bytes;
+    const size_t other_bytes = (size_t)h->sc.n_tris * 9 * sizeof(float);  // tri_v_other of a host call, staged beside the rays
     // io_buf: the packed rays, the hit records (8 bytes on a hit8 scene; none for occlusion), the staging area of a host call, then the block
     // cleared first (DeviceStats, the redo counters) and the redo list
     Layout L;
     const size_t o_ra = L.add(q16, 16), o_rb = L.add(q16, 16), o_hit = L.add(occ ? 0 : (h->hit8 ? q16 / 2 : q16), 16);
-    const size_t o_stage = L.add(host ? std::max(stage_in, stage_out) : 0, 16);
+    const size_t o_stage = L.add(host ? std::max(stage_in, stage_out) : 0, 16), o_other = L.add(host && pts ? other_bytes : 0, 16);
     const size_t o_stats = L.add(sizeof(DeviceStats), 256), o_redo = L.add(2 * sizeof(uint32_t), 64), o_idx = L.add((size_t)n * sizeof(uint32_t), 256);
     if (int e = h->io_buf.ensure(L.bytes)) return e;
     char* b = (char*)h->io_buf.p;
@@ -1815,6 +1820,11 @@ int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool ho
         dev.tri = (int32_t*)(stage + f_bytes);
         dev.uv = io.uv ? (float*)(stage + 2 * f_bytes) : nullptr;
         dev.occluded = (uint8_t*)stage;
+        if (pts) {
+            dev.point = (float*)stage;
+            dev.tri_v_other = (const float*)(b + o_other);
+            HIPC(hipMemcpyAsync((void*)dev.tri_v_other, io.tri_v_other, other_bytes, hipMemcpyHostToDevice, stream));
+        }
         HIPC(hipMemcpyAsync((void*)dev.org, io.org, in_bytes, hipMemcpyHostToDevice, stream));
         HIPC(hipMemcpyAsync((void*)dev.dir, io.dir, in_bytes, hipMemcpyHostToDevice, stream));
         if (io.t_max) HIPC(hipMemcpyAsync((void*)dev.t_max, io.t_max, f_bytes, hipMemcpyHostToDevice, stream));
@@ -1835,7 +1845,10 @@ int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool ho
     else
         launchTraceClosest(h, queryKernel(h, query), queryFixKernel(h, query), stream, (uint32_t*)h->spill.p, src, occ ? (f4*)dev.occluded : hit, n32, d_stats, redo);
     HIPC(hipEventRecord(e1, stream));
-    if (!occ) {
+    if (pts) {
+        if (h->hit8) hipLaunchKernelGGL(k_hit_points<true>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.tri_v_other, dev.point, n32);
+        else hipLaunchKernelGGL(k_hit_points<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.tri_v_other, dev.point, n32);
+    } else if (!occ) {
         if (h->hit8) hipLaunchKernelGGL(k_unpack_hits<true>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.t, dev.tri, dev.uv, n32);
         else hipLaunchKernelGGL(k_unpack_hits<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.t, dev.tri, dev.uv, n32);
     }
@@ -1847,6 +1860,7 @@ int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool ho
     HIPC(hipEventElapsedTime(&ms, e0, e1));
     if (host) {
         if (occ) HIPC(hipMemcpy(io.occluded, dev.occluded, n, hipMemcpyDeviceToHost));
+        else if (pts) HIPC(hipMemcpy(io.point, dev.point, in_bytes, hipMemcpyDeviceToHost));
         else {
             HIPC(hipMemcpy(io.t, dev.t, f_bytes, hipMemcpyDeviceToHost));
             HIPC(hipMemcpy(io.tri, dev.tri, f_bytes, hipMemcpyDeviceToHost));
@@ -1881,6 +1895,32 @@ int trt_trace_closest_device(trt_handle* h, uint64_t n, const float* org, const 
 {
     return traceBatch(h, n, RayBatch{org, dir, t_max, t, tri, uv, nullptr}, t_max ? QUERY_CLOSEST : QUERY_NONE, false, (hipStream_t)hip_stream, stats,
                       "trt_trace_closest_device");
+}
+
+namespace {
+// trt_trace_points*: the checks that come before traceBatch's own (a null array, then the triangle count)
+int tracePoints(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* tri_v_other, uint32_t n_tris, float* point, bool host,
+                hipStream_t stream, trt_stats* stats, const char* what)
+{
+    if (!h || !org || !dir || !tri_v_other || !point) return fail(TRT_EINVAL, std::string(what) + ": null argument");
+    if (n_tris != h->sc.n_tris) return fail(TRT_EINVAL, std::string(what) + ": n_tris differs from the handle's");
+    RayBatch io{org, dir, nullptr, nullptr, nullptr, nullptr, nullptr};
+    io.tri_v_other = tri_v_other;
+    io.point = point;
+    return traceBatch(h, n, io, QUERY_NONE, host, stream, stats, what);
+}
+}  // namespace
+
+int trt_trace_points(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* tri_v_other, uint32_t n_tris, float* point,
+                     trt_stats* stats)
+{
+    return tracePoints(h, n, org, dir, tri_v_other, n_tris, point, true, nullptr, stats, "trt_trace_points");
+}
+
+int trt_trace_points_device(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* tri_v_other, uint32_t n_tris, float* point,
+                            void* hip_stream, trt_stats* stats)
+{
+    return tracePoints(h, n, org, dir, tri_v_other, n_tris, point, false, (hipStream_t)hip_stream, stats, "trt_trace_points_device");
 }
 
 int trt_trace_occluded(trt_handle* h, uint64_t n, const float* org, const float* dir, const float* t_max, uint8_t* occluded, trt_stats* stats)
@@ -2337,24 +2377,26 @@ struct ReprojectIo {
     const float *color, *variance, *albedo, *normal, *depth;
     const float *prev_cv, *prev_len, *prev_normal, *prev_depth;
     float *out_color, *out_variance, *out_cv, *out_len;
+    const float* prev_point = nullptr;  // trt_reproject_motion*: W*H*3, required there
 };
 
 // The checks of include/trt.h, in its order; fills the kernel's arguments.
-int reprojectArgs(const trt_reproject_params* prm, int width, int height, const ReprojectIo& io, bool host, trt_rp_args& a, const char* what)
+int reprojectArgs(const trt_reproject_params* prm, int width, int height, const ReprojectIo& io, bool host, bool motion, trt_rp_args& a, const char* what)
 {
-    const bool required = io.color && io.variance && io.albedo && io.normal && io.depth && io.out_color && io.out_variance && io.out_cv && io.out_len;
+    const bool required = io.color && io.variance && io.albedo && io.normal && io.depth && io.out_color && io.out_variance && io.out_cv && io.out_len &&
+                          (!motion || io.prev_point);
     const int given = (io.prev_cv ? 1 : 0) + (io.prev_len ? 1 : 0) + (io.prev_normal ? 1 : 0) + (io.prev_depth ? 1 : 0);
     if (const char* msg = trt_rp_check(prm, width, height, required, given, a)) return fail(TRT_EINVAL, std::string(what) + ": " + msg);
     if (!host && ((((uintptr_t)io.out_cv) | ((uintptr_t)io.prev_cv)) & 15u)) return fail(TRT_EINVAL, std::string(what) + ": prev_cv and out_cv must be 16-byte aligned");
     return TRT_OK;
 }
 
-// One call: (host: upload) -> k_reproject -> (host: download), all on `stream`.
+// One call: (host: upload) -> k_reproject, or k_reproject_motion with `motion` -> (host: download), all on `stream`.
 int reproject(int device, const trt_reproject_params* prm, int width, int height, const ReprojectIo& io, bool host, hipStream_t stream, trt_stats* stats,
-              const char* what)
+              const char* what, bool motion = false)
 {
     trt_rp_args a{};
-    if (int e = reprojectArgs(prm, width, height, io, host, a, what)) return e;
+    if (int e = reprojectArgs(prm, width, height, io, host, motion, a, what)) return e;
     if (int e = useDevice(device)) return e;
     const size_t n = (size_t)width * (size_t)height, f1 = n * sizeof(float), f3 = 3 * f1, f4 = 4 * f1;
     const bool hist = a.history != 0;
@@ -2366,11 +2408,13 @@ int reproject(int device, const trt_reproject_params* prm, int width, int height
         const size_t o_c = L.add(f3, 256), o_v = L.add(f1, 256), o_a = L.add(f3, 256), o_n = L.add(f3, 256), o_z = L.add(f1, 256);
         const size_t o_pc = L.add(hist ? f4 : 0, 256), o_pl = L.add(hist ? f1 : 0, 256), o_pn = L.add(hist ? f3 : 0, 256), o_pz = L.add(hist ? f1 : 0, 256);
         const size_t o_oc = L.add(f3, 256), o_ov = L.add(f1, 256), o_ocv = L.add(f4, 256), o_ol = L.add(f1, 256);
+        const size_t o_pp = L.add(motion ? f3 : 0, 256);
         HIPC(hipMalloc(&S.p, L.bytes));
         char* b = (char*)S.p;
         dev = ReprojectIo{(const float*)(b + o_c), (const float*)(b + o_v), (const float*)(b + o_a), (const float*)(b + o_n), (const float*)(b + o_z),
                           hist ? (const float*)(b + o_pc) : nullptr, hist ? (const float*)(b + o_pl) : nullptr, hist ? (const float*)(b + o_pn) : nullptr,
                           hist ? (const float*)(b + o_pz) : nullptr, (float*)(b + o_oc), (float*)(b + o_ov), (float*)(b + o_ocv), (float*)(b + o_ol)};
+        if (motion) dev.prev_point = (const float*)(b + o_pp);
     }
     HIPC(hipEventRecord(S.ev[0], stream));
     if (host) {
@@ -2379,6 +2423,7 @@ int reproject(int device, const trt_reproject_params* prm, int width, int height
         HIPC(hipMemcpyAsync((void*)dev.albedo, io.albedo, f3, hipMemcpyHostToDevice, stream));
         HIPC(hipMemcpyAsync((void*)dev.normal, io.normal, f3, hipMemcpyHostToDevice, stream));
         HIPC(hipMemcpyAsync((void*)dev.depth, io.depth, f1, hipMemcpyHostToDevice, stream));
+        if (motion) HIPC(hipMemcpyAsync((void*)dev.prev_point, io.prev_point, f3, hipMemcpyHostToDevice, stream));
         if (hist) {
             HIPC(hipMemcpyAsync((void*)dev.prev_cv, io.prev_cv, f4, hipMemcpyHostToDevice, stream));
             HIPC(hipMemcpyAsync((void*)dev.prev_len, io.prev_len, f1, hipMemcpyHostToDevice, stream));
@@ -2388,9 +2433,13 @@ int reproject(int device, const trt_reproject_params* prm, int width, int height
     }
     const dim3 grid((unsigned)((width + RP_BX - 1) / RP_BX), (unsigned)((height + RP_BY - 1) / RP_BY)), block(RP_BX, RP_BY);
     HIPC(hipEventRecord(S.ev[1], stream));
-    hipLaunchKernelGGL(k_reproject, grid, block, 0, stream, a, dev.color, dev.variance, dev.albedo, dev.normal, dev.depth,
-                       trt_rp_fetch{(const trt_dn4*)dev.prev_cv, dev.prev_len, dev.prev_normal, dev.prev_depth}, dev.out_color, dev.out_variance,
-                       (trt_dn4*)dev.out_cv, dev.out_len);
+    const trt_rp_fetch fetch{(const trt_dn4*)dev.prev_cv, dev.prev_len, dev.prev_normal, dev.prev_depth};
+    if (motion)
+        hipLaunchKernelGGL(k_reproject_motion, grid, block, 0, stream, a, dev.color, dev.variance, dev.albedo, dev.normal, dev.depth, dev.prev_point, fetch,
+                           dev.out_color, dev.out_variance, (trt_dn4*)dev.out_cv, dev.out_len);
+    else
+        hipLaunchKernelGGL(k_reproject, grid, block, 0, stream, a, dev.color, dev.variance, dev.albedo, dev.normal, dev.depth, fetch, dev.out_color,
+                           dev.out_variance, (trt_dn4*)dev.out_cv, dev.out_len);
     HIPC(hipGetLastError());
     HIPC(hipEventRecord(S.ev[2], stream));
     if (host) {
@@ -2436,6 +2485,26 @@ int trt_reproject_device(int device, const trt_reproject_params* params, int wid
     return reproject(device, params, width, height,
                      ReprojectIo{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len},
                      false, (hipStream_t)hip_stream, stats, "trt_reproject_device");
+}
+
+int trt_reproject_motion(int device, const trt_reproject_params* params, int width, int height, const float* color, const float* variance,
+                         const float* albedo, const float* normal, const float* depth, const float* prev_point, const float* prev_cv,
+                         const float* prev_len, const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance,
+                         float* out_cv, float* out_len, trt_stats* stats)
+{
+    ReprojectIo io{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len};
+    io.prev_point = prev_point;
+    return reproject(device, params, width, height, io, true, nullptr, stats, "trt_reproject_motion", true);
+}
+
+int trt_reproject_motion_device(int device, const trt_reproject_params* params, int width, int height, const float* color, const float* variance,
+                                const float* albedo, const float* normal, const float* depth, const float* prev_point, const float* prev_cv,
+                                const float* prev_len, const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance,
+                                float* out_cv, float* out_len, void* hip_stream, trt_stats* stats)
+{
+    ReprojectIo io{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len};
+    io.prev_point = prev_point;
+    return reproject(device, params, width, height, io, false, (hipStream_t)hip_stream, stats, "trt_reproject_motion_device", true);
 }
 
 }  // extern "C"

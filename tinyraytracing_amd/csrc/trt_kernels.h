@@ -1833,6 +1833,36 @@ __global__ __launch_bounds__(256) void k_unpack_hits(SceneDev sc, const f4* __re
     }
 }
 
+// ray-batch entries (trt_trace_points*): the hit records into point[n][3] — hitPoint() on the caller's coordinates tri_v_other[n_tris][3][3] of
+// the triangle that was hit, three quiet NaNs for a miss.  (u, v) as k_unpack_hits has them (HIT8: formed on the packed ray).  Per ray 16 or 8
+// bytes of record (and the 32-byte ray with HIT8) stream in, the triangle's 36 bytes are gathered, 12 bytes go out; t, tri and uv are not stored.
+template <bool HIT8>
+__global__ __launch_bounds__(256) void k_hit_points(SceneDev sc, const f4* __restrict__ ra, const f4* __restrict__ rb, const f4* __restrict__ hit,
+                                                    const float* __restrict__ tri_v_other, float* __restrict__ point, uint32_t n)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        f4 hit4;
+        if constexpr (HIT8) {
+            const trt_v2f h = reinterpret_cast<const trt_v2f*>(hit)[i];
+            hit4 = mk4(h.x, h.y, 0.0f, 0.0f);
+            hitBarycentrics(sc.tri_isect, ra[i], rb[i], hit4);
+        } else {
+            hit4 = hit[i];
+        }
+        const int32_t tri = (int32_t)f2u(hit4.y);
+        f3 p = mk3(u2f(TRT_POINT_MISS_BITS), u2f(TRT_POINT_MISS_BITS), u2f(TRT_POINT_MISS_BITS));
+        if (tri >= 0) {
+            const float* c = tri_v_other + (size_t)tri * 9;
+            const float v9[9] = {c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8]};
+            p = hitPoint(v9, hit4.z, hit4.w);
+        }
+        point[(size_t)i * 3] = p.x;
+        point[(size_t)i * 3 + 1] = p.y;
+        point[(size_t)i * 3 + 2] = p.z;
+    }
+}
+
 // ray-batch entry (trt_trace_closest): SoA repack of host org/dir arrays
 __global__ __launch_bounds__(256) void k_pack_rays(const float* __restrict__ org, const float* __restrict__ dir, f4* __restrict__ ra, f4* __restrict__ rb, uint32_t n)
 {

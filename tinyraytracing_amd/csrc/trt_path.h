@@ -304,6 +304,16 @@ TRT_HD inline bool triTest(const TriIsect& T, f3 o, f3 d, float& t_out, float& u
     return true;
 }
 
+// trt_trace_points (include/trt.h): the point with the barycentrics (u, v) of a hit on OTHER coordinates v9[3][3] of the triangle that was
+// hit — where that piece of surface is, or was, on another set of vertex positions.  w = (1 - u) - v; per component (w a + u b) + v c: plain
+// fp32 in this order, no contraction, the same bits on every build.  A miss is three quiet NaNs.
+#define TRT_POINT_MISS_BITS 0x7FC00000u
+TRT_HD inline f3 hitPoint(const float* v9, float u, float v)
+{
+    const float w = (1.0f - u) - v;
+    return mk3((w * v9[0] + u * v9[3]) + v * v9[6], (w * v9[1] + u * v9[4]) + v * v9[7], (w * v9[2] + u * v9[5]) + v * v9[8]);
+}
+
 // ---------------------------------------------------- interactAABB (a4) ----
 // bvh.cpp:231-245: slab test; `entry` receives t0 (used for ordering/culling).
 // trt_fminf / trt_fmaxf (trt_prims.h: fminf / fmaxf, with the zeros ordered on every build) differ

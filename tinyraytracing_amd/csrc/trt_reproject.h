@@ -241,6 +241,65 @@ static inline TRT_HD trt_rp_pixel_out trt_rp_pixel(const trt_rp_args& a, const H
     return o;
 }
 
+// ---- trt_reproject_motion: the surface may have moved ------------------------------------------------------------------------------------
+// Steps 3 and 4 with the world point given: `point` is where the surface seen through the pixel was at the time of the history frame
+// (trt_trace_points on the geometry of that time).  From v = point - prev.eye on, trt_rp_project's operations in trt_rp_project's order, so
+// the point that function forms itself gives that function's bits.  a.cur and a.same are not used: a still camera does not mean a still
+// surface.  false: no such place — anything that is not a number (a miss of trt_trace_points is three NaNs), a point behind or on the
+// previous eye, a degenerate camera, a z' that is not finite (a point some 1e19 away, whose |v|^2 leaves fp32).
+static inline TRT_HD bool trt_rp_project_point(const trt_rp_args& a, const float* point, float& fx, float& fy, float& zp)
+{
+    const float W = (float)a.width, H = (float)a.height;
+    float v[3], A[3];
+    TRT_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        v[k] = point[k] - a.prev.eye[k];
+        A[k] = a.prev.lower_left_corner[k] - a.prev.eye[k];
+    }
+    const float det = trt_rp_det(A, a.prev.horizontal, a.prev.vertical);
+    if (det == 0.0f) return false;
+    const float k = trt_rp_det(v, a.prev.horizontal, a.prev.vertical) / det;
+    if (!(k > 0.0f)) return false;
+    const float sp = (trt_rp_det(A, v, a.prev.vertical) / det) / k;
+    const float tp = (trt_rp_det(A, a.prev.horizontal, v) / det) / k;
+    if (a.fixed) {
+        fx = sp * W - 0.5f;
+        fy = ((float)(a.height - 1) + 0.5f) - tp * H;
+    } else {
+        fx = sp * (W - 1.0f);
+        fy = H - tp * (H - 1.0f);
+    }
+    zp = trt_sqrt(trt_rp_dot(v, v));
+    return zp <= 3.4028235e38f;
+}
+
+// Steps 1 to 7 of one pixel (where it lies in the current image does not matter) with steps 3 and 4 taken from prev_point[3]: trt_rp_pixel's functions in trt_rp_pixel's order otherwise.
+template <class H>
+static inline TRT_HD trt_rp_pixel_out trt_rp_pixel_motion(const trt_rp_args& a, const H& hist, const float* color, float variance,
+                                                          const float* albedo, const float* normal, float depth, const float* prev_point)
+{
+    trt_rp_pixel_out o;
+    const trt_dn4 f = trt_dn_factor(albedo[0], albedo[1], albedo[2]);
+    const trt_dn4 c = trt_dn_demodulate(color[0], color[1], color[2], variance, f);
+    o.color[0] = color[0];
+    o.color[1] = color[1];
+    o.color[2] = color[2];
+    o.variance = variance;
+    o.cv = c;
+    o.len = 1.0f;
+    if (!a.history || !trt_dn_hit(depth)) return o;
+    float fx, fy, zp;
+    if (!trt_rp_project_point(a, prev_point, fx, fy, zp)) return o;
+    const trt_rp_history h = trt_rp_gather(a, hist, fx, fy, zp, normal);
+    if (!h.found) return o;
+    o.cv = trt_rp_blend(a, c, h.cv, h.len, o.len);
+    trt_dn_remodulate(o.cv, f, o.color);
+    const float l = trt_dn_lum(f.x, f.y, f.z);
+    const float m = l > 1e-6f ? l : 1e-6f;
+    o.variance = o.cv.w * (m * m);
+    return o;
+}
+
 // The history in row-major global memory with 16-byte aligned cv records: the fetch of the kernel (the CPU build reads cv float by float).
 struct trt_rp_fetch {
     const trt_dn4* cvb;
