@@ -109,6 +109,8 @@ struct trt_handle {
     bool hit8 = false;        // and the render's hit records are 8 bytes (t, bits(tri)); k_shade forms (u, v) itself — needs k_shade<31> (every table in LDS)
     bool bin_walk = false;    // and the closest-hit queue kernel sorts each wave's rays by the leaves they reach (trt_kernels.h traceQueueBinned; TRT_BIN_WALK=0 at
                               // trt_create keeps traceQueueUniform's kernel: A/B, tests)
+    bool fuse_primary = false;  // and, with one light, bounce 0 of a tile render is ONE kernel: k_shade's FUSE flavour walks the camera rays itself, no hit record
+                                // is written or read (trt_kernels.h fusedWalk; TRT_FUSE_PRIMARY=0 at trt_create keeps the two kernels: A/B, tests)
     int node_kind = 0;        // what the persistent traversal kernels walk: 0 exact 128-B 4-wide nodes, 1 compressed 80-B 8-wide nodes (trt_oct.h)
     uint32_t oct_levels = 0;  // nodes on the longest root path of the oct tree
     bool dbg = false;         // TRT_DEBUG at trt_create: every render prints which k_shade variant it runs
@@ -419,6 +421,8 @@ FixKernel queryFixKernel(const trt_handle* h, int query)
     if (!fixKernel(h, query == QUERY_OCCLUDED, 0)) return nullptr;
     return query == QUERY_OCCLUDED ? k_trace_fix<true, 0, QUERY_OCCLUDED> : k_trace_fix<false, 0, QUERY_CLOSEST>;
 }
+// Bounce 0 of a tile render on a handle with fuse_primary: camera ray, closest hit and shading in one launch
+ShadeKernel fusedShadeKernel() { return k_shade<31u, SHADE_ONE, false, TRT_SHADE1_BLOCK, TRT_SHADE1_WAVES, true, true>; }
 ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list, bool hit8)
 {
     if (hit8) {  // trt_create sets hit8 only with tabs == 31
@@ -755,6 +759,9 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->bin_walk = h->hit8;  // (the flags in LDS and the 8-byte records: what traceQueueBinned's kernel is built for)
     if (const char* e = std::getenv("TRT_BIN_WALK")) h->bin_walk = h->bin_walk && std::atoi(e) != 0;
     if (im.dbg) std::fprintf(stderr, "trt_create: slim walk %d, 8-byte hit records %d, binned walk %d\n", (int)h->slim_walk, (int)h->hit8, (int)h->bin_walk);
+    h->fuse_primary = h->hit8 && s->n_lights == 1;  // (k_shade's one-light flavour on the 8-byte records: what the FUSE kernel is built for)
+    if (const char* e = std::getenv("TRT_FUSE_PRIMARY")) h->fuse_primary = h->fuse_primary && std::atoi(e) != 0;
+    if (im.dbg) std::fprintf(stderr, "trt_create: fused primary %d\n", (int)h->fuse_primary);
 
     // traversal spill area: levels beyond the LDS stack, for the largest grid
     // (k_trace_fix / k_tail walk the caller's BVH2 itself for the rays of raySpecial(), trt_path.h: one entry per level of it)
@@ -779,6 +786,7 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
                     for (bool hit8 : {false, true})
                         if (!hit8 || tabs == 31u)
                             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shadeKernel(tabs, lights, list, hit8)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fusedShadeKernel()), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
     }
 
     *out = h.release();
@@ -1126,11 +1134,14 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const ShadowKernel shadow_k = shadowKernel(h, count);
     const ShadeKernel shade_k = shadeKernel(h->shade_tabs, lights, in.list, h->hit8);
     const TailKernel tail_k = tailKernel(count, in.list);
+    // bounce 0 in one kernel (k_shade's FUSE flavour): tile renders on a handle set up for it; a counting render keeps the two kernels and their counters
+    const bool fuse = h->fuse_primary && lights == SHADE_ONE && !in.list && !in.rays && !count;
     const ShadeArgs shade_args = shadeArgsOf(h, p, in, d_table, rows_lds, d_stats);
     const TileDesc& td = shade_args.td;
     if (h->dbg)
         std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"),
                      lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds, td.grid_ok);
+    if (h->dbg) std::fprintf(stderr, "%s: fused primary %d\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"), (int)fuse);
 
     Timer tm{h, (p->flags & TRT_FLAG_TIMING) != 0};
     trt_stats st;
@@ -1193,10 +1204,12 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     // trace + shade of the slot's current bounce, then the queue lengths on their way to the host
     auto issueFront = [&](PassSlot& S) -> int {
         const RaySource src{S.Q[S.cur].ra, S.Q[S.cur].rb, td, S.s0};
-        tm.launch(TRT_K_TRACE_CLOSEST, S.stream, st, [&] {
-            const bool generated = S.b == 0 && !in.rays;  // the rays of bounce 0 come from the camera, not from the queue
-            launchTraceClosest(h, generated ? camera_k : queue_k, generated ? camera_fix : queue_fix, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
-        });
+        const bool generated = S.b == 0 && !in.rays;  // the rays of bounce 0 come from the camera, not from the queue
+        const bool fused = fuse && generated;         // ... and k_shade traces them itself
+        if (!fused)
+            tm.launch(TRT_K_TRACE_CLOSEST, S.stream, st, [&] {
+                launchTraceClosest(h, generated ? camera_k : queue_k, generated ? camera_fix : queue_fix, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
+            });
         ShadeArgs A = shade_args;
         A.qin = S.Q[S.cur];
         A.hit = S.hit;
@@ -1211,7 +1224,8 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         A.s0 = S.s0;
         A.primary = (S.b == 0 && !in.rays) ? 1u : 0u;
         tm.launch(TRT_K_SHADE, S.stream, st, [&] {
-            hipLaunchKernelGGL(shade_k, dim3(std::min<uint32_t>((S.n_active + shade_block - 1) / shade_block, 65536u)), dim3(shade_block), h->shade_pad_lds, S.stream, h->sc, A);
+            hipLaunchKernelGGL(fused ? fusedShadeKernel() : shade_k, dim3(std::min<uint32_t>((S.n_active + shade_block - 1) / shade_block, 65536u)), dim3(shade_block),
+                               h->shade_pad_lds, S.stream, h->sc, A);
         });
         // (b, c) and (b + 1, c) of the counters in use -> host_counts[2 * c], [2 * c + 1], then the sequence word
         S.seq++;

@@ -200,6 +200,7 @@ __device__ inline unsigned long long waveSum(unsigned long long v)
 // Primary rays (main.cpp:88-95 + Camera::getRay, camera.cpp:19-28) have no kernel of their own:
 // primaryRay() (trt_path.h) is a pure function of the path id, evaluated in registers by the bounce-0
 // traversal kernel (PRIMARY) and again by k_shade, so no camera-ray queue is written to or read from HBM.
+// (k_shade's FUSE flavour evaluates it once and walks the ray itself: bounce 0 of a tile render on a one-light scene of the wave-uniform walk.)
 // path id i = s_local * npix + pixel-in-tile: a wave covers 64 neighbouring pixels.
 
 // ------------------------------------------------------------ K2 / K4 ----
@@ -1358,6 +1359,8 @@ struct RowsShade {
 // HIT8: the hit records are the 8-byte ones of the wave-uniform walk (storeResult), and the barycentrics of the winner are formed here, with the code
 // storeResult<false> runs for the 16-byte record: the same triangle test on the same ray, so the same bits.  The <= 64 intersection records of such a scene
 // (48 B each) are staged in LDS beside the tables of TABS, outside that mask.
+// FUSE (with HIT8, SHADE_ONE, tiles): bounce 0 only, launched in place of k_trace_closest<.., 1> + k_shade — no hit record and no intersection records in LDS
+// (fusedWalk / fusedPrimaryHit below).
 __device__ __forceinline__ void hitBarycentrics(const TriIsect* isect, const f4& ra, const f4& rb, f4& hit4)
 {
     const int32_t tri = (int32_t)f2u(hit4.y);
@@ -1369,6 +1372,90 @@ __device__ __forceinline__ void hitBarycentrics(const TriIsect* isect, const f4&
     hit4.z = u;
     hit4.w = v;
 }
+// FUSE (k_shade's bounce-0 flavour on a hit8 scene with one light, tile renders only): the camera ray's closest hit is found inside k_shade, so bounce 0
+// reads and writes no hit record and forms its camera ray once.  fusedWalk is uniformWalkImpl for that kernel — the same visit set, candidate order,
+// leaf-floor rule and fold — without the candidate queue in LDS (32 KB of a 512-thread block): a candidate's division, cuts and fold run in place, under
+// the candidates' lane mask.  flushPending runs them per lane in the order the candidates were found, which is the order here, so every lane folds the same
+// values in the same order: the same bits.  A wave of camera rays has one or two candidate triangles (4.4 triangle tests per ray, 4.8 per wave), not nearly
+// all of them as a wave of queue rays has.  The candidate's flag word is the scalar-loaded record's own (what the LDS copy of the flags holds), and the
+// winner's (un, vn, det) leave the walk with it: u = un / det, v = vn / det is what hitBarycentrics forms from the same triangle test on the same ray.
+template <bool GLM>
+__device__ __forceinline__ void fusedWalk(const SceneDev& sc, f3 o, f3 d, f3 inv, bool special, float& best_t, int32_t& best_tri, float& best_un,
+                                          float& best_vn, float& best_det)
+{
+    const uint32_t n_nodes = sc.n_nodes;
+    uint32_t reach = 1u;  // bit k: the ray reaches inner node k
+    uint32_t best_flags = 0u;
+    for (uint32_t ni = 0; ni < n_nodes; ++ni) {
+        const bool at = (reach >> ni) & 1u;
+        if (ballotb(at) == 0ull) continue;
+        const f4* np4 = reinterpret_cast<const f4*>(sc.nodes + ni);  // wave-uniform address
+        const f4 q0 = np4[0], q1 = np4[1], q2 = np4[2], q3 = np4[3];
+        float e0 = 0.0f, e1 = 0.0f;
+        bool h0 = at && boxTest(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, e0);
+        bool h1 = at && boxTest(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, e1);
+        if (GLM) {
+            float g0, g1;
+            const bool s0 = boxTestGlm(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, o, inv, g0), s1 = boxTestGlm(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, o, inv, g1);
+            if (special) { h0 = at && s0; h1 = at && s1; e0 = g0; e1 = g1; }
+        }
+        const float f0 = trt_leaf_floor(e0, sc.leaf_alpha), f1 = trt_leaf_floor(e1, sc.leaf_alpha);  // used only where the child is a leaf
+        const uint32_t child[2] = {f2u(q3.x), f2u(q3.y)};
+        const bool hc[2] = {h0, h1};
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const uint32_t ref = child[c];
+            if (!(ref & TRT_LEAF_BIT)) {
+                reach |= hc[c] ? (1u << ref) : 0u;
+                continue;
+            }
+            if (ballotb(hc[c]) == 0ull) continue;
+            const uint32_t first = TRT_LEAF_FIRST(ref), count = TRT_LEAF_COUNT(ref);
+            for (uint32_t k = 0; k < count; ++k) {  // interactBVHNode (bvh.cpp:211-229): index order
+                const TriIsect T = sc.tri_isect[first + k];  // wave-uniform address
+                float tn, un, vn, det;
+                bool ok_det, ok_in;
+                triCandidateParts(T, o, d, tn, un, vn, det, ok_det, ok_in);
+                if (ok_det && ok_in && hc[c]) {  // flushPending's step for this candidate, on the spot
+                    const float t = tn / det;
+                    if (!(t < TRT_T_MIN) && !(t < (c == 0 ? f0 : f1))) {  // bvh.cpp:189; and not in front of the box of its leaf (leafFloor(), trt_path.h)
+                        const int32_t j = (int32_t)(first + k);
+                        const uint32_t fl = f2u(T.c.z);
+                        bool take = t < best_t;
+                        if (t == best_t && best_tri >= 0) {
+                            const bool em = (fl & 1u) != 0, bem = (best_flags & 1u) != 0;
+                            const bool same_leaf = (uint32_t)best_tri >= first && (uint32_t)best_tri < first + count;
+                            take = same_leaf ? em : (em ? (!bem || j < best_tri) : (!bem && j > best_tri));
+                        }
+                        if (take) { best_t = t; best_tri = j; best_flags = fl; best_un = un; best_vn = vn; best_det = det; }
+                    }
+                }
+            }
+        }
+    }
+}
+// Bounce 0 of the FUSE flavour for the lane's camera ray (ra, rb): the hit record k_shade<HIT8> would read, with hitBarycentrics' (u, v), in registers.
+// One vote per wave picks the walk with the literal slab test for a wave that holds a ray with a zero direction component (as k_tail's uniformWalk does);
+// such rays are counted in DeviceStats::redo_rays as the camera kernel counts the ones it parks.  Called by the lanes that hold a path only (the votes of the
+// walk see the active lanes).
+__device__ __forceinline__ f4 fusedPrimaryHit(const SceneDev& sc, const f4& ra, const f4& rb, DeviceStats* stats)
+{
+    const f3 o = mk3(ra.x, ra.y, ra.z), d = mk3(ra.w, rb.x, rb.y);
+    const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    const bool special = raySpecial(inv);
+    float best_t = TRT_INF, un = 0.0f, vn = 0.0f, det = 1.0f;
+    int32_t best_tri = -1;
+    const unsigned long long m_sp = ballotb(special);
+    if (m_sp != 0ull) {  // (wave-uniform, rare)
+        fusedWalk<true>(sc, o, d, inv, special, best_t, best_tri, un, vn, det);
+        if ((threadIdx.x & 63u) == 0) atomicAdd(&stats->redo_rays, (uint32_t)__popcll(m_sp));  // (lane 0 of a wave is active whenever any lane is: i rises with the lane)
+    } else {
+        fusedWalk<false>(sc, o, d, inv, false, best_t, best_tri, un, vn, det);
+    }
+    float u = 0.0f, v = 0.0f;
+    if (best_tri >= 0) { u = un / det; v = vn / det; }
+    return mk4(best_t, u2f((uint32_t)best_tri), u, v);
+}
 template <int LIGHTS>
 __device__ inline ShadowQueue shadeQueue(const ShadeArgs& A, uint32_t li)
 {
@@ -1376,9 +1463,10 @@ __device__ inline ShadowQueue shadeQueue(const ShadeArgs& A, uint32_t li)
     return A.sq[li];
 }
 template <uint32_t TABS, int LIGHTS, bool LIST = false, int BLOCK = (LIGHTS == SHADE_ONE ? TRT_SHADE1_BLOCK : TRT_SHADEN_BLOCK),
-          int WAVES = (LIGHTS == SHADE_ONE ? TRT_SHADE1_WAVES : TRT_SHADEN_WAVES), bool HIT8 = false>
+          int WAVES = (LIGHTS == SHADE_ONE ? TRT_SHADE1_WAVES : TRT_SHADEN_WAVES), bool HIT8 = false, bool FUSE = false>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A)
 {
+    static_assert(!FUSE || (HIT8 && !LIST && LIGHTS == SHADE_ONE), "the fused bounce 0 is built for tile renders of one-light scenes of the wave-uniform walk");
     constexpr int TRT_SHADE_BLOCK = BLOCK;
     constexpr uint32_t TRT_SHADE_ROWS_LDS = shadeRowsLds(BLOCK);
     __shared__ uint32_t s_cnt[3 * (TRT_SHADE_BLOCK / 64 + 1)];
@@ -1386,7 +1474,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
     __shared__ uint32_t s_shaded, s_depth;  // s_depth: 1 + the deepest vertex of the block that hit something (0: none)
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[TABS ? TRT_SHADE_LDS_TABLE_BYTES / 4 : 4];
     __shared__ uint16_t s_rows[LIST ? 1 : TRT_SHADE_ROWS_LDS];
-    __shared__ __attribute__((aligned(16))) uint32_t s_isect[HIT8 ? 64 * 12 : 4];  // HIT8: the scene's intersection records (<= 64, trt_create)
+    __shared__ __attribute__((aligned(16))) uint32_t s_isect[HIT8 && !FUSE ? 64 * 12 : 4];  // HIT8: the scene's intersection records (<= 64, trt_create)
     const TriIsect* isect = reinterpret_cast<const TriIsect*>(s_isect);
     if (threadIdx.x == 0) { s_shaded = 0; s_depth = 0; }
     if (!LIST)
@@ -1416,6 +1504,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
     // is computed, so a tile starts on data that has already arrived.
     auto loadTile = [&](uint32_t i, f4& hit4, f4& ra, f4& rb, f4& bt) {
         hit4 = mk4(TRT_INF, u2f(0xFFFFFFFFu), 0.0f, 0.0f); ra = mk4(0, 0, 0, 0); rb = ra; bt = mk4(1.0f, 1.0f, 1.0f, 0.0f);
+        if (FUSE) return;  // bounce 0 only: the camera ray and its hit are formed in registers (fusedPrimaryHit)
         if (i < A.n) {
             if (HIT8) {
                 const trt_v2f h = TRT_LDQ2(1, reinterpret_cast<const trt_v2f*>(A.hit) + i);
@@ -1444,7 +1533,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
                 f4* l = reinterpret_cast<f4*>(s_tab);
                 if (TABS)
                     for (uint32_t w = threadIdx.x; w < A.lds_image_words; w += TRT_SHADE_BLOCK) l[w] = A.lds_image[w];
-                if (HIT8) {
+                if (HIT8 && !FUSE) {
                     f4* li = reinterpret_cast<f4*>(s_isect);
                     const uint32_t words = 3u * (sc.n_tris < 64u ? sc.n_tris : 64u);
                     for (uint32_t w = threadIdx.x; w < words; w += TRT_SHADE_BLOCK) li[w] = reinterpret_cast<const f4*>(sc.tri_isect)[w];
@@ -1455,7 +1544,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
             rows_visible = true;
         }
 #if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(hit4.x), "+v"(ra.x), "+v"(rb.x), "+v"(bt.x));  // keeps the four loads up here (the compiler would sink them behind the miss test)
+        if (!FUSE) asm volatile("" : "+v"(hit4.x), "+v"(ra.x), "+v"(rb.x), "+v"(bt.x));  // keeps the four loads up here (the compiler would sink them behind the miss test)
 #endif
 #if TRT_SHADE_PIPE
         loadTile(i + per_grid, n_hit, n_ra, n_rb, n_bt);  // n <= 0x7FFF0000 and per_grid <= 2^25: no wrap-around
@@ -1463,7 +1552,14 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         ShadeCtx c;
         c.had_hit = c.shade_ok = c.add_L = false;
         if (i < A.n) {
-            if (A.primary) {
+            if (FUSE) {
+                // camera ray, closest hit and (u, v) in registers.  The walk runs under this branch: its votes then range over the lanes that hold a path — the
+                // lanes beyond A.n are switched off, not carried along as invalid ones (hoisted out of the branch with a `valid` flag, the kernel needs scratch)
+                primaryRay(sc, A.td, A.s0, i, ra, rb, rows);
+                hit4 = fusedPrimaryHit(sc, ra, rb, A.stats);
+                shadeBegin(sc, A.td, A.s0, ra, rb, bt, hit4, c, rows);
+                A.Lacc[i] = c.add_L ? mk4(0.0f + c.addL.x, 0.0f + c.addL.y, 0.0f + c.addL.z, 0.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
+            } else if (A.primary) {
                 // every path passes here exactly once, hit or miss: L starts at 0 (+ the radiance of a directly
                 // visible light, pathTracing.cpp:9-12 through main.cpp:101)
                 primaryRay(sc, A.td, A.s0, i, ra, rb, rows);
