@@ -4,6 +4,9 @@ two kernels TRT_FUSE_PRIMARY=0 keeps, and against the CPU oracle — MI355X only
 The fused walk folds the same candidates in the same order, so every image and counter must come out bit-identical with the switch on
 and off, and equal to the oracle's.  Which route ran is read from the TRT_DEBUG lines (trt_create: fused primary ...; trt_render: fused
 primary ...) and asserted first.
+
+Everything here is the Cornell box (`back`, `lamps`), which has no two triangles at one distance and one or two candidates per wave: geometry on which
+the walk's tie rule, its size limits and hostile cameras decide the picture is in tests/test_gpu_tiny_cases.py (the corpus of tests/tiny_cases.py).
 """
 import ctypes as C
 import re

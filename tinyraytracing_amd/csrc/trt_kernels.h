@@ -561,7 +561,7 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
             int32_t best_tri = -1;
             uint32_t best_flags = 0u;
             uint32_t ni = 0, nt = 0;
-            uniformWalkImpl<false, TRT_TRACE_BLOCK, true, PIPE>(sc, o, d, mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), valid, valid, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
+            uniformWalkImpl<COUNT, TRT_TRACE_BLOCK, true, PIPE>(sc, o, d, mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), valid, valid, my_pend, best_t, best_tri, best_flags, COUNT ? n_inner : ni, COUNT ? n_tri : nt, s_flags);
             if (valid) storeResult<SHADOW, HIT8, QUERY>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         }
         if (lane == 0 && n_parked) atomicAdd(&stats->redo_rays, n_parked);
@@ -578,7 +578,10 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
         float best_t = bounded ? b.w : TRT_INF;
         int32_t best_tri = -1;
         uint32_t best_flags = 0u;
-        uniformWalkImpl<COUNT, TRT_TRACE_BLOCK, false, PIPE>(sc, o, d, inv, valid, false, my_pend, best_t, best_tri, best_flags, n_inner, n_tri, s_flags);
+        // COUNT: a parked ray sits this walk out — its nodes and triangles are counted where it is walked with the literal test, whose visit set is the reference's
+        // (the clean test here can pass or fail a box that the literal one, with its 0 * inf, does not: an origin on a box plane)
+        const bool walked = COUNT ? valid && !raySpecial(inv) : valid;
+        uniformWalkImpl<COUNT, TRT_TRACE_BLOCK, false, PIPE>(sc, o, d, inv, walked, false, my_pend, best_t, best_tri, best_flags, n_inner, n_tri, s_flags);
         const bool special = valid && raySpecial(inv);
         if (valid && !special) storeResult<SHADOW, HIT8, QUERY>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         const unsigned long long m_sp = ballotb(special);
@@ -605,7 +608,7 @@ __device__ __forceinline__ void traceQueueUniform(const SceneDev& sc, const RayS
             int32_t best_tri = -1;
             uint32_t best_flags = 0u;
             uint32_t ni = 0, nt = 0;
-            uniformWalkImpl<false, TRT_TRACE_BLOCK, true, PIPE>(sc, o, d, inv, special, special, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
+            uniformWalkImpl<COUNT, TRT_TRACE_BLOCK, true, PIPE>(sc, o, d, inv, special, special, my_pend, best_t, best_tri, best_flags, COUNT ? n_inner : ni, COUNT ? n_tri : nt, s_flags);
             if (special) storeResult<SHADOW, HIT8, QUERY>(sc, o, d, best_t, best_tri, best_flags, i, SHADOW ? f2u(b.z) : 0u, hit, sw, light_mat, Lacc, any);
         }
         if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
@@ -686,7 +689,7 @@ __device__ __forceinline__ void traceQueueBinned(const SceneDev& sc, const RaySo
             fetchRay<0>(sc, src, valid ? i : n - 1, a, b);
             const f3 o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
             const f3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-            uint32_t reach = valid ? 1u : 0u;
+            uint32_t reach = (COUNT ? valid && !raySpecial(inv) : valid) ? 1u : 0u;  // (COUNT: a parked ray reaches nothing here and is counted by its re-walk, as in traceQueueUniform)
             unsigned long long mask = 0ull;
             for (uint32_t ni = 0; ni < n_nodes; ++ni) {
                 const bool at = (reach >> ni) & 1u;
@@ -810,7 +813,7 @@ __device__ __forceinline__ void traceQueueBinned(const SceneDev& sc, const RaySo
             int32_t best_tri = -1;
             uint32_t best_flags = 0u;
             uint32_t ni = 0, nt = 0;
-            uniformWalkImpl<false, B, true, true>(sc, o, d, mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), valid, valid, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
+            uniformWalkImpl<COUNT, B, true, true>(sc, o, d, mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z), valid, valid, my_pend, best_t, best_tri, best_flags, COUNT ? n_inner : ni, COUNT ? n_tri : nt, s_flags);
             if (valid) storeResult<false, true>(sc, o, d, best_t, best_tri, best_flags, i, 0u, hit, nullptr, 0u, nullptr, false);
         }
         if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
@@ -829,7 +832,7 @@ __device__ __forceinline__ void traceQueueBinned(const SceneDev& sc, const RaySo
             int32_t best_tri = -1;
             uint32_t best_flags = 0u;
             uint32_t ni = 0, nt = 0;
-            uniformWalkImpl<false, B, true, true>(sc, o, d, inv, special, special, my_pend, best_t, best_tri, best_flags, ni, nt, s_flags);
+            uniformWalkImpl<COUNT, B, true, true>(sc, o, d, inv, special, special, my_pend, best_t, best_tri, best_flags, COUNT ? n_inner : ni, COUNT ? n_tri : nt, s_flags);
             if (special) storeResult<false, true>(sc, o, d, best_t, best_tri, best_flags, i, 0u, hit, nullptr, 0u, nullptr, false);
         }
         if (lane == 0) atomicAdd(&stats->redo_rays, n_parked);
