@@ -29,8 +29,8 @@ HOST_HDR := $(wildcard $(PKG)/host/*.h) $(wildcard $(PKG)/csrc/*.h) include/trt.
 HIP_SRC := $(PKG)/csrc/trt_api.hip
 HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include/trt_exact.h
 
-.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu refitcpu rayscpu variants probe exactcheck nodecheck clean
-all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu refitcpu rayscpu cli exactcheck nodecheck
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu refitcpu rayscpu variants probe exactcheck nodecheck clean
+all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu refitcpu rayscpu cli exactcheck nodecheck
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -54,6 +54,10 @@ tests/reproject/libreproject_cpu.so: tests/reproject/reproject_cpu.cpp $(PKG)/cs
 motioncpu: tests/motion/libmotion_cpu.so
 tests/motion/libmotion_cpu.so: tests/motion/motion_cpu.cpp $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/motion/motion_cpu.cpp
+# CPU compile of trt_reproject_moments' per-pixel code (trt_moments.h), for tests only (tests/test_*moments*.py)
+momentscpu: tests/moments/libmoments_cpu.so
+tests/moments/libmoments_cpu.so: tests/moments/moments_cpu.cpp $(PKG)/csrc/trt_moments.h $(PKG)/csrc/trt_reproject.h $(PKG)/csrc/trt_denoise.h include/trt.h include/trt_prims.h include/trt_exact.h
+	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/moments/moments_cpu.cpp
 # CPU compile of the geometry update's per-node functions (trt_refit.h) over collapseBvh / buildOct output, for tests only (tests/test_refit_cpu.py)
 refitcpu: tests/refit/librefit_cpu.so
 tests/refit/librefit_cpu.so: tests/refit/refit_cpu.cpp $(HIP_HDR)
@@ -92,7 +96,7 @@ variants: $(HIP_SRC) $(HIP_HDR)
 	  echo "variant $$name: $$defs"; $(HIPCC) $(HIPFLAGS) $$defs -shared -o $(OUT)/variants/libtrt_hip_$$name.so $(HIP_SRC) || exit 1; done
 
 clean:
-	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so
+	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so
 	$(MAKE) -C oracle clean
 
 # exhaustive (2^32 inputs) proof that include/trt_exact.h returns the bits of sqrtf / 1.0f / sqrtf: run by tests/test_gpu_parity.py

@@ -193,7 +193,7 @@ enum {
     TRT_K_TRACE_SHADOW = 3,
     TRT_K_RESOLVE = 4,
     TRT_K_TAIL = 5,       /* the last, short-queue bounces of a pass fused into one launch */
-    TRT_K_DENOISE = 6,    /* trt_denoise*: the prepare kernel and every level of the a-trous filter; trt_reproject*: its one kernel */
+    TRT_K_DENOISE = 6,    /* trt_denoise*: the prepare kernel and every level of the a-trous filter; trt_reproject*: its one kernel (trt_reproject_moments*: its two) */
     TRT_K_REFIT = 7       /* trt_update_geometry*: every kernel of an update */
 };
 
@@ -625,6 +625,63 @@ int trt_reproject_motion_device(int device, const trt_reproject_params* params, 
                                 const float* albedo, const float* normal, const float* depth, const float* prev_point, const float* prev_cv,
                                 const float* prev_len, const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance,
                                 float* out_cv, float* out_len, void* hip_stream, trt_stats* stats);
+
+/* trt_reproject for frames of ONE sample per pixel: the variance is not an input but estimated, from the history of the luminance's first
+ * two moments where the history is long enough (the moments estimate of SVGF) and from the neighbourhood where it is not.  Inputs of the
+ * current frame: color, albedo, normal, depth as for trt_reproject (no variance), and prev_point W*H*3 as for trt_reproject_motion or NULL.
+ * History, all five or none: trt_reproject's four and
+ *   prev_mom  W*H*4  (m1, m2, s, 0): the accumulated first and second moments of the demodulated luminance l = lum(c), and s = the sum of
+ *                    the squared frame weights that make up the accumulated value (1 for one frame, 1 / N for a running mean of N, towards
+ *                    alpha / (2 - alpha) under the exponential average); an earlier call's out_mom.
+ * Outputs: trt_reproject's four and out_mom W*H*4.  Per pixel p = (x, y), stage A:
+ *  1. Demodulate as trt_reproject's step 1 with variance := 0; l = lum(c).
+ *  2. A pixel with no history (a miss, a NaN depth, a NULL history, a failed projection, W_s < 0.01) gives out_color = the input's bits,
+ *     out_cv = (c, .), out_len = 1, out_mom = (l, l l, 1, 0).
+ *  3. Otherwise (fx, fy, z') by trt_reproject's steps 3 and 4 if prev_point is NULL (the shortcut for byte-identical cameras included), by
+ *     trt_reproject_motion's steps 3' and 4' from prev_point otherwise.
+ *  4. Taps: trt_reproject's step 5 (order, tests, weights; per tap the depth is read, then the normal, cv, the length, mom); m1_h, m2_h, s_h
+ *     = the weighted means of prev_mom over the counting taps, beside c_h and N_h.
+ *  5. Blend: N and alpha' as trt_reproject's step 6, c' = c_h + alpha' (c - c_h); m1' = m1_h + alpha' (l - m1_h);
+ *     m2' = m2_h + alpha' (l l - m2_h); s' = alpha'^2 + (1 - alpha')^2 s_h.  out_cv.rgb = c', out_len = N, out_color = c' a: the bits
+ *     trt_reproject / trt_reproject_motion return on the same inputs (these do not depend on the variance).  out_mom = (m1', m2', s', 0).
+ *  6. The TEMPORAL ROUTE: a hit pixel with N >= min_frames and 1 - s' >= 0.1.  There v = max(0, m2' - m1'^2) / (1 - s') and var' = v s':
+ *     with frame weights a_i that sum to 1 over independent frames of variance sigma^2, E[m2 - m1^2] = sigma^2 (1 - sum a_i^2), and the
+ *     accumulated colour has the variance sigma^2 sum a_i^2.
+ * Stage B, a second kernel, for every hit pixel NOT on the temporal route (one predicate decides for both stages): the (2R+1)^2 window,
+ * R = 3, rows outer, columns inner, over THIS frame's out_mom, normal and depth.  A tap q counts iff it is in the image and a hit; the centre
+ * has w = 1, any other tap w = wn wz with trt_denoise's wn = max(0, n_p . n_q)^sigma_normal and
+ * wz = exp(-|z_p - z_q| / (sigma_depth gz_p |q - p| + 1e-3 z_p)), gz_p trt_denoise's depth gradient, |q - p| by trt_sqrt.
+ *     M1 = sum w m1_q / sum w,  M2 = sum w m2_q / sum w,  W2 = sum w^2 s_q / (sum w)^2;
+ *     1 - W2 >= 0.1:  v = max(0, M2 - M1^2) / (1 - W2);
+ *     otherwise the pixel stands alone behind its edges, nothing can be estimated, and v = M1^2: a relative standard deviation of 1, the
+ *     conservative choice (the filter then smooths such a pixel as far as its edge-stopping weights let it);
+ *     var' = v s'_p.
+ * Both routes: out_cv.w = var', out_variance = var' max(lum(a), 1e-6)^2.  A miss: 0 and 0.
+ * Arithmetic: fp32 in one fixed order, tinyraytracing_amd/csrc/trt_moments.h, which a CPU build of the same code reproduces bit for bit.
+ * Non-finite or hostile values, prev_mom's included (a NaN, a negative s, s > 1), index nothing out of bounds; the results near them are
+ * unspecified. */
+typedef struct trt_moments_params {
+    trt_reproject_params rp;
+    int32_t min_frames;    /* the least history length of the temporal route, 1..255; 0 = 4 */
+    int32_t sigma_normal;  /* stage B's normal exponent, 1..256; 0 = 128 */
+    float sigma_depth;     /* stage B's depth sigma, >= 0; 0 = 1 */
+} trt_moments_params;
+
+/* On HOST buffers (staged for the call: 92 bytes per pixel, 12 more with prev_point, 52 more with a history).  TRT_EINVAL, in this order
+ * before any device work: trt_reproject's checks in its order (required: the four inputs and the five outputs; the history: all five or
+ * none), then min_frames outside 0..255, sigma_normal outside 0..256, a negative or NaN sigma_depth.  stats (optional): launches
+ * [TRT_K_DENOISE] = 2 (stage A and stage B; stage B's blocks without a pixel for it return at once), kernel_ms[TRT_K_DENOISE], render_ms. */
+int trt_reproject_moments(int device, const trt_moments_params* params, int width, int height, const float* color, const float* albedo,
+                          const float* normal, const float* depth, const float* prev_point, const float* prev_cv, const float* prev_len,
+                          const float* prev_normal, const float* prev_depth, const float* prev_mom, float* out_color, float* out_variance,
+                          float* out_cv, float* out_len, float* out_mom, trt_stats* stats);
+/* The same with every buffer in DEVICE memory, as trt_reproject_device: nothing allocated; prev_cv, out_cv, prev_mom and out_mom are read
+ * and written as 16-byte records and must be 16-byte aligned (TRT_EINVAL otherwise).  TRT_MOMENTS_LDS=0 in the environment sends stage B
+ * through its global-memory variant (an A/B switch; same bits). */
+int trt_reproject_moments_device(int device, const trt_moments_params* params, int width, int height, const float* color, const float* albedo,
+                                 const float* normal, const float* depth, const float* prev_point, const float* prev_cv, const float* prev_len,
+                                 const float* prev_normal, const float* prev_depth, const float* prev_mom, float* out_color, float* out_variance,
+                                 float* out_cv, float* out_len, float* out_mom, void* hip_stream, trt_stats* stats);
 
 
 /* ---- one node, several GPUs -------------------------------------------------------------------------------------

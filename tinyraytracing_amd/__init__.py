@@ -797,6 +797,35 @@ class Renderer:
         variance = mean_luminance_variance(sums, sumsq, params.spp).reshape(rows, tw)
         return color, variance, aov, total, stream
 
+    def _camera_colour_inputs(self, params, camera, aov_spp, samples_per_call, what):
+        """_camera_denoiser_inputs without the second moments, for TemporalAccumulator(variance="moments"): the colour sums alone
+        (render_rays_into without sumsq, so params.spp may be 1) and the feature buffers.  -> (color [rows, tw, 3], aov dict, Stats summed,
+        stream pointer)."""
+        import torch
+        if params.spp < 1:
+            raise TrtError(f"{what}: spp must be >= 1")
+        if params.row_mod > 1:
+            raise TrtError(f"{what}: the tile must not interleave rows (it is filtered as one image)")
+        pix, (rows, tw) = self._camera_tile(params, what)
+        k = max(1, min(int(samples_per_call), params.spp))
+        dev = pix.device
+        n = pix.numel()
+        org = torch.empty((k, n, 3), dtype=torch.float32, device=dev)
+        dirs = torch.empty_like(org)
+        sums = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        total = Stats()
+        for s0 in range(0, params.spp, k):
+            s1 = min(s0 + k, params.spp)
+            camera_rays_into(camera, params, pix, s0, s1, org[:s1 - s0], dirs[:s1 - s0], device=self.device, stream_ptr=stream)
+            _add_stats(total, self.render_rays_into(params, org[:s1 - s0], dirs[:s1 - s0], sums, streams=pix, sample_begin=s0, stream_ptr=stream))
+        del org, dirs
+        pa = make_params(params.width, params.height, min(params.spp, 16) if aov_spp is None else aov_spp, params.seed,
+                         tile=(params.x0, params.y0, params.x1, params.y1), max_depth=params.max_depth, flags=params.flags, mem_budget=params.mem_budget)
+        aov, st = self.render_camera_aov(pa, camera, samples_per_call=samples_per_call, want_stats=True, on_device=True)
+        _add_stats(total, st)
+        return sums.to(torch.float32).reshape(rows, tw, 3), aov, total, stream
+
     def render_camera_denoised(self, params, camera, aov_spp=None, samples_per_call=16, iterations=5, sigma_normal=128, sigma_depth=1.0,
                                sigma_luminance=4.0):
         """render_denoised for the tile of `params` as seen by `camera`, on this handle: the same dict (color, variance, albedo, normal, depth,
@@ -1222,6 +1251,96 @@ def reproject_motion_into(color, variance, albedo, normal, depth, prev_point, cu
                              out_length, history, alpha, depth_tolerance, normal_threshold, max_history, flags, stream_ptr)
 
 
+MOMENTS_HISTORY_KEYS = HISTORY_KEYS + ("mom",)
+
+
+def _moments_history_shapes(h, w):
+    return (h, w, 4), (h, w), (h, w, 3), (h, w), (h, w, 4)
+
+
+def _moments_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags, min_frames, sigma_normal, sigma_depth):
+    mp = _abi.MomentsParams()
+    mp.rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
+    mp.min_frames, mp.sigma_normal, mp.sigma_depth = int(min_frames), int(sigma_normal), float(sigma_depth)
+    return mp
+
+
+def _moments_history(history, what):
+    if history is None:
+        return [None] * 5
+    if not isinstance(history, dict) or any(history.get(k) is None for k in MOMENTS_HISTORY_KEYS):
+        raise TrtError(f"{what}: history must be None or a dict with the keys cv, length, normal, depth, mom")
+    return [history[k] for k in MOMENTS_HISTORY_KEYS]
+
+
+def reproject_moments(color, albedo, normal, depth, cur, prev=None, history=None, prev_point=None, alpha=0.2, depth_tolerance=0.1,
+                      normal_threshold=0.9, max_history=255.0, flags=0, min_frames=4, sigma_normal=128, sigma_depth=1.0, device=0, want_stats=False):
+    """reproject() for frames of one sample per pixel (trt_reproject_moments, include/trt.h has the contract): no variance goes in; it is
+    estimated from the history of the luminance's moments where the history is at least min_frames long, and from a 7 x 7 neighbourhood
+    (sigma_normal, sigma_depth: denoise()'s edge-stopping weights) where it is not.  The history has one more entry than reproject()'s:
+    dict(cv, length, normal, depth, mom [h, w, 4]); prev_point [h, w, 3] as for reproject_motion(), or None = the cameras alone.
+    -> dict(color, variance, cv, length, mom)[, Stats]: color and variance go on to denoise(), cv, length and mom are the next history."""
+    what = "reproject_moments"
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    h, w = _image_shape(color, what)
+    bufs = [color]
+    named = [("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w)), ("prev_point", prev_point, (h, w, 3))]
+    named += [("history " + k, a, shape) for k, a, shape in zip(MOMENTS_HISTORY_KEYS, _moments_history(history, what), _moments_history_shapes(h, w))]
+    for name, a, shape in named:
+        if a is None:
+            bufs.append(None)
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise TrtError(f"{what}: {name} must have shape {shape}, not {a.shape}")
+        bufs.append(a)
+    out = {"color": np.empty((h, w, 3), np.float32), "variance": np.empty((h, w), np.float32), "cv": np.empty((h, w, 4), np.float32),
+           "length": np.empty((h, w), np.float32), "mom": np.empty((h, w, 4), np.float32)}
+    mp = _moments_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags, min_frames, sigma_normal, sigma_depth)
+    st = Stats()
+    lib = _abi.load_hip()
+    fp = C.POINTER(C.c_float)
+    rc = lib.trt_reproject_moments(int(device), C.byref(mp), w, h, *[None if b is None else b.ctypes.data_as(fp) for b in bufs],
+                                   *[out[k].ctypes.data_as(fp) for k in ("color", "variance", "cv", "length", "mom")], C.byref(st))
+    if rc != 0:
+        raise TrtError(f"trt_reproject_moments failed ({rc}): {lib.trt_last_error().decode()}")
+    return (out, st) if want_stats else out
+
+
+def reproject_moments_into(color, albedo, normal, depth, cur, prev, out_color, out_variance, out_cv, out_length, out_mom, history=None,
+                           prev_point=None, alpha=0.2, depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, flags=0, min_frames=4,
+                           sigma_normal=128, sigma_depth=1.0, stream_ptr=0):
+    """trt_reproject_moments_device: the buffers of reproject_moments() as contiguous float32 torch tensors on one device (the history's
+    and prev_point too; out_color [h, w, 3], out_variance [h, w], out_cv [h, w, 4], out_length [h, w], out_mom [h, w, 4]; no output may be
+    an input), the work on stream `stream_ptr` (0 = default).  Writes the five outputs; -> Stats."""
+    what = "reproject_moments_into"
+    if not _is_torch(color) or color.dim() != 3:
+        raise TrtError(f"{what}: color must be a float32 tensor [height, width, 3]")
+    h, w = _image_shape(color, what)
+    dev = color.device
+    named = [("color", color, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w)),
+             ("prev_point", prev_point, (h, w, 3))]
+    named += [("history " + k, t, shape) for k, t, shape in zip(MOMENTS_HISTORY_KEYS, _moments_history(history, what), _moments_history_shapes(h, w))]
+    named += [("out_color", out_color, (h, w, 3)), ("out_variance", out_variance, (h, w)), ("out_cv", out_cv, (h, w, 4)), ("out_length", out_length, (h, w)),
+              ("out_mom", out_mom, (h, w, 4))]
+    ptrs = []
+    for name, t, shape in named:
+        if t is None and (name.startswith("history") or name == "prev_point"):
+            ptrs.append(None)
+            continue
+        if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape
+                or t.device != dev):
+            raise TrtError(f"{what}: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+        ptrs.append(C.c_void_p(t.data_ptr()))
+    mp = _moments_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags, min_frames, sigma_normal, sigma_depth)
+    st = Stats()
+    lib = _abi.load_hip()
+    rc = lib.trt_reproject_moments_device(int(dev.index or 0), C.byref(mp), w, h, *ptrs, C.c_void_p(stream_ptr), C.byref(st))
+    if rc != 0:
+        raise TrtError(f"trt_reproject_moments_device failed ({rc}): {lib.trt_last_error().decode()}")
+    return st
+
+
 class TemporalAccumulator:
     """A frame loop over a moving camera: every frame is rendered, blended into the reprojected history of the frames before it
     (reproject_into) and then filtered (denoise_into).  `params` names the image (its tile must be the whole image, spp >= 2, no row
@@ -1229,20 +1348,28 @@ class TemporalAccumulator:
     trt_reproject's, aov_spp and samples_per_call render_camera_denoised's, denoise_kw (iterations, sigma_normal, sigma_depth,
     sigma_luminance) denoise_into's.  The history lives in torch tensors on the renderer's device and belongs to this object alone: the
     handle keeps nothing, and two accumulators on one renderer do not interact.
+    variance="samples" (the default) takes the variance from the samples of each frame, hence spp >= 2.  variance="moments" takes it from
+    the history instead (reproject_moments_into: the luminance's moments over time, a spatial estimate while the history is shorter than
+    min_frames): spp may be 1, only the colour sums are rendered, the history keeps one more record (mom), and frame()'s own `variance`
+    is None.  The accumulated colour and the history length are the same either way.
     Geometry that moves keeps its history too: after Renderer.update_geometry_from(v1) (or update_geometry) pass the vertices the handle had
     when the previous frame was rendered, frame(camera, moved_from=v0), and every pixel looks its history up where the surface it shows
     was then.  The loop is `r.update_geometry_from(v1); acc.frame(cam, moved_from=v0)`; without moved_from a moved surface keeps or loses
     its history by the depth and normal tests alone, as trt_reproject documents."""
 
     def __init__(self, renderer, params, alpha=0.2, depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, aov_spp=None,
-                 samples_per_call=16, **denoise_kw):
+                 samples_per_call=16, variance="samples", min_frames=4, **denoise_kw):
         unknown = set(denoise_kw) - {"iterations", "sigma_normal", "sigma_depth", "sigma_luminance"}
         if unknown:
             raise TrtError(f"TemporalAccumulator: unknown argument {sorted(unknown)[0]}")
+        if variance not in ("samples", "moments"):
+            raise TrtError("TemporalAccumulator: variance must be 'samples' or 'moments'")
         if (params.x0, params.y0, params.x1, params.y1) != (0, 0, params.width, params.height):
             raise TrtError("TemporalAccumulator: the tile must be the whole image (the cameras' pixel grid is the image's)")
-        if params.spp < 2:
+        if variance == "samples" and params.spp < 2:
             raise TrtError("TemporalAccumulator: spp must be >= 2 (the variance needs two samples)")
+        if params.spp < 1:
+            raise TrtError("TemporalAccumulator: spp must be >= 1")
         if params.row_mod > 1:
             raise TrtError("TemporalAccumulator: the tile must not interleave rows (it is filtered as one image)")
         self.renderer = renderer
@@ -1251,6 +1378,9 @@ class TemporalAccumulator:
                                  flags=params.flags & TRT_FLAG_FIXED_PIXELS)
         self.render_kw = dict(aov_spp=aov_spp, samples_per_call=samples_per_call)
         self.denoise_kw = denoise_kw
+        self.variance = variance
+        # stage B of reproject_moments_into weighs its taps as the filter does
+        self.moments_kw = dict(min_frames=min_frames, **{k: denoise_kw[k] for k in ("sigma_normal", "sigma_depth") if k in denoise_kw})
         self.frame_index = 0  # frames rendered so far; reset() does not rewind it, so that no seed is used twice
         self._history = None
         self._camera = None
@@ -1266,7 +1396,8 @@ class TemporalAccumulator:
         """Renders the frame seen by `camera` with seed params.seed + frame_index (mod 2^32), accumulates and denoises it.  -> dict(color,
         variance, albedo, normal, depth: the frame's own buffers; accumulated, accumulated_variance: the blend with the reprojected history;
         history_length; denoised: the filtered accumulated image) as float32 arrays (on_device: torch tensors on the renderer's device), and
-        stats: the Stats of every call summed.
+        stats: the Stats of every call summed.  With variance="moments" the frame has no variance of its own (`variance` is None) and
+        accumulated_variance is reproject_moments_into's estimate.
         moved_from: None, or the tri_v the handle's geometry had when the previous frame was rendered (float32 [n_tris, 3, 3], a torch tensor
         on the renderer's device or a numpy array): the history is then found through center_rays -> Renderer.trace_points_into(...,
         moved_from) -> reproject_motion_into, all on the frame's stream, in place of reproject_into.  Its shape is checked before anything
@@ -1285,12 +1416,29 @@ class TemporalAccumulator:
                 raise TrtError(f"TemporalAccumulator.frame: moved_from holds {moved_from.shape[0]} triangles, the handle {n_tris}")
         p = Params.from_buffer_copy(self.params)
         p.seed = (self.params.seed + self.frame_index) & 0xFFFFFFFF
-        color, variance, aov, total, stream = self.renderer._camera_denoiser_inputs(p, camera, self.render_kw["aov_spp"], self.render_kw["samples_per_call"],
-                                                                                   "TemporalAccumulator.frame")
+        moments = self.variance == "moments"
+        if moments:
+            color, aov, total, stream = self.renderer._camera_colour_inputs(p, camera, self.render_kw["aov_spp"], self.render_kw["samples_per_call"],
+                                                                            "TemporalAccumulator.frame")
+            variance = None
+        else:
+            color, variance, aov, total, stream = self.renderer._camera_denoiser_inputs(p, camera, self.render_kw["aov_spp"], self.render_kw["samples_per_call"],
+                                                                                       "TemporalAccumulator.frame")
         h, w = color.shape[0], color.shape[1]
-        acc, acc_var = torch.empty_like(color), torch.empty_like(variance)
-        cv, length = torch.empty((h, w, 4), dtype=torch.float32, device=color.device), torch.empty_like(variance)
-        if moved_from is None or self._history is None:
+        acc, acc_var = torch.empty_like(color), torch.empty_like(aov["depth"])
+        cv, length = torch.empty((h, w, 4), dtype=torch.float32, device=color.device), torch.empty_like(aov["depth"])
+        mom = torch.empty_like(cv) if moments else None
+        if moments:
+            point = None
+            if moved_from is not None and self._history is not None:
+                v0 = moved_from if _is_torch(moved_from) else torch.from_numpy(moved_from).to(color.device)
+                org, dirs = center_rays(camera, w, h, flags=self.reproject_kw["flags"], device=color.device)
+                point = torch.empty((h * w, 3), dtype=torch.float32, device=color.device)
+                _add_stats(total, self.renderer.trace_points_into(org, dirs, v0.contiguous(), point, stream_ptr=stream))
+                point = point.view(h, w, 3)
+            _add_stats(total, reproject_moments_into(color, aov["albedo"], aov["normal"], aov["depth"], camera, self._camera, acc, acc_var, cv, length, mom,
+                                                     history=self._history, prev_point=point, stream_ptr=stream, **self.reproject_kw, **self.moments_kw))
+        elif moved_from is None or self._history is None:
             _add_stats(total, reproject_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], camera, self._camera, acc, acc_var, cv, length,
                                              history=self._history, stream_ptr=stream, **self.reproject_kw))
         else:
@@ -1303,6 +1451,8 @@ class TemporalAccumulator:
         denoised = torch.empty_like(color)
         _add_stats(total, denoise_into(acc, acc_var, aov["albedo"], aov["normal"], aov["depth"], denoised, stream_ptr=stream, **self.denoise_kw))
         self._history = {"cv": cv, "length": length, "normal": aov["normal"], "depth": aov["depth"]}
+        if moments:
+            self._history["mom"] = mom
         self._camera = Camera.from_buffer_copy(camera)
         self.frame_index += 1
         out = {"color": color, "variance": variance, "accumulated": acc, "accumulated_variance": acc_var, "history_length": length, "denoised": denoised}
@@ -1310,7 +1460,7 @@ class TemporalAccumulator:
         if on_device:  # history_length, normal and depth are the next frame's history: the caller gets copies to do with as they please
             out.update({k_: out[k_].clone() for k_ in ("history_length", "normal", "depth")})
         else:
-            out = {k_: v.cpu().numpy() for k_, v in out.items()}
+            out = {k_: None if v is None else v.cpu().numpy() for k_, v in out.items()}
         out["stats"] = total
         return out
 

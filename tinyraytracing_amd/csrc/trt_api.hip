@@ -25,6 +25,7 @@
 #include "trt_oct_build.h"
 #include "trt_denoise_kernels.h"
 #include "trt_reproject_kernels.h"
+#include "trt_moments_kernels.h"
 #include "trt_refit_kernels.h"
 
 using namespace trtd;
@@ -2519,6 +2520,121 @@ int trt_reproject_motion_device(int device, const trt_reproject_params* params, 
     ReprojectIo io{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len};
     io.prev_point = prev_point;
     return reproject(device, params, width, height, io, false, (hipStream_t)hip_stream, stats, "trt_reproject_motion_device", true);
+}
+
+}  // extern "C"
+
+// ---- trt_reproject_moments / trt_reproject_moments_device ------------------------------------------------------------------------------
+
+namespace {
+
+struct MomentsIo {
+    const float *color, *albedo, *normal, *depth, *prev_point;  // prev_point: optional
+    const float *prev_cv, *prev_len, *prev_normal, *prev_depth, *prev_mom;
+    float *out_color, *out_variance, *out_cv, *out_len, *out_mom;
+};
+
+// One call: (host: upload) -> k_reproject_moments -> k_moments_variance -> (host: download), all on `stream`.
+// TRT_MOMENTS_LDS=0 in the environment sends stage B through its global-memory variant (A/B of the LDS tile; same bits).
+int reprojectMoments(int device, const trt_moments_params* prm, int width, int height, const MomentsIo& io, bool host, hipStream_t stream,
+                     trt_stats* stats, const char* what)
+{
+    trt_mv_args a{};
+    const bool required = io.color && io.albedo && io.normal && io.depth && io.out_color && io.out_variance && io.out_cv && io.out_len && io.out_mom;
+    const int given = (io.prev_cv ? 1 : 0) + (io.prev_len ? 1 : 0) + (io.prev_normal ? 1 : 0) + (io.prev_depth ? 1 : 0) + (io.prev_mom ? 1 : 0);
+    if (const char* msg = trt_mv_check(prm, width, height, required, given, a)) return fail(TRT_EINVAL, std::string(what) + ": " + msg);
+    if (!host && ((((uintptr_t)io.out_cv) | ((uintptr_t)io.prev_cv) | ((uintptr_t)io.out_mom) | ((uintptr_t)io.prev_mom)) & 15u))
+        return fail(TRT_EINVAL, std::string(what) + ": prev_cv, out_cv, prev_mom and out_mom must be 16-byte aligned");
+    if (int e = useDevice(device)) return e;
+    const size_t n = (size_t)width * (size_t)height, f1 = n * sizeof(float), f3 = 3 * f1, f4 = 4 * f1;
+    const bool hist = a.rp.history != 0, motion = io.prev_point != nullptr;
+    DenoiseScratch S;  // the staging of the host entry (none for the device entry) and the events
+    MomentsIo dev = io;
+    for (hipEvent_t& e : S.ev) HIPC(hipEventCreate(&e));
+    if (host) {
+        Layout L;
+        const size_t o_c = L.add(f3, 256), o_a = L.add(f3, 256), o_n = L.add(f3, 256), o_z = L.add(f1, 256), o_pp = L.add(motion ? f3 : 0, 256);
+        const size_t o_pc = L.add(hist ? f4 : 0, 256), o_pl = L.add(hist ? f1 : 0, 256), o_pn = L.add(hist ? f3 : 0, 256), o_pz = L.add(hist ? f1 : 0, 256);
+        const size_t o_pm = L.add(hist ? f4 : 0, 256);
+        const size_t o_oc = L.add(f3, 256), o_ov = L.add(f1, 256), o_ocv = L.add(f4, 256), o_ol = L.add(f1, 256), o_om = L.add(f4, 256);
+        HIPC(hipMalloc(&S.p, L.bytes));
+        char* b = (char*)S.p;
+        auto in = [&](size_t o, bool there) { return there ? (const float*)(b + o) : nullptr; };
+        dev = MomentsIo{in(o_c, true), in(o_a, true), in(o_n, true), in(o_z, true), in(o_pp, motion), in(o_pc, hist), in(o_pl, hist), in(o_pn, hist),
+                        in(o_pz, hist), in(o_pm, hist), (float*)(b + o_oc), (float*)(b + o_ov), (float*)(b + o_ocv), (float*)(b + o_ol), (float*)(b + o_om)};
+    }
+    HIPC(hipEventRecord(S.ev[0], stream));
+    if (host) {
+        HIPC(hipMemcpyAsync((void*)dev.color, io.color, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.albedo, io.albedo, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.normal, io.normal, f3, hipMemcpyHostToDevice, stream));
+        HIPC(hipMemcpyAsync((void*)dev.depth, io.depth, f1, hipMemcpyHostToDevice, stream));
+        if (motion) HIPC(hipMemcpyAsync((void*)dev.prev_point, io.prev_point, f3, hipMemcpyHostToDevice, stream));
+        if (hist) {
+            HIPC(hipMemcpyAsync((void*)dev.prev_cv, io.prev_cv, f4, hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync((void*)dev.prev_len, io.prev_len, f1, hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync((void*)dev.prev_normal, io.prev_normal, f3, hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync((void*)dev.prev_depth, io.prev_depth, f1, hipMemcpyHostToDevice, stream));
+            HIPC(hipMemcpyAsync((void*)dev.prev_mom, io.prev_mom, f4, hipMemcpyHostToDevice, stream));
+        }
+    }
+    const char* lds_env = std::getenv("TRT_MOMENTS_LDS");
+    const bool lds = !(lds_env && lds_env[0] == '0');
+    const dim3 grid((unsigned)((width + MV_BX - 1) / MV_BX), (unsigned)((height + MV_BY - 1) / MV_BY)), block(MV_BX, MV_BY);
+    HIPC(hipEventRecord(S.ev[1], stream));
+    const trt_mv_fetch fetch{(const trt_dn4*)dev.prev_cv, dev.prev_len, dev.prev_normal, dev.prev_depth, (const trt_dn4*)dev.prev_mom};
+    hipLaunchKernelGGL(motion ? k_reproject_moments<true> : k_reproject_moments<false>, grid, block, 0, stream, a, dev.color, dev.albedo, dev.normal,
+                       dev.depth, dev.prev_point, fetch, dev.out_color, dev.out_variance, (trt_dn4*)dev.out_cv, dev.out_len, (trt_dn4*)dev.out_mom);
+    hipLaunchKernelGGL(lds ? k_moments_variance<true> : k_moments_variance<false>, grid, block, 0, stream, a, dev.albedo, dev.normal, dev.depth,
+                       (const float*)dev.out_len, (const trt_dn4*)dev.out_mom, dev.out_cv, dev.out_variance);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(S.ev[2], stream));
+    if (host) {
+        HIPC(hipMemcpyAsync(io.out_color, dev.out_color, f3, hipMemcpyDeviceToHost, stream));
+        HIPC(hipMemcpyAsync(io.out_variance, dev.out_variance, f1, hipMemcpyDeviceToHost, stream));
+        HIPC(hipMemcpyAsync(io.out_cv, dev.out_cv, f4, hipMemcpyDeviceToHost, stream));
+        HIPC(hipMemcpyAsync(io.out_len, dev.out_len, f1, hipMemcpyDeviceToHost, stream));
+        HIPC(hipMemcpyAsync(io.out_mom, dev.out_mom, f4, hipMemcpyDeviceToHost, stream));
+    }
+    HIPC(hipEventRecord(S.ev[3], stream));
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+    if (stats) {
+        float k_ms = 0.f, all_ms = 0.f;
+        HIPC(hipEventElapsedTime(&k_ms, S.ev[1], S.ev[2]));
+        HIPC(hipEventElapsedTime(&all_ms, S.ev[0], S.ev[3]));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->launches[TRT_K_DENOISE] = 2;
+        stats->kernel_ms[TRT_K_DENOISE] = k_ms;
+        stats->render_ms = all_ms;
+    }
+    return TRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int trt_reproject_moments(int device, const trt_moments_params* params, int width, int height, const float* color, const float* albedo,
+                          const float* normal, const float* depth, const float* prev_point, const float* prev_cv, const float* prev_len,
+                          const float* prev_normal, const float* prev_depth, const float* prev_mom, float* out_color, float* out_variance,
+                          float* out_cv, float* out_len, float* out_mom, trt_stats* stats)
+{
+    return reprojectMoments(device, params, width, height,
+                            MomentsIo{color, albedo, normal, depth, prev_point, prev_cv, prev_len, prev_normal, prev_depth, prev_mom, out_color,
+                                      out_variance, out_cv, out_len, out_mom},
+                            true, nullptr, stats, "trt_reproject_moments");
+}
+
+int trt_reproject_moments_device(int device, const trt_moments_params* params, int width, int height, const float* color, const float* albedo,
+                                 const float* normal, const float* depth, const float* prev_point, const float* prev_cv, const float* prev_len,
+                                 const float* prev_normal, const float* prev_depth, const float* prev_mom, float* out_color, float* out_variance,
+                                 float* out_cv, float* out_len, float* out_mom, void* hip_stream, trt_stats* stats)
+{
+    return reprojectMoments(device, params, width, height,
+                            MomentsIo{color, albedo, normal, depth, prev_point, prev_cv, prev_len, prev_normal, prev_depth, prev_mom, out_color,
+                                      out_variance, out_cv, out_len, out_mom},
+                            false, (hipStream_t)hip_stream, stats, "trt_reproject_moments_device");
 }
 
 }  // extern "C"

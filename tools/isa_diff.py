@@ -36,6 +36,8 @@ def functions(elf):
         if m:
             cur = m.group(1)
             out[cur] = []
+        elif cur and line.strip() == "...":
+            continue  # objdump's mark for the zero padding up to the next function's alignment: no instruction, and it moves with the layout
         elif cur and line.strip():
             ins = re.sub(r"^[0-9a-f]+:\s*", "", line.split("//")[0].strip())
             out[cur].append(re.sub(r"<[^>]+>", "<L>", ins))
