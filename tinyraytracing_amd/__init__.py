@@ -1083,52 +1083,82 @@ def _image_shape(color, what):
     return int(color.shape[0]), int(color.shape[1])
 
 
+def _device_image(color, what):
+    """The image a device entry works on, from its color tensor -> height, width, device."""
+    if not _is_torch(color) or color.dim() != 3:
+        raise TrtError(f"{what}: color must be a float32 tensor [height, width, 3]")
+    return _image_shape(color, what) + (color.device,)
+
+
+# The image-space passes (denoise*, reproject*) check their arrays in one place each.  `named` lists (name, array, shape, optional) in the
+# order of the C entry's arguments; only an optional entry may be None, and a None that is not optional fails as any other wrong array.
+
+def _host_planes(what, named):
+    """-> the arrays as contiguous float32 (None for an absent optional one)."""
+    arrays = []
+    for name, a, shape, optional in named:
+        if a is not None or not optional:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise TrtError(f"{what}: {name} must have shape {shape}, not {a.shape}")
+        arrays.append(a)
+    return arrays
+
+
+def _device_planes(what, dev, named):
+    """-> the tensors' addresses as c_void_p (None for an absent optional one)."""
+    ptrs = []
+    for name, t, shape, optional in named:
+        if t is None and optional:
+            ptrs.append(None)
+            continue
+        if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape
+                or t.device != dev):
+            raise TrtError(f"{what}: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
+        ptrs.append(C.c_void_p(t.data_ptr()))
+    return ptrs
+
+
+def _float_ptrs(arrays):
+    return [None if a is None else a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrays]
+
+
+def _call_hip(entry, *args):
+    """Calls `entry` of libtrt_hip.so -> the Stats it filled."""
+    st = Stats()
+    lib = _abi.load_hip()
+    rc = getattr(lib, entry)(*args, C.byref(st))
+    if rc != 0:
+        raise TrtError(f"{entry} failed ({rc}): {lib.trt_last_error().decode()}")
+    return st
+
+
 def denoise(color, variance, albedo, normal, depth, iterations=5, sigma_normal=128, sigma_depth=1.0, sigma_luminance=4.0, device=0, want_stats=False):
     """The edge-avoiding a-trous filter on `device` (trt_denoise, include/trt.h has the contract): color, albedo, normal [h, w, 3],
     variance (of the pixel's mean luminance) and depth [h, w], all converted to float32.  -> denoised float32 [h, w, 3][, Stats]."""
     color = np.ascontiguousarray(color, dtype=np.float32)
     h, w = _image_shape(color, "denoise")
-    bufs = [color]
-    for name, a, shape in (("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise TrtError(f"denoise: {name} must have shape {shape}, not {a.shape}")
-        bufs.append(a)
+    bufs = _host_planes("denoise", [("color", color, (h, w, 3), False), ("variance", variance, (h, w), False), ("albedo", albedo, (h, w, 3), False),
+                                    ("normal", normal, (h, w, 3), False), ("depth", depth, (h, w), False)])
     out = np.empty((h, w, 3), np.float32)
     dp = _denoise_params(iterations, sigma_normal, sigma_depth, sigma_luminance)
-    st = Stats()
-    lib = _abi.load_hip()
-    fp = C.POINTER(C.c_float)
-    rc = lib.trt_denoise(int(device), C.byref(dp), w, h, *[b.ctypes.data_as(fp) for b in bufs], out.ctypes.data_as(fp), C.byref(st))
-    if rc != 0:
-        raise TrtError(f"trt_denoise failed ({rc}): {lib.trt_last_error().decode()}")
+    st = _call_hip("trt_denoise", int(device), C.byref(dp), w, h, *_float_ptrs(bufs + [out]))
     return (out, st) if want_stats else out
 
 
 def denoise_into(color, variance, albedo, normal, depth, out, iterations=5, sigma_normal=128, sigma_depth=1.0, sigma_luminance=4.0, stream_ptr=0):
     """trt_denoise_device: the buffers of denoise() as contiguous float32 torch tensors on one device (color, albedo, normal and out
     [h, w, 3]; variance and depth [h, w]), the work on stream `stream_ptr` (0 = default).  Writes out; -> Stats."""
-    if not _is_torch(color) or color.dim() != 3:
-        raise TrtError("denoise_into: color must be a float32 tensor [height, width, 3]")
-    h, w = _image_shape(color, "denoise_into")
-    dev = color.device
-    ptrs = []
-    for name, t, shape in (("color", color, (h, w, 3)), ("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)),
-                           ("depth", depth, (h, w)), ("out", out, (h, w, 3))):
-        if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape
-                or t.device != dev):
-            raise TrtError(f"denoise_into: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
-        ptrs.append(C.c_void_p(t.data_ptr()))
+    h, w, dev = _device_image(color, "denoise_into")
+    ptrs = _device_planes("denoise_into", dev, [("color", color, (h, w, 3), False), ("variance", variance, (h, w), False),
+                                                ("albedo", albedo, (h, w, 3), False), ("normal", normal, (h, w, 3), False),
+                                                ("depth", depth, (h, w), False), ("out", out, (h, w, 3), False)])
     dp = _denoise_params(iterations, sigma_normal, sigma_depth, sigma_luminance)
-    st = Stats()
-    lib = _abi.load_hip()
-    rc = lib.trt_denoise_device(int(dev.index or 0), C.byref(dp), w, h, *ptrs, C.c_void_p(stream_ptr), C.byref(st))
-    if rc != 0:
-        raise TrtError(f"trt_denoise_device failed ({rc}): {lib.trt_last_error().decode()}")
-    return st
+    return _call_hip("trt_denoise_device", int(dev.index or 0), C.byref(dp), w, h, *ptrs, C.c_void_p(stream_ptr))
 
 
 HISTORY_KEYS = ("cv", "length", "normal", "depth")
+MOMENTS_HISTORY_KEYS = HISTORY_KEYS + ("mom",)
 
 
 def _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags):
@@ -1139,45 +1169,43 @@ def _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_h
     return rp
 
 
-def _history(history, what):
+def _moments_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags, min_frames, sigma_normal, sigma_depth):
+    mp = _abi.MomentsParams()
+    mp.rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
+    mp.min_frames, mp.sigma_normal, mp.sigma_depth = int(min_frames), int(sigma_normal), float(sigma_depth)
+    return mp
+
+
+def _history_planes(history, what, keys, h, w):
+    """The history's entries of a validator's list: all absent (history None), or every key of `keys` given."""
     if history is None:
-        return [None] * 4
-    if not isinstance(history, dict) or any(history.get(k) is None for k in HISTORY_KEYS):
-        raise TrtError(f"{what}: history must be None or a dict with the keys cv, length, normal, depth")
-    return [history[k] for k in HISTORY_KEYS]
+        history = dict.fromkeys(keys)
+    elif not isinstance(history, dict) or any(history.get(k) is None for k in keys):
+        raise TrtError(f"{what}: history must be None or a dict with the keys {', '.join(keys)}")
+    shapes = {"cv": (h, w, 4), "length": (h, w), "normal": (h, w, 3), "depth": (h, w), "mom": (h, w, 4)}
+    return [("history " + k, history[k], shapes[k], True) for k in keys]
+
+
+def _host_outputs(h, w, keys):
+    shapes = {"color": (h, w, 3), "variance": (h, w), "cv": (h, w, 4), "length": (h, w), "mom": (h, w, 4)}
+    return {k: np.empty(shapes[k], np.float32) for k in keys}
 
 
 def _reproject_host(what, color, variance, albedo, normal, depth, prev_point, cur, prev, history, alpha, depth_tolerance, normal_threshold,
                     max_history, flags, device, want_stats):
-    """reproject() (prev_point None) and reproject_motion() on host arrays."""
+    """reproject() (prev_point None) and reproject_motion() on host arrays.  An input left None goes to the library, which refuses it."""
     color = np.ascontiguousarray(color, dtype=np.float32)
     h, w = _image_shape(color, what)
-    bufs = [color]
-    named = [("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))]
+    named = [("color", color, (h, w, 3), False), ("variance", variance, (h, w), True), ("albedo", albedo, (h, w, 3), True),
+             ("normal", normal, (h, w, 3), True), ("depth", depth, (h, w), True)]
     if what == "reproject_motion":
         if prev_point is None:
             raise TrtError("reproject_motion: prev_point is needed")
-        named.append(("prev_point", prev_point, (h, w, 3)))
-    named += [("history " + k, a, shape) for k, a, shape in zip(HISTORY_KEYS, _history(history, what), ((h, w, 4), (h, w), (h, w, 3), (h, w)))]
-    for name, a, shape in named:
-        if a is None:
-            bufs.append(None)
-            continue
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise TrtError(f"{what}: {name} must have shape {shape}, not {a.shape}")
-        bufs.append(a)
-    out = {"color": np.empty((h, w, 3), np.float32), "variance": np.empty((h, w), np.float32), "cv": np.empty((h, w, 4), np.float32),
-           "length": np.empty((h, w), np.float32)}
+        named.append(("prev_point", prev_point, (h, w, 3), False))
+    bufs = _host_planes(what, named + _history_planes(history, what, HISTORY_KEYS, h, w))
+    out = _host_outputs(h, w, ("color", "variance", "cv", "length"))
     rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
-    st = Stats()
-    lib = _abi.load_hip()
-    fp = C.POINTER(C.c_float)
-    entry = getattr(lib, "trt_" + what)
-    rc = entry(int(device), C.byref(rp), w, h, *[None if b is None else b.ctypes.data_as(fp) for b in bufs],
-               *[out[k].ctypes.data_as(fp) for k in ("color", "variance", "cv", "length")], C.byref(st))
-    if rc != 0:
-        raise TrtError(f"trt_{what} failed ({rc}): {lib.trt_last_error().decode()}")
+    st = _call_hip("trt_" + what, int(device), C.byref(rp), w, h, *_float_ptrs(bufs + list(out.values())))
     return (out, st) if want_stats else out
 
 
@@ -1206,32 +1234,18 @@ def reproject_motion(color, variance, albedo, normal, depth, prev_point, cur, pr
 def _reproject_device(what, color, variance, albedo, normal, depth, prev_point, cur, prev, out_color, out_variance, out_cv, out_length, history,
                       alpha, depth_tolerance, normal_threshold, max_history, flags, stream_ptr):
     """reproject_into() (prev_point None) and reproject_motion_into() on torch tensors."""
-    if not _is_torch(color) or color.dim() != 3:
-        raise TrtError(f"{what}: color must be a float32 tensor [height, width, 3]")
-    h, w = _image_shape(color, what)
-    dev = color.device
-    named = [("color", color, (h, w, 3)), ("variance", variance, (h, w)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))]
-    if what == "reproject_motion_into":
-        named.append(("prev_point", prev_point, (h, w, 3)))
-    named += [("history " + k, t, shape) for k, t, shape in zip(HISTORY_KEYS, _history(history, what), ((h, w, 4), (h, w), (h, w, 3), (h, w)))]
-    named += [("out_color", out_color, (h, w, 3)), ("out_variance", out_variance, (h, w)), ("out_cv", out_cv, (h, w, 4)), ("out_length", out_length, (h, w))]
-    ptrs = []
-    for name, t, shape in named:
-        if t is None and name.startswith("history"):
-            ptrs.append(None)
-            continue
-        if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape
-                or t.device != dev):
-            raise TrtError(f"{what}: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
-        ptrs.append(C.c_void_p(t.data_ptr()))
+    h, w, dev = _device_image(color, what)
+    motion = what == "reproject_motion_into"
+    named = [("color", color, (h, w, 3), False), ("variance", variance, (h, w), False), ("albedo", albedo, (h, w, 3), False),
+             ("normal", normal, (h, w, 3), False), ("depth", depth, (h, w), False)]
+    named += [("prev_point", prev_point, (h, w, 3), False)] if motion else []
+    named += _history_planes(history, what, HISTORY_KEYS, h, w)
+    named += [("out_color", out_color, (h, w, 3), False), ("out_variance", out_variance, (h, w), False), ("out_cv", out_cv, (h, w, 4), False),
+              ("out_length", out_length, (h, w), False)]
+    ptrs = _device_planes(what, dev, named)
     rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
-    st = Stats()
-    lib = _abi.load_hip()
-    name = "trt_reproject_motion_device" if what == "reproject_motion_into" else "trt_reproject_device"
-    rc = getattr(lib, name)(int(dev.index or 0), C.byref(rp), w, h, *ptrs, C.c_void_p(stream_ptr), C.byref(st))
-    if rc != 0:
-        raise TrtError(f"{name} failed ({rc}): {lib.trt_last_error().decode()}")
-    return st
+    return _call_hip("trt_reproject_motion_device" if motion else "trt_reproject_device", int(dev.index or 0), C.byref(rp), w, h, *ptrs,
+                     C.c_void_p(stream_ptr))
 
 
 def reproject_into(color, variance, albedo, normal, depth, cur, prev, out_color, out_variance, out_cv, out_length, history=None, alpha=0.2,
@@ -1251,28 +1265,6 @@ def reproject_motion_into(color, variance, albedo, normal, depth, prev_point, cu
                              out_length, history, alpha, depth_tolerance, normal_threshold, max_history, flags, stream_ptr)
 
 
-MOMENTS_HISTORY_KEYS = HISTORY_KEYS + ("mom",)
-
-
-def _moments_history_shapes(h, w):
-    return (h, w, 4), (h, w), (h, w, 3), (h, w), (h, w, 4)
-
-
-def _moments_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags, min_frames, sigma_normal, sigma_depth):
-    mp = _abi.MomentsParams()
-    mp.rp = _reproject_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags)
-    mp.min_frames, mp.sigma_normal, mp.sigma_depth = int(min_frames), int(sigma_normal), float(sigma_depth)
-    return mp
-
-
-def _moments_history(history, what):
-    if history is None:
-        return [None] * 5
-    if not isinstance(history, dict) or any(history.get(k) is None for k in MOMENTS_HISTORY_KEYS):
-        raise TrtError(f"{what}: history must be None or a dict with the keys cv, length, normal, depth, mom")
-    return [history[k] for k in MOMENTS_HISTORY_KEYS]
-
-
 def reproject_moments(color, albedo, normal, depth, cur, prev=None, history=None, prev_point=None, alpha=0.2, depth_tolerance=0.1,
                       normal_threshold=0.9, max_history=255.0, flags=0, min_frames=4, sigma_normal=128, sigma_depth=1.0, device=0, want_stats=False):
     """reproject() for frames of one sample per pixel (trt_reproject_moments, include/trt.h has the contract): no variance goes in; it is
@@ -1283,27 +1275,12 @@ def reproject_moments(color, albedo, normal, depth, cur, prev=None, history=None
     what = "reproject_moments"
     color = np.ascontiguousarray(color, dtype=np.float32)
     h, w = _image_shape(color, what)
-    bufs = [color]
-    named = [("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w)), ("prev_point", prev_point, (h, w, 3))]
-    named += [("history " + k, a, shape) for k, a, shape in zip(MOMENTS_HISTORY_KEYS, _moments_history(history, what), _moments_history_shapes(h, w))]
-    for name, a, shape in named:
-        if a is None:
-            bufs.append(None)
-            continue
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise TrtError(f"{what}: {name} must have shape {shape}, not {a.shape}")
-        bufs.append(a)
-    out = {"color": np.empty((h, w, 3), np.float32), "variance": np.empty((h, w), np.float32), "cv": np.empty((h, w, 4), np.float32),
-           "length": np.empty((h, w), np.float32), "mom": np.empty((h, w, 4), np.float32)}
+    named = [("color", color, (h, w, 3), False), ("albedo", albedo, (h, w, 3), True), ("normal", normal, (h, w, 3), True), ("depth", depth, (h, w), True),
+             ("prev_point", prev_point, (h, w, 3), True)]  # an input left None goes to the library, which refuses it
+    bufs = _host_planes(what, named + _history_planes(history, what, MOMENTS_HISTORY_KEYS, h, w))
+    out = _host_outputs(h, w, ("color", "variance", "cv", "length", "mom"))
     mp = _moments_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags, min_frames, sigma_normal, sigma_depth)
-    st = Stats()
-    lib = _abi.load_hip()
-    fp = C.POINTER(C.c_float)
-    rc = lib.trt_reproject_moments(int(device), C.byref(mp), w, h, *[None if b is None else b.ctypes.data_as(fp) for b in bufs],
-                                   *[out[k].ctypes.data_as(fp) for k in ("color", "variance", "cv", "length", "mom")], C.byref(st))
-    if rc != 0:
-        raise TrtError(f"trt_reproject_moments failed ({rc}): {lib.trt_last_error().decode()}")
+    st = _call_hip("trt_reproject_moments", int(device), C.byref(mp), w, h, *_float_ptrs(bufs + list(out.values())))
     return (out, st) if want_stats else out
 
 
@@ -1314,31 +1291,15 @@ def reproject_moments_into(color, albedo, normal, depth, cur, prev, out_color, o
     and prev_point too; out_color [h, w, 3], out_variance [h, w], out_cv [h, w, 4], out_length [h, w], out_mom [h, w, 4]; no output may be
     an input), the work on stream `stream_ptr` (0 = default).  Writes the five outputs; -> Stats."""
     what = "reproject_moments_into"
-    if not _is_torch(color) or color.dim() != 3:
-        raise TrtError(f"{what}: color must be a float32 tensor [height, width, 3]")
-    h, w = _image_shape(color, what)
-    dev = color.device
-    named = [("color", color, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w)),
-             ("prev_point", prev_point, (h, w, 3))]
-    named += [("history " + k, t, shape) for k, t, shape in zip(MOMENTS_HISTORY_KEYS, _moments_history(history, what), _moments_history_shapes(h, w))]
-    named += [("out_color", out_color, (h, w, 3)), ("out_variance", out_variance, (h, w)), ("out_cv", out_cv, (h, w, 4)), ("out_length", out_length, (h, w)),
-              ("out_mom", out_mom, (h, w, 4))]
-    ptrs = []
-    for name, t, shape in named:
-        if t is None and (name.startswith("history") or name == "prev_point"):
-            ptrs.append(None)
-            continue
-        if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != shape
-                or t.device != dev):
-            raise TrtError(f"{what}: {name} must be a contiguous float32 tensor of shape {shape} on {dev}")
-        ptrs.append(C.c_void_p(t.data_ptr()))
+    h, w, dev = _device_image(color, what)
+    named = [("color", color, (h, w, 3), False), ("albedo", albedo, (h, w, 3), False), ("normal", normal, (h, w, 3), False), ("depth", depth, (h, w), False),
+             ("prev_point", prev_point, (h, w, 3), True)]
+    named += _history_planes(history, what, MOMENTS_HISTORY_KEYS, h, w)
+    named += [("out_color", out_color, (h, w, 3), False), ("out_variance", out_variance, (h, w), False), ("out_cv", out_cv, (h, w, 4), False),
+              ("out_length", out_length, (h, w), False), ("out_mom", out_mom, (h, w, 4), False)]
+    ptrs = _device_planes(what, dev, named)
     mp = _moments_params(cur, prev, alpha, depth_tolerance, normal_threshold, max_history, flags, min_frames, sigma_normal, sigma_depth)
-    st = Stats()
-    lib = _abi.load_hip()
-    rc = lib.trt_reproject_moments_device(int(dev.index or 0), C.byref(mp), w, h, *ptrs, C.c_void_p(stream_ptr), C.byref(st))
-    if rc != 0:
-        raise TrtError(f"trt_reproject_moments_device failed ({rc}): {lib.trt_last_error().decode()}")
-    return st
+    return _call_hip("trt_reproject_moments_device", int(dev.index or 0), C.byref(mp), w, h, *ptrs, C.c_void_p(stream_ptr))
 
 
 class TemporalAccumulator:
@@ -1392,6 +1353,18 @@ class TemporalAccumulator:
         self._history = None
         self._camera = None
 
+    def _previous_points(self, camera, moved_from, h, w, device, stream, total):
+        """Where the surface each pixel of `camera` shows lay on the vertices `moved_from` (center_rays -> Renderer.trace_points_into, its
+        Stats added to `total`) -> float32 [h, w, 3] on `device`; None, and nothing traced, on a first frame or without moved_from."""
+        import torch
+        if moved_from is None or self._history is None:
+            return None
+        v0 = moved_from if _is_torch(moved_from) else torch.from_numpy(moved_from).to(device)
+        org, dirs = center_rays(camera, w, h, flags=self.reproject_kw["flags"], device=device)
+        point = torch.empty((h * w, 3), dtype=torch.float32, device=device)
+        _add_stats(total, self.renderer.trace_points_into(org, dirs, v0.contiguous(), point, stream_ptr=stream))
+        return point.view(h, w, 3)
+
     def frame(self, camera, on_device=False, moved_from=None):
         """Renders the frame seen by `camera` with seed params.seed + frame_index (mod 2^32), accumulates and denoises it.  -> dict(color,
         variance, albedo, normal, depth: the frame's own buffers; accumulated, accumulated_variance: the blend with the reprojected history;
@@ -1428,25 +1401,15 @@ class TemporalAccumulator:
         acc, acc_var = torch.empty_like(color), torch.empty_like(aov["depth"])
         cv, length = torch.empty((h, w, 4), dtype=torch.float32, device=color.device), torch.empty_like(aov["depth"])
         mom = torch.empty_like(cv) if moments else None
+        point = self._previous_points(camera, moved_from, h, w, color.device, stream, total)
         if moments:
-            point = None
-            if moved_from is not None and self._history is not None:
-                v0 = moved_from if _is_torch(moved_from) else torch.from_numpy(moved_from).to(color.device)
-                org, dirs = center_rays(camera, w, h, flags=self.reproject_kw["flags"], device=color.device)
-                point = torch.empty((h * w, 3), dtype=torch.float32, device=color.device)
-                _add_stats(total, self.renderer.trace_points_into(org, dirs, v0.contiguous(), point, stream_ptr=stream))
-                point = point.view(h, w, 3)
             _add_stats(total, reproject_moments_into(color, aov["albedo"], aov["normal"], aov["depth"], camera, self._camera, acc, acc_var, cv, length, mom,
                                                      history=self._history, prev_point=point, stream_ptr=stream, **self.reproject_kw, **self.moments_kw))
-        elif moved_from is None or self._history is None:
+        elif point is None:
             _add_stats(total, reproject_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], camera, self._camera, acc, acc_var, cv, length,
                                              history=self._history, stream_ptr=stream, **self.reproject_kw))
         else:
-            v0 = moved_from if _is_torch(moved_from) else torch.from_numpy(moved_from).to(color.device)
-            org, dirs = center_rays(camera, w, h, flags=self.reproject_kw["flags"], device=color.device)
-            point = torch.empty((h * w, 3), dtype=torch.float32, device=color.device)
-            _add_stats(total, self.renderer.trace_points_into(org, dirs, v0.contiguous(), point, stream_ptr=stream))
-            _add_stats(total, reproject_motion_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], point.view(h, w, 3), camera, self._camera,
+            _add_stats(total, reproject_motion_into(color, variance, aov["albedo"], aov["normal"], aov["depth"], point, camera, self._camera,
                                                     acc, acc_var, cv, length, history=self._history, stream_ptr=stream, **self.reproject_kw))
         denoised = torch.empty_like(color)
         _add_stats(total, denoise_into(acc, acc_var, aov["albedo"], aov["normal"], aov["depth"], denoised, stream_ptr=stream, **self.denoise_kw))

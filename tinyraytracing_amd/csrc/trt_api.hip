@@ -2264,16 +2264,86 @@ struct DenoiseIo {
     float* out;
 };
 
-// Scratch and events of one call, released on every way out of it.
-struct DenoiseScratch {
+// The skeleton the image-space passes share (trt_denoise, trt_reproject, trt_reproject_motion, trt_reproject_moments and their _device
+// entries): the planes of one call, each width*height*{1,3,4} floats, its scratch, its four events and its statistics.  A host entry stages
+// the present planes through one allocation; a device entry uses the caller's pointers in place and, without scratch, allocates nothing.
+// The driver lists its planes once (in / out / scratch return the plane's index), calls begin(), launches on S[index], calls finish().
+// Everything is released on every way out.
+struct ImageStage {
+    enum Kind { IN, OUT, SCRATCH };
+    struct Plane {
+        Kind kind;
+        void* user;     // the caller's array; null for scratch
+        size_t bytes;
+        bool present;   // an absent plane is neither staged nor copied, and the kernels get a null pointer for it
+        void* dev;      // after begin(): the staging (host entries, scratch) or `user`
+    };
+    const size_t pixels;
+    const bool host;
+    std::vector<Plane> planes;
+    hipStream_t stream = nullptr;
     void* p = nullptr;
     hipEvent_t ev[4] = {};
-    ~DenoiseScratch()
+
+    ImageStage(int width, int height, bool host_) : pixels((size_t)width * (size_t)height), host(host_) {}
+    ImageStage(const ImageStage&) = delete;
+    ~ImageStage()
     {
         if (p) (void)hipFree(p);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
     }
+    int add(Kind kind, const void* user, size_t bytes, bool present)
+    {
+        planes.push_back(Plane{kind, const_cast<void*>(user), bytes, present, nullptr});
+        return (int)planes.size() - 1;
+    }
+    int in(const float* user, int floats, bool present = true) { return add(IN, user, pixels * floats * sizeof(float), present); }
+    int out(float* user, int floats) { return add(OUT, user, pixels * floats * sizeof(float), true); }
+    int scratch(size_t bytes) { return add(SCRATCH, nullptr, bytes, true); }
+    float* operator[](int i) const { return (float*)planes[i].dev; }
+
+    // One hipMalloc for whatever is staged (256-byte aligned regions, in the order listed), then event 0, the inputs' upload, event 1.
+    int begin(hipStream_t stream_)
+    {
+        stream = stream_;
+        Layout L;
+        std::vector<size_t> at(planes.size());
+        for (size_t i = 0; i < planes.size(); ++i)
+            if (staged(planes[i])) at[i] = L.add(planes[i].bytes, 256);
+        if (L.bytes) HIPC(hipMalloc(&p, L.bytes));
+        for (hipEvent_t& e : ev) HIPC(hipEventCreate(&e));
+        for (size_t i = 0; i < planes.size(); ++i) planes[i].dev = staged(planes[i]) ? (char*)p + at[i] : planes[i].present ? planes[i].user : nullptr;
+        HIPC(hipEventRecord(ev[0], stream));
+        for (const Plane& b : planes)
+            if (b.kind == IN && staged(b)) HIPC(hipMemcpyAsync(b.dev, b.user, b.bytes, hipMemcpyHostToDevice, stream));
+        HIPC(hipEventRecord(ev[1], stream));
+        return TRT_OK;
+    }
+    // Behind the launches: event 2, the outputs' download, event 3, the wait, and the statistics of the `launches` kernels.
+    int finish(trt_stats* stats, uint64_t launches)
+    {
+        HIPC(hipGetLastError());
+        HIPC(hipEventRecord(ev[2], stream));
+        for (const Plane& b : planes)
+            if (b.kind == OUT && staged(b)) HIPC(hipMemcpyAsync(b.user, b.dev, b.bytes, hipMemcpyDeviceToHost, stream));
+        HIPC(hipEventRecord(ev[3], stream));
+        HIPC(hipStreamSynchronize(stream));
+        HIPC(hipGetLastError());
+        if (stats) {
+            float k_ms = 0.f, all_ms = 0.f;
+            HIPC(hipEventElapsedTime(&k_ms, ev[1], ev[2]));
+            HIPC(hipEventElapsedTime(&all_ms, ev[0], ev[3]));
+            std::memset(stats, 0, sizeof(*stats));
+            stats->launches[TRT_K_DENOISE] = launches;
+            stats->kernel_ms[TRT_K_DENOISE] = k_ms;
+            stats->render_ms = all_ms;
+        }
+        return TRT_OK;
+    }
+
+private:
+    bool staged(const Plane& b) const { return b.present && (host || b.kind == SCRATCH); }
 };
 
 // The checks of include/trt.h; fills the level arguments (step 1) and the number of levels.
@@ -2307,34 +2377,18 @@ int denoise(int device, const trt_denoise_params* prm, int width, int height, co
     int levels = 0;
     if (int e = denoiseArgs(prm, width, height, io, a, levels, what)) return e;
     if (int e = useDevice(device)) return e;
-    const size_t n = (size_t)width * (size_t)height, f1 = n * sizeof(float), f3 = 3 * f1, r16 = n * sizeof(trt_dn4);
-    Layout L;
-    const size_t o_cv0 = L.add(r16, 256), o_cv1 = L.add(r16, 256), o_gd = L.add(r16, 256), o_aux = L.add(r16, 256);
-    // host entries stage color, variance, albedo, normal, depth and out
-    const size_t o_c = L.add(host ? f3 : 0, 256), o_v = L.add(host ? f1 : 0, 256), o_a = L.add(host ? f3 : 0, 256), o_n = L.add(host ? f3 : 0, 256);
-    const size_t o_z = L.add(host ? f1 : 0, 256), o_o = L.add(host ? f3 : 0, 256);
-    DenoiseScratch S;
-    HIPC(hipMalloc(&S.p, L.bytes));
-    for (hipEvent_t& e : S.ev) HIPC(hipEventCreate(&e));
-    char* b = (char*)S.p;
-    trt_dn4* cv[2] = {(trt_dn4*)(b + o_cv0), (trt_dn4*)(b + o_cv1)};
-    trt_dn4* gd = (trt_dn4*)(b + o_gd);
-    trt_dn4* aux = (trt_dn4*)(b + o_aux);
-    DenoiseIo dev = io;
-    HIPC(hipEventRecord(S.ev[0], stream));
-    if (host) {
-        dev = DenoiseIo{(const float*)(b + o_c), (const float*)(b + o_v), (const float*)(b + o_a), (const float*)(b + o_n), (const float*)(b + o_z), (float*)(b + o_o)};
-        HIPC(hipMemcpyAsync((void*)dev.color, io.color, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.variance, io.variance, f1, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.albedo, io.albedo, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.normal, io.normal, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.depth, io.depth, f1, hipMemcpyHostToDevice, stream));
-    }
     const char* lds_env = std::getenv("TRT_DENOISE_LDS");
     const bool lds = !(lds_env && lds_env[0] == '0');
     const dim3 grid((unsigned)((width + DN_BX - 1) / DN_BX), (unsigned)((height + DN_BY - 1) / DN_BY)), block(DN_BX, DN_BY);
-    HIPC(hipEventRecord(S.ev[1], stream));
-    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, stream, width, height, dev.color, dev.variance, dev.albedo, dev.normal, dev.depth, cv[0], gd, aux);
+    ImageStage S(width, height, host);
+    const size_t r16 = S.pixels * sizeof(trt_dn4);
+    const int cv0 = S.scratch(r16), cv1 = S.scratch(r16), guide = S.scratch(r16), auxiliary = S.scratch(r16);
+    const int color = S.in(io.color, 3), variance = S.in(io.variance, 1), albedo = S.in(io.albedo, 3), normal = S.in(io.normal, 3), depth = S.in(io.depth, 1);
+    const int out = S.out(io.out, 3);
+    if (int e = S.begin(stream)) return e;
+    trt_dn4* cv[2] = {(trt_dn4*)S[cv0], (trt_dn4*)S[cv1]};
+    trt_dn4 *gd = (trt_dn4*)S[guide], *aux = (trt_dn4*)S[auxiliary];
+    hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, stream, width, height, S[color], S[variance], S[albedo], S[normal], S[depth], cv[0], gd, aux);
     for (int k = 0; k < levels; ++k) {
         a.step = 1 << k;
         const trt_dn4* in = cv[k & 1];
@@ -2345,24 +2399,9 @@ int denoise(int device, const trt_denoise_params* prm, int width, int height, co
         static const LevelKernel table[3][2] = {{k_denoise_level<0, false>, k_denoise_level<0, true>},
                                                 {k_denoise_level<1, false>, k_denoise_level<1, true>},
                                                 {k_denoise_level<2, false>, k_denoise_level<2, true>}};
-        hipLaunchKernelGGL(table[lds_step][last ? 1 : 0], grid, block, 0, stream, a, in, (const trt_dn4*)gd, (const trt_dn4*)aux, nxt, dev.out);
+        hipLaunchKernelGGL(table[lds_step][last ? 1 : 0], grid, block, 0, stream, a, in, (const trt_dn4*)gd, (const trt_dn4*)aux, nxt, S[out]);
     }
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(S.ev[2], stream));
-    if (host) HIPC(hipMemcpyAsync(io.out, dev.out, f3, hipMemcpyDeviceToHost, stream));
-    HIPC(hipEventRecord(S.ev[3], stream));
-    HIPC(hipStreamSynchronize(stream));
-    HIPC(hipGetLastError());
-    if (stats) {
-        float k_ms = 0.f, all_ms = 0.f;
-        HIPC(hipEventElapsedTime(&k_ms, S.ev[1], S.ev[2]));
-        HIPC(hipEventElapsedTime(&all_ms, S.ev[0], S.ev[3]));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->launches[TRT_K_DENOISE] = 1 + (uint64_t)levels;
-        stats->kernel_ms[TRT_K_DENOISE] = k_ms;
-        stats->render_ms = all_ms;
-    }
-    return TRT_OK;
+    return S.finish(stats, 1 + (uint64_t)levels);
 }
 
 }  // namespace
@@ -2390,9 +2429,9 @@ namespace {
 
 struct ReprojectIo {
     const float *color, *variance, *albedo, *normal, *depth;
+    const float* prev_point;  // trt_reproject_motion*: W*H*3, required there; null in trt_reproject*
     const float *prev_cv, *prev_len, *prev_normal, *prev_depth;
     float *out_color, *out_variance, *out_cv, *out_len;
-    const float* prev_point = nullptr;  // trt_reproject_motion*: W*H*3, required there
 };
 
 // The checks of include/trt.h, in its order; fills the kernel's arguments.
@@ -2413,69 +2452,22 @@ int reproject(int device, const trt_reproject_params* prm, int width, int height
     trt_rp_args a{};
     if (int e = reprojectArgs(prm, width, height, io, host, motion, a, what)) return e;
     if (int e = useDevice(device)) return e;
-    const size_t n = (size_t)width * (size_t)height, f1 = n * sizeof(float), f3 = 3 * f1, f4 = 4 * f1;
     const bool hist = a.history != 0;
-    DenoiseScratch S;  // the staging of the host entry (none for the device entry) and the events
-    ReprojectIo dev = io;
-    for (hipEvent_t& e : S.ev) HIPC(hipEventCreate(&e));
-    if (host) {
-        Layout L;
-        const size_t o_c = L.add(f3, 256), o_v = L.add(f1, 256), o_a = L.add(f3, 256), o_n = L.add(f3, 256), o_z = L.add(f1, 256);
-        const size_t o_pc = L.add(hist ? f4 : 0, 256), o_pl = L.add(hist ? f1 : 0, 256), o_pn = L.add(hist ? f3 : 0, 256), o_pz = L.add(hist ? f1 : 0, 256);
-        const size_t o_oc = L.add(f3, 256), o_ov = L.add(f1, 256), o_ocv = L.add(f4, 256), o_ol = L.add(f1, 256);
-        const size_t o_pp = L.add(motion ? f3 : 0, 256);
-        HIPC(hipMalloc(&S.p, L.bytes));
-        char* b = (char*)S.p;
-        dev = ReprojectIo{(const float*)(b + o_c), (const float*)(b + o_v), (const float*)(b + o_a), (const float*)(b + o_n), (const float*)(b + o_z),
-                          hist ? (const float*)(b + o_pc) : nullptr, hist ? (const float*)(b + o_pl) : nullptr, hist ? (const float*)(b + o_pn) : nullptr,
-                          hist ? (const float*)(b + o_pz) : nullptr, (float*)(b + o_oc), (float*)(b + o_ov), (float*)(b + o_ocv), (float*)(b + o_ol)};
-        if (motion) dev.prev_point = (const float*)(b + o_pp);
-    }
-    HIPC(hipEventRecord(S.ev[0], stream));
-    if (host) {
-        HIPC(hipMemcpyAsync((void*)dev.color, io.color, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.variance, io.variance, f1, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.albedo, io.albedo, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.normal, io.normal, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.depth, io.depth, f1, hipMemcpyHostToDevice, stream));
-        if (motion) HIPC(hipMemcpyAsync((void*)dev.prev_point, io.prev_point, f3, hipMemcpyHostToDevice, stream));
-        if (hist) {
-            HIPC(hipMemcpyAsync((void*)dev.prev_cv, io.prev_cv, f4, hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync((void*)dev.prev_len, io.prev_len, f1, hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync((void*)dev.prev_normal, io.prev_normal, f3, hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync((void*)dev.prev_depth, io.prev_depth, f1, hipMemcpyHostToDevice, stream));
-        }
-    }
     const dim3 grid((unsigned)((width + RP_BX - 1) / RP_BX), (unsigned)((height + RP_BY - 1) / RP_BY)), block(RP_BX, RP_BY);
-    HIPC(hipEventRecord(S.ev[1], stream));
-    const trt_rp_fetch fetch{(const trt_dn4*)dev.prev_cv, dev.prev_len, dev.prev_normal, dev.prev_depth};
+    ImageStage S(width, height, host);
+    const int color = S.in(io.color, 3), variance = S.in(io.variance, 1), albedo = S.in(io.albedo, 3), normal = S.in(io.normal, 3), depth = S.in(io.depth, 1);
+    const int prev_point = S.in(io.prev_point, 3, motion);
+    const int prev_cv = S.in(io.prev_cv, 4, hist), prev_len = S.in(io.prev_len, 1, hist), prev_normal = S.in(io.prev_normal, 3, hist), prev_depth = S.in(io.prev_depth, 1, hist);
+    const int out_color = S.out(io.out_color, 3), out_variance = S.out(io.out_variance, 1), out_cv = S.out(io.out_cv, 4), out_len = S.out(io.out_len, 1);
+    if (int e = S.begin(stream)) return e;
+    const trt_rp_fetch fetch{(const trt_dn4*)S[prev_cv], S[prev_len], S[prev_normal], S[prev_depth]};
     if (motion)
-        hipLaunchKernelGGL(k_reproject_motion, grid, block, 0, stream, a, dev.color, dev.variance, dev.albedo, dev.normal, dev.depth, dev.prev_point, fetch,
-                           dev.out_color, dev.out_variance, (trt_dn4*)dev.out_cv, dev.out_len);
+        hipLaunchKernelGGL(k_reproject_motion, grid, block, 0, stream, a, S[color], S[variance], S[albedo], S[normal], S[depth], S[prev_point], fetch,
+                           S[out_color], S[out_variance], (trt_dn4*)S[out_cv], S[out_len]);
     else
-        hipLaunchKernelGGL(k_reproject, grid, block, 0, stream, a, dev.color, dev.variance, dev.albedo, dev.normal, dev.depth, fetch, dev.out_color,
-                           dev.out_variance, (trt_dn4*)dev.out_cv, dev.out_len);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(S.ev[2], stream));
-    if (host) {
-        HIPC(hipMemcpyAsync(io.out_color, dev.out_color, f3, hipMemcpyDeviceToHost, stream));
-        HIPC(hipMemcpyAsync(io.out_variance, dev.out_variance, f1, hipMemcpyDeviceToHost, stream));
-        HIPC(hipMemcpyAsync(io.out_cv, dev.out_cv, f4, hipMemcpyDeviceToHost, stream));
-        HIPC(hipMemcpyAsync(io.out_len, dev.out_len, f1, hipMemcpyDeviceToHost, stream));
-    }
-    HIPC(hipEventRecord(S.ev[3], stream));
-    HIPC(hipStreamSynchronize(stream));
-    HIPC(hipGetLastError());
-    if (stats) {
-        float k_ms = 0.f, all_ms = 0.f;
-        HIPC(hipEventElapsedTime(&k_ms, S.ev[1], S.ev[2]));
-        HIPC(hipEventElapsedTime(&all_ms, S.ev[0], S.ev[3]));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->launches[TRT_K_DENOISE] = 1;
-        stats->kernel_ms[TRT_K_DENOISE] = k_ms;
-        stats->render_ms = all_ms;
-    }
-    return TRT_OK;
+        hipLaunchKernelGGL(k_reproject, grid, block, 0, stream, a, S[color], S[variance], S[albedo], S[normal], S[depth], fetch, S[out_color],
+                           S[out_variance], (trt_dn4*)S[out_cv], S[out_len]);
+    return S.finish(stats, 1);
 }
 
 }  // namespace
@@ -2488,7 +2480,7 @@ int trt_reproject(int device, const trt_reproject_params* params, int width, int
                   trt_stats* stats)
 {
     return reproject(device, params, width, height,
-                     ReprojectIo{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len},
+                     ReprojectIo{color, variance, albedo, normal, depth, nullptr, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len},
                      true, nullptr, stats, "trt_reproject");
 }
 
@@ -2498,7 +2490,7 @@ int trt_reproject_device(int device, const trt_reproject_params* params, int wid
                          float* out_len, void* hip_stream, trt_stats* stats)
 {
     return reproject(device, params, width, height,
-                     ReprojectIo{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len},
+                     ReprojectIo{color, variance, albedo, normal, depth, nullptr, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len},
                      false, (hipStream_t)hip_stream, stats, "trt_reproject_device");
 }
 
@@ -2507,8 +2499,7 @@ int trt_reproject_motion(int device, const trt_reproject_params* params, int wid
                          const float* prev_len, const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance,
                          float* out_cv, float* out_len, trt_stats* stats)
 {
-    ReprojectIo io{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len};
-    io.prev_point = prev_point;
+    const ReprojectIo io{color, variance, albedo, normal, depth, prev_point, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len};
     return reproject(device, params, width, height, io, true, nullptr, stats, "trt_reproject_motion", true);
 }
 
@@ -2517,8 +2508,7 @@ int trt_reproject_motion_device(int device, const trt_reproject_params* params, 
                                 const float* prev_len, const float* prev_normal, const float* prev_depth, float* out_color, float* out_variance,
                                 float* out_cv, float* out_len, void* hip_stream, trt_stats* stats)
 {
-    ReprojectIo io{color, variance, albedo, normal, depth, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len};
-    io.prev_point = prev_point;
+    const ReprojectIo io{color, variance, albedo, normal, depth, prev_point, prev_cv, prev_len, prev_normal, prev_depth, out_color, out_variance, out_cv, out_len};
     return reproject(device, params, width, height, io, false, (hipStream_t)hip_stream, stats, "trt_reproject_motion_device", true);
 }
 
@@ -2546,69 +2536,24 @@ int reprojectMoments(int device, const trt_moments_params* prm, int width, int h
     if (!host && ((((uintptr_t)io.out_cv) | ((uintptr_t)io.prev_cv) | ((uintptr_t)io.out_mom) | ((uintptr_t)io.prev_mom)) & 15u))
         return fail(TRT_EINVAL, std::string(what) + ": prev_cv, out_cv, prev_mom and out_mom must be 16-byte aligned");
     if (int e = useDevice(device)) return e;
-    const size_t n = (size_t)width * (size_t)height, f1 = n * sizeof(float), f3 = 3 * f1, f4 = 4 * f1;
     const bool hist = a.rp.history != 0, motion = io.prev_point != nullptr;
-    DenoiseScratch S;  // the staging of the host entry (none for the device entry) and the events
-    MomentsIo dev = io;
-    for (hipEvent_t& e : S.ev) HIPC(hipEventCreate(&e));
-    if (host) {
-        Layout L;
-        const size_t o_c = L.add(f3, 256), o_a = L.add(f3, 256), o_n = L.add(f3, 256), o_z = L.add(f1, 256), o_pp = L.add(motion ? f3 : 0, 256);
-        const size_t o_pc = L.add(hist ? f4 : 0, 256), o_pl = L.add(hist ? f1 : 0, 256), o_pn = L.add(hist ? f3 : 0, 256), o_pz = L.add(hist ? f1 : 0, 256);
-        const size_t o_pm = L.add(hist ? f4 : 0, 256);
-        const size_t o_oc = L.add(f3, 256), o_ov = L.add(f1, 256), o_ocv = L.add(f4, 256), o_ol = L.add(f1, 256), o_om = L.add(f4, 256);
-        HIPC(hipMalloc(&S.p, L.bytes));
-        char* b = (char*)S.p;
-        auto in = [&](size_t o, bool there) { return there ? (const float*)(b + o) : nullptr; };
-        dev = MomentsIo{in(o_c, true), in(o_a, true), in(o_n, true), in(o_z, true), in(o_pp, motion), in(o_pc, hist), in(o_pl, hist), in(o_pn, hist),
-                        in(o_pz, hist), in(o_pm, hist), (float*)(b + o_oc), (float*)(b + o_ov), (float*)(b + o_ocv), (float*)(b + o_ol), (float*)(b + o_om)};
-    }
-    HIPC(hipEventRecord(S.ev[0], stream));
-    if (host) {
-        HIPC(hipMemcpyAsync((void*)dev.color, io.color, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.albedo, io.albedo, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.normal, io.normal, f3, hipMemcpyHostToDevice, stream));
-        HIPC(hipMemcpyAsync((void*)dev.depth, io.depth, f1, hipMemcpyHostToDevice, stream));
-        if (motion) HIPC(hipMemcpyAsync((void*)dev.prev_point, io.prev_point, f3, hipMemcpyHostToDevice, stream));
-        if (hist) {
-            HIPC(hipMemcpyAsync((void*)dev.prev_cv, io.prev_cv, f4, hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync((void*)dev.prev_len, io.prev_len, f1, hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync((void*)dev.prev_normal, io.prev_normal, f3, hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync((void*)dev.prev_depth, io.prev_depth, f1, hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync((void*)dev.prev_mom, io.prev_mom, f4, hipMemcpyHostToDevice, stream));
-        }
-    }
     const char* lds_env = std::getenv("TRT_MOMENTS_LDS");
     const bool lds = !(lds_env && lds_env[0] == '0');
     const dim3 grid((unsigned)((width + MV_BX - 1) / MV_BX), (unsigned)((height + MV_BY - 1) / MV_BY)), block(MV_BX, MV_BY);
-    HIPC(hipEventRecord(S.ev[1], stream));
-    const trt_mv_fetch fetch{(const trt_dn4*)dev.prev_cv, dev.prev_len, dev.prev_normal, dev.prev_depth, (const trt_dn4*)dev.prev_mom};
-    hipLaunchKernelGGL(motion ? k_reproject_moments<true> : k_reproject_moments<false>, grid, block, 0, stream, a, dev.color, dev.albedo, dev.normal,
-                       dev.depth, dev.prev_point, fetch, dev.out_color, dev.out_variance, (trt_dn4*)dev.out_cv, dev.out_len, (trt_dn4*)dev.out_mom);
-    hipLaunchKernelGGL(lds ? k_moments_variance<true> : k_moments_variance<false>, grid, block, 0, stream, a, dev.albedo, dev.normal, dev.depth,
-                       (const float*)dev.out_len, (const trt_dn4*)dev.out_mom, dev.out_cv, dev.out_variance);
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(S.ev[2], stream));
-    if (host) {
-        HIPC(hipMemcpyAsync(io.out_color, dev.out_color, f3, hipMemcpyDeviceToHost, stream));
-        HIPC(hipMemcpyAsync(io.out_variance, dev.out_variance, f1, hipMemcpyDeviceToHost, stream));
-        HIPC(hipMemcpyAsync(io.out_cv, dev.out_cv, f4, hipMemcpyDeviceToHost, stream));
-        HIPC(hipMemcpyAsync(io.out_len, dev.out_len, f1, hipMemcpyDeviceToHost, stream));
-        HIPC(hipMemcpyAsync(io.out_mom, dev.out_mom, f4, hipMemcpyDeviceToHost, stream));
-    }
-    HIPC(hipEventRecord(S.ev[3], stream));
-    HIPC(hipStreamSynchronize(stream));
-    HIPC(hipGetLastError());
-    if (stats) {
-        float k_ms = 0.f, all_ms = 0.f;
-        HIPC(hipEventElapsedTime(&k_ms, S.ev[1], S.ev[2]));
-        HIPC(hipEventElapsedTime(&all_ms, S.ev[0], S.ev[3]));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->launches[TRT_K_DENOISE] = 2;
-        stats->kernel_ms[TRT_K_DENOISE] = k_ms;
-        stats->render_ms = all_ms;
-    }
-    return TRT_OK;
+    ImageStage S(width, height, host);
+    const int color = S.in(io.color, 3), albedo = S.in(io.albedo, 3), normal = S.in(io.normal, 3), depth = S.in(io.depth, 1);
+    const int prev_point = S.in(io.prev_point, 3, motion);
+    const int prev_cv = S.in(io.prev_cv, 4, hist), prev_len = S.in(io.prev_len, 1, hist), prev_normal = S.in(io.prev_normal, 3, hist), prev_depth = S.in(io.prev_depth, 1, hist);
+    const int prev_mom = S.in(io.prev_mom, 4, hist);
+    const int out_color = S.out(io.out_color, 3), out_variance = S.out(io.out_variance, 1), out_cv = S.out(io.out_cv, 4), out_len = S.out(io.out_len, 1);
+    const int out_mom = S.out(io.out_mom, 4);
+    if (int e = S.begin(stream)) return e;
+    const trt_mv_fetch fetch{(const trt_dn4*)S[prev_cv], S[prev_len], S[prev_normal], S[prev_depth], (const trt_dn4*)S[prev_mom]};
+    hipLaunchKernelGGL(motion ? k_reproject_moments<true> : k_reproject_moments<false>, grid, block, 0, stream, a, S[color], S[albedo], S[normal],
+                       S[depth], S[prev_point], fetch, S[out_color], S[out_variance], (trt_dn4*)S[out_cv], S[out_len], (trt_dn4*)S[out_mom]);
+    hipLaunchKernelGGL(lds ? k_moments_variance<true> : k_moments_variance<false>, grid, block, 0, stream, a, S[albedo], S[normal], S[depth],
+                       (const float*)S[out_len], (const trt_dn4*)S[out_mom], S[out_cv], S[out_variance]);
+    return S.finish(stats, 2);
 }
 
 }  // namespace
