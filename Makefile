@@ -29,8 +29,11 @@ HOST_HDR := $(wildcard $(PKG)/host/*.h) $(wildcard $(PKG)/csrc/*.h) include/trt.
 HIP_SRC := $(PKG)/csrc/trt_api.hip
 HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include/trt_exact.h
 
-.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu refitcpu rayscpu variants probe exactcheck nodecheck clean
-all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu refitcpu rayscpu cli exactcheck nodecheck
+# test-only library of tests/test_shade_cases_cpu.py: part of `all` wherever its source is in the tree
+SHADE_MUTANTS := $(if $(wildcard tests/hostsim/shade_mutants.cpp),shademutants)
+
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu refitcpu rayscpu variants probe exactcheck nodecheck shadecheck shademutants clean
+all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu refitcpu rayscpu cli exactcheck nodecheck shadecheck $(SHADE_MUTANTS)
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -40,8 +43,12 @@ oracle:
 	$(MAKE) -C oracle
 # CPU compile of the device-side path functions, for tests only (tests/hostsim)
 hostsim: tests/hostsim/libhostsim.so
-tests/hostsim/libhostsim.so: tests/hostsim/hostsim.cpp $(HIP_HDR)
+tests/hostsim/libhostsim.so: tests/hostsim/hostsim.cpp $(wildcard tests/hostsim/*.h) tools/shade_cases.h $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/hostsim/hostsim.cpp
+# deliberately altered copies of three shading functions run through the sections of tools/shade_cases.h, for the sensitivity check of tests/test_shade_cases_cpu.py
+shademutants: tests/hostsim/libshade_mutants.so
+tests/hostsim/libshade_mutants.so: tests/hostsim/shade_mutants.cpp tests/hostsim/shade_cases_host.h tools/shade_cases.h $(HIP_HDR)
+	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/hostsim/shade_mutants.cpp
 # CPU compile of the a-trous filter's per-pixel code (trt_denoise.h), for tests only (tests/test_*denoise*.py)
 denoisecpu: tests/denoise/libdenoise_cpu.so
 tests/denoise/libdenoise_cpu.so: tests/denoise/denoise_cpu.cpp $(PKG)/csrc/trt_denoise.h include/trt.h include/trt_prims.h include/trt_exact.h
@@ -96,7 +103,7 @@ variants: $(HIP_SRC) $(HIP_HDR)
 	  echo "variant $$name: $$defs"; $(HIPCC) $(HIPFLAGS) $$defs -shared -o $(OUT)/variants/libtrt_hip_$$name.so $(HIP_SRC) || exit 1; done
 
 clean:
-	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so
+	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/hostsim/libshade_mutants.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so
 	$(MAKE) -C oracle clean
 
 # exhaustive (2^32 inputs) proof that include/trt_exact.h returns the bits of sqrtf / 1.0f / sqrtf: run by tests/test_gpu_parity.py
@@ -108,6 +115,12 @@ tools/exact_unary_check: tools/exact_unary_check.hip include/trt_exact.h include
 nodecheck: tools/node_visit_check
 tools/node_visit_check: tools/node_visit_check.hip $(HIP_HDR)
 	$(HIPCC) $(HIPFLAGS) -o $@ tools/node_visit_check.hip
+
+# the shading functions (cameraRay, makeVertex, lightSample, nextRay, sampleDir, shadeBegin / shadeNext) and the primitives under them as gfx950 compiles
+# them (the flags of the library), one thread per case, and digests over all 2^24 uniforms: run by tests/test_gpu_shade_cases.py
+shadecheck: tools/shade_case_check
+tools/shade_case_check: tools/shade_case_check.hip tools/shade_cases.h $(HIP_HDR)
+	$(HIPCC) $(HIPFLAGS) -o $@ tools/shade_case_check.hip
 
 # chip-ceiling probe + TCC counter calibration workload (tools/calibrate_counters.sh runs it on the GPU box)
 probe: tools/gather_probe

@@ -124,7 +124,8 @@ static inline TRT_HD void trt_sincos2pi(float u, float* c_out, float* s_out)
     }
 }
 
-/* natural log of a positive normal float (abs/rel error ~1e-7, relative near 1). */
+/* natural log of a positive normal float (abs/rel error ~1e-7, relative near 1).  Measured against float64 over the primitive cases of
+ * tests/shade_cases.py (tests/test_shade_cases_cpu.py asserts it): relative error <= 7.8e-8. */
 static inline TRT_HD float trt_logf(float x)
 {
     uint32_t b = trt_f2u(x);
@@ -150,7 +151,8 @@ static inline TRT_HD float trt_logf(float x)
     return fmaf(fe, 0.693359375f, f + y);
 }
 
-/* e^x for x <= 0 (the only range the path needs); flushes to 0 below 2^-126. */
+/* e^x for x <= 0 (the only range the path needs); flushes to 0 below 2^-126 — from x <= -87 on, where e^x is 1.6e-38.
+ * Measured as above for x > -86.5: relative error <= 8.0e-8. */
 static inline TRT_HD float trt_expf_neg(float x)
 {
     if (!(x > -87.0f)) return 0.0f;
@@ -172,7 +174,8 @@ static inline TRT_HD float trt_expf_neg(float x)
 
 /* x^y for x in [0,1], y > 0: Blinn-Phong lobe pow(cos_alpha, Ns)
  * (pathTracing.cpp:69) and the lobe inverse CDF pow(u, 1/(Ns+1))
- * (pathTracing.cpp:125).  y == 1 is exact. */
+ * (pathTracing.cpp:125).  y == 1 is exact.  Measured as above for y log x > -86.5: relative error
+ * <= 1.4e-7 * max(1, |y log x|) (the error of the exponent enters the result relatively). */
 static inline TRT_HD float trt_pow01(float x, float y)
 {
     if (y == 1.0f) return x;

@@ -735,3 +735,27 @@ extern "C" void hostsim_plane_maybe(const uint32_t* bits, uint32_t lg, uint64_t 
     sc.plane_shift = 32u - lg;
     for (uint64_t i = 0; i < n; ++i) out[i] = planeMaybe(sc, axis[i], x[i]) ? 1 : 0;
 }
+
+// ---- case by case: the shading functions and the primitives under them (tests/test_shade_cases_cpu.py; tests/test_gpu_shade_cases.py compares the words of
+// tools/shade_case_check.hip, the same functions as gfx950 compiles them, with what these entries return).  The section functions are the tool's own.
+#include "shade_cases_host.h"
+
+// the words of a whole case file (layout: tools/shade_cases.h), in the tool's order; 2 for a file the tool would refuse
+extern "C" int hostsim_shade_case_file(const uint8_t* buf, uint64_t size, uint32_t* out, uint64_t n_words)
+{
+    return shadecases::runFileHost<shadecases::HeaderFns>(buf, size, out, n_words);
+}
+// digests first .. first + n - 1 of the tool's digest mode (digestAt)
+extern "C" int hostsim_shade_digests(uint32_t first, uint64_t n, uint64_t* out)
+{
+    if ((uint64_t)first + n > shadecases::digestTotal()) return 2;
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long long i = 0; i < (long long)n; ++i) out[i] = shadecases::digestAt(first + (uint32_t)i);
+    return 0;
+}
+// the table records a handle forms from the caller's (makeMaterialDev)
+extern "C" int hostsim_make_material_dev(uint64_t n, const trt_material* m, MaterialDev* out)
+{
+    for (uint64_t i = 0; i < n; ++i) out[i] = makeMaterialDev(m[i]);
+    return 0;
+}

@@ -274,3 +274,46 @@ def plane_maybe(bits, lg, axis, x):
     lib().hostsim_plane_maybe.argtypes = [_vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp]
     lib().hostsim_plane_maybe(np.ascontiguousarray(bits, np.uint32).ctypes.data, lg, x.size, axis.ctypes.data, x.ctypes.data, out.ctypes.data)
     return out.astype(bool)
+
+
+# ---- case by case (tests/test_shade_cases_cpu.py, tests/test_gpu_shade_cases.py): the sections of tools/shade_cases.h from the CPU build --------------------
+MUTANTS_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim", "libshade_mutants.so")
+_mutants = None
+
+
+def make_material_dev(raw):
+    """makeMaterialDev on [n] trt_material records (shade_cases.RAW_MAT_DT) -> [n] 96-B device records as bytes of shade_cases.MAT_DT."""
+    raw = np.ascontiguousarray(raw)
+    assert raw.dtype.itemsize == 64
+    out = np.zeros((len(raw), 96), np.uint8)
+    assert _call("hostsim_make_material_dev", len(raw), raw, out) == 0
+    return out.reshape(-1)
+
+
+def shade_case_words(file_bytes, n_words, mutant=None):
+    """The output words of a whole case file (shade_cases.case_bytes), in the tool's order; None for a file the tool refuses (exit code 2).
+    mutant 1..3: the same sections on the altered copies of tests/hostsim/shade_mutants.cpp (0: its copy of the headers' own)."""
+    buf = np.frombuffer(file_bytes, np.uint8)
+    out = np.zeros(n_words, np.uint32)
+    if mutant is None:
+        rc = _call("hostsim_shade_case_file", buf, len(buf), out, int(n_words))
+    else:
+        global _mutants
+        if _mutants is None:
+            _mutants = C.CDLL(MUTANTS_SO)
+        f = _mutants.shade_mutant_case_file
+        f.restype, f.argtypes = C.c_int, [C.c_int, _vp, C.c_uint64, _vp, C.c_uint64]
+        rc = f(int(mutant), buf.ctypes.data, len(buf), out.ctypes.data, int(n_words))
+    assert rc in (0, 2), rc
+    return out if rc == 0 else None
+
+
+def shade_digests(first=0, count=None):
+    """Digests first .. first + count - 1 of the tool's digest mode (shade_cases.DIGEST_STREAMS)."""
+    import shade_cases as SC
+    count = SC.DIGEST_TOTAL - first if count is None else count
+    out = np.zeros(count, np.uint64)
+    f = lib().hostsim_shade_digests
+    f.restype, f.argtypes = C.c_int, [C.c_uint32, C.c_uint64, _vp]
+    assert f(int(first), int(count), out.ctypes.data) == 0
+    return out
