@@ -43,7 +43,7 @@ oracle:
 	$(MAKE) -C oracle
 # CPU compile of the device-side path functions, for tests only (tests/hostsim)
 hostsim: tests/hostsim/libhostsim.so
-tests/hostsim/libhostsim.so: tests/hostsim/hostsim.cpp $(wildcard tests/hostsim/*.h) tools/shade_cases.h $(HIP_HDR)
+tests/hostsim/libhostsim.so: tests/hostsim/hostsim.cpp $(wildcard tests/hostsim/*.h) $(wildcard tests/refit/*.h) tools/shade_cases.h $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/hostsim/hostsim.cpp
 # deliberately altered copies of three shading functions run through the sections of tools/shade_cases.h, for the sensitivity check of tests/test_shade_cases_cpu.py
 shademutants: tests/hostsim/libshade_mutants.so
@@ -67,7 +67,7 @@ tests/moments/libmoments_cpu.so: tests/moments/moments_cpu.cpp $(PKG)/csrc/trt_m
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/moments/moments_cpu.cpp
 # CPU compile of the geometry update's per-node functions (trt_refit.h) over collapseBvh / buildOct output, for tests only (tests/test_refit_cpu.py)
 refitcpu: tests/refit/librefit_cpu.so
-tests/refit/librefit_cpu.so: tests/refit/refit_cpu.cpp $(HIP_HDR)
+tests/refit/librefit_cpu.so: tests/refit/refit_cpu.cpp $(wildcard tests/refit/*.h) $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -pthread -I$(PKG)/csrc -shared -o $@ tests/refit/refit_cpu.cpp
 # CPU compile of the per-ray functions of trt_render_rays (trt_path.h: rayRecord, rayValid, cameraRecord), for tests only (tests/test_render_rays_cpu.py)
 rayscpu: tests/render_rays/librays_cpu.so

@@ -18,6 +18,7 @@
 #include "trt_wide.h"
 #include "trt_oct_build.h"
 #include "trt_refit.h"
+#include "../refit/refit_loops.h"
 
 using namespace trtd;
 
@@ -71,6 +72,11 @@ struct HostScene {
     int nk = 0;  // node kind the traversal walks: 0 exact 4-wide nodes, 1 compressed 8-wide nodes (TRT_NODE_KIND)
     SceneDev sc{};
     uint32_t bvh2_depth = 0;  // inner nodes on the longest root path of the caller's BVH2
+    // ---- a scene refitted in place (refit(): what trt_update_geometry leaves of a handle created on the scene this was built from)
+    const trt_scene* src = nullptr;        // the scene this was built from: topology, materials and lights never change
+    std::vector<trt_bvh_node> nodes2;      // the BVH2 of an intermediate step (refit() without a moved scene)
+    std::vector<RefitBox> exact8;  // the 8-wide pass's scratch, kept from one refit to the next as the handle keeps it
+    bool oct_left = false;                 // an 8-wide node no longer qualified: on the 4-wide nodes for good
     // a reference stack with the bounds the GPU drivers' stacks are sized by: stack_need entries for the 4-wide walk, the BVH2's inner
     // depth for the literal walk (it pushes at most one entry per inner node on its path)
     ArrayStack stack() const
@@ -80,7 +86,7 @@ struct HostScene {
         k.bvh2_cap = bvh2_depth;
         return k;
     }
-    explicit HostScene(const trt_scene* s)
+    explicit HostScene(const trt_scene* s) : src(s)
     {
         g_breaches = 0;  // every entry that walks rays builds its scene first: a breach is reported by the entry whose walk made it
         {
@@ -156,6 +162,43 @@ struct HostScene {
         sc.n_lights = s->n_lights;
         sc.light0_area = s->n_lights ? s->lights[0].area : 0.0f;
         sc.cam = s->camera;
+    }
+
+    // The handle's state after trt_update_geometry(tri_v), by the per-node functions of trt_refit.h in the loops of tests/refit/refit_loops.h: triangle
+    // records, the 4-wide nodes in their own tree, on node kind 1 the triangle records in node order and the 8-wide nodes.  `order` (refitloops::Order)
+    // and `keep_light_boxes` plant driver faults for the sensitivity check; 0 / false is the update.  What the BVH2 of the moved scene decides — its
+    // nodes, the leaf boxes, the light boxes, the plane filter, leaf_alpha — is taken from `moved` (the scene Scene.set_vertices left for tri_v) when
+    // given, else from this scene's own BVH2 refitted by refitNode2 (an intermediate step).  false: an 8-wide node no longer qualified; the scene
+    // walks its 4-wide nodes from here on, as the handle does.
+    bool refit(const float* tri_v, const trt_scene* moved, int order, bool keep_light_boxes)
+    {
+        const uint32_t n = src->n_tris;
+        if (nk == 1 && exact8.empty()) {  // the scratch as an earlier update in the right order leaves it: a refit to the boxes a tree has reproduces its nodes
+            OctTree seed = oct;
+            (void)refitloops::refitOctTree(seed, isect.data(), leaf_boxes.data(), exact8, refitloops::DEEPEST_FIRST);
+        }
+        for (uint32_t i = 0; i < n; ++i) refitTri(i, tri_v, moved ? moved->tri_vn : nullptr, isect.data(), shade.data());
+        if (nodes2.empty()) nodes2.assign(src->nodes, src->nodes + src->n_nodes);
+        if (moved) leaf_boxes = leafBoxesOf(moved->nodes, moved->n_nodes, n);
+        else refitloops::refit2(nodes2, n, tri_v, leaf_boxes);
+        const trt_bvh_node* nodes = moved ? moved->nodes : nodes2.data();
+        sc.nodes = nodes;
+        sc.leaf_box = leaf_boxes.data();
+        refitloops::refitWideTree(wide.nodes, leaf_boxes.data(), order);
+        bool still_oct = true;
+        if (nk == 1) {
+            still_oct = refitloops::refitOctTree(oct, isect.data(), leaf_boxes.data(), exact8, order);
+            if (!still_oct) { nk = 0; oct_left = true; }
+        }
+        std::vector<LightBox> lb = lightBoxesOf(leaf_boxes, src->tri_mat, n, src->lights, src->n_lights);
+        for (size_t l = 0; keep_light_boxes && l < lb.size(); ++l)
+            for (int a = 0; a < 3; ++a) { lb[l].lo[a] = std::fmin(lb[l].lo[a], light_boxes[l].lo[a]); lb[l].hi[a] = std::fmax(lb[l].hi[a], light_boxes[l].hi[a]); }
+        light_boxes = lb;
+        sc.plane_shift = 32u - wide_detail::planeFilterBuild(nodes, src->n_nodes, plane_bits);
+        sc.plane_bits = plane_bits.data();
+        sc.leaf_alpha = sceneLeafAlpha(nodes, src->n_nodes);
+        if (sc.cull_alpha != std::numeric_limits<float>::infinity()) sc.cull_alpha = sc.leaf_alpha;  // a tree that did not nest when built stays without distance culling
+        return still_oct;
     }
 };
 }  // namespace
@@ -394,6 +437,54 @@ extern "C" int hostsim_trace_counts(const trt_scene* s, int nk, uint64_t n, cons
         else (void)traceClosestPass<ArrayStack, true, 0, false>(hs.sc, o, d, stk, ni, nt);
         visits[i] = ni;
         tests[i] = nt;
+    }
+    return g_breaches.exchange(0) ? 2 : 0;
+}
+
+// ---- a handle created on scene `before` and updated to tris[0], .., tris[k - 1] in turn (tests/test_refit_work_cpu.py, tests/test_gpu_refit_work.py): the records and
+// the per-ray work of its ray queries, for the counters of TRT_FLAG_COUNT.  `after` = the scene Scene.set_vertices left for tris[k - 1] (ignored when k = 0).
+// nk: the node kind the handle was created on.  any: the occlusion query.  bound (may be null): per-ray t_init.  light >= 0 (node kind 1, closest): the rays are
+// walked as the parity-mode shadow rays of that light (its light box ends them early, the bound is a hint).  order / keep_light_boxes: see HostScene::refit.
+// Records: as hostsim_query form 0.  visits[i] / tests[i]: the first pass of the per-lane search (hostsim_trace_counts' numbers: traceClosestPass / traceOctPass),
+// 0 for a ray of raySpecial() — the drivers hand those to k_trace_fix, which does not count.
+// Returns 0; 1: bad arguments, or node kind 1 asked of a tree that does not qualify; 2: TRT_WALK_CHECK; 3: an 8-wide node no longer qualified during an update and
+// go_on = 0.  With go_on the walk continues on node kind 0, as the handle does; *walked_kind (may be null) = the node kind the rays were walked on.
+extern "C" int hostsim_refit_trace_counts(const trt_scene* before, uint32_t k, const float* const* tris, const trt_scene* after, int nk, int any, int go_on, int order,
+                                          int keep_light_boxes, int light, uint64_t n, const float* org, const float* dir, const float* bound, float* t, int32_t* tri,
+                                          float* uv, uint32_t* visits, uint32_t* tests, int32_t* walked_kind)
+{
+    if (!before || (k && (!tris || !after)) || !org || !dir || !t || !tri || !visits || !tests) return 1;
+    if (k && (after->n_tris != before->n_tris || after->n_nodes != before->n_nodes)) return 1;
+    const int old = g_node_kind;
+    g_node_kind = nk;
+    HostScene hs(before);
+    g_node_kind = old;
+    if (nk && !hs.nk) return 1;
+    for (uint32_t j = 0; j < k; ++j) (void)hs.refit(tris[j], j + 1 == k ? after : nullptr, order, keep_light_boxes != 0);
+    if (hs.oct_left && !go_on) return 3;
+    if (walked_kind) *walked_kind = hs.nk;
+    const LightBox* lbox = (light >= 0 && (size_t)light < hs.light_boxes.size() && hs.nk && !any) ? &hs.light_boxes[(size_t)light] : nullptr;
+    const bool redo = lbox != nullptr;
+#pragma omp parallel for schedule(dynamic, 256)
+    for (long long i = 0; i < (long long)n; ++i) {
+        ArrayStack stk = hs.stack();
+        OctArrayStack ostk;
+        uint32_t ni = 0, nt = 0, ci = 0, ct = 0;
+        const f3 o = ld3(org + i * 3), d = ld3(dir + i * 3);
+        const float t_init = bound ? bound[i] : TRT_INF;
+        Hit h = hs.nk ? traceClosestOct<OctArrayStack, ArrayStack, false>(hs.sc, o, d, ostk, stk, ni, nt, t_init, any != 0, redo, lbox)
+                      : traceClosest<ArrayStack, false, 0>(hs.sc, o, d, stk, ni, nt, t_init, any != 0);
+        if (!any && !redo && !(h.t < t_init)) h.tri = -1;
+        const bool hit = h.tri >= 0;
+        t[i] = hit ? h.t : TRT_INF;
+        tri[i] = hit ? h.tri : -1;
+        if (uv) { uv[i * 2] = hit ? h.u : 0.0f; uv[i * 2 + 1] = hit ? h.v : 0.0f; }
+        if (!raySpecial(mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z))) {
+            if (hs.nk) (void)traceOctPass<OctArrayStack, true>(hs.sc, o, d, ostk, ci, ct, t_init, any != 0, redo, lbox);
+            else (void)traceClosestPass<ArrayStack, true, 0, false>(hs.sc, o, d, stk, ci, ct, t_init, any != 0);
+        }
+        visits[i] = ci;
+        tests[i] = ct;
     }
     return g_breaches.exchange(0) ? 2 : 0;
 }

@@ -101,6 +101,53 @@ def trace_counts(flat, node_kind, org, direction):
     return v, t
 
 
+# ---- a handle created on one scene and updated (tests/test_refit_work_cpu.py, tests/test_gpu_refit_work.py) ------------------------------------------
+NO_LONGER_OCT = 3  # what refit_trace_counts reports when an update left an 8-wide node that no longer qualifies and go_on is not set
+# the driver faults tests/refit/refit_loops.h can plant (refitloops::Order; LIGHT_UNION: the previous light boxes are kept and united with the new ones)
+ALTER_NONE, ALTER_SKIP_DEEPEST, ALTER_SHALLOWEST_FIRST, ALTER_LIGHT_UNION = 0, 1, 2, 3
+
+
+class RefitWork:
+    """rc: 0 or NO_LONGER_OCT (then nothing else is set); kind: the node kind the rays were walked on; t, tri, uv: the records; visits, tests:
+    per-ray work of the first pass of the search, 0 for the rays with a zero direction component (the drivers hand those to k_trace_fix uncounted)."""
+
+    def __init__(self, rc, kind=None, t=None, tri=None, uv=None, visits=None, tests=None):
+        self.rc, self.kind, self.t, self.tri, self.uv, self.visits, self.tests = rc, kind, t, tri, uv, visits, tests
+
+    def sums(self):
+        return int(self.visits.sum(dtype=np.uint64)), int(self.tests.sum(dtype=np.uint64))
+
+
+def refit_trace_counts(flat_before, tri_vs, flat_after, node_kind, org, direction, any=False, bound=None, go_on=False, alter=ALTER_NONE, light=-1):
+    """What a handle created on `flat_before` (node kind 0 / 1) answers after being updated to each of tri_vs ([n, 3, 3] float32) in turn, and the
+    work it does: HostScene::refit (tests/hostsim/hostsim.cpp) runs the per-node functions of csrc/trt_refit.h in place; flat_after is the scene
+    Scene.set_vertices left for tri_vs[-1] (None with an empty list: the handle as created).  any: the occlusion query; bound: per-ray t_init;
+    go_on: continue on node kind 0 when an 8-wide node no longer qualified, as the handle does; light >= 0 (node kind 1, closest): walk the rays as
+    that light's parity-mode shadow rays.  -> RefitWork."""
+    org, direction = _rays(org, direction)
+    n = org.shape[0]
+    vs = [np.ascontiguousarray(v, np.float32).reshape(-1, 3, 3) for v in tri_vs]
+    n_tris = flat_before.contents.n_tris
+    assert all(v.shape[0] == n_tris for v in vs) and (flat_after is not None or not vs)
+    ptrs = (C.c_void_p * max(len(vs), 1))(*[v.ctypes.data for v in vs])
+    b = None if bound is None else np.ascontiguousarray(bound, np.float32).reshape(n)
+    t, tri, uv = np.empty(n, np.float32), np.empty(n, np.int32), np.empty((n, 2), np.float32)
+    visits, tests = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    kind = C.c_int32(-1)
+    f = lib().hostsim_refit_trace_counts
+    f.restype = C.c_int
+    f.argtypes = [C.POINTER(SceneFlat), C.c_uint32, _vp, C.POINTER(SceneFlat), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, _vp,
+                  _vp, _vp, _vp, C.POINTER(C.c_int32)]
+    order, keep = (0, 1) if alter == ALTER_LIGHT_UNION else (int(alter), 0)
+    rc = f(flat_before, len(vs), C.cast(ptrs, _vp), flat_after, int(node_kind), int(bool(any)), int(bool(go_on)), order, keep, int(light), n, org.ctypes.data,
+           direction.ctypes.data, None if b is None else b.ctypes.data, t.ctypes.data, tri.ctypes.data, uv.ctypes.data, visits.ctypes.data, tests.ctypes.data, C.byref(kind))
+    if rc == NO_LONGER_OCT:
+        return RefitWork(rc)
+    assert rc != 1, "bad arguments, or node kind 1 asked of a tree that does not qualify"
+    _ok(rc, "hostsim_refit_trace_counts")
+    return RefitWork(0, int(kind.value), t, tri, uv, visits, tests)
+
+
 def oct_fallbacks(flat, org, direction):
     """How many of the rays end the oct traversal on a result that fails the check (and take the exact form)."""
     org = np.ascontiguousarray(org, np.float32).reshape(-1, 3)

@@ -82,6 +82,50 @@ def jitter(tri_v, seed=5, amp=3.0):
     return (v + rng.uniform(-amp, amp, v.shape).astype(np.float32)).astype(np.float32)
 
 
+def shrink_about_centroid(tri_v, sel, factor=0.5):
+    """The triangles `sel` (a mask) scaled by `factor` about the centroid of their vertices: an object at half its size, so every box above it
+    must get smaller — a box an update leaves as it was is then a loose box, and a loose box is more traversal work.  One formula per
+    coordinate, so a vertex gets the same position in every triangle that shares it."""
+    v = np.asarray(tri_v, np.float32).copy()
+    sel = np.asarray(sel, bool)
+    assert sel.any()
+    p = v[sel].reshape(-1, 3)
+    c = p.mean(0, dtype=np.float64).astype(np.float32)
+    v[sel] = (c + (p - c) * np.float32(factor)).astype(np.float32).reshape(-1, 3, 3)
+    return v
+
+
+def central_object(tri_v, fraction=0.5):
+    """Mask of the triangles that lie wholly in the middle `fraction` of the scene's bounds on every axis: the part shrink_about_centroid shrinks
+    on scenes that are one object (blob) or have no movable one by name."""
+    v = np.asarray(tri_v, np.float32)
+    p = v.reshape(-1, 3)
+    lo, hi = p.min(0), p.max(0)
+    mid, half = (lo + hi) * np.float32(0.5), (hi - lo) * np.float32(0.5 * fraction)
+    sel = (np.abs(v - mid) <= half).all((1, 2))
+    assert sel.any() and not sel.all()
+    return sel
+
+
+def light_far_away(scene, light=0, distance=40.0):
+    """The scene's vertices with the triangles of light `light`'s material translated by `distance` scene diagonals, from the light's centroid through
+    the centre of the scene's bounds and out on the other side: far out, so the light's box and every box above its leaves grow by that much and
+    moving back must shrink them again — and a light box that kept the far position as well (a union) holds the whole way there, the scene
+    included, so no shadow ray starts outside it.  -> (vertices, mask of the moved triangles)."""
+    a = scene.arrays()
+    v = a["tri_v"].copy()
+    f = scene.flat.contents
+    assert light < f.n_lights
+    sel = a["tri_mat"] == f.lights[light].mat
+    assert sel.any() and not sel.all()
+    p = v.reshape(-1, 3)
+    lo, hi = p.min(0), p.max(0)
+    way = ((lo + hi) * 0.5 - v[sel].reshape(-1, 3).mean(0)).astype(np.float64)
+    way /= np.linalg.norm(way)
+    v[sel] = (v[sel] + (way * distance * np.linalg.norm(hi - lo)).astype(np.float32)).astype(np.float32)
+    return v, sel
+
+
 def move_material(scene, name, delta=None, rotate_deg=0.0):
     """The scene's vertices with the triangles of material `name` rotated about the y axis through their centre and translated."""
     a = scene.arrays()

@@ -197,9 +197,9 @@ def test_boxes_past_2_to_the_40(monkeypatch):
 
 
 @pytest.mark.parametrize("name,n", [("blob", 200000), ("soup", 100000), ("staircase", None)])
-def test_an_updated_handle_keeps_its_node_kind_and_visits_what_a_fresh_one_visits(name, n, monkeypatch):
-    """Same boxes, same slots: on the 8-wide nodes A (refitted) and B (fresh, same collapse inputs apart from the dynamic programme's choice) report
-    the node kind of trt_create; on the 4-wide nodes likewise."""
+def test_an_updated_handle_keeps_its_node_kind(name, n, monkeypatch):
+    """On the 8-wide nodes an updated handle reports the node kind of trt_create; on the 4-wide nodes likewise.  (What it visits there:
+    tests/test_gpu_refit_work.py.)"""
     for kind, node_bytes in (("1", 80), ("0", 128)):
         s = T.Scene.named(name, W, H, n=n) if n else T.Scene.named(name, W, H)
         v = RR.jitter(s.arrays()["tri_v"], amp=0.01 if name == "staircase" else 1.0)
