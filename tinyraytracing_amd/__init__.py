@@ -230,6 +230,24 @@ def _add_stats(total, st):
     total.inner_node_bytes = st.inner_node_bytes
 
 
+def _call(lib, entry, *args, after=()):
+    """Calls `entry` of the library `lib` with a fresh Stats behind `args` (and `after` behind that) -> the Stats it filled."""
+    st = Stats()
+    rc = getattr(lib, entry)(*args, C.byref(st), *after)
+    if rc != 0:
+        raise TrtError(f"{entry} failed ({rc}): {lib.trt_last_error().decode()}")
+    return st
+
+
+def _tile_pixels(params, what):
+    """-> the rows ys and columns xs of the tile of `params` and its pixels y * width + x in tile order (int64)."""
+    ys = np.asarray(rows_selected(params), np.int64)
+    xs = np.arange(params.x0, params.x1, dtype=np.int64)
+    if ys.size == 0 or xs.size == 0:
+        raise TrtError(f"{what}: empty tile")
+    return ys, xs, (ys[:, None] * params.width + xs[None, :]).reshape(-1)
+
+
 class AdaptiveResult(NamedTuple):
     image: object    # sum * spp / n_q per pixel, float64 [rows, tile_w, 3] (numpy, or a torch tensor with on_device)
     counts: object   # n_q: pixel q holds samples [0, n_q) of its stream
@@ -251,37 +269,30 @@ class Renderer:
         self._h = h
         self.device = int(device)
 
+    def _tile_shape(self, params, what=None):
+        """(rows, tile_w) of the tile of `params`; an empty tile is refused in the name of `what` (None: left to the library)."""
+        nrows, tw = self._lib.trt_rows_selected(C.byref(params)), params.x1 - params.x0
+        if what and (nrows <= 0 or tw <= 0):
+            raise TrtError(f"{what}: empty tile")
+        return nrows, tw
+
     def render(self, params):
         """render() -> (float32 image [rows, tile_w, 3] linear radiance, Stats).  Host output."""
-        nrows = self._lib.trt_rows_selected(C.byref(params))
-        tw = params.x1 - params.x0
-        if nrows <= 0 or tw <= 0:
-            raise TrtError("render: empty tile")
-        out = np.empty((nrows, tw, 3), dtype=np.float32)
-        st = Stats()
-        rc = self._lib.trt_render(self._h, C.byref(params), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return out, st
+        out = np.empty(self._tile_shape(params, "render") + (3,), dtype=np.float32)
+        return out, _call(self._lib, "trt_render", self._h, C.byref(params), out.ctypes.data_as(C.POINTER(C.c_float)))
 
     def render_samples(self, params, sample_begin, sample_end, accum=None):
         """Progressive render (trt_render_samples): adds samples [sample_begin, sample_end) of params.spp onto
         `accum` (float64 [rows, tile_w, 3], the running per-pixel sums; None = start from zeros).
         Returns (image so far, accum, Stats); save accum + sample_end to checkpoint, pass them back to resume."""
-        nrows = self._lib.trt_rows_selected(C.byref(params))
-        tw = params.x1 - params.x0
-        if nrows <= 0 or tw <= 0:
-            raise TrtError("render_samples: empty tile")
+        shape = self._tile_shape(params, "render_samples") + (3,)
         if accum is None:
-            accum = np.zeros((nrows, tw, 3), dtype=np.float64)
-        if accum.dtype != np.float64 or accum.shape != (nrows, tw, 3) or not accum.flags["C_CONTIGUOUS"]:
+            accum = np.zeros(shape, dtype=np.float64)
+        if accum.dtype != np.float64 or accum.shape != shape or not accum.flags["C_CONTIGUOUS"]:
             raise TrtError("render_samples: accum must be a contiguous float64 array of shape (rows, tile_w, 3)")
-        out = np.empty((nrows, tw, 3), dtype=np.float32)
-        st = Stats()
-        rc = self._lib.trt_render_samples(self._h, C.byref(params), int(sample_begin), int(sample_end), accum.ctypes.data_as(C.POINTER(C.c_double)),
-                                          out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render_samples failed ({rc}): {self._lib.trt_last_error().decode()}")
+        out = np.empty(shape, dtype=np.float32)
+        st = _call(self._lib, "trt_render_samples", self._h, C.byref(params), int(sample_begin), int(sample_end), accum.ctypes.data_as(C.POINTER(C.c_double)),
+                   out.ctypes.data_as(C.POINTER(C.c_float)))
         return out, accum, st
 
     def render_pixels(self, params, pixels, sample_begin, sample_end, sums=None, sumsq=None):
@@ -295,12 +306,9 @@ class Renderer:
         n = pixels.size
         sums = self._moments(sums, n, "sums")
         sumsq = self._moments(sumsq, n, "sumsq")
-        st = Stats()
         fp = C.POINTER(C.c_double)
-        rc = self._lib.trt_render_pixels(self._h, C.byref(params), n, pixels.ctypes.data_as(C.POINTER(C.c_uint32)), int(sample_begin), int(sample_end),
-                                         sums.ctypes.data_as(fp), sumsq.ctypes.data_as(fp), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render_pixels failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_render_pixels", self._h, C.byref(params), n, pixels.ctypes.data_as(C.POINTER(C.c_uint32)), int(sample_begin), int(sample_end),
+                   sums.ctypes.data_as(fp), sumsq.ctypes.data_as(fp))
         return sums, sumsq, st
 
     @staticmethod
@@ -324,12 +332,9 @@ class Renderer:
             elif a.device != dev or a.dtype != torch.float64 or tuple(a.shape) != (n, 3) or not a.is_contiguous():
                 raise TrtError(f"render_pixels: {what} must be a contiguous float64 tensor of shape ({n}, 3) on {dev}")
             out.append(a)
-        st = Stats()
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self._lib.trt_render_pixels_device(self._h, C.byref(params), n, C.c_void_p(pixels.data_ptr()), int(sample_begin), int(sample_end),
-                                                C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(stream), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render_pixels_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_render_pixels_device", self._h, C.byref(params), n, C.c_void_p(pixels.data_ptr()), int(sample_begin), int(sample_end),
+                   C.c_void_p(out[0].data_ptr()), C.c_void_p(out[1].data_ptr()), C.c_void_p(stream))
         return out[0], out[1], st
 
     def render_adaptive(self, params, rel_error, min_spp, max_spp, batch, on_device=False):
@@ -339,11 +344,7 @@ class Renderer:
         -> AdaptiveResult(image = sum * spp / n_q, float64 [rows, tile_w, 3]; counts n_q [rows, tile_w]; error [rows, tile_w];
         stats summed over the calls; rounds).  on_device: the sums, the estimates and the selection live in torch tensors on this
         device (the image is returned there too) and nothing of the image crosses to the host between rounds."""
-        ys = np.asarray(rows_selected(params), np.int64)
-        xs = np.arange(params.x0, params.x1, dtype=np.int64)
-        if ys.size == 0 or xs.size == 0:
-            raise TrtError("render_adaptive: empty tile")
-        pixels = (ys[:, None] * params.width + xs[None, :]).reshape(-1)
+        ys, xs, pixels = _tile_pixels(params, "render_adaptive")
         k = pixels.size
         total = Stats()
 
@@ -383,14 +384,10 @@ class Renderer:
             raise TrtError("render_denoised: spp must be >= 2 (the variance needs two samples)")
         if params.row_mod > 1:
             raise TrtError("render_denoised: the tile must not interleave rows (it is filtered as one image)")
-        ys = np.asarray(rows_selected(params), np.int64)
-        xs = np.arange(params.x0, params.x1, dtype=np.int64)
-        if ys.size == 0 or xs.size == 0:
-            raise TrtError("render_denoised: empty tile")
+        ys, xs, pixels = _tile_pixels(params, "render_denoised")
         shape = (ys.size, xs.size)
-        pixels = (ys[:, None] * params.width + xs[None, :]).reshape(-1).astype(np.uint32)
         total = Stats()
-        sums, sumsq, st = self.render_pixels(params, pixels, 0, params.spp)
+        sums, sumsq, st = self.render_pixels(params, pixels.astype(np.uint32), 0, params.spp)
         _add_stats(total, st)
         pa = make_params(params.width, params.height, params.spp if aov_spp is None else aov_spp, params.seed, tile=(params.x0, params.y0, params.x1, params.y1),
                          max_depth=params.max_depth, flags=params.flags, mem_budget=params.mem_budget)
@@ -410,22 +407,14 @@ class Renderer:
 
     def render_into(self, params, out_tensor, stream_ptr=0):
         """Renders into a CUDA/HIP torch tensor (float32, >= rows*tile_w*3 elements) on this device."""
-        nrows = self._lib.trt_rows_selected(C.byref(params))
-        tw = params.x1 - params.x0
+        nrows, tw = self._tile_shape(params)
         need = nrows * tw * 3
         if out_tensor.numel() < need or str(out_tensor.dtype) != "torch.float32" or not out_tensor.is_cuda or not out_tensor.is_contiguous():
             raise TrtError("render_into: need a contiguous float32 device tensor with rows*tile_w*3 elements")
-        st = Stats()
-        rc = self._lib.trt_render_device(self._h, C.byref(params), C.c_void_p(out_tensor.data_ptr()), C.c_void_p(stream_ptr), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render_device failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return st
+        return _call(self._lib, "trt_render_device", self._h, C.byref(params), C.c_void_p(out_tensor.data_ptr()), C.c_void_p(stream_ptr))
 
     def _aov_shapes(self, params, what):
-        nrows = self._lib.trt_rows_selected(C.byref(params))
-        tw = params.x1 - params.x0
-        if nrows <= 0 or tw <= 0:
-            raise TrtError(f"{what}: empty tile")
+        nrows, tw = self._tile_shape(params, what)
         return {"albedo": (nrows, tw, 3), "normal": (nrows, tw, 3), "depth": (nrows, tw)}
 
     def render_aov(self, params, want_stats=False):
@@ -433,12 +422,8 @@ class Renderer:
         albedo (texel or Kd), shading normal (not renormalised) and distance; a miss counts as 0, 0 and TRT_INF.
         -> dict(albedo=float32 [rows, tile_w, 3], normal=float32 [rows, tile_w, 3], depth=float32 [rows, tile_w])[, Stats]."""
         out = {k: np.empty(shape, np.float32) for k, shape in self._aov_shapes(params, "render_aov").items()}
-        st = Stats()
         fp = C.POINTER(C.c_float)
-        rc = self._lib.trt_render_aov(self._h, C.byref(params), out["albedo"].ctypes.data_as(fp), out["normal"].ctypes.data_as(fp),
-                                      out["depth"].ctypes.data_as(fp), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render_aov failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_render_aov", self._h, C.byref(params), out["albedo"].ctypes.data_as(fp), out["normal"].ctypes.data_as(fp), out["depth"].ctypes.data_as(fp))
         return (out, st) if want_stats else out
 
     def render_aov_into(self, params, albedo=None, normal=None, depth=None, stream_ptr=0):
@@ -448,21 +433,8 @@ class Renderer:
         given = {"albedo": albedo, "normal": normal, "depth": depth}
         if all(t is None for t in given.values()):
             raise TrtError("render_aov_into: at least one of albedo, normal, depth is needed")
-        ptrs = []
-        for k, t in given.items():
-            if t is None:
-                ptrs.append(None)
-                continue
-            need = int(np.prod(shapes[k]))
-            if (not _is_torch(t) or str(t.dtype) != "torch.float32" or not t.is_cuda or not t.is_contiguous() or t.numel() < need
-                    or (t.device.index is not None and t.device.index != self.device)):
-                raise TrtError(f"render_aov_into: {k} must be a contiguous float32 tensor on cuda:{self.device} with {need} elements")
-            ptrs.append(C.c_void_p(t.data_ptr()))
-        st = Stats()
-        rc = self._lib.trt_render_aov_device(self._h, C.byref(params), ptrs[0], ptrs[1], ptrs[2], C.c_void_p(stream_ptr), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render_aov_device failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return st
+        ptrs = self._device_arrays("render_aov_into", [(k, t, ("torch.float32",), int(np.prod(shapes[k]))) for k, t in given.items()], at_least=True)
+        return _call(self._lib, "trt_render_aov_device", self._h, C.byref(params), *ptrs, C.c_void_p(stream_ptr))
 
     @staticmethod
     def _rays(org, direction, t_max, what):
@@ -484,17 +456,12 @@ class Renderer:
         t = np.empty(n, np.float32)
         tri = np.empty(n, np.int32)
         uv = np.empty((n, 2), np.float32)
-        st = Stats()
         fp = C.POINTER(C.c_float)
+        out = (t.ctypes.data_as(fp), tri.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(fp))
         if t_max is None:
-            rc = self._lib.trt_trace_closest(self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp), t.ctypes.data_as(fp),
-                                             tri.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(fp), C.byref(st))
+            st = _call(self._lib, "trt_trace_closest", self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp), *out)
         else:
-            rc = self._lib.trt_trace_closest_range(self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp), t_max.ctypes.data_as(fp),
-                                                   t.ctypes.data_as(fp), tri.ctypes.data_as(C.POINTER(C.c_int32)), uv.ctypes.data_as(fp), C.byref(st))
-        if rc != 0:
-            name = "trt_trace_closest" if t_max is None else "trt_trace_closest_range"
-            raise TrtError(f"{name} failed ({rc}): {self._lib.trt_last_error().decode()}")
+            st = _call(self._lib, "trt_trace_closest_range", self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp), t_max.ctypes.data_as(fp), *out)
         return (t, tri, uv, st) if want_stats else (t, tri, uv)
 
     def trace_occluded(self, org, direction, t_max=None, want_stats=False):
@@ -502,23 +469,22 @@ class Renderer:
         ray, None = TRT_INF).  The walk stops at the first such hit.  Returns occluded[, Stats]."""
         org, direction, t_max, n = self._rays(org, direction, t_max, "trace_occluded")
         occ = np.empty(n, np.uint8)
-        st = Stats()
         fp = C.POINTER(C.c_float)
-        rc = self._lib.trt_trace_occluded(self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp),
-                                          None if t_max is None else t_max.ctypes.data_as(fp), occ.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_trace_occluded failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_trace_occluded", self._h, n, org.ctypes.data_as(fp), direction.ctypes.data_as(fp),
+                   None if t_max is None else t_max.ctypes.data_as(fp), occ.ctypes.data_as(C.POINTER(C.c_uint8)))
         occ = occ.view(np.bool_)
         return (occ, st) if want_stats else occ
 
-    def _device_arrays(self, what, n, arrays):
-        """Checks torch tensors of this device for the *_into entries: arrays = [(name, tensor or None, dtypes, elements)].  -> pointers."""
+    def _device_arrays(self, what, arrays, at_least=False):
+        """Checks torch tensors of this device for the *_into entries: arrays = [(name, tensor or None, dtypes, elements)]; a tensor holds
+        exactly that many elements, or with at_least that many or more.  -> pointers."""
         ptrs = []
         for name, t, dtypes, need in arrays:
             if t is None:
                 ptrs.append(None)
                 continue
-            if (not _is_torch(t) or str(t.dtype) not in dtypes or not t.is_cuda or not t.is_contiguous() or t.numel() != need
+            if (not _is_torch(t) or str(t.dtype) not in dtypes or not t.is_cuda or not t.is_contiguous()
+                    or (t.numel() < need if at_least else t.numel() != need)
                     or (t.device.index is not None and t.device.index != self.device)):
                 raise TrtError(f"{what}: {name} must be a contiguous {' or '.join(d[6:] for d in dtypes)} tensor on cuda:{self.device} "
                                f"with {need} elements")
@@ -536,30 +502,22 @@ class Renderer:
         stream `stream_ptr` (0 = default).  -> Stats."""
         n = self._ray_count(org, "trace_closest_into")
         f32 = ("torch.float32",)
-        p = self._device_arrays("trace_closest_into", n, [("org", org, f32, 3 * n), ("direction", direction, f32, 3 * n), ("t_max", t_max, f32, n),
-                                                          ("t", t, f32, n), ("tri", tri, ("torch.int32",), n), ("uv", uv, f32, 2 * n)])
+        p = self._device_arrays("trace_closest_into", [("org", org, f32, 3 * n), ("direction", direction, f32, 3 * n), ("t_max", t_max, f32, n),
+                                                       ("t", t, f32, n), ("tri", tri, ("torch.int32",), n), ("uv", uv, f32, 2 * n)])
         if t is None or tri is None:
             raise TrtError("trace_closest_into: t and tri are needed")
-        st = Stats()
-        rc = self._lib.trt_trace_closest_device(self._h, n, *p, C.c_void_p(stream_ptr), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_trace_closest_device failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return st
+        return _call(self._lib, "trt_trace_closest_device", self._h, n, *p, C.c_void_p(stream_ptr))
 
     def trace_occluded_into(self, org, direction, occluded, t_max=None, stream_ptr=0):
         """trt_trace_occluded_device: org / direction / t_max as for trace_closest_into; occluded: a uint8 or bool tensor [n] on this device that
         receives 1 / True where some hit counts.  The work runs on stream `stream_ptr` (0 = default).  -> Stats."""
         n = self._ray_count(org, "trace_occluded_into")
         f32 = ("torch.float32",)
-        p = self._device_arrays("trace_occluded_into", n, [("org", org, f32, 3 * n), ("direction", direction, f32, 3 * n), ("t_max", t_max, f32, n),
-                                                           ("occluded", occluded, ("torch.uint8", "torch.bool"), n)])
+        p = self._device_arrays("trace_occluded_into", [("org", org, f32, 3 * n), ("direction", direction, f32, 3 * n), ("t_max", t_max, f32, n),
+                                                        ("occluded", occluded, ("torch.uint8", "torch.bool"), n)])
         if occluded is None:
             raise TrtError("trace_occluded_into: occluded is needed")
-        st = Stats()
-        rc = self._lib.trt_trace_occluded_device(self._h, n, *p, C.c_void_p(stream_ptr), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_trace_occluded_device failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return st
+        return _call(self._lib, "trt_trace_occluded_device", self._h, n, *p, C.c_void_p(stream_ptr))
 
     def trace_points(self, org, dir, tri_v_other, want_stats=False):
         """trt_trace_points on host arrays: per ray the closest hit on this handle's current geometry, evaluated with its barycentrics on
@@ -570,12 +528,8 @@ class Renderer:
         if v.ndim != 3 or v.shape[1:] != (3, 3):
             raise TrtError("trace_points: tri_v_other must be a float32 array of shape (n_tris, 3, 3)")
         point = np.empty((n, 3), np.float32)
-        st = Stats()
         fp = C.POINTER(C.c_float)
-        rc = self._lib.trt_trace_points(self._h, n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp), v.ctypes.data_as(fp), v.shape[0],
-                                        point.ctypes.data_as(fp), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_trace_points failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_trace_points", self._h, n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp), v.ctypes.data_as(fp), v.shape[0], point.ctypes.data_as(fp))
         return (point, st) if want_stats else point
 
     def trace_points_into(self, org, dir, tri_v_other, point, stream_ptr=0):
@@ -586,15 +540,11 @@ class Renderer:
             raise TrtError("trace_points_into: tri_v_other must be a float32 tensor of shape (n_tris, 3, 3)")
         nt = tri_v_other.shape[0]
         f32 = ("torch.float32",)
-        p = self._device_arrays("trace_points_into", n, [("org", org, f32, 3 * n), ("dir", dir, f32, 3 * n), ("tri_v_other", tri_v_other, f32, 9 * nt),
-                                                         ("point", point, f32, 3 * n)])
+        p = self._device_arrays("trace_points_into", [("org", org, f32, 3 * n), ("dir", dir, f32, 3 * n), ("tri_v_other", tri_v_other, f32, 9 * nt),
+                                                      ("point", point, f32, 3 * n)])
         if any(x is None for x in p):
             raise TrtError("trace_points_into: org, dir, tri_v_other and point are needed")
-        st = Stats()
-        rc = self._lib.trt_trace_points_device(self._h, n, p[0], p[1], p[2], nt, p[3], C.c_void_p(stream_ptr), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_trace_points_device failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return st
+        return _call(self._lib, "trt_trace_points_device", self._h, n, p[0], p[1], p[2], nt, p[3], C.c_void_p(stream_ptr))
 
     def render_rays(self, params, org, dir, streams=None, sample_begin=0, sums=None, sumsq=None):
         """Full paths along caller-supplied rays (trt_render_rays, include/trt.h): org / dir are float32 [S, n, 3] — sample-major, the rays of
@@ -615,13 +565,10 @@ class Renderer:
                 raise TrtError(f"render_rays: streams must hold {n} ids")
         sums = self._moments(sums, n, "sums")
         sumsq = self._moments(sumsq, n, "sumsq")
-        st = Stats()
         fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
-        rc = self._lib.trt_render_rays(self._h, C.byref(params), n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp),
-                                       None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint32)), int(sample_begin),
-                                       int(sample_begin) + n_samples, sums.ctypes.data_as(dp), sumsq.ctypes.data_as(dp), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render_rays failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_render_rays", self._h, C.byref(params), n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp),
+                   None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint32)), int(sample_begin), int(sample_begin) + n_samples,
+                   sums.ctypes.data_as(dp), sumsq.ctypes.data_as(dp))
         return sums, sumsq, st
 
     def render_rays_into(self, params, org, dir, sums, sumsq=None, streams=None, sample_begin=0, stream_ptr=0):
@@ -631,17 +578,13 @@ class Renderer:
             raise TrtError("render_rays_into: org must be a float32 tensor of shape (S, n, 3)")
         n_samples, n = int(org.shape[0]), int(org.shape[1])
         f32, f64 = ("torch.float32",), ("torch.float64",)
-        p = self._device_arrays("render_rays_into", n, [("org", org, f32, 3 * n * n_samples), ("dir", dir, f32, 3 * n * n_samples),
-                                                        ("streams", streams, ("torch.int32", "torch.uint32"), n), ("sums", sums, f64, 3 * n),
-                                                        ("sumsq", sumsq, f64, 3 * n)])
+        p = self._device_arrays("render_rays_into", [("org", org, f32, 3 * n * n_samples), ("dir", dir, f32, 3 * n * n_samples),
+                                                     ("streams", streams, ("torch.int32", "torch.uint32"), n), ("sums", sums, f64, 3 * n),
+                                                     ("sumsq", sumsq, f64, 3 * n)])
         if dir is None or sums is None:
             raise TrtError("render_rays_into: dir and sums are needed")
-        st = Stats()
-        rc = self._lib.trt_render_rays_device(self._h, C.byref(params), n, p[0], p[1], p[2], int(sample_begin), int(sample_begin) + n_samples,
-                                              p[3], p[4], C.c_void_p(stream_ptr), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_render_rays_device failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return st
+        return _call(self._lib, "trt_render_rays_device", self._h, C.byref(params), n, p[0], p[1], p[2], int(sample_begin), int(sample_begin) + n_samples,
+                     p[3], p[4], C.c_void_p(stream_ptr))
 
     def render_camera(self, params, camera, samples_per_call=1, want_stats=False, on_device=False):
         """The tile of `params` as seen by `camera` (a Camera, e.g. from look_at) — on THIS handle, whatever camera its scene was created with:
@@ -649,15 +592,9 @@ class Renderer:
         time, accumulated in sample order.  -> float32 image [rows, tile_w, 3], bit-identical to Renderer(scene with that camera).render(params)
         [, Stats summed over the calls].  on_device: the image stays a torch tensor on this device (nothing but the stats crosses to the host)."""
         import torch
-        ys = np.asarray(rows_selected(params), np.int64)
-        xs = np.arange(params.x0, params.x1, dtype=np.int64)
-        if ys.size == 0 or xs.size == 0:
-            raise TrtError("render_camera: empty tile")
-        if params.width * params.height > 0x7FFFFFFF:
-            raise TrtError("render_camera: needs width * height < 2^31 (int32 pixel tensors)")
+        pix, (rows, tw) = self._camera_tile(params, "render_camera")
         k = max(1, min(int(samples_per_call), params.spp))
-        dev = torch.device("cuda", self.device)
-        pix = torch.from_numpy((ys[:, None] * params.width + xs[None, :]).reshape(-1).astype(np.int32)).to(dev)
+        dev = pix.device
         n = pix.numel()
         org = torch.empty((k, n, 3), dtype=torch.float32, device=dev)
         dirs = torch.empty_like(org)
@@ -668,7 +605,7 @@ class Renderer:
             s1 = min(s0 + k, params.spp)
             camera_rays_into(camera, params, pix, s0, s1, org[:s1 - s0], dirs[:s1 - s0], device=self.device, stream_ptr=stream)
             _add_stats(total, self.render_rays_into(params, org[:s1 - s0], dirs[:s1 - s0], sums, streams=pix, sample_begin=s0, stream_ptr=stream))
-        image = sums.to(torch.float32).reshape(ys.size, xs.size, 3)
+        image = sums.to(torch.float32).reshape(rows, tw, 3)
         if not on_device:
             image = image.cpu().numpy()
         return (image, total) if want_stats else image
@@ -698,13 +635,10 @@ class Renderer:
         for k, a in out.items():
             if not isinstance(a, np.ndarray) or a.dtype != np.float64 or a.shape != shapes[k] or not a.flags["C_CONTIGUOUS"]:
                 raise TrtError(f"render_aov_rays: {k} must be a contiguous float64 array of shape {shapes[k]}")
-        st = Stats()
         fp, dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
         ptrs = [out[k].ctypes.data_as(dp) if k in out else None for k in ("albedo", "normal", "depth")]
-        rc = self._lib.trt_aov_rays(self._h, C.byref(params), n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp), int(sample_begin),
-                                    int(sample_begin) + n_samples, ptrs[0], ptrs[1], ptrs[2], C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_aov_rays failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_aov_rays", self._h, C.byref(params), n, org.ctypes.data_as(fp), dir.ctypes.data_as(fp), int(sample_begin),
+                   int(sample_begin) + n_samples, *ptrs)
         return (out, st) if want_stats else out
 
     def render_aov_rays_into(self, params, org, dir, albedo=None, normal=None, depth=None, sample_begin=0, stream_ptr=0):
@@ -716,28 +650,20 @@ class Renderer:
         if albedo is None and normal is None and depth is None:
             raise TrtError("render_aov_rays_into: at least one of albedo, normal, depth is needed")
         f32, f64 = ("torch.float32",), ("torch.float64",)
-        p = self._device_arrays("render_aov_rays_into", n, [("org", org, f32, 3 * n * n_samples), ("dir", dir, f32, 3 * n * n_samples),
-                                                            ("albedo", albedo, f64, 3 * n), ("normal", normal, f64, 3 * n), ("depth", depth, f64, n)])
+        p = self._device_arrays("render_aov_rays_into", [("org", org, f32, 3 * n * n_samples), ("dir", dir, f32, 3 * n * n_samples),
+                                                         ("albedo", albedo, f64, 3 * n), ("normal", normal, f64, 3 * n), ("depth", depth, f64, n)])
         if dir is None:
             raise TrtError("render_aov_rays_into: dir is needed")
-        st = Stats()
-        rc = self._lib.trt_aov_rays_device(self._h, C.byref(params), n, p[0], p[1], int(sample_begin), int(sample_begin) + n_samples,
-                                           p[2], p[3], p[4], C.c_void_p(stream_ptr), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_aov_rays_device failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return st
+        return _call(self._lib, "trt_aov_rays_device", self._h, C.byref(params), n, p[0], p[1], int(sample_begin), int(sample_begin) + n_samples,
+                     p[2], p[3], p[4], C.c_void_p(stream_ptr))
 
     def _camera_tile(self, params, what):
         """The pixels of the tile of `params` in tile order as an int32 tensor on this device, and the tile's (rows, width)."""
         import torch
-        ys = np.asarray(rows_selected(params), np.int64)
-        xs = np.arange(params.x0, params.x1, dtype=np.int64)
-        if ys.size == 0 or xs.size == 0:
-            raise TrtError(f"{what}: empty tile")
+        ys, xs, pixels = _tile_pixels(params, what)
         if params.width * params.height > 0x7FFFFFFF:
             raise TrtError(f"{what}: needs width * height < 2^31 (int32 pixel tensors)")
-        dev = torch.device("cuda", self.device)
-        return torch.from_numpy((ys[:, None] * params.width + xs[None, :]).reshape(-1).astype(np.int32)).to(dev), (int(ys.size), int(xs.size))
+        return torch.from_numpy(pixels.astype(np.int32)).to(torch.device("cuda", self.device)), (int(ys.size), int(xs.size))
 
     def render_camera_aov(self, params, camera, samples_per_call=16, want_stats=False, on_device=False):
         """The feature buffers of the tile of `params` as seen by `camera` — on THIS handle, whatever camera its scene was created with, as
@@ -876,10 +802,7 @@ class Renderer:
                 keep.append(vn)
                 upd.tri_vn = vn.ctypes.data
             self._light_tables(upd, lights_from)
-        st = Stats()
-        rc = self._lib.trt_update_geometry(self._h, C.byref(upd), n, C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_update_geometry failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_update_geometry", self._h, C.byref(upd), n)
         return st if want_stats else None
 
     def update_geometry_from(self, tri_v, tri_vn=None, lights_from=None, stream_ptr=0):
@@ -888,15 +811,11 @@ class Renderer:
         if not _is_torch(tri_v) or tri_v.dim() != 3 or tuple(tri_v.shape[1:]) != (3, 3):
             raise TrtError("update_geometry_from: tri_v must be a float32 tensor of shape (n, 3, 3)")
         n = tri_v.shape[0]
-        p = self._device_arrays("update_geometry_from", n, [("tri_v", tri_v, ("torch.float32",), 9 * n), ("tri_vn", tri_vn, ("torch.float32",), 9 * n)])
+        p = self._device_arrays("update_geometry_from", [("tri_v", tri_v, ("torch.float32",), 9 * n), ("tri_vn", tri_vn, ("torch.float32",), 9 * n)])
         upd = _abi.GeometryUpdate()
         upd.tri_v, upd.tri_vn = p[0], p[1]
         self._light_tables(upd, lights_from)
-        st = Stats()
-        rc = self._lib.trt_update_geometry_device(self._h, C.byref(upd), n, C.c_void_p(stream_ptr), C.byref(st))
-        if rc != 0:
-            raise TrtError(f"trt_update_geometry_device failed ({rc}): {self._lib.trt_last_error().decode()}")
-        return st
+        return _call(self._lib, "trt_update_geometry_device", self._h, C.byref(upd), n, C.c_void_p(stream_ptr))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -930,11 +849,8 @@ class GroupRenderer:
         """-> (float32 image [tile rows, tile_w, 3], Stats summed over the devices, gather + un-interleave ms)."""
         th, tw = params.y1 - params.y0, params.x1 - params.x0
         out = np.empty((th, tw, 3), dtype=np.float32)
-        st = Stats()
         gms = C.c_double(0.0)
-        rc = self._lib.trt_group_render(self._g, C.byref(params), out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(st), C.byref(gms))
-        if rc != 0:
-            raise TrtError(f"trt_group_render failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_group_render", self._g, C.byref(params), out.ctypes.data_as(C.POINTER(C.c_float)), after=(C.byref(gms),))
         return out, st, gms.value
 
     def render_into(self, params, out_tensor):
@@ -943,11 +859,8 @@ class GroupRenderer:
         th, tw = params.y1 - params.y0, params.x1 - params.x0
         if out_tensor.numel() < th * tw * 3 or str(out_tensor.dtype) != "torch.float32" or not out_tensor.is_cuda or not out_tensor.is_contiguous():
             raise TrtError("render_into: need a contiguous float32 device tensor with tile rows * tile_w * 3 elements")
-        st = Stats()
         gms = C.c_double(0.0)
-        rc = self._lib.trt_group_render_device(self._g, C.byref(params), C.c_void_p(out_tensor.data_ptr()), C.byref(st), C.byref(gms))
-        if rc != 0:
-            raise TrtError(f"trt_group_render_device failed ({rc}): {self._lib.trt_last_error().decode()}")
+        st = _call(self._lib, "trt_group_render_device", self._g, C.byref(params), C.c_void_p(out_tensor.data_ptr()), after=(C.byref(gms),))
         return st, gms.value
 
     def close(self):
@@ -1125,12 +1038,7 @@ def _float_ptrs(arrays):
 
 def _call_hip(entry, *args):
     """Calls `entry` of libtrt_hip.so -> the Stats it filled."""
-    st = Stats()
-    lib = _abi.load_hip()
-    rc = getattr(lib, entry)(*args, C.byref(st))
-    if rc != 0:
-        raise TrtError(f"{entry} failed ({rc}): {lib.trt_last_error().decode()}")
-    return st
+    return _call(_abi.load_hip(), entry, *args)
 
 
 def denoise(color, variance, albedo, normal, depth, iterations=5, sigma_normal=128, sigma_depth=1.0, sigma_luminance=4.0, device=0, want_stats=False):

@@ -1022,24 +1022,78 @@ void addDeviceStats(trt_stats& st, const DeviceStats& ds, const trt_handle* h)
     st.inner_node_bytes = h->trace_impl == 0 ? (uint32_t)sizeof(trt_bvh_node) : (h->node_kind == 1 ? 80u : (uint32_t)sizeof(WideNode));
 }
 
-// From the first pass on, work is in flight on the slot streams.  Whatever way renderCore is left, nothing may still be running on
-// them when it returns: a late kernel of a failed call would write the arena, Lacc and the pinned counters of the NEXT call on this
-// handle.  The guard drains them (and keeps the sequence numbers monotonic).
-struct Drain {
+// The frame of a call that traces rays, at its start and its end only: the Timer and the trt_stats the call fills, the block of device
+// counters (DeviceStats first) it clears and reads back, the events that bracket it on the caller's stream, and the drain: from arm() on
+// work is in flight on the caller's stream and the slot streams, and whatever way the driver is left, nothing may still be running on them
+// when it returns: a late kernel of a failed call would write the arena, Lacc, io_buf and the pinned counters of the NEXT call on this
+// handle.  The destructor drains them (and keeps the slots' sequence numbers monotonic) unless finish() got through.  `slots` outlive the frame.
+struct CallFrame {
     trt_handle* h;
-    PassSlot* slots;
-    int n;
-    hipStream_t caller;
-    bool armed = true;
-    ~Drain()
+    hipStream_t stream;
+    Timer tm;
+    trt_stats st{};
+    DeviceStats* d_stats = nullptr;
+    DeviceStats ds;
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_resolved = nullptr;  // events 0/1 bracket the call on `stream`, 2 chains renderCore's ordered resolves
+    PassSlot* slots = nullptr;
+    int n_slots = 0;
+    bool armed = false;
+    CallFrame(trt_handle* h_, hipStream_t stream_, bool timing) : h(h_), stream(stream_), tm{h_, timing} {}
+    // the counters: `bytes` from the DeviceStats at `block` on
+    int clear(void* block, size_t bytes) { d_stats = (DeviceStats*)block; HIPC(hipMemsetAsync(block, 0, bytes, stream)); return TRT_OK; }
+    void arm(PassSlot* s = nullptr, int n = 0) { slots = s; n_slots = n; armed = true; }
+    int begin(PassSlot* s = nullptr, int n = 0)  // the bracket opens, then the drain is armed; with slots there is a resolve chain
     {
-        for (int k = 0; k < n; ++k) h->slot_seq[k] = slots[k].seq;
+        ev_begin = tm.get(0);
+        ev_end = tm.get(1);
+        if (s) ev_resolved = tm.get(2);
+        if (!ev_begin || !ev_end || (s && !ev_resolved)) return fail(TRT_EHIP, "hipEventCreate failed");
+        HIPC(hipEventRecord(ev_begin, stream));
+        arm(s, n);
+        return TRT_OK;
+    }
+    int readBack()  // the bracket closes (where begin() opened one), the counters are on their way; the driver queues its own results behind them
+    {
+        if (ev_end) HIPC(hipEventRecord(ev_end, stream));
+        HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
+        return TRT_OK;
+    }
+    int finish(trt_stats* stats_out, uint32_t passes)  // after readBack(): the stream is synchronised, st completed and given to stats_out (may be null)
+    {
+        HIPC(hipStreamSynchronize(stream));
+        HIPC(hipGetLastError());
+        armed = false;  // everything this call enqueued has completed
+        float ms = 0.f;
+        if (ev_end) HIPC(hipEventElapsedTime(&ms, ev_begin, ev_end));
+        st.render_ms = ms;
+        for (const auto& sp : tm.spans) {
+            float k_ms = 0.f;
+            if (hipEventElapsedTime(&k_ms, h->events[sp.e0], h->events[sp.e1]) == hipSuccess) st.kernel_ms[sp.k] += k_ms;
+        }
+        addDeviceStats(st, ds, h);
+        st.passes = passes;
+        if (stats_out) *stats_out = st;
+        return TRT_OK;
+    }
+    ~CallFrame()
+    {
+        for (int k = 0; k < n_slots; ++k) h->slot_seq[k] = slots[k].seq;
         if (!armed) return;
-        for (int k = 0; k < n; ++k) (void)hipStreamSynchronize(slots[k].stream);
-        (void)hipStreamSynchronize(caller);
+        for (int k = 0; k < n_slots; ++k) (void)hipStreamSynchronize(slots[k].stream);
+        (void)hipStreamSynchronize(stream);
         (void)hipGetLastError();
     }
 };
+
+// A pass's slice of the caller's host arrays org / dir (comps floats each) into its staging places on the device; org and dir then point there
+int stageRaySlice(const float*& org, const float*& dir, size_t comps, float* stage_org, float* stage_dir, hipStream_t stream)
+{
+    HIPC(hipMemcpyAsync(stage_org, org, comps * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIPC(hipMemcpyAsync(stage_dir, dir, comps * sizeof(float), hipMemcpyHostToDevice, stream));
+    org = stage_org;
+    dir = stage_dir;
+    return TRT_OK;
+}
 
 // The passes of a render call and the arena for them.  Default budget: three quarters of what is free on the device (the scene is already
 // resident); halved while the arena cannot be had.
@@ -1109,9 +1163,12 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const void* d_table = own_table ? (const void*)(sb + o_table) : (const void*)in.pixels;
     double* d_sum = in.host ? (double*)(sb + o_sum) : in.sum;
     double* d_sq = !in.sumsq ? nullptr : (in.host ? (double*)(sb + o_sumsq) : in.sumsq);
-    HIPC(hipMemsetAsync(d_stats, 0, o_sum - o_stats, stream));
-    if (int e = stageInput(in, p, sb + o_table, table_bytes, d_sum, d_sq, (uint32_t*)(sb + o_list_max), stream)) return e;
     PassSlot slots[N_SLOTS];
+    CallFrame fr(h, stream, (p->flags & TRT_FLAG_TIMING) != 0);
+    Timer& tm = fr.tm;
+    trt_stats& st = fr.st;
+    if (int e = fr.clear(d_stats, o_sum - o_stats)) return e;
+    if (int e = stageInput(in, p, sb + o_table, table_bytes, d_sum, d_sq, (uint32_t*)(sb + o_list_max), stream)) return e;
     for (int k = 0; k < plan.slots; ++k) {
         PassSlot& S = slots[k];
         S.stream = h->slot_streams[k];
@@ -1144,15 +1201,9 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
                      lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds, td.grid_ok);
     if (h->dbg) std::fprintf(stderr, "%s: fused primary %d\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"), (int)fuse);
 
-    Timer tm{h, (p->flags & TRT_FLAG_TIMING) != 0};
-    trt_stats st;
-    std::memset(&st, 0, sizeof(st));
-    // events 0/1 bracket the render on the caller's stream, 2 chains the ordered resolves
-    hipEvent_t ev_begin = tm.get(0), ev_end = tm.get(1), ev_resolved = tm.get(2);
-    if (!ev_begin || !ev_end || !ev_resolved) return fail(TRT_EHIP, "hipEventCreate failed");
-    HIPC(hipEventRecord(ev_begin, stream));
-    Drain drain{h, slots, plan.slots, stream};
-    for (int k = 0; k < plan.slots; ++k) HIPC(hipStreamWaitEvent(slots[k].stream, ev_begin, 0));
+    if (int e = fr.begin(slots, plan.slots)) return e;
+    const hipEvent_t ev_resolved = fr.ev_resolved;
+    for (int k = 0; k < plan.slots; ++k) HIPC(hipStreamWaitEvent(slots[k].stream, fr.ev_begin, 0));
 
     uint32_t next_chunk = 0, resolved_upto = 0;
     auto startPass = [&](PassSlot& S) -> int {
@@ -1175,13 +1226,8 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         const size_t at = (size_t)(S.s0 - s_begin) * npix * 3, comps = (size_t)S.n_active * 3;
         const float* org = in.org + at;
         const float* dir = in.dir + at;
-        if (in.host) {
-            float* stage = (float*)S.Q[1].ra;
-            HIPC(hipMemcpyAsync(stage, org, comps * sizeof(float), hipMemcpyHostToDevice, S.stream));
-            HIPC(hipMemcpyAsync(stage + comps, dir, comps * sizeof(float), hipMemcpyHostToDevice, S.stream));
-            org = stage;
-            dir = stage + comps;
-        }
+        if (in.host)
+            if (int e = stageRaySlice(org, dir, comps, (float*)S.Q[1].ra, (float*)S.Q[1].ra + comps, S.stream)) return e;
         unsigned long long* packed = (unsigned long long*)(sb + o_pack) + (&S - slots);
         HIPC(hipMemsetAsync(packed, 0, sizeof(*packed), S.stream));
         tm.launch(TRT_K_GEN_PRIMARY, S.stream, st, [&] {
@@ -1307,28 +1353,47 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         hipLaunchKernelGGL(k_finalize, dim3(std::min<uint32_t>((npix * 3 + 255) / 256, 65536u)), dim3(256), 0, stream, d_sum, in.out_dev, npix * 3);
         tm.end(stream);
     }
-    HIPC(hipEventRecord(ev_end, stream));
-    DeviceStats ds;
-    HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
+    st.rows_rendered = in.rows.size();  // 0 for a pixel list
+    if (int e = fr.readBack()) return e;
     if (in.host && in.sum) {
         HIPC(hipMemcpyAsync(in.sum, d_sum, acc_bytes, hipMemcpyDeviceToHost, stream));
         if (d_sq) HIPC(hipMemcpyAsync(in.sumsq, d_sq, acc_bytes, hipMemcpyDeviceToHost, stream));
     }
-    HIPC(hipStreamSynchronize(stream));
-    HIPC(hipGetLastError());
-    drain.armed = false;  // everything this call enqueued has completed
+    return fr.finish(stats_out, plan.n_chunks);
+}
 
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_begin, ev_end));
-    st.render_ms = ms;
-    for (const auto& sp : tm.spans) {
-        float k_ms = 0.f;
-        if (hipEventElapsedTime(&k_ms, h->events[sp.e0], h->events[sp.e1]) == hipSuccess) st.kernel_ms[sp.k] += k_ms;
-    }
-    addDeviceStats(st, ds, h);
-    st.passes = plan.n_chunks;
-    st.rows_rendered = in.rows.size();  // 0 for a pixel list
-    if (stats_out) *stats_out = st;
+// p with the whole image as its tile and every row selected: the list entries ignore the caller's tile and row interleave
+trt_params wholeImage(trt_params p)
+{
+    p.x0 = 0; p.y0 = 0; p.x1 = p.width; p.y1 = p.height;
+    p.row_block = 1; p.row_mod = 1; p.row_rem = 0;
+    return p;
+}
+
+// What the sampled-list entries (trt_render_pixels*, trt_render_rays*, trt_aov_rays*) check and do once their trt_params are through, in
+// this order: the sample range; `refused`, the entry's complaint about its arrays or null; n entries against the path ids of a pass
+// (`too_long`: the entry's words for it); the stats zeroed.  -> empty: nothing to trace, the call is over.
+int listCall(int32_t sample_begin, int32_t sample_end, uint32_t n, const char* refused, const char* too_long, trt_stats* stats, bool& empty)
+{
+    if (sample_begin < 0 || sample_begin > sample_end) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin <= end");
+    if (refused) return fail(TRT_EINVAL, refused);
+    if (n > MAX_PASS_PATHS) return fail(TRT_EINVAL, too_long);
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    empty = n == 0 || sample_begin == sample_end;
+    return TRT_OK;
+}
+
+// The tile of p (checked) as a RenderInput: its selected rows, its width and first column, its pixels — at most max_npix
+int tileInput(const trt_params* p, RenderInput& in, uint64_t max_npix)
+{
+    for (int y = p->y0; y < p->y1; ++y)
+        if (rowSelected(p, y)) in.rows.push_back(y);
+    if (in.rows.empty()) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
+    in.tile_w = p->x1 - p->x0;
+    in.x0 = p->x0;
+    const uint64_t npix64 = (uint64_t)in.rows.size() * (uint32_t)in.tile_w;
+    if (npix64 > max_npix) return fail(TRT_EINVAL, "tile too large");
+    in.npix = (uint32_t)npix64;
     return TRT_OK;
 }
 
@@ -1339,19 +1404,12 @@ int renderTile(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
 {
     HIPC(hipSetDevice(h->device));
     RenderInput in;
-    for (int y = p->y0; y < p->y1; ++y)
-        if (rowSelected(p, y)) in.rows.push_back(y);
-    if (in.rows.empty()) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
-    in.tile_w = p->x1 - p->x0;
-    in.x0 = p->x0;
-    const size_t out_bytes = in.rows.size() * (size_t)in.tile_w * 3 * sizeof(float);
+    if (int e = tileInput(p, in, 0x7FFFFFFFull)) return e;
+    const size_t out_bytes = (size_t)in.npix * 3 * sizeof(float);
     if (!out_dev) {
         if (int e = h->out_buf.ensure(out_bytes)) return e;
         out_dev = (float*)h->out_buf.p;
     }
-    const uint64_t npix64 = (uint64_t)in.rows.size() * (uint32_t)in.tile_w;
-    if (npix64 > 0x7FFFFFFFull) return fail(TRT_EINVAL, "tile too large");
-    in.npix = (uint32_t)npix64;
     in.sum = accum_host;
     in.out_dev = out_dev;
     if (int e = renderCore(h, p, s_begin, s_end, in, (hipStream_t)hip_stream, stats)) return e;
@@ -1377,7 +1435,10 @@ int aovCore(trt_handle* h, const trt_params* p, const RenderInput& in, float* co
     char* sb = (char*)h->small_buf.p;
     DeviceStats* d_stats = (DeviceStats*)(sb + o_stats);
     double* d_sum = (double*)(sb + o_sum);
-    HIPC(hipMemsetAsync(d_stats, 0, o_sum - o_stats, stream));
+    CallFrame fr(h, stream, (p->flags & TRT_FLAG_TIMING) != 0);
+    Timer& tm = fr.tm;
+    trt_stats& st = fr.st;
+    if (int e = fr.clear(d_stats, o_sum - o_stats)) return e;
     HIPC(hipMemsetAsync(d_sum, 0, sum_bytes, stream));
     HIPC(hipMemcpyAsync(sb + o_table, in.rows.data(), table_bytes, hipMemcpyHostToDevice, stream));
     f4* hit = nullptr;
@@ -1390,21 +1451,13 @@ int aovCore(trt_handle* h, const trt_params* p, const RenderInput& in, float* co
     const TileDesc td = shadeArgsOf(h, p, in, sb + o_table, 0u, d_stats).td;
     const dim3 rg(std::min<uint32_t>((npix + 255) / 256, 65536u)), rb(256);
 
-    Timer tm{h, (p->flags & TRT_FLAG_TIMING) != 0};
-    trt_stats st;
-    std::memset(&st, 0, sizeof(st));
-    hipEvent_t ev_begin = tm.get(0), ev_end = tm.get(1);
-    if (!ev_begin || !ev_end) return fail(TRT_EHIP, "hipEventCreate failed");
-    HIPC(hipEventRecord(ev_begin, stream));
-    Drain drain{h, nullptr, 0, stream};
+    if (int e = fr.begin()) return e;
+    const auto aov_k = h->hit8 ? k_aov<true> : k_aov<false>;
     for (uint32_t c = 0; c < plan.n_chunks; ++c) {
         const uint32_t s0 = c * plan.chunk, sc_count = std::min(plan.chunk, spp - s0), n = npix * sc_count;
         const RaySource src{nullptr, nullptr, td, s0};
         tm.launch(TRT_K_TRACE_CLOSEST, stream, st, [&] { launchTraceClosest(h, camera_k, camera_fix, stream, spill, src, hit, n, d_stats, redo); });
-        tm.launch(TRT_K_RESOLVE, stream, st, [&] {
-            if (h->hit8) hipLaunchKernelGGL(k_aov<true>, rg, rb, 0, stream, h->sc, td, s0, (const f4*)hit, d_sum, npix, sc_count, (float)p->spp);
-            else hipLaunchKernelGGL(k_aov<false>, rg, rb, 0, stream, h->sc, td, s0, (const f4*)hit, d_sum, npix, sc_count, (float)p->spp);
-        });
+        tm.launch(TRT_K_RESOLVE, stream, st, [&] { hipLaunchKernelGGL(aov_k, rg, rb, 0, stream, h->sc, td, s0, (const f4*)hit, d_sum, npix, sc_count, (float)p->spp); });
         st.rays_camera += n;
     }
     tm.begin(TRT_K_RESOLVE, stream);
@@ -1416,25 +1469,9 @@ int aovCore(trt_handle* h, const trt_params* p, const RenderInput& in, float* co
             hipLaunchKernelGGL(k_finalize, dim3(std::min<uint32_t>((m + 255) / 256, 65536u)), dim3(256), 0, stream, d_sum + sum_at[k], out[k], m);
         }
     tm.end(stream);
-    HIPC(hipEventRecord(ev_end, stream));
-    DeviceStats ds;
-    HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
-    HIPC(hipStreamSynchronize(stream));
-    HIPC(hipGetLastError());
-    drain.armed = false;
-
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_begin, ev_end));
-    st.render_ms = ms;
-    for (const auto& span : tm.spans) {
-        float k_ms = 0.f;
-        if (hipEventElapsedTime(&k_ms, h->events[span.e0], h->events[span.e1]) == hipSuccess) st.kernel_ms[span.k] += k_ms;
-    }
-    addDeviceStats(st, ds, h);
-    st.passes = plan.n_chunks;
     st.rows_rendered = in.rows.size();
-    if (stats_out) *stats_out = st;
-    return TRT_OK;
+    if (int e = fr.readBack()) return e;
+    return fr.finish(stats_out, plan.n_chunks);
 }
 
 // The checks of include/trt.h, then aovCore into the caller's device buffers (`host` false) or into out_buf and from there to the host
@@ -1444,14 +1481,7 @@ int renderAov(trt_handle* h, const trt_params* p, float* albedo, float* normal, 
     if (!albedo && !normal && !depth) return fail(TRT_EINVAL, "trt_render_aov: every output buffer is null");
     HIPC(hipSetDevice(h->device));
     RenderInput in;
-    for (int y = p->y0; y < p->y1; ++y)
-        if (rowSelected(p, y)) in.rows.push_back(y);
-    if (in.rows.empty()) return fail(TRT_EINVAL, "row interleave selects no rows of the tile");
-    in.tile_w = p->x1 - p->x0;
-    in.x0 = p->x0;
-    const uint64_t npix64 = (uint64_t)in.rows.size() * (uint32_t)in.tile_w;
-    if (npix64 > 0x7FFFFFFFull / 7) return fail(TRT_EINVAL, "tile too large");
-    in.npix = (uint32_t)npix64;
+    if (int e = tileInput(p, in, 0x7FFFFFFFull / 7)) return e;
     float* const user[3] = {albedo, normal, depth};
     const size_t floats[3] = {(size_t)in.npix * 3, (size_t)in.npix * 3, (size_t)in.npix};
     float* out[3] = {albedo, normal, depth};
@@ -1479,12 +1509,10 @@ int aovRays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, co
 {
     if (!h || !p) return fail(TRT_EINVAL, "null handle/params");
     if (p->spp < 1) return fail(TRT_EINVAL, "spp must be >= 1");
-    if (sample_begin < 0 || sample_begin > sample_end) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin <= end");
-    if (n > 0 && (!org || !dir)) return fail(TRT_EINVAL, "null ray arrays");
-    if (!albedo && !normal && !depth) return fail(TRT_EINVAL, "trt_aov_rays: every sum is null");
-    if (n > MAX_PASS_PATHS) return fail(TRT_EINVAL, "more rays per sample than the path ids of one pass can number (0x7FFF0000)");
-    if (stats_out) std::memset(stats_out, 0, sizeof(*stats_out));
-    if (n == 0 || sample_begin == sample_end) return TRT_OK;
+    const char* const refused = (n > 0 && (!org || !dir)) ? "null ray arrays" : ((!albedo && !normal && !depth) ? "trt_aov_rays: every sum is null" : nullptr);
+    bool empty = false;
+    if (int e = listCall(sample_begin, sample_end, n, refused, "more rays per sample than the path ids of one pass can number (0x7FFF0000)", stats_out, empty)) return e;
+    if (empty) return TRT_OK;
     HIPC(hipSetDevice(h->device));
     hipStream_t stream = host ? nullptr : (hipStream_t)hip_stream;
     const uint32_t n_samples = (uint32_t)(sample_end - sample_begin);
@@ -1505,7 +1533,10 @@ int aovRays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, co
     DeviceStats* d_stats = (DeviceStats*)(sb + o_stats);
     unsigned long long* d_valid = (unsigned long long*)(sb + o_valid);
     double* sum[3] = {albedo, normal, depth};
-    HIPC(hipMemsetAsync(d_stats, 0, o_sum - o_stats, stream));
+    CallFrame fr(h, stream, (p->flags & TRT_FLAG_TIMING) != 0);
+    Timer& tm = fr.tm;
+    trt_stats& st = fr.st;
+    if (int e = fr.clear(d_stats, o_sum - o_stats)) return e;
     if (host) {
         double* q = (double*)(sb + o_sum);
         for (int k = 0; k < 3; ++k) {
@@ -1525,60 +1556,32 @@ int aovRays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, co
     src.ra = ra;
     src.rb = rb;
 
-    Timer tm{h, (p->flags & TRT_FLAG_TIMING) != 0};
-    trt_stats st;
-    std::memset(&st, 0, sizeof(st));
-    hipEvent_t ev_begin = tm.get(0), ev_end = tm.get(1);
-    if (!ev_begin || !ev_end) return fail(TRT_EHIP, "hipEventCreate failed");
-    HIPC(hipEventRecord(ev_begin, stream));
-    Drain drain{h, nullptr, 0, stream};
+    if (int e = fr.begin()) return e;
     const dim3 block(256);
+    const auto aov_k = h->hit8 ? k_aov_rays<true> : k_aov_rays<false>;
     for (uint32_t c = 0; c < plan.n_chunks; ++c) {
         const uint32_t s0 = c * plan.chunk, sc_count = std::min(plan.chunk, n_samples - s0), cnt = n * sc_count;
         const size_t at = (size_t)s0 * n * 3, comps = (size_t)cnt * 3;
         const float* d_org = org + at;
         const float* d_dir = dir + at;
-        if (host) {  // the stream orders this pass's copies behind the last pass's packing
-            float* stage = (float*)h->io_buf.p;
-            HIPC(hipMemcpyAsync(stage, org + at, comps * sizeof(float), hipMemcpyHostToDevice, stream));
-            HIPC(hipMemcpyAsync(stage + slice_floats, dir + at, comps * sizeof(float), hipMemcpyHostToDevice, stream));
-            d_org = stage;
-            d_dir = stage + slice_floats;
-        }
+        if (host)  // the stream orders this pass's copies behind the last pass's packing
+            if (int e = stageRaySlice(d_org, d_dir, comps, (float*)h->io_buf.p, (float*)h->io_buf.p + slice_floats, stream)) return e;
         tm.launch(TRT_K_GEN_PRIMARY, stream, st, [&] {
             hipLaunchKernelGGL(k_aov_rays_pack, dim3(std::min<uint32_t>((cnt + 255) / 256, 65536u)), block, 0, stream, d_org, d_dir, cnt, ra, rb, d_valid);
         });
         tm.launch(TRT_K_TRACE_CLOSEST, stream, st, [&] { launchTraceClosest(h, queue_k, queue_fix, stream, spill, src, hit, cnt, d_stats, redo); });
         tm.launch(TRT_K_RESOLVE, stream, st, [&] {
             const dim3 grid(std::min<uint32_t>((n + 255) / 256, 65536u));
-            if (h->hit8) hipLaunchKernelGGL(k_aov_rays<true>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, sum[0], sum[1], sum[2], n, sc_count, (float)p->spp);
-            else hipLaunchKernelGGL(k_aov_rays<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, sum[0], sum[1], sum[2], n, sc_count, (float)p->spp);
+            hipLaunchKernelGGL(aov_k, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, sum[0], sum[1], sum[2], n, sc_count, (float)p->spp);
         });
     }
-    HIPC(hipEventRecord(ev_end, stream));
-    DeviceStats ds;
-    unsigned long long n_valid = 0;
-    HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
-    HIPC(hipMemcpyAsync(&n_valid, d_valid, sizeof(n_valid), hipMemcpyDeviceToHost, stream));
+    static_assert(sizeof(st.rays_camera) == sizeof(*d_valid), "the count of valid rays lands in the stats");
+    if (int e = fr.readBack()) return e;
+    HIPC(hipMemcpyAsync(&st.rays_camera, d_valid, sizeof(*d_valid), hipMemcpyDeviceToHost, stream));
     if (host)
         for (int k = 0; k < 3; ++k)
             if (user[k]) HIPC(hipMemcpyAsync(user[k], sum[k], doubles[k] * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIPC(hipStreamSynchronize(stream));
-    HIPC(hipGetLastError());
-    drain.armed = false;
-
-    float ms = 0.f;
-    HIPC(hipEventElapsedTime(&ms, ev_begin, ev_end));
-    st.render_ms = ms;
-    for (const auto& span : tm.spans) {
-        float k_ms = 0.f;
-        if (hipEventElapsedTime(&k_ms, h->events[span.e0], h->events[span.e1]) == hipSuccess) st.kernel_ms[span.k] += k_ms;
-    }
-    addDeviceStats(st, ds, h);
-    st.rays_camera = n_valid;
-    st.passes = plan.n_chunks;
-    if (stats_out) *stats_out = st;
-    return TRT_OK;
+    return fr.finish(stats_out, plan.n_chunks);
 }
 }  // namespace
 
@@ -1604,15 +1607,13 @@ int renderPixels(trt_handle* h, const trt_params* p_in, uint32_t n_pixels, const
                  double* sumsq, void* hip_stream, trt_stats* stats, bool host)
 {
     if (!h || !p_in) return fail(TRT_EINVAL, "null handle/params");
-    trt_params p = *p_in;
-    p.x0 = 0; p.y0 = 0; p.x1 = p.width; p.y1 = p.height;
-    p.row_block = 1; p.row_mod = 1; p.row_rem = 0;
+    const trt_params p = wholeImage(*p_in);
     if (int e = checkParams(h, &p)) return e;
-    if (sample_begin < 0 || sample_begin > sample_end) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin <= end");
-    if (n_pixels > 0 && (!pixels || !sum)) return fail(TRT_EINVAL, "null pixel list or sums");
-    if (n_pixels > MAX_PASS_PATHS) return fail(TRT_EINVAL, "pixel list longer than the path ids of one pass can number (0x7FFF0000)");
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n_pixels == 0 || sample_begin == sample_end) return TRT_OK;
+    bool empty = false;
+    if (int e = listCall(sample_begin, sample_end, n_pixels, (n_pixels > 0 && (!pixels || !sum)) ? "null pixel list or sums" : nullptr,
+                         "pixel list longer than the path ids of one pass can number (0x7FFF0000)", stats, empty))
+        return e;
+    if (empty) return TRT_OK;
     HIPC(hipSetDevice(h->device));
     RenderInput in;
     in.list = true;
@@ -1647,15 +1648,14 @@ int renderRays(trt_handle* h, const trt_params* p_in, uint32_t n, const float* o
     if (!h || !p_in) return fail(TRT_EINVAL, "null handle/params");
     if (p_in->spp < 1) return fail(TRT_EINVAL, "spp must be >= 1");
     if (p_in->max_depth < 0) return fail(TRT_EINVAL, "max_depth must be >= 0");
-    if (sample_begin < 0 || sample_begin > sample_end) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin <= end");
-    if (n > 0 && (!org || !dir || !sum)) return fail(TRT_EINVAL, "null ray arrays or sums");
-    if (n > MAX_PASS_PATHS) return fail(TRT_EINVAL, "more rays per sample than the path ids of one pass can number (0x7FFF0000)");
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if (n == 0 || sample_begin == sample_end) return TRT_OK;
+    bool empty = false;
+    if (int e = listCall(sample_begin, sample_end, n, (n > 0 && (!org || !dir || !sum)) ? "null ray arrays or sums" : nullptr,
+                         "more rays per sample than the path ids of one pass can number (0x7FFF0000)", stats, empty))
+        return e;
+    if (empty) return TRT_OK;
     trt_params p = *p_in;
     p.width = p.height = 2;
-    p.x0 = 0; p.y0 = 0; p.x1 = p.width; p.y1 = p.height;
-    p.row_block = 1; p.row_mod = 1; p.row_rem = 0;
+    p = wholeImage(p);
     HIPC(hipSetDevice(h->device));
     RenderInput in;
     in.list = true;
@@ -1827,6 +1827,8 @@ int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool ho
     DeviceStats* d_stats = (DeviceStats*)(b + o_stats);
     const RedoList redo{(uint32_t*)(b + o_redo), (uint32_t*)(b + o_idx)};  // rays for k_trace_fix (trt_kernels.h)
     RayBatch dev = io;  // where the kernels read and write
+    CallFrame fr(h, stream, false);  // its Timer for the handle's events 0 and 1, which bracket the traversal alone: no span, no render_ms
+    fr.arm();  // from the first copy on something writes io_buf, which the next call on the handle reuses
     if (host) {
         dev.org = (const float*)stage;
         dev.dir = (const float*)(stage + in_bytes);
@@ -1844,12 +1846,11 @@ int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool ho
         HIPC(hipMemcpyAsync((void*)dev.dir, io.dir, in_bytes, hipMemcpyHostToDevice, stream));
         if (io.t_max) HIPC(hipMemcpyAsync((void*)dev.t_max, io.t_max, f_bytes, hipMemcpyHostToDevice, stream));
     }
-    HIPC(hipMemsetAsync(d_stats, 0, o_idx - o_stats, stream));
+    if (int e = fr.clear(d_stats, o_idx - o_stats)) return e;
     const dim3 grid(std::min<uint32_t>((n32 + 255) / 256, 65536u)), block(256);
     if (query == QUERY_NONE) hipLaunchKernelGGL(k_pack_rays, grid, block, 0, stream, dev.org, dev.dir, ra, rb, n32);
     else hipLaunchKernelGGL(k_pack_rays_bounded, grid, block, 0, stream, dev.org, dev.dir, dev.t_max, ra, rb, n32);
-    Timer tm{h, false};  // for the handle's events 0 and 1, which bracket the traversal
-    hipEvent_t e0 = tm.get(0), e1 = tm.get(1);
+    hipEvent_t e0 = fr.tm.get(0), e1 = fr.tm.get(1);
     if (!e0 || !e1) return fail(TRT_EHIP, "hipEventCreate failed");
     HIPC(hipEventRecord(e0, stream));
     RaySource src{};
@@ -1860,17 +1861,12 @@ int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool ho
     else
         launchTraceClosest(h, queryKernel(h, query), queryFixKernel(h, query), stream, (uint32_t*)h->spill.p, src, occ ? (f4*)dev.occluded : hit, n32, d_stats, redo);
     HIPC(hipEventRecord(e1, stream));
-    if (pts) {
-        if (h->hit8) hipLaunchKernelGGL(k_hit_points<true>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.tri_v_other, dev.point, n32);
-        else hipLaunchKernelGGL(k_hit_points<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.tri_v_other, dev.point, n32);
-    } else if (!occ) {
-        if (h->hit8) hipLaunchKernelGGL(k_unpack_hits<true>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.t, dev.tri, dev.uv, n32);
-        else hipLaunchKernelGGL(k_unpack_hits<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.t, dev.tri, dev.uv, n32);
-    }
-    DeviceStats ds;
-    HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
-    HIPC(hipStreamSynchronize(stream));
-    HIPC(hipGetLastError());
+    if (pts)
+        hipLaunchKernelGGL(h->hit8 ? k_hit_points<true> : k_hit_points<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.tri_v_other, dev.point, n32);
+    else if (!occ)
+        hipLaunchKernelGGL(h->hit8 ? k_unpack_hits<true> : k_unpack_hits<false>, grid, block, 0, stream, h->sc, (const f4*)ra, (const f4*)rb, (const f4*)hit, dev.t, dev.tri, dev.uv, n32);
+    if (int e = fr.readBack()) return e;
+    if (int e = fr.finish(nullptr, 0)) return e;  // the counters are in fr.st; the caller's stats wait for the bracket's time and the host entry's copies
     float ms = 0.f;
     HIPC(hipEventElapsedTime(&ms, e0, e1));
     if (host) {
@@ -1883,8 +1879,7 @@ int traceBatch(trt_handle* h, uint64_t n, const RayBatch& io, int query, bool ho
         }
     }
     if (stats_out) {
-        std::memset(stats_out, 0, sizeof(*stats_out));
-        addDeviceStats(*stats_out, ds, h);  // what the traversal and fix kernels do not count stays zero: d_stats was cleared
+        *stats_out = fr.st;  // what the traversal and fix kernels do not count is zero: d_stats was cleared
         const int k = occ ? TRT_K_TRACE_SHADOW : TRT_K_TRACE_CLOSEST;
         stats_out->kernel_ms[k] = ms;
         stats_out->launches[k] = 1;
