@@ -193,7 +193,7 @@ enum {
     TRT_K_TRACE_SHADOW = 3,
     TRT_K_RESOLVE = 4,
     TRT_K_TAIL = 5,       /* the last, short-queue bounces of a pass fused into one launch */
-    TRT_K_DENOISE = 6,    /* trt_denoise*: the prepare kernel and every level of the a-trous filter; trt_reproject*: its one kernel (trt_reproject_moments*: its two) */
+    TRT_K_DENOISE = 6,    /* trt_denoise*: the prepare kernel and every level of the a-trous filter; trt_reproject*: its one kernel (trt_reproject_moments*: its two); trt_despeckle*: its one kernel */
     TRT_K_REFIT = 7       /* trt_update_geometry*: every kernel of an update */
 };
 
@@ -682,6 +682,61 @@ int trt_reproject_moments_device(int device, const trt_moments_params* params, i
                                  const float* normal, const float* depth, const float* prev_point, const float* prev_cv, const float* prev_len,
                                  const float* prev_normal, const float* prev_depth, const float* prev_mom, float* out_color, float* out_variance,
                                  float* out_cv, float* out_len, float* out_mom, void* hip_stream, trt_stats* stats);
+
+/* ---- firefly clamp: bound a pixel's luminance by its neighbourhood, before the history and the filter ------------------------------------
+ * A stateless image-space operation shaped like trt_denoise: one W x H image, no scene handle, no state in the library.  It runs on the
+ * frame's own buffers BEFORE trt_reproject* and trt_denoise: next-event estimation divides by the squared distance to the light sample, so
+ * one sample close to a light is worth thousands of its neighbours, the filter spreads such a pixel into a blotch (its luminance weight is
+ * relative to the pixel's own deviation), the history keeps it for 1 / alpha frames, and trt_reproject_moments' m2 carries it into every
+ * pixel that later gathers it.  All buffers float, rows top to bottom:
+ *   color W*H*3, albedo W*H*3 and depth W*H as for trt_denoise;
+ *   variance W*H and out_variance W*H: both or neither (NULL);
+ *   out_color W*H*3; out_scale W*H or NULL: the factor each pixel's colour was multiplied by.
+ * No output may alias an input (a pixel reads its neighbours; not checked).  Per pixel p, window radius R, k = sigma:
+ *  1. a = the demodulation factor and c = color / a as trt_denoise's step 1 (the same functions, variance 0), l_p = lum(c): the clamp works
+ *     in the domain the filter and the history work in.
+ *  2. A miss (depth >= TRT_INF, or a NaN) passes through: out_color and out_variance = the input's bits, out_scale = 1.
+ *  3. The (2R+1)^2 window, rows outer and columns inner, the centre left out.  A tap q counts iff it is in the image, a hit, and l_q is
+ *     finite.  n = the number of counting taps, S1 = sum l_q, S2 = sum l_q^2, accumulated in fp32 in that order.
+ *  4. n < TRT_DS_MIN_TAPS: the pixel passes through (whatever its value: step 9).
+ *  5. m = S1 / n,  v = max(0, S2 / n - m m),  T = m + k sqrt(v)   (trt_sqrt).
+ *  6. l_p finite and l_p <= T: the pixel passes through.  A FLAT window, every counting tap equal to l_p, is this case with l_p = m = T; it is
+ *     decided by comparing the taps, not by the rounded sums (the fp32 sum of n equal numbers over n may fall an ulp short of them), so that
+ *     a constant image and the inside of a directly seen emitter keep their bits.
+ *  7. l_p finite and l_p > T: s = T / l_p (one fp32 division), out_color = color s, out_variance = (variance s) s, out_scale = s.
+ *  8. l_p or a colour channel not finite (and n >= TRT_DS_MIN_TAPS): the pixel is REPLACED, out_color = m a, out_variance = variance if that
+ *     is finite, else 0, out_scale = 0.  This is the one place in the chain where a NaN sample can be stopped before it enters a history for good.
+ *  9. With n < TRT_DS_MIN_TAPS such a pixel passes through, as in step 4.
+ * What k = 3 leaves alone: with a fraction f of the window at luminance L and the rest near 0, m = f L and v = f (1 - f) L^2, so T >= L iff
+ * f + k sqrt(f (1 - f)) >= 1; for k = 3 that is f >= 0.1.  A straight edge (5 of 8 taps at R = 1), the corner of a bright region (3 of 8) and
+ * a bright line one pixel wide (2 of 8; 4 of 24 at R = 2) are therefore untouched whatever the contrast, and a lone bright pixel (0 of 8) is
+ * brought down to T of its surroundings.  One bright tap among 8 is f = 0.125: of two ADJACENT fireflies neither is clamped at R = 1 (each
+ * vouches for the other); at R = 2 (1 of 24) both are.
+ * Limits: the clamp is BIASED, it removes energy (DESIGN.md has the measured amounts); it cannot tell an emitter or a highlight smaller than
+ * a tenth of the window from a firefly and clamps both.  It is therefore OFF by default wherever the library offers it.
+ * Arithmetic: fp32 in one fixed order, tinyraytracing_amd/csrc/trt_despeckle.h, which a CPU build of the same code reproduces bit for bit.
+ * Hostile values (NaN, infinite or negative colours, albedos and depths) index nothing out of bounds. */
+typedef struct trt_despeckle_params {
+    int32_t radius;   /* window radius R, 1 or 2; 0 = 1 */
+    float sigma;      /* k >= 0; 0 = 3 */
+    uint32_t flags;   /* reserved, 0 */
+} trt_despeckle_params;
+#define TRT_DS_MIN_TAPS 3
+
+/* On HOST buffers on `device` (HIP ordinal; a gfx950, else TRT_ENODEV), staged in device memory for the call (40 bytes per pixel, 4 more
+ * each for variance, out_variance and out_scale).  params may be NULL (every default).  TRT_EINVAL, in this order before any device work:
+ * a null required buffer (color, albedo, depth, out_color); variance without out_variance or the reverse; width or height < 1;
+ * width * height > TRT_DENOISE_MAX_PIXELS; radius other than 0, 1 or 2; a negative or NaN sigma; nonzero flags.  stats (optional):
+ * launches[TRT_K_DENOISE] = 1 (the one kernel), kernel_ms[TRT_K_DENOISE], render_ms = the call's device time (copies included); every other
+ * field 0. */
+int trt_despeckle(int device, const trt_despeckle_params* params, int width, int height, const float* color, const float* variance,
+                  const float* albedo, const float* depth, float* out_color, float* out_variance, float* out_scale, trt_stats* stats);
+/* The same with every buffer in DEVICE memory of `device`, the work enqueued on hip_stream (NULL = default stream); returns after that
+ * stream has been synchronised.  Nothing but the stats crosses PCIe and no device memory is allocated.  TRT_DESPECKLE_LDS=0 in the
+ * environment sends the taps to global memory instead of the block's LDS tile (an A/B switch; same bits). */
+int trt_despeckle_device(int device, const trt_despeckle_params* params, int width, int height, const float* color, const float* variance,
+                         const float* albedo, const float* depth, float* out_color, float* out_variance, float* out_scale, void* hip_stream,
+                         trt_stats* stats);
 
 
 /* ---- one node, several GPUs -------------------------------------------------------------------------------------

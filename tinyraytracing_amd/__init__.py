@@ -1065,6 +1065,42 @@ def denoise_into(color, variance, albedo, normal, depth, out, iterations=5, sigm
     return _call_hip("trt_denoise_device", int(dev.index or 0), C.byref(dp), w, h, *ptrs, C.c_void_p(stream_ptr))
 
 
+def _despeckle_params(radius, sigma):
+    dp = _abi.DespeckleParams()
+    dp.radius, dp.sigma, dp.flags = int(radius), float(sigma), 0
+    return dp
+
+
+def despeckle(color, albedo, depth, variance=None, radius=1, sigma=3.0, device=0, want_stats=False):
+    """The firefly clamp on `device` (trt_despeckle, include/trt.h has the contract, its bias and its limits): a hit pixel whose demodulated
+    luminance exceeds mean + sigma * deviation of the (2 radius + 1)^2 window around it (radius 1 or 2, the pixel itself left out) is scaled
+    down to that bound, and a pixel that is not a number is replaced by the window's mean.  It runs on a frame BEFORE reproject*() and
+    denoise().  color, albedo [h, w, 3], depth [h, w], variance [h, w] or None, all converted to float32.
+    -> dict(color [h, w, 3], variance [h, w] (variance * scale^2) or None, scale [h, w]: the factor of each pixel, 1 where it passed)[, Stats]."""
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    h, w = _image_shape(color, "despeckle")
+    bufs = _host_planes("despeckle", [("color", color, (h, w, 3), False), ("variance", variance, (h, w), True), ("albedo", albedo, (h, w, 3), False),
+                                      ("depth", depth, (h, w), False)])
+    out = {"color": np.empty((h, w, 3), np.float32), "variance": None if variance is None else np.empty((h, w), np.float32),
+           "scale": np.empty((h, w), np.float32)}
+    dp = _despeckle_params(radius, sigma)
+    st = _call_hip("trt_despeckle", int(device), C.byref(dp), w, h, *_float_ptrs(bufs + list(out.values())))
+    return (out, st) if want_stats else out
+
+
+def despeckle_into(color, albedo, depth, out_color, variance=None, out_variance=None, out_scale=None, radius=1, sigma=3.0, stream_ptr=0):
+    """trt_despeckle_device: the buffers of despeckle() as contiguous float32 torch tensors on one device (color, albedo and out_color
+    [h, w, 3]; depth [h, w]; variance and out_variance [h, w], both or neither; out_scale [h, w] or None; no output may be an input), the
+    work on stream `stream_ptr` (0 = default).  Writes the outputs that are given; -> Stats."""
+    h, w, dev = _device_image(color, "despeckle_into")
+    ptrs = _device_planes("despeckle_into", dev, [("color", color, (h, w, 3), False), ("variance", variance, (h, w), True),
+                                                  ("albedo", albedo, (h, w, 3), False), ("depth", depth, (h, w), False),
+                                                  ("out_color", out_color, (h, w, 3), False), ("out_variance", out_variance, (h, w), True),
+                                                  ("out_scale", out_scale, (h, w), True)])
+    dp = _despeckle_params(radius, sigma)
+    return _call_hip("trt_despeckle_device", int(dev.index or 0), C.byref(dp), w, h, *ptrs, C.c_void_p(stream_ptr))
+
+
 HISTORY_KEYS = ("cv", "length", "normal", "depth")
 MOMENTS_HISTORY_KEYS = HISTORY_KEYS + ("mom",)
 
@@ -1221,18 +1257,30 @@ class TemporalAccumulator:
     the history instead (reproject_moments_into: the luminance's moments over time, a spatial estimate while the history is shorter than
     min_frames): spp may be 1, only the colour sums are rendered, the history keeps one more record (mom), and frame()'s own `variance`
     is None.  The accumulated colour and the history length are the same either way.
+    despeckle=None (the default) leaves the frames as rendered.  True, or a dict with `radius` and / or `sigma`, sends every frame's colour
+    (and, with variance="samples", its variance) through despeckle_into on the frame's stream before the reprojection: the history and the
+    filter then see the clamped frame, frame() also returns `despeckle_scale`, and its `color` / `variance` stay the frame as rendered.  The
+    clamp is biased and cannot tell a small emitter from a firefly (include/trt.h, trt_despeckle), hence off unless asked for.
     Geometry that moves keeps its history too: after Renderer.update_geometry_from(v1) (or update_geometry) pass the vertices the handle had
     when the previous frame was rendered, frame(camera, moved_from=v0), and every pixel looks its history up where the surface it shows
     was then.  The loop is `r.update_geometry_from(v1); acc.frame(cam, moved_from=v0)`; without moved_from a moved surface keeps or loses
     its history by the depth and normal tests alone, as trt_reproject documents."""
 
     def __init__(self, renderer, params, alpha=0.2, depth_tolerance=0.1, normal_threshold=0.9, max_history=255.0, aov_spp=None,
-                 samples_per_call=16, variance="samples", min_frames=4, **denoise_kw):
+                 samples_per_call=16, variance="samples", min_frames=4, despeckle=None, **denoise_kw):
         unknown = set(denoise_kw) - {"iterations", "sigma_normal", "sigma_depth", "sigma_luminance"}
         if unknown:
             raise TrtError(f"TemporalAccumulator: unknown argument {sorted(unknown)[0]}")
         if variance not in ("samples", "moments"):
             raise TrtError("TemporalAccumulator: variance must be 'samples' or 'moments'")
+        if despeckle is True:
+            despeckle = {}
+        if despeckle is not None:
+            if not isinstance(despeckle, dict):
+                raise TrtError("TemporalAccumulator: despeckle must be None, True or a dict with the keys radius, sigma")
+            unknown = set(despeckle) - {"radius", "sigma"}
+            if unknown:
+                raise TrtError(f"TemporalAccumulator: unknown despeckle key {sorted(unknown, key=str)[0]}")
         if (params.x0, params.y0, params.x1, params.y1) != (0, 0, params.width, params.height):
             raise TrtError("TemporalAccumulator: the tile must be the whole image (the cameras' pixel grid is the image's)")
         if variance == "samples" and params.spp < 2:
@@ -1248,6 +1296,7 @@ class TemporalAccumulator:
         self.render_kw = dict(aov_spp=aov_spp, samples_per_call=samples_per_call)
         self.denoise_kw = denoise_kw
         self.variance = variance
+        self.despeckle_kw = None if despeckle is None else dict(despeckle)
         # stage B of reproject_moments_into weighs its taps as the filter does
         self.moments_kw = dict(min_frames=min_frames, **{k: denoise_kw[k] for k in ("sigma_normal", "sigma_depth") if k in denoise_kw})
         self.frame_index = 0  # frames rendered so far; reset() does not rewind it, so that no seed is used twice
@@ -1278,7 +1327,8 @@ class TemporalAccumulator:
         variance, albedo, normal, depth: the frame's own buffers; accumulated, accumulated_variance: the blend with the reprojected history;
         history_length; denoised: the filtered accumulated image) as float32 arrays (on_device: torch tensors on the renderer's device), and
         stats: the Stats of every call summed.  With variance="moments" the frame has no variance of its own (`variance` is None) and
-        accumulated_variance is reproject_moments_into's estimate.
+        accumulated_variance is reproject_moments_into's estimate.  With despeckle the dict also holds despeckle_scale [h, w], the factor
+        the clamp gave each pixel of the frame before it was accumulated; color and variance are the frame as rendered.
         moved_from: None, or the tri_v the handle's geometry had when the previous frame was rendered (float32 [n_tris, 3, 3], a torch tensor
         on the renderer's device or a numpy array): the history is then found through center_rays -> Renderer.trace_points_into(...,
         moved_from) -> reproject_motion_into, all on the frame's stream, in place of reproject_into.  Its shape is checked before anything
@@ -1309,6 +1359,12 @@ class TemporalAccumulator:
         acc, acc_var = torch.empty_like(color), torch.empty_like(aov["depth"])
         cv, length = torch.empty((h, w, 4), dtype=torch.float32, device=color.device), torch.empty_like(aov["depth"])
         mom = torch.empty_like(cv) if moments else None
+        scale, frame_color, frame_variance = None, color, variance
+        if self.despeckle_kw is not None:  # the history and the filter get the clamped frame; the caller keeps the frame as rendered
+            color, scale = torch.empty_like(frame_color), torch.empty_like(aov["depth"])
+            variance = None if frame_variance is None else torch.empty_like(frame_variance)
+            _add_stats(total, despeckle_into(frame_color, aov["albedo"], aov["depth"], color, variance=frame_variance, out_variance=variance,
+                                             out_scale=scale, stream_ptr=stream, **self.despeckle_kw))
         point = self._previous_points(camera, moved_from, h, w, color.device, stream, total)
         if moments:
             _add_stats(total, reproject_moments_into(color, aov["albedo"], aov["normal"], aov["depth"], camera, self._camera, acc, acc_var, cv, length, mom,
@@ -1326,8 +1382,10 @@ class TemporalAccumulator:
             self._history["mom"] = mom
         self._camera = Camera.from_buffer_copy(camera)
         self.frame_index += 1
-        out = {"color": color, "variance": variance, "accumulated": acc, "accumulated_variance": acc_var, "history_length": length, "denoised": denoised}
+        out = {"color": frame_color, "variance": frame_variance, "accumulated": acc, "accumulated_variance": acc_var, "history_length": length, "denoised": denoised}
         out.update(aov)
+        if scale is not None:
+            out["despeckle_scale"] = scale
         if on_device:  # history_length, normal and depth are the next frame's history: the caller gets copies to do with as they please
             out.update({k_: out[k_].clone() for k_ in ("history_length", "normal", "depth")})
         else:

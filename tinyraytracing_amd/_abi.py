@@ -104,6 +104,10 @@ class MomentsParams(C.Structure):
     _fields_ = [("rp", ReprojectParams), ("min_frames", C.c_int32), ("sigma_normal", C.c_int32), ("sigma_depth", C.c_float)]
 
 
+class DespeckleParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("sigma", C.c_float), ("flags", C.c_uint32)]
+
+
 class GeometryUpdate(C.Structure):
     _fields_ = [("tri_v", C.c_void_p), ("tri_vn", C.c_void_p), ("lights", C.POINTER(Light)), ("light_tris", C.POINTER(LightTri)),
                 ("n_lights", C.c_uint32), ("n_light_tris", C.c_uint32)]
@@ -114,7 +118,7 @@ HIP_SYMBOLS = ["trt_rows_selected", "trt_create", "trt_render", "trt_render_devi
                "trt_camera_rays", "trt_camera_rays_device", "trt_render_aov",
                "trt_render_aov_device", "trt_aov_rays", "trt_aov_rays_device", "trt_trace_closest", "trt_trace_closest_range", "trt_trace_closest_device", "trt_trace_occluded",
                "trt_trace_occluded_device", "trt_trace_points", "trt_trace_points_device", "trt_denoise", "trt_denoise_device", "trt_reproject", "trt_reproject_device",
-               "trt_reproject_motion", "trt_reproject_motion_device", "trt_reproject_moments", "trt_reproject_moments_device",
+               "trt_reproject_motion", "trt_reproject_motion_device", "trt_reproject_moments", "trt_reproject_moments_device", "trt_despeckle", "trt_despeckle_device",
                "trt_update_geometry", "trt_update_geometry_device", "trt_destroy", "trt_last_error", "trt_abi_version", "trt_group_create", "trt_group_render", "trt_group_render_device", "trt_group_size", "trt_group_destroy"]
 BUILD_SYMBOLS = ["trt_build_lbvh", "trt_build_last_error"]
 HOST_SYMBOLS = ["trth_scene_load", "trth_scene_load_opts", "trth_scene_drop_tris", "trth_scene_add_soup", "trth_scene_add_blob", "trth_scene_add_lamps",
@@ -262,6 +266,8 @@ def load_hip():
     lib.trt_reproject_motion_device.argtypes = [C.c_int, C.POINTER(ReprojectParams), C.c_int, C.c_int] + [C.c_void_p] * 15 + [C.POINTER(Stats)]
     lib.trt_reproject_moments.argtypes = [C.c_int, C.POINTER(MomentsParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 15 + [C.POINTER(Stats)]
     lib.trt_reproject_moments_device.argtypes = [C.c_int, C.POINTER(MomentsParams), C.c_int, C.c_int] + [C.c_void_p] * 16 + [C.POINTER(Stats)]
+    lib.trt_despeckle.argtypes = [C.c_int, C.POINTER(DespeckleParams), C.c_int, C.c_int] + [C.POINTER(C.c_float)] * 7 + [C.POINTER(Stats)]
+    lib.trt_despeckle_device.argtypes = [C.c_int, C.POINTER(DespeckleParams), C.c_int, C.c_int] + [C.c_void_p] * 8 + [C.POINTER(Stats)]
     lib.trt_update_geometry.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_uint32, C.POINTER(Stats)]
     lib.trt_update_geometry_device.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
     lib.trt_destroy.argtypes = [C.c_void_p]

@@ -26,6 +26,7 @@
 #include "trt_denoise_kernels.h"
 #include "trt_reproject_kernels.h"
 #include "trt_moments_kernels.h"
+#include "trt_despeckle_kernels.h"
 #include "trt_refit_kernels.h"
 
 using namespace trtd;
@@ -2294,7 +2295,7 @@ struct ImageStage {
         return (int)planes.size() - 1;
     }
     int in(const float* user, int floats, bool present = true) { return add(IN, user, pixels * floats * sizeof(float), present); }
-    int out(float* user, int floats) { return add(OUT, user, pixels * floats * sizeof(float), true); }
+    int out(float* user, int floats, bool present = true) { return add(OUT, user, pixels * floats * sizeof(float), present); }
     int scratch(size_t bytes) { return add(SCRATCH, nullptr, bytes, true); }
     float* operator[](int i) const { return (float*)planes[i].dev; }
 
@@ -2414,6 +2415,63 @@ int trt_denoise_device(int device, const trt_denoise_params* params, int width, 
 {
     return denoise(device, params, width, height, DenoiseIo{color, variance, albedo, normal, depth, out}, false, (hipStream_t)hip_stream, stats,
                    "trt_denoise_device");
+}
+
+}  // extern "C"
+
+// ---- trt_despeckle / trt_despeckle_device ---------------------------------------------------------------------------------------------
+
+namespace {
+
+static_assert(sizeof(trt_despeckle_params) == 12, "trt_despeckle_params is three 4-byte fields (the ctypes mirror holds the same size)");
+
+struct DespeckleIo {
+    const float *color, *variance, *albedo, *depth;  // variance: optional, with out_variance
+    float *out_color, *out_variance, *out_scale;     // out_scale: optional
+};
+
+// One call: (host: upload) -> k_despeckle -> (host: download), all on `stream`.
+// TRT_DESPECKLE_LDS=0 in the environment sends the taps to global memory instead of the LDS tile (A/B; same bits).
+int despeckle(int device, const trt_despeckle_params* prm, int width, int height, const DespeckleIo& io, bool host, hipStream_t stream, trt_stats* stats,
+              const char* what)
+{
+    trt_ds_args a{};
+    const bool required = io.color && io.albedo && io.depth && io.out_color;
+    if (const char* msg = trt_ds_check(prm, width, height, required, (io.variance != nullptr) == (io.out_variance != nullptr), a))
+        return fail(TRT_EINVAL, std::string(what) + ": " + msg);
+    if (int e = useDevice(device)) return e;
+    const char* lds_env = std::getenv("TRT_DESPECKLE_LDS");
+    const bool lds = !(lds_env && lds_env[0] == '0');
+    const bool var = io.variance != nullptr;
+    const dim3 grid((unsigned)((width + DS_BX - 1) / DS_BX), (unsigned)((height + DS_BY - 1) / DS_BY)), block(DS_BX, DS_BY);
+    ImageStage S(width, height, host);
+    const int color = S.in(io.color, 3), variance = S.in(io.variance, 1, var), albedo = S.in(io.albedo, 3), depth = S.in(io.depth, 1);
+    const int out_color = S.out(io.out_color, 3), out_variance = S.out(io.out_variance, 1, var), out_scale = S.out(io.out_scale, 1, io.out_scale != nullptr);
+    if (int e = S.begin(stream)) return e;
+    using Kernel = void (*)(trt_ds_args, const float*, const float*, const float*, const float*, float*, float*, float*);
+    static const Kernel table[2][2] = {{k_despeckle<1, false>, k_despeckle<1, true>}, {k_despeckle<2, false>, k_despeckle<2, true>}};
+    hipLaunchKernelGGL(table[a.radius - 1][lds ? 1 : 0], grid, block, 0, stream, a, (const float*)S[color], (const float*)S[variance],
+                       (const float*)S[albedo], (const float*)S[depth], S[out_color], S[out_variance], S[out_scale]);
+    return S.finish(stats, 1);
+}
+
+}  // namespace
+
+extern "C" {
+
+int trt_despeckle(int device, const trt_despeckle_params* params, int width, int height, const float* color, const float* variance,
+                  const float* albedo, const float* depth, float* out_color, float* out_variance, float* out_scale, trt_stats* stats)
+{
+    return despeckle(device, params, width, height, DespeckleIo{color, variance, albedo, depth, out_color, out_variance, out_scale}, true, nullptr, stats,
+                     "trt_despeckle");
+}
+
+int trt_despeckle_device(int device, const trt_despeckle_params* params, int width, int height, const float* color, const float* variance,
+                         const float* albedo, const float* depth, float* out_color, float* out_variance, float* out_scale, void* hip_stream,
+                         trt_stats* stats)
+{
+    return despeckle(device, params, width, height, DespeckleIo{color, variance, albedo, depth, out_color, out_variance, out_scale}, false,
+                     (hipStream_t)hip_stream, stats, "trt_despeckle_device");
 }
 
 }  // extern "C"
