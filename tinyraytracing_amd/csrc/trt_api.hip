@@ -21,6 +21,7 @@
 
 #include "trt.h"
 #include "trt_kernels.h"
+#include "trt_cull.h"
 #include "trt_wide.h"
 #include "trt_oct_build.h"
 #include "trt_denoise_kernels.h"
@@ -113,6 +114,12 @@ struct trt_handle {
                               // trt_create keeps traceQueueUniform's kernel: A/B, tests)
     bool fuse_primary = false;  // and, with one light, bounce 0 of a tile render is ONE kernel: k_shade's FUSE flavour walks the camera rays itself, no hit record
                                 // is written or read (trt_kernels.h fusedWalk; TRT_FUSE_PRIMARY=0 at trt_create keeps the two kernels: A/B, tests)
+    // Camera rays that provably miss the root's two child boxes are not formed, walked or resolved (trt_cull.h; tile renders without TRT_FLAG_COUNT).
+    // TRT_CULL_PRIMARY=0 at trt_create turns it off (A/B, tests).  root_node is nodes[0] of the caller's BVH2 as the device holds it: trt_create's
+    // copy, and after trt_update_geometry the node that call reads back once its refit is through.
+    bool cull_primary = true;
+    bool root_known = false;
+    trt_bvh_node root_node{};
     int node_kind = 0;        // what the persistent traversal kernels walk: 0 exact 128-B 4-wide nodes, 1 compressed 80-B 8-wide nodes (trt_oct.h)
     uint32_t oct_levels = 0;  // nodes on the longest root path of the oct tree
     bool dbg = false;         // TRT_DEBUG at trt_create: every render prints which k_shade variant it runs
@@ -764,6 +771,10 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->fuse_primary = h->hit8 && s->n_lights == 1;  // (k_shade's one-light flavour on the 8-byte records: what the FUSE kernel is built for)
     if (const char* e = std::getenv("TRT_FUSE_PRIMARY")) h->fuse_primary = h->fuse_primary && std::atoi(e) != 0;
     if (im.dbg) std::fprintf(stderr, "trt_create: fused primary %d\n", (int)h->fuse_primary);
+    h->root_known = s->n_nodes > 0 && s->nodes != nullptr;
+    if (h->root_known) h->root_node = s->nodes[0];
+    if (const char* e = std::getenv("TRT_CULL_PRIMARY")) h->cull_primary = std::atoi(e) != 0;
+    if (im.dbg) std::fprintf(stderr, "trt_create: cull primary %d\n", (int)h->cull_primary);
 
     // traversal spill area: levels beyond the LDS stack, for the largest grid
     // (k_trace_fix / k_tail walk the caller's BVH2 itself for the rays of raySpecial(), trt_path.h: one entry per level of it)
@@ -978,6 +989,7 @@ ShadeArgs shadeArgsOf(const trt_handle* h, const trt_params* p, const RenderInpu
     td.grid_rcp[1] = 1.0 / double(p->height - 1.0);
     td.grid_rcp[2] = 1.0 / double(p->width);
     td.grid_rcp[3] = 1.0 / double(p->height);
+    for (int32_t& c : td.cull) c = 0;  // nothing culled: renderCore sets it for the calls that cull
     A.shadow_count_stride = COUNT_STRIDE;
     A.max_depth = p->max_depth;
     A.lds_mat_bytes = h->lds_tab[0];
@@ -1195,7 +1207,25 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const TailKernel tail_k = tailKernel(count, in.list);
     // bounce 0 in one kernel (k_shade's FUSE flavour): tile renders on a handle set up for it; a counting render keeps the two kernels and their counters
     const bool fuse = h->fuse_primary && lights == SHADE_ONE && !in.list && !in.rays && !count;
-    const ShadeArgs shade_args = shadeArgsOf(h, p, in, d_table, rows_lds, d_stats);
+    ShadeArgs shade_args = shadeArgsOf(h, p, in, d_table, rows_lds, d_stats);
+    // camera rays that provably miss the root's two child boxes (trt_cull.h): tile renders only; a counting render keeps the root visit of every ray
+    bool culls = false;
+    TileDesc td_cull = shade_args.td;  // what k_resolve_tile gets
+    if (!in.list && !in.rays && !count && !d_sq && h->cull_primary) {
+        const CullBound cb = cullBound(h->sc.cam, p->width, p->height, (p->flags & TRT_FLAG_FIXED_PIXELS) != 0, h->root_known ? &h->root_node : nullptr, h->sc.n_nodes);
+        culls = cb.active && (cb.v[0] | cb.v[1] | cb.v[2] | cb.v[3]) != 0;  // (a scene that fills the frame: nothing lies outside, the render runs the kernels it ran)
+        for (int k = 0; k < 8; ++k) td_cull.cull[k] = cb.v[k];
+        // k_shade's FUSE flavour keeps the classes of the tile's columns and rows in LDS: wider or taller tiles are culled in the resolve only
+        if (culls && fuse && in.tile_w <= (int32_t)TRT_SHADE_CULL_COLS && rows_lds != 0u) shade_args.td = td_cull;
+        if (h->dbg) {
+            if (cb.active)
+                std::fprintf(stderr, "trt_render: cull primary columns [%d, %d] rows [%d, %d] band rows [%d, %d] band columns [%d, %d]\n", cb.j_lo, cb.j_hi, cb.i_lo, cb.i_hi,
+                             cb.row_lo, cb.row_hi, cb.col_lo, cb.col_hi);
+            else std::fprintf(stderr, "trt_render: cull primary off: %s\n", cb.why);
+        }
+    } else if (h->dbg && !in.list && !in.rays) {
+        std::fprintf(stderr, "trt_render: cull primary off: %s\n", count ? "counting render" : "TRT_CULL_PRIMARY=0");
+    }
     const TileDesc& td = shade_args.td;
     if (h->dbg)
         std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"),
@@ -1321,6 +1351,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         tm.launch(TRT_K_RESOLVE, S.stream, st, [&] {
             const dim3 rg(std::min<uint32_t>((npix + 255) / 256, 65536u)), rb(256);
             if (d_sq) hipLaunchKernelGGL(k_resolve_moments, rg, rb, 0, S.stream, S.Lacc, d_sum, d_sq, npix, S.sc_count, (float)p->spp);
+            else if (culls) hipLaunchKernelGGL(k_resolve_tile, rg, rb, 0, S.stream, S.Lacc, d_sum, td_cull, S.sc_count, (float)p->spp);
             else hipLaunchKernelGGL(k_resolve, rg, rb, 0, S.stream, S.Lacc, d_sum, npix, S.sc_count, (float)p->spp);
         });
         HIPC(hipEventRecord(ev_resolved, S.stream));
@@ -2846,6 +2877,8 @@ int updateGeometry(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris,
     HIPC(hipGetLastError());
 
     h->sc.leaf_alpha = sceneLeafAlpha(&root, 1);
+    h->root_node = root;  // what cullBound() projects from now on (trt_cull.h)
+    h->root_known = true;
     if (h->sc.cull_alpha != std::numeric_limits<float>::infinity()) h->sc.cull_alpha = h->sc.leaf_alpha;  // a tree that did not nest at trt_create stays without distance culling
     if (light_boxes)
         for (uint32_t l = 0; l < nl; ++l) {

@@ -1330,6 +1330,8 @@ constexpr uint32_t TRT_SHADE_LDS_TABLE_BYTES = 24 * 1024;
 // rows of the tile's row table kept in LDS as 16-bit values: 8192 in 512-thread blocks (3 x 41 KB per CU), 2304 — a 4K image has 2160 — in
 // 256-thread blocks (5 x 29 KB per CU); taller tiles read the table from global memory
 constexpr uint32_t shadeRowsLds(int block) { return block >= 512 ? 8192u : 2304u; }
+// columns of a tile whose cull class k_shade's FUSE flavour keeps in LDS (a byte each); wider tiles are not culled there
+constexpr uint32_t TRT_SHADE_CULL_COLS = 4096u;
 
 // The tile's row table as k_shade sees it: a 16-bit copy in LDS when it fits.  The key of a path's random stream hangs on the
 // image row, i.e. on this look-up: from global memory it is a dependent load in every vertex, and — the memory counter being
@@ -1451,7 +1453,8 @@ __device__ __forceinline__ f4 fusedPrimaryHit(const SceneDev& sc, const f4& ra, 
     const unsigned long long m_sp = ballotb(special);
     if (m_sp != 0ull) {  // (wave-uniform, rare)
         fusedWalk<true>(sc, o, d, inv, special, best_t, best_tri, un, vn, det);
-        if ((threadIdx.x & 63u) == 0) atomicAdd(&stats->redo_rays, (uint32_t)__popcll(m_sp));  // (lane 0 of a wave is active whenever any lane is: i rises with the lane)
+        // (one lane of those that are here: lane 0 may hold a culled path, or none)
+        if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)ballotb(true)) - 1)) atomicAdd(&stats->redo_rays, (uint32_t)__popcll(m_sp));
     } else {
         fusedWalk<false>(sc, o, d, inv, false, best_t, best_tri, un, vn, det);
     }
@@ -1478,10 +1481,27 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
     __shared__ __attribute__((aligned(16))) uint32_t s_tab[TABS ? TRT_SHADE_LDS_TABLE_BYTES / 4 : 4];
     __shared__ uint16_t s_rows[LIST ? 1 : TRT_SHADE_ROWS_LDS];
     __shared__ __attribute__((aligned(16))) uint32_t s_isect[HIT8 && !FUSE ? 64 * 12 : 4];  // HIT8: the scene's intersection records (<= 64, trt_create)
+    // FUSE: which columns of the tile and which of its rows lie outside the cull rectangle (bit 0) or in a guard band (bit 1), TileDesc::cull.  Filled once per
+    // block, so that the eight integers are not live in the tile loop (there they cost what they save: scalar registers spilled and reloaded per tile).
+    __shared__ uint8_t s_colcls[FUSE ? TRT_SHADE_CULL_COLS : 1], s_rowcls[FUSE ? TRT_SHADE_ROWS_LDS : 1];
     const TriIsect* isect = reinterpret_cast<const TriIsect*>(s_isect);
     if (threadIdx.x == 0) { s_shaded = 0; s_depth = 0; }
     if (!LIST)
         for (uint32_t r = threadIdx.x; r < A.rows_lds; r += TRT_SHADE_BLOCK) s_rows[r] = (uint16_t)A.td.rows[r];
+    // (renderCore leaves TileDesc::cull zero for this kernel unless the tile is at most TRT_SHADE_CULL_COLS wide and its row table is in LDS)
+    const bool culls = FUSE && (A.td.cull[0] | A.td.cull[1] | A.td.cull[2] | A.td.cull[3]) != 0;
+    if (FUSE && culls) {
+        const uint32_t nc = (uint32_t)A.td.tile_w < (uint32_t)TRT_SHADE_CULL_COLS ? (uint32_t)A.td.tile_w : (uint32_t)TRT_SHADE_CULL_COLS;
+        for (uint32_t cc = threadIdx.x; cc < nc; cc += TRT_SHADE_BLOCK) {
+            const int x = A.td.x0 + (int)cc;
+            s_colcls[cc] = (uint8_t)((x < A.td.cull[0] || x >= A.td.width - A.td.cull[1] ? 1u : 0u) | ((uint32_t)(x - A.td.cull[6]) < (uint32_t)A.td.cull[7] ? 2u : 0u));
+        }
+        const uint32_t nr = A.rows_lds < TRT_SHADE_ROWS_LDS ? A.rows_lds : TRT_SHADE_ROWS_LDS;
+        for (uint32_t r = threadIdx.x; r < nr; r += TRT_SHADE_BLOCK) {
+            const int y = A.td.rows[r];
+            s_rowcls[r] = (uint8_t)((y < A.td.cull[2] || y >= A.td.height - A.td.cull[3] ? 1u : 0u) | ((uint32_t)(y - A.td.cull[4]) < (uint32_t)A.td.cull[5] ? 2u : 0u));
+        }
+    }
     std::conditional_t<LIST, PixelList, RowsShade> rows;
     if constexpr (!LIST) {
         rows.lds = s_rows;
@@ -1558,10 +1578,19 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
             if (FUSE) {
                 // camera ray, closest hit and (u, v) in registers.  The walk runs under this branch: its votes then range over the lanes that hold a path — the
                 // lanes beyond A.n are switched off, not carried along as invalid ones (hoisted out of the branch with a `valid` flag, the kernel needs scratch)
-                primaryRay(sc, A.td, A.s0, i, ra, rb, rows);
-                hit4 = fusedPrimaryHit(sc, ra, rb, A.stats);
-                shadeBegin(sc, A.td, A.s0, ra, rb, bt, hit4, c, rows);
-                A.Lacc[i] = c.add_L ? mk4(0.0f + c.addL.x, 0.0f + c.addL.y, 0.0f + c.addL.z, 0.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
+                // A path whose pixel is culled (TileDesc::cull, trt_cull.h: its camera ray provably misses the scene) is a lane without a hit from here on: no
+                // ray, no walk (it stays out of the votes as the lanes beyond A.n do), no vertex, and no Lacc — k_resolve_tile never reads the sum of a culled
+                // path.  The class of its column and of its row come from the two byte tables in LDS (bit 0: outside the rectangle, bit 1: in a band).
+                const uint32_t s_local = divMagic(i, A.td.npix, A.td.npix_magic), pl = i - s_local * A.td.npix;
+                const uint32_t r = divMagic(pl, (uint32_t)A.td.tile_w, A.td.tile_w_magic), col = pl - r * (uint32_t)A.td.tile_w;
+                bool live = true;
+                if (culls) live = ((s_colcls[col] | s_rowcls[r]) & 3u) != 1u;
+                if (live) {
+                    cameraRecord(sc, A.td, rows(A.td, r), A.td.x0 + (int)col, A.s0 + s_local, i, ra, rb);
+                    hit4 = fusedPrimaryHit(sc, ra, rb, A.stats);
+                    shadeBegin(sc, A.td, A.s0, ra, rb, bt, hit4, c, rows);
+                    A.Lacc[i] = c.add_L ? mk4(0.0f + c.addL.x, 0.0f + c.addL.y, 0.0f + c.addL.z, 0.0f) : mk4(0.0f, 0.0f, 0.0f, 0.0f);
+                }
             } else if (A.primary) {
                 // every path passes here exactly once, hit or miss: L starts at 0 (+ the radiance of a directly
                 // visible light, pathTracing.cpp:9-12 through main.cpp:101)
@@ -1784,6 +1813,28 @@ __global__ __launch_bounds__(256) void k_resolve(const f4* __restrict__ Lacc, do
 {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += stride) {
+        double r = acc[(size_t)p * 3 + 0], g = acc[(size_t)p * 3 + 1], b = acc[(size_t)p * 3 + 2];
+        for (uint32_t s = 0; s < s_count; ++s) {
+            const f4 L = Lacc[(size_t)s * npix + p];
+            r += (double)(L.x / spp);
+            g += (double)(L.y / spp);
+            b += (double)(L.z / spp);
+        }
+        acc[(size_t)p * 3 + 0] = r;
+        acc[(size_t)p * 3 + 1] = g;
+        acc[(size_t)p * 3 + 2] = b;
+    }
+}
+
+// k_resolve for a tile render that culls camera rays (TileDesc::cull): a culled pixel is left alone.  Every sample of it would add +0.0 to its
+// sums, which is the identity (the sums start at +0.0, or at what earlier calls left of such additions; only a -0.0 handed in by a caller
+// would have become +0.0), and where k_shade culls too its Lacc entries were never written: they must not be read.
+__global__ __launch_bounds__(256) void k_resolve_tile(const f4* __restrict__ Lacc, double* __restrict__ acc, TileDesc td, uint32_t s_count, float spp)
+{
+    const uint32_t stride = gridDim.x * blockDim.x, npix = td.npix;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += stride) {
+        const uint32_t row = divMagic(p, (uint32_t)td.tile_w, td.tile_w_magic), col = p - row * (uint32_t)td.tile_w;
+        if (pixelCulled(td, td.rows[row], td.x0 + (int)col)) continue;
         double r = acc[(size_t)p * 3 + 0], g = acc[(size_t)p * 3 + 1], b = acc[(size_t)p * 3 + 2];
         for (uint32_t s = 0; s < s_count; ++s) {
             const f4 L = Lacc[(size_t)s * npix + p];

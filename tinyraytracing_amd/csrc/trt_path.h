@@ -900,7 +900,19 @@ struct TileDesc {
     uint32_t npix_magic, tile_w_magic;  // magicOf(npix), magicOf(tile_w)
     uint32_t grid_ok;     // grid_rcp may be used: 2 <= width, height <= 65536 (the operand range trt_div_by is checked for)
     double grid_rcp[4];   // 1 / (W - 1), 1 / (H - 1), 1 / W, 1 / H, correctly rounded (host)
+    // Camera rays that provably miss the scene (trt_cull.h, set by renderCore for tile renders without TRT_FLAG_COUNT): image columns culled on
+    // the left and on the right, rows at the top and at the bottom, then (first, count) of a band of rows and of a band of columns that are
+    // kept whatever the rectangle says.  All zero — every other entry point — culls nothing.
+    int32_t cull[8];
 };
+
+// Is the camera ray of image pixel (y, x) culled?  (Outside the rectangle and in neither band.)
+TRT_HD inline bool pixelCulled(const TileDesc& td, int y, int x)
+{
+    const bool out = x < td.cull[0] || x >= td.width - td.cull[1] || y < td.cull[2] || y >= td.height - td.cull[3];
+    const bool band = (uint32_t)(y - td.cull[4]) < (uint32_t)td.cull[5] || (uint32_t)(x - td.cull[6]) < (uint32_t)td.cull[7];
+    return out && !band;
+}
 
 // n / d for a divisor whose magic number m = min(floor(2^32 / d), 2^32 - 1) was formed on the host (TileDesc): the high word of
 // n m is floor(n / d) or one less for every n < 2^32 (n m / 2^32 > n / d - n / 2^32 > n / d - 1), so one correction gives the
