@@ -248,6 +248,34 @@ def test_host_and_device_entries_agree_and_bad_arguments_leave_the_handle_alone(
         assert all(st.launches[k] == 0 for k in range(7))
 
 
+# launches[TRT_K_REFIT] of one update of `back` per wave driver and node kind: recorded on the GPU from the build of the commit before the update's host
+# driver was split into stages (the vertex check, the triangle records, one launch per level of each tree the handle walks, the plane filter, the light boxes)
+REFIT_LAUNCHES = [({"TRT_TRACE_IMPL": "0"}, 10), ({"TRT_TRACE_IMPL": "3", "TRT_NODE_KIND": "0"}, 10), ({"TRT_TRACE_IMPL": "3", "TRT_NODE_KIND": "1"}, 13)]
+
+
+@pytest.mark.parametrize("env,launches", REFIT_LAUNCHES, ids=lambda x: ",".join(f"{k}={v}" for k, v in x.items()) if isinstance(x, dict) else str(x))
+def test_an_update_reports_the_launches_it_made_and_nothing_else(env, launches, monkeypatch):
+    """The bit-for-bit tests cannot see a launch that was added, dropped or moved out of the count: the count of each entry is a literal, the
+    first update of a handle (which also numbers its trees: those launches are not the update's) reports what the later ones report."""
+    import torch
+    s = T.Scene.named("back", W, H)
+    v, _ = RR.move_inner_object(s)
+    A = renderer(s, env, monkeypatch)
+    s.set_vertices(v)
+    dv = torch.from_numpy(v).to(torch.device("cuda", 0))
+    stats = [("host entry with light tables", A.update_geometry(s, want_stats=True)),
+             ("device entry with light tables", A.update_geometry_from(dv, lights_from=s)),
+             ("host entry without tables", A.update_geometry(v, want_stats=True))]
+    for what, st in stats:
+        print(f"{env} {what}: launches {list(st.launches)} kernel_ms {st.kernel_ms[T.TRT_K_REFIT]:.4f} render_ms {st.render_ms:.4f}")
+    for what, st in stats:
+        assert st.launches[T.TRT_K_REFIT] == launches, what
+        assert all(st.launches[k] == 0 for k in range(len(st.launches)) if k != T.TRT_K_REFIT), what
+        assert st.render_ms >= st.kernel_ms[T.TRT_K_REFIT] > 0, what
+    A.close()
+    s.close()
+
+
 def _vertex_eye_scene_displaced(tmp_path):
     """test_hostsim_parity's vertex-eye scene with its one triangle elsewhere, loaded from a file of its own: no box of this tree — the box of the root's empty
     second leaf included, which an update leaves alone — has a plane of the fixture's."""

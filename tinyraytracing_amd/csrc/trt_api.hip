@@ -91,6 +91,40 @@ struct DevBuf {
     }
 };
 
+// The bracket of a call that reports three fields of trt_stats (the image-space passes, the geometry update): four events on the call's
+// stream — 0 before everything, 1 before the first kernel, 2 behind the last, 3 behind everything — and, once the stream is synchronised,
+// the statistics they give.  The events are created on demand and live as long as the bracket.
+struct EventBracket {
+    hipEvent_t ev[4] = {};
+    EventBracket() = default;
+    EventBracket(const EventBracket&) = delete;
+    ~EventBracket()
+    {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    int create()
+    {
+        for (hipEvent_t& e : ev)
+            if (!e) HIPC(hipEventCreate(&e));
+        return TRT_OK;
+    }
+    int record(int i, hipStream_t stream) { HIPC(hipEventRecord(ev[i], stream)); return TRT_OK; }
+    // every field 0 but the `launches` of `kernel_slot`, its kernel_ms (events 1 -> 2) and render_ms (events 0 -> 3); stats may be null
+    int fill(trt_stats* stats, int kernel_slot, uint64_t launches) const
+    {
+        if (!stats) return TRT_OK;
+        float k_ms = 0.f, all_ms = 0.f;
+        HIPC(hipEventElapsedTime(&k_ms, ev[1], ev[2]));
+        HIPC(hipEventElapsedTime(&all_ms, ev[0], ev[3]));
+        std::memset(stats, 0, sizeof(*stats));
+        stats->launches[kernel_slot] = launches;
+        stats->kernel_ms[kernel_slot] = k_ms;
+        stats->render_ms = all_ms;
+        return TRT_OK;
+    }
+};
+
 }  // namespace
 
 struct trt_handle {
@@ -160,7 +194,7 @@ struct trt_handle {
                                                        // of its slots; cursor + flags + light boxes
         std::vector<uint32_t> level2, level4, level8;  // level l = order[level[l] .. level[l + 1])
         DevBuf light_of_mat;
-        hipEvent_t ev[4] = {};
+        EventBracket bracket;
     } refit;
     ~trt_handle()
     {
@@ -170,8 +204,6 @@ struct trt_handle {
         refit.exact8.release();
         refit.small.release();
         refit.light_of_mat.release();
-        for (hipEvent_t e : refit.ev)
-            if (e) (void)hipEventDestroy(e);
         for (void* p : scene_allocs) (void)hipFree(p);
         arena.release();
         spill.release();
@@ -1035,47 +1067,64 @@ void addDeviceStats(trt_stats& st, const DeviceStats& ds, const trt_handle* h)
     st.inner_node_bytes = h->trace_impl == 0 ? (uint32_t)sizeof(trt_bvh_node) : (h->node_kind == 1 ? 80u : (uint32_t)sizeof(WideNode));
 }
 
+// The drain of a call with work in flight: from arm() on, whatever way the driver is left, nothing may still be running on the caller's
+// stream or the slot streams when it returns (a late kernel or copy of a failed call would write what the NEXT call on the handle uses, or
+// host memory that died with the return).  The destructor synchronises them unless the driver got through and disarmed it.  A driver
+// declares it after every host end of an asynchronous copy, so that it is destroyed before them.  `slots` outlive the drain.
+struct Drain {
+    hipStream_t stream;
+    PassSlot* slots = nullptr;
+    int n_slots = 0;
+    bool armed = false;
+    explicit Drain(hipStream_t stream_) : stream(stream_) {}
+    Drain(const Drain&) = delete;
+    void arm(PassSlot* s = nullptr, int n = 0) { slots = s; n_slots = n; armed = true; }
+    ~Drain()
+    {
+        if (!armed) return;
+        for (int k = 0; k < n_slots; ++k) (void)hipStreamSynchronize(slots[k].stream);
+        (void)hipStreamSynchronize(stream);
+        (void)hipGetLastError();
+    }
+};
+
 // The frame of a call that traces rays, at its start and its end only: the Timer and the trt_stats the call fills, the block of device
-// counters (DeviceStats first) it clears and reads back, the events that bracket it on the caller's stream, and the drain: from arm() on
-// work is in flight on the caller's stream and the slot streams, and whatever way the driver is left, nothing may still be running on them
-// when it returns: a late kernel of a failed call would write the arena, Lacc, io_buf and the pinned counters of the NEXT call on this
-// handle.  The destructor drains them (and keeps the slots' sequence numbers monotonic) unless finish() got through.  `slots` outlive the frame.
+// counters (DeviceStats first) it clears and reads back, the events that bracket it on the caller's stream, and the Drain (the last member:
+// it runs before `ds`, the landing place of readBack()'s copy, goes away), armed by begin() or arm() and disarmed by finish().  The
+// destructor keeps the slots' sequence numbers monotonic on every way out.
 struct CallFrame {
     trt_handle* h;
-    hipStream_t stream;
     Timer tm;
     trt_stats st{};
     DeviceStats* d_stats = nullptr;
     DeviceStats ds;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_resolved = nullptr;  // events 0/1 bracket the call on `stream`, 2 chains renderCore's ordered resolves
-    PassSlot* slots = nullptr;
-    int n_slots = 0;
-    bool armed = false;
-    CallFrame(trt_handle* h_, hipStream_t stream_, bool timing) : h(h_), stream(stream_), tm{h_, timing} {}
+    hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_resolved = nullptr;  // events 0/1 bracket the call on the stream, 2 chains renderCore's ordered resolves
+    Drain drain;
+    CallFrame(trt_handle* h_, hipStream_t stream_, bool timing) : h(h_), tm{h_, timing}, drain(stream_) {}
     // the counters: `bytes` from the DeviceStats at `block` on
-    int clear(void* block, size_t bytes) { d_stats = (DeviceStats*)block; HIPC(hipMemsetAsync(block, 0, bytes, stream)); return TRT_OK; }
-    void arm(PassSlot* s = nullptr, int n = 0) { slots = s; n_slots = n; armed = true; }
+    int clear(void* block, size_t bytes) { d_stats = (DeviceStats*)block; HIPC(hipMemsetAsync(block, 0, bytes, drain.stream)); return TRT_OK; }
+    void arm() { drain.arm(); }
     int begin(PassSlot* s = nullptr, int n = 0)  // the bracket opens, then the drain is armed; with slots there is a resolve chain
     {
         ev_begin = tm.get(0);
         ev_end = tm.get(1);
         if (s) ev_resolved = tm.get(2);
         if (!ev_begin || !ev_end || (s && !ev_resolved)) return fail(TRT_EHIP, "hipEventCreate failed");
-        HIPC(hipEventRecord(ev_begin, stream));
-        arm(s, n);
+        HIPC(hipEventRecord(ev_begin, drain.stream));
+        drain.arm(s, n);
         return TRT_OK;
     }
     int readBack()  // the bracket closes (where begin() opened one), the counters are on their way; the driver queues its own results behind them
     {
-        if (ev_end) HIPC(hipEventRecord(ev_end, stream));
-        HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, stream));
+        if (ev_end) HIPC(hipEventRecord(ev_end, drain.stream));
+        HIPC(hipMemcpyAsync(&ds, d_stats, sizeof(ds), hipMemcpyDeviceToHost, drain.stream));
         return TRT_OK;
     }
     int finish(trt_stats* stats_out, uint32_t passes)  // after readBack(): the stream is synchronised, st completed and given to stats_out (may be null)
     {
-        HIPC(hipStreamSynchronize(stream));
+        HIPC(hipStreamSynchronize(drain.stream));
         HIPC(hipGetLastError());
-        armed = false;  // everything this call enqueued has completed
+        drain.armed = false;  // everything this call enqueued has completed
         float ms = 0.f;
         if (ev_end) HIPC(hipEventElapsedTime(&ms, ev_begin, ev_end));
         st.render_ms = ms;
@@ -1090,11 +1139,7 @@ struct CallFrame {
     }
     ~CallFrame()
     {
-        for (int k = 0; k < n_slots; ++k) h->slot_seq[k] = slots[k].seq;
-        if (!armed) return;
-        for (int k = 0; k < n_slots; ++k) (void)hipStreamSynchronize(slots[k].stream);
-        (void)hipStreamSynchronize(stream);
-        (void)hipGetLastError();
+        for (int k = 0; k < drain.n_slots; ++k) h->slot_seq[k] = drain.slots[k].seq;
     }
 };
 
@@ -2310,15 +2355,13 @@ struct ImageStage {
     std::vector<Plane> planes;
     hipStream_t stream = nullptr;
     void* p = nullptr;
-    hipEvent_t ev[4] = {};
+    EventBracket bracket;
 
     ImageStage(int width, int height, bool host_) : pixels((size_t)width * (size_t)height), host(host_) {}
     ImageStage(const ImageStage&) = delete;
     ~ImageStage()
     {
         if (p) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
     }
     int add(Kind kind, const void* user, size_t bytes, bool present)
     {
@@ -2339,34 +2382,24 @@ struct ImageStage {
         for (size_t i = 0; i < planes.size(); ++i)
             if (staged(planes[i])) at[i] = L.add(planes[i].bytes, 256);
         if (L.bytes) HIPC(hipMalloc(&p, L.bytes));
-        for (hipEvent_t& e : ev) HIPC(hipEventCreate(&e));
+        if (int e = bracket.create()) return e;
         for (size_t i = 0; i < planes.size(); ++i) planes[i].dev = staged(planes[i]) ? (char*)p + at[i] : planes[i].present ? planes[i].user : nullptr;
-        HIPC(hipEventRecord(ev[0], stream));
+        if (int e = bracket.record(0, stream)) return e;
         for (const Plane& b : planes)
             if (b.kind == IN && staged(b)) HIPC(hipMemcpyAsync(b.dev, b.user, b.bytes, hipMemcpyHostToDevice, stream));
-        HIPC(hipEventRecord(ev[1], stream));
-        return TRT_OK;
+        return bracket.record(1, stream);
     }
     // Behind the launches: event 2, the outputs' download, event 3, the wait, and the statistics of the `launches` kernels.
     int finish(trt_stats* stats, uint64_t launches)
     {
         HIPC(hipGetLastError());
-        HIPC(hipEventRecord(ev[2], stream));
+        if (int e = bracket.record(2, stream)) return e;
         for (const Plane& b : planes)
             if (b.kind == OUT && staged(b)) HIPC(hipMemcpyAsync(b.user, b.dev, b.bytes, hipMemcpyDeviceToHost, stream));
-        HIPC(hipEventRecord(ev[3], stream));
+        if (int e = bracket.record(3, stream)) return e;
         HIPC(hipStreamSynchronize(stream));
         HIPC(hipGetLastError());
-        if (stats) {
-            float k_ms = 0.f, all_ms = 0.f;
-            HIPC(hipEventElapsedTime(&k_ms, ev[1], ev[2]));
-            HIPC(hipEventElapsedTime(&all_ms, ev[0], ev[3]));
-            std::memset(stats, 0, sizeof(*stats));
-            stats->launches[TRT_K_DENOISE] = launches;
-            stats->kernel_ms[TRT_K_DENOISE] = k_ms;
-            stats->render_ms = all_ms;
-        }
-        return TRT_OK;
+        return bracket.fill(stats, TRT_K_DENOISE, launches);
     }
 
 private:
@@ -2673,12 +2706,35 @@ namespace {
 
 inline dim3 refitGrid(uint64_t n) { return dim3((unsigned)std::max<uint64_t>(1, (n + REFIT_BLOCK - 1) / REFIT_BLOCK)); }
 
-// First update of a handle: the breadth-first node lists of both trees (one launch and one 4-byte read-back per level), the
-// material-to-light table and the events.  Nothing a render reads is written.
+// What one update keeps on the host from its first enqueue to its last exit: every host end of an asynchronous copy (sources and landing
+// places) and the host entry's copy of the vertices on the device.  updateGeometry declares it before its Drain, so on every way out the
+// stream is synchronised first and this goes away — the vertices are released — after it.
+struct RefitHost {
+    std::vector<LightDev> lights;        // sources: the caller's light tables in device layout
+    std::vector<LightTriDev> ltris;
+    std::vector<float> cum;
+    std::vector<int32_t> light_of_mat;   // source (the first update)
+    std::vector<uint32_t> light_box;     // source (the empty boxes), then landing place: 6 ordered keys per light
+    uint32_t cursor = 0;                 // landing places: the numbering's node count (the first update), nodes[0], the 8-wide refit's flag
+    trt_bvh_node root{};
+    uint32_t oct_failed = 0;
+    void* v = nullptr;                   // the staged vertices and normals (host entry)
+    void* vn = nullptr;
+    RefitHost() = default;
+    RefitHost(const RefitHost&) = delete;
+    ~RefitHost()
+    {
+        if (v) (void)hipFree(v);
+        if (vn) (void)hipFree(vn);
+    }
+};
+
+// First update of a handle: the breadth-first node lists of both trees (one launch and one 4-byte read-back per level) and the
+// material-to-light table.  Nothing a render reads is written.
 template <class Bfs>
-int refitNumber(Bfs launch, uint32_t n_nodes, uint32_t* d_order, uint32_t* d_cursor, hipStream_t stream, std::vector<uint32_t>& level)
+int refitNumber(Bfs launch, uint32_t n_nodes, uint32_t* d_order, uint32_t* d_cursor, hipStream_t stream, std::vector<uint32_t>& level, uint32_t& cur)
 {
-    const uint32_t root[2] = {0u, 1u};  // order[0] = node 0; cursor = 1
+    static const uint32_t root[2] = {0u, 1u};  // order[0] = node 0; cursor = 1
     HIPC(hipMemcpyAsync(d_order, &root[0], sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     HIPC(hipMemcpyAsync(d_cursor, &root[1], sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     level.assign(1, 0u);
@@ -2686,7 +2742,6 @@ int refitNumber(Bfs launch, uint32_t n_nodes, uint32_t* d_order, uint32_t* d_cur
     while (begin < end) {
         level.push_back(end);
         launch(begin, end);
-        uint32_t cur = 0;
         HIPC(hipMemcpyAsync(&cur, d_cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIPC(hipStreamSynchronize(stream));
         if (cur > n_nodes || level.size() > (size_t)MAX_BVH_DEPTH * 2 + 4) return fail(TRT_EHIP, "trt_update_geometry: the handle's tree does not number (internal error)");
@@ -2696,7 +2751,7 @@ int refitNumber(Bfs launch, uint32_t n_nodes, uint32_t* d_order, uint32_t* d_cur
     return TRT_OK;
 }
 
-int refitPrepare(trt_handle* h, hipStream_t stream)
+int refitPrepare(trt_handle* h, hipStream_t stream, RefitHost& H)
 {
     trt_handle::Refit& R = h->refit;
     if (R.ready) return TRT_OK;
@@ -2705,25 +2760,24 @@ int refitPrepare(trt_handle* h, hipStream_t stream)
     if (int e = R.order4.ensure((size_t)std::max(nw, 1u) * sizeof(uint32_t))) return e;
     if (int e = R.small.ensure((size_t)(16 + 6 * (size_t)std::max(h->sc.n_lights, 1u)) * sizeof(uint32_t))) return e;
     if (int e = R.light_of_mat.ensure((size_t)std::max(h->n_materials, 1u) * sizeof(int32_t))) return e;
-    for (hipEvent_t& e : R.ev)
-        if (!e) HIPC(hipEventCreate(&e));
     uint32_t* cursor = (uint32_t*)R.small.p;
     uint32_t* o2 = (uint32_t*)R.order2.p;
     uint32_t* o4 = (uint32_t*)R.order4.p;
     if (int e = refitNumber([&](uint32_t b, uint32_t en) { hipLaunchKernelGGL(k_refit_bfs2, refitGrid(en - b), dim3(REFIT_BLOCK), 0, stream, h->sc.nodes, o2, b, en, cursor, nn); },
-                            nn, o2, cursor, stream, R.level2)) return e;
+                            nn, o2, cursor, stream, R.level2, H.cursor)) return e;
     if (nw)
         if (int e = refitNumber([&](uint32_t b, uint32_t en) { hipLaunchKernelGGL(k_refit_bfs4, refitGrid(en - b), dim3(REFIT_BLOCK), 0, stream, h->sc.wnodes, o4, b, en, cursor, nw); },
-                                nw, o4, cursor, stream, R.level4)) return e;
+                                nw, o4, cursor, stream, R.level4, H.cursor)) return e;
     if (h->node_kind == 1 && h->sc.onodes) {
         const uint32_t no = h->sc.n_onodes;
         if (int e = R.order8.ensure((size_t)std::max(no, 1u) * sizeof(uint32_t))) return e;
         if (int e = R.exact8.ensure((size_t)std::max(no, 1u) * sizeof(RefitBox))) return e;
         uint32_t* o8 = (uint32_t*)R.order8.p;
         if (int e = refitNumber([&](uint32_t b, uint32_t en) { hipLaunchKernelGGL(k_refit_bfs8, refitGrid(en - b), dim3(REFIT_BLOCK), 0, stream, h->sc.onodes, o8, b, en, cursor, no); },
-                                no, o8, cursor, stream, R.level8)) return e;
+                                no, o8, cursor, stream, R.level8, H.cursor)) return e;
     }
-    std::vector<int32_t> lom(std::max(h->n_materials, 1u), -1);
+    std::vector<int32_t>& lom = H.light_of_mat;
+    lom.assign(std::max(h->n_materials, 1u), -1);
     for (size_t l = h->light_mats.size(); l-- > 0;)
         if (h->light_mats[l] < h->n_materials) lom[h->light_mats[l]] = (int32_t)l;  // the first light of a material stands for all of them
     HIPC(hipMemcpyAsync(R.light_of_mat.p, lom.data(), lom.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
@@ -2733,174 +2787,200 @@ int refitPrepare(trt_handle* h, hipStream_t stream)
     return TRT_OK;
 }
 
-struct RefitStage {  // the host entry's copy of the vertices, released on every way out
-    void* v = nullptr;
-    void* vn = nullptr;
-    ~RefitStage()
-    {
-        if (v) (void)hipFree(v);
-        if (vn) (void)hipFree(vn);
-    }
-};
+inline bool refitsOct(const trt_handle* h) { return h->node_kind == 1 && !h->refit.level8.empty(); }  // after refitPrepare
+inline bool refitsLightBoxes(const trt_handle* h) { return h->sc.n_lights && !h->light_boxes_fixed; }
 
-int updateGeometry(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris, bool host, hipStream_t stream, trt_stats* stats, const char* what)
+// The checks that need no device
+int checkUpdate(const trt_handle* h, const trt_geometry_update* u, uint32_t n_tris, const std::string& w)
 {
-    const std::string w(what);
     if (!h || !u) return fail(TRT_EINVAL, w + ": null handle / update");
     if (!u->tri_v && h->sc.n_tris) return fail(TRT_EINVAL, w + ": tri_v is null");
     if (n_tris != h->sc.n_tris) return fail(TRT_EINVAL, w + ": n_tris differs from the handle's (topology cannot change)");
     if ((u->lights == nullptr) != (u->light_tris == nullptr) && (u->lights || h->n_light_tris)) return fail(TRT_EINVAL, w + ": lights and light_tris come together");
-    std::vector<LightDev> lights;
-    std::vector<LightTriDev> ltris;
-    std::vector<float> cum;
-    const bool new_lights = u->lights != nullptr;
-    if (new_lights) {
-        if (u->n_lights != h->sc.n_lights || u->n_light_tris != h->n_light_tris) return fail(TRT_EINVAL, w + ": light counts differ from the handle's");
-        for (uint32_t l = 0; l < u->n_lights; ++l) {
-            const trt_light& L = u->lights[l];
-            if (L.mat < 0 || (uint32_t)L.mat >= h->n_materials) return fail(TRT_EINVAL, w + ": light material id out of range");
-            if ((uint32_t)L.mat != h->light_mats[l]) return fail(TRT_EINVAL, w + ": a light's material differs from the handle's");
-            if ((uint64_t)L.tri_first + L.tri_count > u->n_light_tris) return fail(TRT_EINVAL, w + ": light triangle range out of bounds");
-        }
-        std::vector<MaterialDev> mats(h->n_materials);  // radiance comes from the materials (makeLightDev); they live on the device only
-        HIPC(hipSetDevice(h->device));
-        HIPC(hipMemcpy(mats.data(), h->sc.materials, mats.size() * sizeof(MaterialDev), hipMemcpyDeviceToHost));
-        lights.resize(u->n_lights);
-        for (uint32_t l = 0; l < u->n_lights; ++l) lights[l] = makeLightDevFrom(u->lights[l], mats[(size_t)u->lights[l].mat].radiance);
-        ltris.resize(u->n_light_tris);
-        cum.resize(u->n_light_tris);
-        for (uint32_t k = 0; k < u->n_light_tris; ++k) { ltris[k] = makeLightTriDev(u->light_tris[k]); cum[k] = u->light_tris[k].cum_area; }
-        bool monotone = true;
-        for (uint32_t l = 0; l < u->n_lights; ++l)
-            for (uint32_t k = 0; k < u->lights[l].tri_count; ++k) {
-                const float c = cum[u->lights[l].tri_first + k];
-                if (!(c == c) || (k && c < cum[u->lights[l].tri_first + k - 1])) monotone = false;
-            }
-        // a handle that bisects the packed CDF keeps doing so (k_shade's LDS layout is fixed at trt_create): a CDF it cannot bisect is refused
-        if (h->sc.light_cum && !monotone) return fail(TRT_EINVAL, w + ": a light's cumulative areas decrease or are NaN (this handle bisects them)");
+    return TRT_OK;
+}
+
+// The caller's light tables, when given, checked and in device layout (H.lights, H.ltris, H.cum); nothing is enqueued
+int updateLightTables(const trt_handle* h, const trt_geometry_update* u, const std::string& w, RefitHost& H)
+{
+    if (!u->lights) return TRT_OK;
+    if (u->n_lights != h->sc.n_lights || u->n_light_tris != h->n_light_tris) return fail(TRT_EINVAL, w + ": light counts differ from the handle's");
+    for (uint32_t l = 0; l < u->n_lights; ++l) {
+        const trt_light& L = u->lights[l];
+        if (L.mat < 0 || (uint32_t)L.mat >= h->n_materials) return fail(TRT_EINVAL, w + ": light material id out of range");
+        if ((uint32_t)L.mat != h->light_mats[l]) return fail(TRT_EINVAL, w + ": a light's material differs from the handle's");
+        if ((uint64_t)L.tri_first + L.tri_count > u->n_light_tris) return fail(TRT_EINVAL, w + ": light triangle range out of bounds");
     }
-    HIPC(hipSetDevice(h->device));
-    trt_handle::Refit& R = h->refit;
-    for (hipEvent_t& e : R.ev)
-        if (!e) HIPC(hipEventCreate(&e));
-    HIPC(hipEventRecord(R.ev[0], stream));  // render_ms of a handle's first update holds the numbering of its trees
-    if (int e = refitPrepare(h, stream)) return e;
+    std::vector<MaterialDev> mats(h->n_materials);  // radiance comes from the materials (makeLightDev); they live on the device only
+    HIPC(hipMemcpy(mats.data(), h->sc.materials, mats.size() * sizeof(MaterialDev), hipMemcpyDeviceToHost));
+    H.lights.resize(u->n_lights);
+    for (uint32_t l = 0; l < u->n_lights; ++l) H.lights[l] = makeLightDevFrom(u->lights[l], mats[(size_t)u->lights[l].mat].radiance);
+    H.ltris.resize(u->n_light_tris);
+    H.cum.resize(u->n_light_tris);
+    for (uint32_t k = 0; k < u->n_light_tris; ++k) { H.ltris[k] = makeLightTriDev(u->light_tris[k]); H.cum[k] = u->light_tris[k].cum_area; }
+    bool monotone = true;
+    for (uint32_t l = 0; l < u->n_lights; ++l)
+        for (uint32_t k = 0; k < u->lights[l].tri_count; ++k) {
+            const float c = H.cum[u->lights[l].tri_first + k];
+            if (!(c == c) || (k && c < H.cum[u->lights[l].tri_first + k - 1])) monotone = false;
+        }
+    // a handle that bisects the packed CDF keeps doing so (k_shade's LDS layout is fixed at trt_create): a CDF it cannot bisect is refused
+    if (h->sc.light_cum && !monotone) return fail(TRT_EINVAL, w + ": a light's cumulative areas decrease or are NaN (this handle bisects them)");
+    return TRT_OK;
+}
+
+// The host entry's vertices (and normals, when given) into device memory of the call's own; d_v and d_vn then point there
+int stageVertices(const trt_geometry_update* u, uint32_t n, hipStream_t stream, RefitHost& H, const float*& d_v, const float*& d_vn)
+{
+    const size_t bytes = (size_t)n * 9 * sizeof(float);
+    HIPC(hipMalloc(&H.v, bytes));
+    HIPC(hipMemcpyAsync(H.v, u->tri_v, bytes, hipMemcpyHostToDevice, stream));
+    d_v = (const float*)H.v;
+    if (!u->tri_vn) return TRT_OK;
+    HIPC(hipMalloc(&H.vn, bytes));
+    HIPC(hipMemcpyAsync(H.vn, u->tri_vn, bytes, hipMemcpyHostToDevice, stream));
+    d_vn = (const float*)H.vn;
+    return TRT_OK;
+}
+
+// Nothing is written before the vertices have passed: one launch, one flag, read back on the spot
+int checkVertices(const trt_handle* h, const float* d_v, hipStream_t stream, const std::string& w)
+{
+    uint32_t* flag = (uint32_t*)h->refit.small.p + 1;
+    HIPC(hipMemsetAsync(flag, 0, sizeof(uint32_t), stream));
+    const uint64_t nf = (uint64_t)h->sc.n_tris * 9;
+    hipLaunchKernelGGL(k_refit_check, dim3((unsigned)std::min<uint64_t>(4096, std::max<uint64_t>(1, (nf + REFIT_BLOCK - 1) / REFIT_BLOCK))), dim3(REFIT_BLOCK), 0, stream, d_v, nf, flag);
+    uint32_t bad = 0;
+    HIPC(hipMemcpyAsync(&bad, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+    if (bad) return fail(TRT_EINVAL, w + ": a vertex coordinate is NaN or infinite");
+    return TRT_OK;
+}
+
+// Bottom-up over a tree that refitNumber numbered: launch(begin, end) once per level, the deepest first -> the launches
+template <class Launch>
+uint64_t refitLevels(const std::vector<uint32_t>& level, Launch launch)
+{
+    uint64_t launches = 0;
+    for (size_t l = level.empty() ? 0 : level.size() - 1; l-- > 0; ++launches) launch(level[l], level[l + 1]);
+    return launches;
+}
+
+// The refit itself: the triangle records, the caller's BVH2, the 4-wide nodes, the 8-wide nodes of a handle that walks them, the plane
+// filter and the light boxes (trt_refit_kernels.h) -> `launches` grows by what was launched
+int refitLaunches(trt_handle* h, const float* d_v, const float* d_vn, hipStream_t stream, RefitHost& H, uint64_t& launches)
+{
+    const trt_handle::Refit& R = h->refit;
     const uint32_t n = h->sc.n_tris, nn = h->sc.n_nodes, nw = h->sc.n_wnodes, nl = h->sc.n_lights;
-    uint32_t* flag = (uint32_t*)R.small.p + 1;
+    const dim3 block(REFIT_BLOCK);
     uint32_t* oct_fail = (uint32_t*)R.small.p + 2;
     uint32_t* lbox = (uint32_t*)R.small.p + 16;
-
-    RefitStage S;
-    const float* d_v = u->tri_v;
-    const float* d_vn = u->tri_vn;
-    if (host && n) {
-        const size_t bytes = (size_t)n * 9 * sizeof(float);
-        HIPC(hipMalloc(&S.v, bytes));
-        HIPC(hipMemcpyAsync(S.v, u->tri_v, bytes, hipMemcpyHostToDevice, stream));
-        d_v = (const float*)S.v;
-        if (u->tri_vn) {
-            HIPC(hipMalloc(&S.vn, bytes));
-            HIPC(hipMemcpyAsync(S.vn, u->tri_vn, bytes, hipMemcpyHostToDevice, stream));
-            d_vn = (const float*)S.vn;
-        }
-    }
-    uint64_t launches = 0;
-    HIPC(hipEventRecord(R.ev[1], stream));
-    {   // nothing is written before the vertices have passed
-        HIPC(hipMemsetAsync(flag, 0, sizeof(uint32_t), stream));
-        const uint64_t nf = (uint64_t)n * 9;
-        hipLaunchKernelGGL(k_refit_check, dim3((unsigned)std::min<uint64_t>(4096, std::max<uint64_t>(1, (nf + REFIT_BLOCK - 1) / REFIT_BLOCK))), dim3(REFIT_BLOCK), 0, stream, d_v, nf, flag);
-        ++launches;
-        uint32_t bad = 0;
-        HIPC(hipMemcpyAsync(&bad, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIPC(hipStreamSynchronize(stream));
-        HIPC(hipGetLastError());
-        if (bad) return fail(TRT_EINVAL, w + ": a vertex coordinate is NaN or infinite");
-    }
     if (n) {
-        hipLaunchKernelGGL(k_refit_tris, refitGrid(n), dim3(REFIT_BLOCK), 0, stream, n, d_v, d_vn, (TriIsect*)h->sc.tri_isect, (TriShade*)h->sc.tri_shade);
+        hipLaunchKernelGGL(k_refit_tris, refitGrid(n), block, 0, stream, n, d_v, d_vn, (TriIsect*)h->sc.tri_isect, (TriShade*)h->sc.tri_shade);
         ++launches;
     }
-    for (size_t l = R.level2.size() - 1; l-- > 0;) {
-        const uint32_t b = R.level2[l], e = R.level2[l + 1];
-        hipLaunchKernelGGL(k_refit_level2, refitGrid(e - b), dim3(REFIT_BLOCK), 0, stream, (trt_bvh_node*)h->sc.nodes, nn, (const uint32_t*)R.order2.p, b, e, d_v, (f4*)h->sc.leaf_box);
-        ++launches;
-    }
-    for (size_t l = R.level4.empty() ? 0 : R.level4.size() - 1; l-- > 0;) {
-        const uint32_t b = R.level4[l], e = R.level4[l + 1];
-        hipLaunchKernelGGL(k_refit_level4, refitGrid(e - b), dim3(REFIT_BLOCK), 0, stream, (WideNode*)h->sc.wnodes, nw, (const uint32_t*)R.order4.p, b, e, h->sc.leaf_box);
-        ++launches;
-    }
-    const bool oct = h->node_kind == 1 && !R.level8.empty();
-    if (oct) {   // the 8-wide nodes: triangle records in node order, then the nodes level by level with their children's exact boxes in scratch
+    launches += refitLevels(R.level2, [&](uint32_t b, uint32_t e) {
+        hipLaunchKernelGGL(k_refit_level2, refitGrid(e - b), block, 0, stream, (trt_bvh_node*)h->sc.nodes, nn, (const uint32_t*)R.order2.p, b, e, d_v, (f4*)h->sc.leaf_box);
+    });
+    launches += refitLevels(R.level4, [&](uint32_t b, uint32_t e) {
+        hipLaunchKernelGGL(k_refit_level4, refitGrid(e - b), block, 0, stream, (WideNode*)h->sc.wnodes, nw, (const uint32_t*)R.order4.p, b, e, h->sc.leaf_box);
+    });
+    if (refitsOct(h)) {   // the 8-wide nodes: triangle records in node order, then the nodes level by level with their children's exact boxes in scratch
         HIPC(hipMemsetAsync(oct_fail, 0, sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(k_refit_tri_trav, refitGrid(h->n_tri_trav), dim3(REFIT_BLOCK), 0, stream, h->n_tri_trav, h->sc.tri_isect, (TriIsect*)h->sc.tri_trav);
+        hipLaunchKernelGGL(k_refit_tri_trav, refitGrid(h->n_tri_trav), block, 0, stream, h->n_tri_trav, h->sc.tri_isect, (TriIsect*)h->sc.tri_trav);
         ++launches;
-        for (size_t l = R.level8.size() - 1; l-- > 0;) {
-            const uint32_t b = R.level8[l], e = R.level8[l + 1];
-            hipLaunchKernelGGL(k_refit_level8, refitGrid(e - b), dim3(REFIT_BLOCK), 0, stream, (OctNode*)h->sc.onodes, h->sc.n_onodes, (const uint32_t*)R.order8.p, b, e,
+        launches += refitLevels(R.level8, [&](uint32_t b, uint32_t e) {
+            hipLaunchKernelGGL(k_refit_level8, refitGrid(e - b), block, 0, stream, (OctNode*)h->sc.onodes, h->sc.n_onodes, (const uint32_t*)R.order8.p, b, e,
                                h->sc.tri_trav, h->sc.leaf_box, (RefitBox*)R.exact8.p, oct_fail);
-            ++launches;
-        }
+        });
     }
     if (h->sc.plane_bits) {
         const size_t words = (size_t)((1ull << (32u - h->sc.plane_shift)) / 32);
         HIPC(hipMemsetAsync((void*)h->sc.plane_bits, 0, words * sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(k_refit_planes, refitGrid(nn), dim3(REFIT_BLOCK), 0, stream, h->sc.nodes, nn, (uint32_t*)h->sc.plane_bits, h->sc.plane_shift);
+        hipLaunchKernelGGL(k_refit_planes, refitGrid(nn), block, 0, stream, h->sc.nodes, nn, (uint32_t*)h->sc.plane_bits, h->sc.plane_shift);
         ++launches;
     }
-    std::vector<uint32_t> lb_host((size_t)6 * nl);
-    const bool light_boxes = nl && !h->light_boxes_fixed;
-    if (light_boxes) {
+    H.light_box.resize((size_t)6 * nl);
+    if (refitsLightBoxes(h)) {
         for (uint32_t l = 0; l < nl; ++l)
-            for (int a = 0; a < 3; ++a) { lb_host[6 * l + a] = refitOrdered(3.0e38f); lb_host[6 * l + 3 + a] = refitOrdered(-3.0e38f); }
-        HIPC(hipMemcpyAsync(lbox, lb_host.data(), lb_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(k_refit_light_boxes, refitGrid(n), dim3(REFIT_BLOCK), 0, stream, n, h->sc.tri_isect, h->sc.leaf_box, (const int32_t*)R.light_of_mat.p, h->n_materials, lbox);
+            for (int a = 0; a < 3; ++a) { H.light_box[6 * l + a] = refitOrdered(3.0e38f); H.light_box[6 * l + 3 + a] = refitOrdered(-3.0e38f); }
+        HIPC(hipMemcpyAsync(lbox, H.light_box.data(), H.light_box.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(k_refit_light_boxes, refitGrid(n), block, 0, stream, n, h->sc.tri_isect, h->sc.leaf_box, (const int32_t*)R.light_of_mat.p, h->n_materials, lbox);
         ++launches;
     }
     HIPC(hipGetLastError());
-    HIPC(hipEventRecord(R.ev[2], stream));
-    trt_bvh_node root{};
-    HIPC(hipMemcpyAsync(&root, h->sc.nodes, sizeof(root), hipMemcpyDeviceToHost, stream));
-    uint32_t oct_failed = 0;
-    if (oct) HIPC(hipMemcpyAsync(&oct_failed, oct_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (light_boxes) HIPC(hipMemcpyAsync(lb_host.data(), lbox, lb_host.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    if (new_lights) {
-        if (!lights.empty()) HIPC(hipMemcpyAsync((void*)h->sc.lights, lights.data(), lights.size() * sizeof(LightDev), hipMemcpyHostToDevice, stream));
-        if (!ltris.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_tris, ltris.data(), ltris.size() * sizeof(LightTriDev), hipMemcpyHostToDevice, stream));
-        if (h->sc.light_cum && !cum.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_cum, cum.data(), cum.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    }
-    if (h->lds_image)
-        if (int e = packLdsImage(h, stream)) return e;
-    HIPC(hipEventRecord(R.ev[3], stream));
-    HIPC(hipStreamSynchronize(stream));
-    HIPC(hipGetLastError());
+    return TRT_OK;
+}
 
-    h->sc.leaf_alpha = sceneLeafAlpha(&root, 1);
-    h->root_node = root;  // what cullBound() projects from now on (trt_cull.h)
+// Behind the kernels: what the commit needs comes back (H.root, H.oct_failed, H.light_box), the new light tables go up, k_shade's LDS image follows them
+int exchangeTables(trt_handle* h, bool new_lights, hipStream_t stream, RefitHost& H)
+{
+    const trt_handle::Refit& R = h->refit;
+    HIPC(hipMemcpyAsync(&H.root, h->sc.nodes, sizeof(H.root), hipMemcpyDeviceToHost, stream));
+    if (refitsOct(h)) HIPC(hipMemcpyAsync(&H.oct_failed, (uint32_t*)R.small.p + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (refitsLightBoxes(h)) HIPC(hipMemcpyAsync(H.light_box.data(), (uint32_t*)R.small.p + 16, H.light_box.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (new_lights) {
+        if (!H.lights.empty()) HIPC(hipMemcpyAsync((void*)h->sc.lights, H.lights.data(), H.lights.size() * sizeof(LightDev), hipMemcpyHostToDevice, stream));
+        if (!H.ltris.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_tris, H.ltris.data(), H.ltris.size() * sizeof(LightTriDev), hipMemcpyHostToDevice, stream));
+        if (h->sc.light_cum && !H.cum.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_cum, H.cum.data(), H.cum.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
+    if (h->lds_image) return packLdsImage(h, stream);
+    return TRT_OK;
+}
+
+// The handle's host state follows what the device now holds: only after the stream has been synchronised without an error
+void commitUpdate(trt_handle* h, const trt_geometry_update* u, const RefitHost& H)
+{
+    const uint32_t nl = h->sc.n_lights;
+    h->sc.leaf_alpha = sceneLeafAlpha(&H.root, 1);
+    h->root_node = H.root;  // what cullBound() projects from now on (trt_cull.h)
     h->root_known = true;
     if (h->sc.cull_alpha != std::numeric_limits<float>::infinity()) h->sc.cull_alpha = h->sc.leaf_alpha;  // a tree that did not nest at trt_create stays without distance culling
-    if (light_boxes)
+    if (refitsLightBoxes(h))
         for (uint32_t l = 0; l < nl; ++l) {
             const uint32_t m = h->light_mats[l];
             uint32_t from = l;  // lights of one material share the box of the first of them
             for (uint32_t k = 0; k < l; ++k)
                 if (h->light_mats[k] == m) { from = k; break; }
-            for (int a = 0; a < 3; ++a) { h->light_boxes[l].lo[a] = refitUnordered(lb_host[6 * from + a]); h->light_boxes[l].hi[a] = refitUnordered(lb_host[6 * from + 3 + a]); }
+            for (int a = 0; a < 3; ++a) { h->light_boxes[l].lo[a] = refitUnordered(H.light_box[6 * from + a]); h->light_boxes[l].hi[a] = refitUnordered(H.light_box[6 * from + 3 + a]); }
         }
-    if (new_lights) h->sc.light0_area = nl ? u->lights[0].area : 0.0f;
+    if (u->lights) h->sc.light0_area = nl ? u->lights[0].area : 0.0f;
     // boxes that reach 2^40 (or an extent the bytes cannot hold): the tree no longer qualifies for the 8-wide nodes — the exact 4-wide ones from here on, for good
-    if (oct && oct_failed) h->node_kind = 0;
-    if (stats) {
-        float k_ms = 0.f, all_ms = 0.f;
-        HIPC(hipEventElapsedTime(&k_ms, R.ev[1], R.ev[2]));
-        HIPC(hipEventElapsedTime(&all_ms, R.ev[0], R.ev[3]));
-        std::memset(stats, 0, sizeof(*stats));
-        stats->launches[TRT_K_REFIT] = launches;
-        stats->kernel_ms[TRT_K_REFIT] = k_ms;
-        stats->render_ms = all_ms;
-    }
-    return TRT_OK;
+    if (refitsOct(h) && H.oct_failed) h->node_kind = 0;
+}
+
+// The stages of an update, in the order include/trt.h promises: every check before anything is written.  The bracket (events 0..3 of the
+// handle, TRT_K_REFIT) opens before refitPrepare: render_ms of a handle's first update holds the numbering of its trees.
+int updateGeometry(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris, bool host, hipStream_t stream, trt_stats* stats, const char* what)
+{
+    const std::string w(what);
+    if (int e = checkUpdate(h, u, n_tris, w)) return e;
+    HIPC(hipSetDevice(h->device));
+    RefitHost H;  // before the drain: it goes away after the stream has been synchronised
+    if (int e = updateLightTables(h, u, w, H)) return e;
+    EventBracket& B = h->refit.bracket;
+    if (int e = B.create()) return e;
+    Drain drain(stream);
+    drain.arm();
+    if (int e = B.record(0, stream)) return e;
+    if (int e = refitPrepare(h, stream, H)) return e;
+    const float* d_v = u->tri_v;
+    const float* d_vn = u->tri_vn;
+    if (host && h->sc.n_tris)
+        if (int e = stageVertices(u, h->sc.n_tris, stream, H, d_v, d_vn)) return e;
+    if (int e = B.record(1, stream)) return e;
+    if (int e = checkVertices(h, d_v, stream, w)) return e;
+    uint64_t launches = 1;  // k_refit_check
+    if (int e = refitLaunches(h, d_v, d_vn, stream, H, launches)) return e;
+    if (int e = B.record(2, stream)) return e;
+    if (int e = exchangeTables(h, u->lights != nullptr, stream, H)) return e;
+    if (int e = B.record(3, stream)) return e;
+    HIPC(hipStreamSynchronize(stream));
+    HIPC(hipGetLastError());
+    drain.armed = false;  // everything this call enqueued has completed
+    commitUpdate(h, u, H);
+    return B.fill(stats, TRT_K_REFIT, launches);
 }
 
 }  // namespace
