@@ -254,7 +254,10 @@ int trt_render_device(trt_handle* h, const trt_params* p, float* out_rgb_dev,
  * order, onto `accum` — HOST, rows_selected * (x1-x0) * 3 doubles, in/out: the running sums of
  * (double)(L_s / spp).  Calls that cover [0, spp) in increasing order, starting from zeros, leave exactly
  * the sums of one trt_render call (and in out_rgb_host — optional, may be NULL — exactly its image), so
- * a long render can be shown while it converges, check-pointed (save accum + sample_end) and resumed. */
+ * a long render can be shown while it converges, check-pointed (save accum + sample_end) and resumed.
+ * A pixel whose camera rays provably miss the scene (trt_cull.h) is left alone instead of having +0.0
+ * added to it per sample: the same value for every accum but one — a -0.0 handed in for such a pixel
+ * stays -0.0 where the additions would have made it +0.0 (as they do with TRT_CULL_PRIMARY=0). */
 int trt_render_samples(trt_handle* h, const trt_params* p, int32_t sample_begin, int32_t sample_end,
                        double* accum_host, float* out_rgb_host, trt_stats* stats);
 

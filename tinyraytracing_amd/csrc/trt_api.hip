@@ -1254,14 +1254,15 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const bool fuse = h->fuse_primary && lights == SHADE_ONE && !in.list && !in.rays && !count;
     ShadeArgs shade_args = shadeArgsOf(h, p, in, d_table, rows_lds, d_stats);
     // camera rays that provably miss the root's two child boxes (trt_cull.h): tile renders only; a counting render keeps the root visit of every ray
-    bool culls = false;
+    bool culls = false, shade_culls = false;
     TileDesc td_cull = shade_args.td;  // what k_resolve_tile gets
     if (!in.list && !in.rays && !count && !d_sq && h->cull_primary) {
         const CullBound cb = cullBound(h->sc.cam, p->width, p->height, (p->flags & TRT_FLAG_FIXED_PIXELS) != 0, h->root_known ? &h->root_node : nullptr, h->sc.n_nodes);
         culls = cb.active && (cb.v[0] | cb.v[1] | cb.v[2] | cb.v[3]) != 0;  // (a scene that fills the frame: nothing lies outside, the render runs the kernels it ran)
         for (int k = 0; k < 8; ++k) td_cull.cull[k] = cb.v[k];
         // k_shade's FUSE flavour keeps the classes of the tile's columns and rows in LDS: wider or taller tiles are culled in the resolve only
-        if (culls && fuse && in.tile_w <= (int32_t)TRT_SHADE_CULL_COLS && rows_lds != 0u) shade_args.td = td_cull;
+        shade_culls = culls && fuse && in.tile_w <= (int32_t)TRT_SHADE_CULL_COLS && rows_lds != 0u;
+        if (shade_culls) shade_args.td = td_cull;
         if (h->dbg) {
             if (cb.active)
                 std::fprintf(stderr, "trt_render: cull primary columns [%d, %d] rows [%d, %d] band rows [%d, %d] band columns [%d, %d]\n", cb.j_lo, cb.j_hi, cb.i_lo, cb.i_hi,
@@ -1271,6 +1272,8 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     } else if (h->dbg && !in.list && !in.rays) {
         std::fprintf(stderr, "trt_render: cull primary off: %s\n", count ? "counting render" : "TRT_CULL_PRIMARY=0");
     }
+    // which of the two routes this call takes: 1 = k_shade skips the culled paths itself, 0 = at most k_resolve_tile skips their pixels
+    if (h->dbg && !in.list && !in.rays) std::fprintf(stderr, "trt_render: cull in k_shade %d\n", (int)shade_culls);
     const TileDesc& td = shade_args.td;
     if (h->dbg)
         std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"),
