@@ -32,8 +32,8 @@ HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include
 # test-only library of tests/test_shade_cases_cpu.py: part of `all` wherever its source is in the tree
 SHADE_MUTANTS := $(if $(wildcard tests/hostsim/shade_mutants.cpp),shademutants)
 
-.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu variants probe exactcheck nodecheck shadecheck shademutants clean
-all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu cli exactcheck nodecheck shadecheck $(SHADE_MUTANTS)
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu variants probe exactcheck nodecheck shadecheck shademutants clean
+all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu cli exactcheck nodecheck shadecheck $(SHADE_MUTANTS)
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -81,6 +81,10 @@ tests/render_rays/librays_cpu.so: tests/render_rays/rays_cpu.cpp $(HIP_HDR)
 cullcpu: tests/cull/libcull_cpu.so
 tests/cull/libcull_cpu.so: tests/cull/cull_cpu.cpp $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -I$(PKG)/csrc -shared -o $@ tests/cull/cull_cpu.cpp
+# CPU compile of the shadow-queue placement of the render loop (trt_sched.h), for tests only (tests/test_sched_cpu.py)
+schedcpu: tests/sched/libsched_cpu.so
+tests/sched/libsched_cpu.so: tests/sched/sched_cpu.cpp $(PKG)/csrc/trt_sched.h
+	$(CXX) $(CXXFLAGS) -I$(PKG)/csrc -shared -o $@ tests/sched/sched_cpu.cpp
 
 $(OUT)/libtrt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(OUT)
@@ -111,7 +115,7 @@ variants: $(HIP_SRC) $(HIP_HDR)
 	  echo "variant $$name: $$defs"; $(HIPCC) $(HIPFLAGS) $$defs -shared -o $(OUT)/variants/libtrt_hip_$$name.so $(HIP_SRC) || exit 1; done
 
 clean:
-	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/hostsim/libshade_mutants.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/despeckle/libdespeckle_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so tests/cull/libcull_cpu.so
+	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/hostsim/libshade_mutants.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/despeckle/libdespeckle_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so tests/cull/libcull_cpu.so tests/sched/libsched_cpu.so
 	$(MAKE) -C oracle clean
 
 # exhaustive (2^32 inputs) proof that include/trt_exact.h returns the bits of sqrtf / 1.0f / sqrtf: run by tests/test_gpu_parity.py

@@ -22,6 +22,7 @@
 #include "trt.h"
 #include "trt_kernels.h"
 #include "trt_cull.h"
+#include "trt_sched.h"
 #include "trt_wide.h"
 #include "trt_oct_build.h"
 #include "trt_denoise_kernels.h"
@@ -185,6 +186,14 @@ struct trt_handle {
     int fail_at_bounce = -1;                           // TRT_TEST_FAIL_AT_BOUNCE at trt_create: the next render reports an injected failure
                                                        // after issuing that bounce (exercises the error path; consumed once)
     std::vector<hipEvent_t> events;
+    // The shadow walks of bounce b beside closest hits and k_shade of bounce b + 1 (renderCore): a second stream for them and the
+    // events that tie the two — per bounce parity, [0..1] behind k_shade on the pass's stream, [2..3] behind the last shadow launch on this one.
+    // Made once, without timing.  TRT_SHADOW_STREAM=0 at trt_create keeps every kernel of a pass on one stream (A/B, tests).
+    hipStream_t side_stream = nullptr;
+    hipEvent_t side_events[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool shadow_stream = true;
+    bool refracts = false;    // a material with Ni > 1: only then k_shade's queue flavour adds to Lacc past bounce 0 (TRANSMISSION, trt_path.h shadeBegin)
+    bool dbg_sched = false;   // TRT_DEBUG and TRT_DEBUG_SCHEDULE=1 at trt_create: renderCore prints every operation it enqueues (SchedTrace)
     // trt_update_geometry: what trt_create leaves behind for it costs no device memory; the rest is made at the first update and kept
     uint32_t n_materials = 0, n_light_tris = 0, n_tri_trav = 0;
     bool light_boxes_fixed = false;                    // TRT_SHADOW_STOP=0 at trt_create: every light's box is all of space and stays so
@@ -212,6 +221,8 @@ struct trt_handle {
         io_buf.release();
         for (hipEvent_t e : events) (void)hipEventDestroy(e);
         for (hipStream_t st : slot_streams) if (st) (void)hipStreamDestroy(st);
+        for (hipEvent_t e : side_events) if (e) (void)hipEventDestroy(e);
+        if (side_stream) (void)hipStreamDestroy(side_stream);
         if (pinned_counts) (void)hipHostFree(pinned_counts);
     }
 };
@@ -816,6 +827,12 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->spill_words_per_slot = (size_t)spill_levels * SPILL_STRIDE;
     if (int e = h->spill.ensure(h->spill_words_per_slot * 2 * sizeof(uint32_t))) return e;  // one area per concurrent pass
     for (hipStream_t& st : h->slot_streams) HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    HIPC(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : h->side_events) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (const char* e = std::getenv("TRT_SHADOW_STREAM")) h->shadow_stream = std::atoi(e) != 0;
+    for (const MaterialDev& m : im.mats) h->refracts = h->refracts || m.Ni > 1.0f;
+    if (const char* e = std::getenv("TRT_DEBUG_SCHEDULE")) h->dbg_sched = im.dbg && std::atoi(e) != 0;
+    if (im.dbg) std::fprintf(stderr, "trt_create: shadow stream %d\n", (int)h->shadow_stream);
     h->count_rows = countRows(h->sc.n_lights);
     const size_t pinned_words = 2 * (2 * (size_t)h->count_rows + 16);  // per slot: counters + sequence word
     HIPC(hipHostMalloc((void**)&h->pinned_counts, pinned_words * sizeof(uint32_t), hipHostMallocDefault));
@@ -889,6 +906,10 @@ struct PassSlot {
     enum State { IDLE, PACK, PACKWAIT, ISSUE, WAIT, RESOLVE } state = IDLE;  // PACK / PACKWAIT: trt_render_rays only (the caller's rays into the queue)
     uint32_t chunk = 0, s0 = 0, sc_count = 0, n_active = 0, b = 0;
     int cur = 0;
+    // two-ended shadow queues (trt_sched.h): where this bounce's k_shade writes its records, the interval the latest shadow launches read, and
+    // the event behind them while the pass's stream has not yet waited for it
+    uint64_t sq_at = 0, rd_at = 0, rd_n = 0;
+    int side_ev = -1;
 };
 // Path ids of one pass run up to 0x7FFF0000 (the queue lengths of k_shade): one sample of every listed pixel must fit.
 constexpr uint32_t MAX_PASS_PATHS = 0x7FFF0000u;
@@ -1068,21 +1089,23 @@ void addDeviceStats(trt_stats& st, const DeviceStats& ds, const trt_handle* h)
 }
 
 // The drain of a call with work in flight: from arm() on, whatever way the driver is left, nothing may still be running on the caller's
-// stream or the slot streams when it returns (a late kernel or copy of a failed call would write what the NEXT call on the handle uses, or
+// stream, the slot streams or the handle's side stream when it returns (a late kernel or copy of a failed call would write what the NEXT call on the handle uses, or
 // host memory that died with the return).  The destructor synchronises them unless the driver got through and disarmed it.  A driver
 // declares it after every host end of an asynchronous copy, so that it is destroyed before them.  `slots` outlive the drain.
 struct Drain {
     hipStream_t stream;
+    hipStream_t side;  // the handle's side stream (shadow walks of a render): whatever the call was, nothing of the handle's may be left running on it
     PassSlot* slots = nullptr;
     int n_slots = 0;
     bool armed = false;
-    explicit Drain(hipStream_t stream_) : stream(stream_) {}
+    Drain(hipStream_t stream_, const trt_handle* h) : stream(stream_), side(h->side_stream) {}
     Drain(const Drain&) = delete;
     void arm(PassSlot* s = nullptr, int n = 0) { slots = s; n_slots = n; armed = true; }
     ~Drain()
     {
         if (!armed) return;
         for (int k = 0; k < n_slots; ++k) (void)hipStreamSynchronize(slots[k].stream);
+        if (side) (void)hipStreamSynchronize(side);
         (void)hipStreamSynchronize(stream);
         (void)hipGetLastError();
     }
@@ -1100,7 +1123,7 @@ struct CallFrame {
     DeviceStats ds;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_resolved = nullptr;  // events 0/1 bracket the call on the stream, 2 chains renderCore's ordered resolves
     Drain drain;
-    CallFrame(trt_handle* h_, hipStream_t stream_, bool timing) : h(h_), tm{h_, timing}, drain(stream_) {}
+    CallFrame(trt_handle* h_, hipStream_t stream_, bool timing) : h(h_), tm{h_, timing}, drain(stream_, h_) {}
     // the counters: `bytes` from the DeviceStats at `block` on
     int clear(void* block, size_t bytes) { d_stats = (DeviceStats*)block; HIPC(hipMemsetAsync(block, 0, bytes, drain.stream)); return TRT_OK; }
     void arm() { drain.arm(); }
@@ -1198,6 +1221,34 @@ int stageInput(const RenderInput& in, const trt_params* p, void* d_table, size_t
     return TRT_OK;
 }
 
+// The schedule of a render call as data (TRT_DEBUG with TRT_DEBUG_SCHEDULE=1; tests/sched_graph.py reads it): one line per operation the pass
+// loop enqueues — a launch, a memset, a resolve — with its stream (call, slot0, slot1, side), the events that stream was told to wait for since
+// its last operation, the event recorded right behind it, and the half-open element ranges it reads and writes, by buffer.  Formed from the
+// variables the launches use; "-" is the empty list.
+struct SchedTrace {
+    enum { CALL = 0, SLOT0 = 1, SIDE = 3 };
+    bool on = false;
+    std::string pending[4];
+    void wait(int s, const char* ev)
+    {
+        if (!on) return;
+        if (!pending[s].empty()) pending[s] += ',';
+        pending[s] += ev;
+    }
+    static std::string iv(const char* buf, uint64_t lo, uint64_t hi) { return std::string(buf) + "[" + std::to_string(lo) + "," + std::to_string(hi) + ")"; }
+    static std::string iv(const char* buf, uint32_t k, uint64_t lo, uint64_t hi) { return iv((std::string(buf) + std::to_string(k)).c_str(), lo, hi); }
+    void op(const char* what, int s, uint32_t pass, int bounce, int light, const char* record, const std::string& reads, const std::string& writes)
+    {
+        if (!on) return;
+        static const char* const names[4] = {"call", "slot0", "slot1", "side"};
+        std::fprintf(stderr, "trt_sched: op=%s pass=%u bounce=%d light=%d stream=%s wait=%s record=%s read=%s write=%s\n", what, pass, bounce, light, names[s],
+                     pending[s].empty() ? "-" : pending[s].c_str(), record ? record : "-", reads.empty() ? "-" : reads.c_str(), writes.empty() ? "-" : writes.c_str());
+        pending[s].clear();
+    }
+};
+const char* const SIDE_EVENT_NAMES[4] = {"shade0", "shade1", "shadow0", "shadow1"};
+inline ShadowQueue queueAt(ShadowQueue q, uint64_t at) { return ShadowQueue{q.sa + at, q.sb + at, q.sw + at}; }
+
 // The render loop behind every render entry: samples [s_begin, s_end) of p->spp of what `in` describes, added in sample order onto
 // its per-pixel sums.  The entry points have checked p and the sample range and made h's device current.
 int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_end, const RenderInput& in, hipStream_t stream, trt_stats* stats_out)
@@ -1279,10 +1330,45 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"),
                      lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds, td.grid_ok);
     if (h->dbg) std::fprintf(stderr, "%s: fused primary %d\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"), (int)fuse);
+    // The shadow walks of bounce b on the handle's side stream, beside closest hits and k_shade of bounce b + 1.  The loop stays
+    // on one stream where per-kernel times or counters are asked for, where k_shade's queue flavour adds to Lacc itself (TRANSMISSION rays: a
+    // material with Ni > 1), where closest-hit and shadow launches share a redo list and a spill area (the per-lane drivers), where k_shade
+    // computes its queue addresses itself (SHADE_MANY), and where two passes mix already.
+    const char* serial_why = nullptr;
+    if (!h->shadow_stream) serial_why = "TRT_SHADOW_STREAM=0";
+    else if (tm.on) serial_why = "TRT_FLAG_TIMING";
+    else if (count) serial_why = "counting render";
+    else if (plan.slots != 1) serial_why = "two passes in flight";
+    else if (nl == 0) serial_why = "no lights";
+    else if (h->refracts) serial_why = "a material with Ni > 1 (k_shade adds to Lacc)";
+    else if (h->trace_impl != 0) serial_why = "per-lane walk (shared redo list and spill area)";
+    else if (lights == SHADE_MANY) serial_why = "SHADE_MANY (queue addresses formed in k_shade)";
+    const bool side = serial_why == nullptr;
+    const hipStream_t side_stream = h->side_stream;
+    if (h->dbg) {
+        const char* entry = in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render");
+        if (side) std::fprintf(stderr, "%s: shadow stream on\n", entry);
+        else std::fprintf(stderr, "%s: shadow stream off: %s\n", entry, serial_why);
+    }
+    SchedTrace tr;
+    tr.on = h->dbg_sched;
+    auto slotOf = [&](const PassSlot& S) { return SchedTrace::SLOT0 + (int)(&S - slots); };
+    // main stream <- event of the side stream behind the pass's latest shadow launches (once: what follows on the stream is ordered behind it too)
+    auto joinSide = [&](PassSlot& S) -> int {
+        if (S.side_ev < 0) return TRT_OK;
+        HIPC(hipStreamWaitEvent(S.stream, h->side_events[S.side_ev], 0));
+        tr.wait(slotOf(S), SIDE_EVENT_NAMES[S.side_ev]);
+        S.side_ev = -1;
+        return TRT_OK;
+    };
 
     if (int e = fr.begin(slots, plan.slots)) return e;
     const hipEvent_t ev_resolved = fr.ev_resolved;
-    for (int k = 0; k < plan.slots; ++k) HIPC(hipStreamWaitEvent(slots[k].stream, fr.ev_begin, 0));
+    if (tr.on) tr.op("clear", SchedTrace::CALL, 0, -1, -1, "begin", "", SchedTrace::iv("stats", 0, 1) + "," + SchedTrace::iv("sum", 0, npix));
+    for (int k = 0; k < plan.slots; ++k) {
+        HIPC(hipStreamWaitEvent(slots[k].stream, fr.ev_begin, 0));
+        tr.wait(SchedTrace::SLOT0 + k, "begin");
+    }
 
     uint32_t next_chunk = 0, resolved_upto = 0;
     auto startPass = [&](PassSlot& S) -> int {
@@ -1293,7 +1379,10 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         S.n_active = npix * S.sc_count;
         S.b = 0;
         S.cur = 0;
+        S.rd_n = 0;
+        // (the side stream's launches of the slot's previous pass: its resolve, earlier on this stream, has waited for them)
         HIPC(hipMemsetAsync(S.d_counts, 0, counts_bytes, S.stream));
+        if (tr.on) tr.op("memset", slotOf(S), S.chunk, -1, -1, nullptr, "", SchedTrace::iv("d_counts", 0, COUNT_STRIDE));
         if (!in.rays) st.rays_camera += S.n_active;  // bounce 0 generates its camera rays inside the traversal and shade kernels
         S.state = in.rays ? PassSlot::PACK : PassSlot::ISSUE;
         return TRT_OK;
@@ -1313,6 +1402,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
             hipLaunchKernelGGL(k_rays_pack, dim3(std::min<uint32_t>((S.n_active + 255) / 256, 65536u)), dim3(256), 0, S.stream, org, dir, S.n_active, S.Q[0], S.Lacc,
                                (uint32_t*)packed);
         });
+        if (tr.on) tr.op("pack", slotOf(S), S.chunk, -1, -1, nullptr, "", SchedTrace::iv("Q", 0, 0, S.n_active) + "," + SchedTrace::iv("Lacc", 0, S.n_active));
         S.seq++;
         hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(64), 0, S.stream, S.d_counts, COUNT_STRIDE, 0u, 1u, packed, (volatile uint32_t*)S.host_counts, 2u * count_rows, S.seq);
         S.state = PassSlot::PACKWAIT;
@@ -1332,10 +1422,29 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         const RaySource src{S.Q[S.cur].ra, S.Q[S.cur].rb, td, S.s0};
         const bool generated = S.b == 0 && !in.rays;  // the rays of bounce 0 come from the camera, not from the queue
         const bool fused = fuse && generated;         // ... and k_shade traces them itself
-        if (!fused)
+        const int ts = slotOf(S);
+        if (!fused) {
             tm.launch(TRT_K_TRACE_CLOSEST, S.stream, st, [&] {
                 launchTraceClosest(h, generated ? camera_k : queue_k, generated ? camera_fix : queue_fix, S.stream, S.spill, src, S.hit, S.n_active, d_stats, S.redo);
             });
+            if (tr.on) tr.op("closest", ts, S.chunk, (int)S.b, -1, nullptr, generated ? std::string() : SchedTrace::iv("Q", (uint32_t)S.cur, 0, S.n_active), SchedTrace::iv("hit", 0, S.n_active));
+        }
+        // Where this bounce's shadow records go (trt_sched.h).  On the side route k_shade is ordered behind the shadow walks of bounce b - 2, which
+        // read the end it now writes (long through, as a rule), and behind those of bounce b - 1 only where their records reach into its interval.
+        S.sq_at = 0;
+        if (side) {
+            const ShadowPlace place = shadowPlace(plan.N, S.b, S.rd_at, S.rd_n, S.n_active);
+            S.sq_at = place.at;
+            if (S.b >= 2) {
+                HIPC(hipStreamWaitEvent(S.stream, h->side_events[2 + (S.b & 1u)], 0));
+                tr.wait(ts, SIDE_EVENT_NAMES[2 + (S.b & 1u)]);
+            }
+            if (place.wait) {
+                HIPC(hipStreamWaitEvent(S.stream, h->side_events[2 + ((S.b - 1u) & 1u)], 0));
+                tr.wait(ts, SIDE_EVENT_NAMES[2 + ((S.b - 1u) & 1u)]);
+                S.side_ev = -1;  // everything on the side stream so far
+            }
+        }
         ShadeArgs A = shade_args;
         A.qin = S.Q[S.cur];
         A.hit = S.hit;
@@ -1343,7 +1452,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         A.qout = S.Q[S.cur ^ 1];
         if (lights == SHADE_MANY) A.sq_arena = S.shadow;
         else
-            for (uint32_t l = 0; l < (uint32_t)TRT_MAX_LIGHTS; ++l) A.sq[l] = l < nl ? S.shadow.queue(l) : ShadowQueue{nullptr, nullptr, nullptr};
+            for (uint32_t l = 0; l < (uint32_t)TRT_MAX_LIGHTS; ++l) A.sq[l] = l < nl ? queueAt(S.shadow.queue(l), S.sq_at) : ShadowQueue{nullptr, nullptr, nullptr};
         A.pair_count = pairCounter(S.d_counts, count_rows, S.b);
         A.shadow_counts = S.d_counts + (size_t)COUNT_STRIDE + S.b;  // light l: + l * COUNT_STRIDE
         A.Lacc = S.Lacc;
@@ -1353,11 +1462,22 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
             hipLaunchKernelGGL(fused ? fusedShadeKernel() : shade_k, dim3(std::min<uint32_t>((S.n_active + shade_block - 1) / shade_block, 65536u)), dim3(shade_block),
                                h->shade_pad_lds, S.stream, h->sc, A);
         });
+        if (side) HIPC(hipEventRecord(h->side_events[S.b & 1u], S.stream));  // what this bounce's shadow launches wait for
+        if (tr.on) {
+            std::string rd = fused ? std::string() : SchedTrace::iv("hit", 0, S.n_active), wr = SchedTrace::iv("Q", (uint32_t)(S.cur ^ 1), 0, S.n_active);
+            if (!generated) rd += std::string(rd.empty() ? "" : ",") + SchedTrace::iv("Q", (uint32_t)S.cur, 0, S.n_active);
+            for (uint32_t l = 0; l < nl; ++l) wr += "," + SchedTrace::iv("shadow", l, S.sq_at, S.sq_at + S.n_active);
+            wr += "," + SchedTrace::iv("d_counts", S.b, S.b + 1u);
+            // Lacc: bounce 0 initialises it (caller-supplied rays: adds to the zeroes of k_rays_pack); later bounces add to it only for TRANSMISSION rays
+            if (S.b == 0 || h->refracts) wr += "," + SchedTrace::iv("Lacc", 0, (uint64_t)npix * S.sc_count);
+            tr.op("shade", ts, S.chunk, (int)S.b, -1, side ? SIDE_EVENT_NAMES[S.b & 1u] : nullptr, rd, wr);
+        }
         // (b, c) and (b + 1, c) of the counters in use -> host_counts[2 * c], [2 * c + 1], then the sequence word
         S.seq++;
         const uint32_t publish_block = std::min(1024u, (2u * (1u + nl) + 63u) & ~63u);
         hipLaunchKernelGGL(k_publish_counts, dim3(1), dim3(publish_block), 0, S.stream, S.d_counts, COUNT_STRIDE, S.b, 1u + nl,
                            pairCounter(S.d_counts, count_rows, S.b), (volatile uint32_t*)S.host_counts, 2u * count_rows, S.seq);
+        if (tr.on) tr.op("publish", ts, S.chunk, (int)S.b, -1, nullptr, SchedTrace::iv("d_counts", S.b, S.b + 2u), "");
         S.state = PassSlot::WAIT;
         if (h->fail_at_bounce >= 0 && (int)S.b == h->fail_at_bounce) {  // test hook: fail with this bounce's kernels in flight
             h->fail_at_bounce = -1;
@@ -1368,14 +1488,38 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     // queue lengths are back: shadow rays of this bounce, then the next bounce / the tail / the end of the pass
     auto completeBounce = [&](PassSlot& S) -> int {
         if (int e = awaitCounts(S, count_rows)) return e;
+        // on the side route: behind this bounce's k_shade by its event, behind the shadow launches of every earlier bounce by the stream's order,
+        // light after light — the order of the additions into a path's Lacc is the one stream's
+        const hipStream_t shadow_stream = side ? side_stream : S.stream;
+        const int ss = side ? (int)SchedTrace::SIDE : slotOf(S);
+        uint32_t ns_max = 0, l_last = nl;
         for (uint32_t l = 0; l < nl; ++l) {
             const uint32_t ns = S.host_counts[2 * (1 + l)];
             if (ns > S.n_active) return fail(TRT_EHIP, "internal error: shadow queue longer than its input");
+            ns_max = std::max(ns_max, ns);
+            if (ns) l_last = l;
+        }
+        if (side) {
+            HIPC(hipStreamWaitEvent(side_stream, h->side_events[S.b & 1u], 0));
+            tr.wait(ss, SIDE_EVENT_NAMES[S.b & 1u]);
+        }
+        for (uint32_t l = 0; l < nl; ++l) {
+            const uint32_t ns = S.host_counts[2 * (1 + l)];
             if (!ns) continue;
-            tm.launch(TRT_K_TRACE_SHADOW, S.stream, st, [&] {
-                launchTraceShadow(h, shadow_k, shadow_fix, S.stream, S.spill, S.shadow.queue(l), ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee, S.redo, h->light_boxes[l]);
+            tm.launch(TRT_K_TRACE_SHADOW, shadow_stream, st, [&] {
+                launchTraceShadow(h, shadow_k, shadow_fix, shadow_stream, S.spill, queueAt(S.shadow.queue(l), S.sq_at), ns, h->light_mats[l], S.Lacc, d_stats, td.fixed_nee,
+                                  S.redo, h->light_boxes[l]);
             });
+            if (side && l == l_last) HIPC(hipEventRecord(h->side_events[2 + (S.b & 1u)], side_stream));
+            if (tr.on)
+                tr.op("shadow", ss, S.chunk, (int)S.b, (int)l, side && l == l_last ? SIDE_EVENT_NAMES[2 + (S.b & 1u)] : nullptr,
+                      SchedTrace::iv("shadow", l, S.sq_at, S.sq_at + ns) + "," + SchedTrace::iv("Lacc", 0, (uint64_t)npix * S.sc_count), SchedTrace::iv("Lacc", 0, (uint64_t)npix * S.sc_count));
             st.rays_shadow += ns;
+        }
+        if (side) {
+            if (l_last != nl) S.side_ev = 2 + (int)(S.b & 1u);  // (a bounce without shadow rays leaves the event of the latest launches in place)
+            S.rd_at = S.sq_at;
+            S.rd_n = ns_max;
         }
         const uint32_t n_next = S.host_counts[1];
         if (n_next > S.n_active) return fail(TRT_EHIP, "internal error: queue grew");
@@ -1386,7 +1530,11 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         if (S.n_active > 0 && (S.n_active <= h->tail_n || S.b >= MAX_BOUNCES)) {
             // few paths left: finish them in one launch (k_tail) instead of ~3 launches + a host round trip per bounce
             const TailArgs TA{S.Q[S.cur], S.n_active, S.Lacc, td, S.s0, p->max_depth, S.spill, SPILL_STRIDE, h->trace_impl == 0 ? 1u : 0u, d_stats};
+            if (int e = joinSide(S)) return e;  // k_tail reads and adds to Lacc: behind every shadow launch of the pass
             tm.launch(TRT_K_TAIL, S.stream, st, [&] { hipLaunchKernelGGL(tail_k, dim3(tailGrid(S.n_active)), dim3(TRT_TRACE_BLOCK), 0, S.stream, h->sc, TA); });
+            if (tr.on)
+                tr.op("tail", slotOf(S), S.chunk, (int)S.b, -1, nullptr, SchedTrace::iv("Q", (uint32_t)S.cur, 0, S.n_active) + "," + SchedTrace::iv("Lacc", 0, (uint64_t)npix * S.sc_count),
+                      SchedTrace::iv("Lacc", 0, (uint64_t)npix * S.sc_count));
             S.n_active = 0;
         }
         S.state = S.n_active ? PassSlot::ISSUE : PassSlot::RESOLVE;
@@ -1395,7 +1543,12 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     // per-pixel accumulation in sample order: pass c is resolved only after pass c-1 (on whichever stream that ran)
     auto tryResolve = [&](PassSlot& S) -> int {
         if (S.chunk != resolved_upto) return TRT_OK;  // an earlier pass is still in flight on the other slot
-        if (resolved_upto > 0) HIPC(hipStreamWaitEvent(S.stream, ev_resolved, 0));  // recorded by the previous resolve, earlier in host order
+        if (resolved_upto > 0) {  // recorded by the previous resolve, earlier in host order
+            HIPC(hipStreamWaitEvent(S.stream, ev_resolved, 0));
+            tr.wait(slotOf(S), "resolved");
+        }
+        // the resolve reads Lacc, and the slot's next pass overwrites Lacc and the shadow queues: behind every shadow launch of this pass
+        if (int e = joinSide(S)) return e;
         tm.launch(TRT_K_RESOLVE, S.stream, st, [&] {
             const dim3 rg(std::min<uint32_t>((npix + 255) / 256, 65536u)), rb(256);
             if (d_sq) hipLaunchKernelGGL(k_resolve_moments, rg, rb, 0, S.stream, S.Lacc, d_sum, d_sq, npix, S.sc_count, (float)p->spp);
@@ -1403,6 +1556,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
             else hipLaunchKernelGGL(k_resolve, rg, rb, 0, S.stream, S.Lacc, d_sum, npix, S.sc_count, (float)p->spp);
         });
         HIPC(hipEventRecord(ev_resolved, S.stream));
+        if (tr.on) tr.op("resolve", slotOf(S), S.chunk, -1, -1, "resolved", SchedTrace::iv("Lacc", 0, (uint64_t)npix * S.sc_count) + "," + SchedTrace::iv("sum", 0, npix), SchedTrace::iv("sum", 0, npix));
         resolved_upto++;
         return startPass(S);
     };
@@ -1428,11 +1582,13 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     if (resolved_upto != plan.n_chunks) return fail(TRT_EHIP, "internal error: passes left unresolved");
 
     HIPC(hipStreamWaitEvent(stream, ev_resolved, 0));
+    tr.wait(SchedTrace::CALL, "resolved");
     if (in.out_dev) {
         tm.begin(TRT_K_RESOLVE, stream);
         hipLaunchKernelGGL(k_finalize, dim3(std::min<uint32_t>((npix * 3 + 255) / 256, 65536u)), dim3(256), 0, stream, d_sum, in.out_dev, npix * 3);
         tm.end(stream);
     }
+    if (tr.on) tr.op(in.out_dev ? "finalize" : "readback", SchedTrace::CALL, 0, -1, -1, nullptr, SchedTrace::iv("sum", 0, npix) + "," + SchedTrace::iv("stats", 0, 1), "");
     st.rows_rendered = in.rows.size();  // 0 for a pixel list
     if (int e = fr.readBack()) return e;
     if (in.host && in.sum) {
@@ -2964,7 +3120,7 @@ int updateGeometry(trt_handle* h, const trt_geometry_update* u, uint32_t n_tris,
     if (int e = updateLightTables(h, u, w, H)) return e;
     EventBracket& B = h->refit.bracket;
     if (int e = B.create()) return e;
-    Drain drain(stream);
+    Drain drain(stream, h);
     drain.arm();
     if (int e = B.record(0, stream)) return e;
     if (int e = refitPrepare(h, stream, H)) return e;
