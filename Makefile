@@ -32,8 +32,8 @@ HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include
 # test-only library of tests/test_shade_cases_cpu.py: part of `all` wherever its source is in the tree
 SHADE_MUTANTS := $(if $(wildcard tests/hostsim/shade_mutants.cpp),shademutants)
 
-.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu variants probe exactcheck nodecheck shadecheck shademutants clean
-all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu cli exactcheck nodecheck shadecheck $(SHADE_MUTANTS)
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu onelightcpu variants probe exactcheck nodecheck shadecheck shademutants clean
+all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu onelightcpu cli exactcheck nodecheck shadecheck $(SHADE_MUTANTS)
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -85,6 +85,10 @@ tests/cull/libcull_cpu.so: tests/cull/cull_cpu.cpp $(HIP_HDR)
 schedcpu: tests/sched/libsched_cpu.so
 tests/sched/libsched_cpu.so: tests/sched/sched_cpu.cpp $(PKG)/csrc/trt_sched.h
 	$(CXX) $(CXXFLAGS) -I$(PKG)/csrc -shared -o $@ tests/sched/sched_cpu.cpp
+# CPU build of TRT_FLAG_ONE_LIGHT: hostsim_render's loop with the light loop replaced by lightPick -> lightSample -> occlusion test, for tests only (tests/test_*one_light*.py)
+onelightcpu: tests/onelight/libonelight_cpu.so
+tests/onelight/libonelight_cpu.so: tests/onelight/onelight_cpu.cpp tests/hostsim/hostsim.cpp $(wildcard tests/hostsim/*.h) $(wildcard tests/refit/*.h) tools/shade_cases.h $(HIP_HDR)
+	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/onelight/onelight_cpu.cpp
 
 $(OUT)/libtrt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(OUT)
@@ -108,14 +112,14 @@ $(OUT)/tinyrt: $(PKG)/host/main.cpp $(PKG)/host/render.cpp $(HOST_HDR) include/t
 # name=defines, "+" separating the -D options
 # (round 4's k_shade occupancy arms — block sizes 256 / 512 / 640 / 768 at 4, 5 and 6 waves per SIMD — are on record in profiles/r04_ab_shade_tail.txt; what
 # won is in the default build: TRT_SHADE1_* / TRT_SHADEN_* in trt_kernels.h.  shade_old = round 3's configuration for the A/B.)
-VARIANTS := w8=-DTRT_TRACE_MINWAVES=8 nt0=-DTRT_NT=0 nt15=-DTRT_NT=15 shade_old=-DTRT_SHADE1_BLOCK=512+-DTRT_SHADE1_WAVES=4+-DTRT_SHADEN_BLOCK=512+-DTRT_SHADEN_WAVES=4
+VARIANTS := w8=-DTRT_TRACE_MINWAVES=8 nt0=-DTRT_NT=0 nt15=-DTRT_NT=15 shade_old=-DTRT_SHADE1_BLOCK=512+-DTRT_SHADE1_WAVES=4+-DTRT_SHADEN_BLOCK=512+-DTRT_SHADEN_WAVES=4 shadep256=-DTRT_SHADEP_BLOCK=256+-DTRT_SHADEP_WAVES=5
 variants: $(HIP_SRC) $(HIP_HDR)
 	@mkdir -p $(OUT)/variants
 	@for v in $(VARIANTS); do name=$${v%%=*}; defs=$$(echo "$${v#*=}" | tr '+' ' '); \
 	  echo "variant $$name: $$defs"; $(HIPCC) $(HIPFLAGS) $$defs -shared -o $(OUT)/variants/libtrt_hip_$$name.so $(HIP_SRC) || exit 1; done
 
 clean:
-	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/hostsim/libshade_mutants.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/despeckle/libdespeckle_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so tests/cull/libcull_cpu.so tests/sched/libsched_cpu.so
+	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/hostsim/libshade_mutants.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/despeckle/libdespeckle_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so tests/cull/libcull_cpu.so tests/sched/libsched_cpu.so tests/onelight/libonelight_cpu.so
 	$(MAKE) -C oracle clean
 
 # exhaustive (2^32 inputs) proof that include/trt_exact.h returns the bits of sqrtf / 1.0f / sqrtf: run by tests/test_gpu_parity.py

@@ -90,7 +90,8 @@ typedef struct trt_material {
  * (pathTracing.cpp:11) and the direct term (pathTracing.cpp:65) read materials[mat].radiance, and so does this library.
  * A scene may have 0 to TRT_MAX_SCENE_LIGHTS lights (trt_create refuses more with TRT_EINVAL).  Every light adds a 48-B shadow-ray
  * record per path to the queue memory of a pass (trt_params::mem_budget: 132 + 48 * n_lights bytes per path), 16 KiB of
- * counters per pass slot, and one shadow-ray launch per bounce. */
+ * counters per pass slot, and one shadow-ray launch per bounce.  With TRT_FLAG_ONE_LIGHT a render has one such record and one
+ * such launch whatever the light count (132 + 48 bytes per path). */
 #define TRT_MAX_SCENE_LIGHTS 65535u
 typedef struct trt_light {
     int32_t mat;          /* material id of mtlname */
@@ -168,6 +169,23 @@ typedef struct trt_scene {
                                   * multiplies by (pathTracing.cpp:91-93, quirk Q8).  With it the HIP path reproduces staircase/image256.png to its noise floor
                                   * (profiles/r04_staircase_residual.txt); scenes whose glossy materials have Kd = Ks (veach-mis) or none (back) do not change.
                                   * Off = parity with the committed source. */
+#define TRT_FLAG_ONE_LIGHT 128u /* stochastic light selection: every shaded path vertex samples ONE light, picked with probability proportional to its power, instead of
+                                  * every light (pathTracing.cpp:34), and divides by that probability — unbiased, and a scene of any light count then has the shadow
+                                  * rays, the launches and the path memory of a one-light scene.
+                                  *   Needs TRT_FLAG_FIXED_NEE (rays aimed at different lights share one queue because the occlusion test needs no light material):
+                                  *   TRT_FLAG_ONE_LIGHT without TRT_FLAG_FIXED_NEE is TRT_EINVAL, the handle stays usable.  Honoured by the entries that trace full
+                                  *   paths (trt_render, _device, _samples, trt_render_pixels*, trt_render_rays*, trt_group_render*); the AOV and ray-query entries
+                                  *   ignore it.  Off = every other mode, bit for bit.
+                                  *   Weights: w_l = area_l * lum(radiance_l), lum = (0.2126 r + 0.7152 g) + 0.0722 b in fp32, radiance the light MATERIAL's;
+                                  *   w_l = 0 unless area and luminance are both finite and > 0.  cdf_l = cdf_{l-1} + w_l in fp32, index order.
+                                  *   Draw: one uniform u of the path's stream BEFORE the draws of the light sample; r = u * cdf_{L-1}; the pick is the first l with
+                                  *   r < cdf_l (none by rounding: the last l with w_l > 0); the sample's contribution is multiplied by inv_p = cdf_{L-1} / w_l
+                                  *   (one fp32 division, applied to the three components before the product with the path throughput).  cdf_{L-1} zero or not
+                                  *   finite: the draw is spent, no light is sampled at the vertex.  The probability realised differs from w_l / sum(w) by the
+                                  *   rounding of the fp32 prefix sums, about 1e-7 relative: that is the estimator's bias.
+                                  *   Fewer than 2 lights: the flag does nothing, no draw is taken (TRT_FLAG_FIXED_NEE's render bit for bit).
+                                  *   Path memory: 132 + 48 bytes per path and sample whatever the light count (trt_params::mem_budget).  trt_stats::rays_shadow
+                                  *   counts what is traced: at most one ray per shaded vertex. */
 
 typedef struct trt_params {
     int32_t width, height;   /* full image size (scene.img_width/height, scene.cpp:13-14) */
@@ -181,7 +199,7 @@ typedef struct trt_params {
     int32_t row_block, row_mod, row_rem;
     int32_t max_depth;       /* 0 = unbounded like the reference (pathTracing.cpp:78-99) */
     uint32_t flags;
-    uint64_t mem_budget;     /* bytes of HBM for path/queue state (132 + 48 * n_lights per path and sample in a pass); 0 = three quarters of
+    uint64_t mem_budget;     /* bytes of HBM for path/queue state (132 + 48 * n_lights per path and sample in a pass; 132 + 48 under TRT_FLAG_ONE_LIGHT, whatever the light count); 0 = three quarters of
                               * what is free (one pass when it fits); too small for one sample of every pixel of the tile: TRT_ENOMEM */
 } trt_params;
 

@@ -362,6 +362,13 @@ int checkParams(const trt_handle* h, const trt_params* p)
     if ((uint64_t)p->width * (uint64_t)p->height > 0xFFFFFFFFull) return fail(TRT_EINVAL, "image too large");
     return TRT_OK;
 }
+// The estimator flags of the entries that trace full paths (the AOV and ray-query entries ignore them)
+int checkEstimator(const trt_params* p)
+{
+    if ((p->flags & TRT_FLAG_ONE_LIGHT) && !(p->flags & TRT_FLAG_FIXED_NEE))
+        return fail(TRT_EINVAL, "TRT_FLAG_ONE_LIGHT needs TRT_FLAG_FIXED_NEE (rays to different lights share one queue of occlusion tests)");
+    return TRT_OK;
+}
 
 bool rowSelected(const trt_params* p, int y) { return p->row_mod <= 1 || ((y / p->row_block) % p->row_mod) == p->row_rem; }
 
@@ -478,19 +485,24 @@ ShadeKernel fusedShadeKernel() { return k_shade<31u, SHADE_ONE, false, TRT_SHADE
 ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list, bool hit8)
 {
     if (hit8) {  // trt_create sets hit8 only with tabs == 31
-        const ShadeKernel s[2][3] = {
+        const ShadeKernel s[2][4] = {
             {k_shade<31u, SHADE_ONE, false, TRT_SHADE1_BLOCK, TRT_SHADE1_WAVES, true>, k_shade<31u, SHADE_FEW, false, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>,
-             k_shade<31u, SHADE_MANY, false, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>},
+             k_shade<31u, SHADE_MANY, false, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>, k_shade<31u, SHADE_PICK, false, TRT_SHADEP_BLOCK, TRT_SHADEP_WAVES, true>},
             {k_shade<31u, SHADE_ONE, true, TRT_SHADE1_BLOCK, TRT_SHADE1_WAVES, true>, k_shade<31u, SHADE_FEW, true, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>,
-             k_shade<31u, SHADE_MANY, true, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>}};
+             k_shade<31u, SHADE_MANY, true, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>, k_shade<31u, SHADE_PICK, true, TRT_SHADEP_BLOCK, TRT_SHADEP_WAVES, true>}};
         return s[list][lights];
     }
-    const ShadeKernel k[5][2][3] = {
-        {{k_shade<31u, SHADE_ONE>, k_shade<31u, SHADE_FEW>, k_shade<31u, SHADE_MANY>}, {k_shade<31u, SHADE_ONE, true>, k_shade<31u, SHADE_FEW, true>, k_shade<31u, SHADE_MANY, true>}},
-        {{k_shade<15u, SHADE_ONE>, k_shade<15u, SHADE_FEW>, k_shade<15u, SHADE_MANY>}, {k_shade<15u, SHADE_ONE, true>, k_shade<15u, SHADE_FEW, true>, k_shade<15u, SHADE_MANY, true>}},
-        {{k_shade<7u, SHADE_ONE>, k_shade<7u, SHADE_FEW>, k_shade<7u, SHADE_MANY>}, {k_shade<7u, SHADE_ONE, true>, k_shade<7u, SHADE_FEW, true>, k_shade<7u, SHADE_MANY, true>}},
-        {{k_shade<3u, SHADE_ONE>, k_shade<3u, SHADE_FEW>, k_shade<3u, SHADE_MANY>}, {k_shade<3u, SHADE_ONE, true>, k_shade<3u, SHADE_FEW, true>, k_shade<3u, SHADE_MANY, true>}},
-        {{k_shade<0u, SHADE_ONE>, k_shade<0u, SHADE_FEW>, k_shade<0u, SHADE_MANY>}, {k_shade<0u, SHADE_ONE, true>, k_shade<0u, SHADE_FEW, true>, k_shade<0u, SHADE_MANY, true>}}};
+    const ShadeKernel k[5][2][4] = {
+        {{k_shade<31u, SHADE_ONE>, k_shade<31u, SHADE_FEW>, k_shade<31u, SHADE_MANY>, k_shade<31u, SHADE_PICK>},
+         {k_shade<31u, SHADE_ONE, true>, k_shade<31u, SHADE_FEW, true>, k_shade<31u, SHADE_MANY, true>, k_shade<31u, SHADE_PICK, true>}},
+        {{k_shade<15u, SHADE_ONE>, k_shade<15u, SHADE_FEW>, k_shade<15u, SHADE_MANY>, k_shade<15u, SHADE_PICK>},
+         {k_shade<15u, SHADE_ONE, true>, k_shade<15u, SHADE_FEW, true>, k_shade<15u, SHADE_MANY, true>, k_shade<15u, SHADE_PICK, true>}},
+        {{k_shade<7u, SHADE_ONE>, k_shade<7u, SHADE_FEW>, k_shade<7u, SHADE_MANY>, k_shade<7u, SHADE_PICK>},
+         {k_shade<7u, SHADE_ONE, true>, k_shade<7u, SHADE_FEW, true>, k_shade<7u, SHADE_MANY, true>, k_shade<7u, SHADE_PICK, true>}},
+        {{k_shade<3u, SHADE_ONE>, k_shade<3u, SHADE_FEW>, k_shade<3u, SHADE_MANY>, k_shade<3u, SHADE_PICK>},
+         {k_shade<3u, SHADE_ONE, true>, k_shade<3u, SHADE_FEW, true>, k_shade<3u, SHADE_MANY, true>, k_shade<3u, SHADE_PICK, true>}},
+        {{k_shade<0u, SHADE_ONE>, k_shade<0u, SHADE_FEW>, k_shade<0u, SHADE_MANY>, k_shade<0u, SHADE_PICK>},
+         {k_shade<0u, SHADE_ONE, true>, k_shade<0u, SHADE_FEW, true>, k_shade<0u, SHADE_MANY, true>, k_shade<0u, SHADE_PICK, true>}}};
     return k[tabs == 31u ? 0 : (tabs == 15u ? 1 : (tabs == 7u ? 2 : (tabs == 3u ? 3 : 4)))][list][lights];
 }
 // (named in this order: named the other way round, k_tail<true, true> / <false, false> build 1 instruction shorter / longer, tools/isa_diff.py)
@@ -539,6 +551,7 @@ struct SceneImage {
     std::vector<LightBox> light_boxes;
     std::vector<MaterialDev> mats;
     std::vector<LightDev> lights;
+    std::vector<float> light_sel;
     std::vector<LightTriDev> ltris;
     std::vector<float> cum;
     bool cum_monotone = true;
@@ -648,6 +661,8 @@ int buildSceneImage(const trt_scene* s, SceneImage& im)
     for (uint32_t i = 0; i < s->n_materials; ++i) im.mats[i] = makeMaterialDev(s->materials[i]);
     im.lights.resize(s->n_lights);
     for (uint32_t i = 0; i < s->n_lights; ++i) im.lights[i] = makeLightDev(s->lights[i], s->materials);
+    im.light_sel.resize(s->n_lights);  // TRT_FLAG_ONE_LIGHT: the running sums of the selection weights (lightPick, trt_path.h)
+    lightSelTable(im.lights.data(), s->n_lights, im.light_sel.data());
     im.ltris.resize(s->n_light_tris);
     for (uint32_t i = 0; i < s->n_light_tris; ++i) im.ltris[i] = makeLightTriDev(s->light_tris[i]);
     // packed CDF for the bisection in lightSample; only when every light's CDF is non-decreasing and NaN-free
@@ -757,6 +772,9 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->sc.light_cum = nullptr;
     if (im.cum_monotone)
         if (int e = upload(h.get(), im.cum.data(), im.cum.size(), &h->sc.light_cum)) return e;
+    h->sc.light_sel = nullptr;  // (fewer than two lights: nothing is ever picked)
+    if (s->n_lights >= 2)
+        if (int e = upload(h.get(), im.light_sel.data(), im.light_sel.size(), &h->sc.light_sel)) return e;
     if (int e = upload(h.get(), im.tex.data(), im.tex.size(), &h->sc.textures)) return e;
     if (int e = upload(h.get(), im.tex_bytes.data(), im.tex_bytes.size(), &h->sc.tex_bytes)) return e;
     lap("uploads");
@@ -844,7 +862,7 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
         // more than 64 KiB per block needs the opt-in; a refusal shows as a launch error, not as a silent no-op
         for (uint32_t tabs : {31u, 15u, 7u, 3u, 0u})
             for (bool list : {false, true})
-                for (int lights : {SHADE_ONE, SHADE_FEW, SHADE_MANY})
+                for (int lights : {SHADE_ONE, SHADE_FEW, SHADE_MANY, SHADE_PICK})
                     for (bool hit8 : {false, true})
                         if (!hit8 || tabs == 31u)
                             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shadeKernel(tabs, lights, list, hit8)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
@@ -968,10 +986,14 @@ struct Footprint {
     int max_slots;                             // passes in flight at once
     uint64_t per_path;                         // bytes of arena per path
     size_t (*bytes)(uint64_t N, uint32_t nl);  // the arena of a pass of N paths
+    const char* stated;                        // the figure as include/trt.h states it (TRT_ENOMEM's text)
 };
-Footprint renderFootprint(uint32_t nl) { return Footprint{N_SLOTS, SlotLayout::bytesPerPath(nl), SlotLayout::bytes}; }
-Footprint aovFootprint() { return Footprint{1, AovLayout::bytes_per_path, AovLayout::bytes}; }
-Footprint aovRaysFootprint() { return Footprint{1, AovRaysLayout::bytes_per_path, AovRaysLayout::bytes}; }
+Footprint renderFootprint(uint32_t nl)
+{
+    return Footprint{N_SLOTS, SlotLayout::bytesPerPath(nl), SlotLayout::bytes, "132 + 48 * n_lights bytes per path, 132 + 48 with TRT_FLAG_ONE_LIGHT"};
+}
+Footprint aovFootprint() { return Footprint{1, AovLayout::bytes_per_path, AovLayout::bytes, "20 bytes per path"}; }
+Footprint aovRaysFootprint() { return Footprint{1, AovRaysLayout::bytes_per_path, AovRaysLayout::bytes, "52 bytes per path"}; }
 bool planPasses(uint32_t npix, uint32_t n_samples, uint32_t nl, uint64_t budget, int slots_wanted, const Footprint& fp, PassPlan& pl)
 {
     const uint64_t cap_paths = std::min<uint64_t>(budget / fp.per_path, MAX_PASS_PATHS);
@@ -1018,6 +1040,9 @@ struct RenderInput {
     float* out_dev = nullptr;
 };
 
+// TRT_FLAG_ONE_LIGHT takes effect on scenes of two or more lights (include/trt.h): the call then has ONE shadow queue whatever the light count
+inline bool picksOneLight(const trt_handle* h, const trt_params* p) { return (p->flags & TRT_FLAG_ONE_LIGHT) != 0 && h->sc.n_lights >= 2u; }
+
 // The arguments of k_shade that every bounce of a render call shares, its TileDesc among them (d_table: the row table or the list on the device)
 ShadeArgs shadeArgsOf(const trt_handle* h, const trt_params* p, const RenderInput& in, const void* d_table, uint32_t rows_lds, DeviceStats* d_stats)
 {
@@ -1035,6 +1060,7 @@ ShadeArgs shadeArgsOf(const trt_handle* h, const trt_params* p, const RenderInpu
     td.fixed_pixels = (p->flags & TRT_FLAG_FIXED_PIXELS) ? 1u : 0u;
     td.ray_offset = (p->flags & TRT_FLAG_RAY_OFFSET) ? 1u : 0u;
     td.specular_ks = (p->flags & TRT_FLAG_SPECULAR_KS) ? 1u : 0u;
+    td.one_light = picksOneLight(h, p) ? 1u : 0u;
     td.npix_magic = magicOf(in.npix);
     td.tile_w_magic = magicOf((uint32_t)td.tile_w);
     td.grid_ok = (p->width >= 2 && p->height >= 2 && p->width <= 65536 && p->height <= 65536) ? 1u : 0u;
@@ -1178,9 +1204,9 @@ int stageRaySlice(const float*& org, const float*& dir, size_t comps, float* sta
 
 // The passes of a render call and the arena for them.  Default budget: three quarters of what is free on the device (the scene is already
 // resident); halved while the arena cannot be had.
-int planArena(trt_handle* h, const trt_params* p, uint32_t npix, uint32_t n_samples, bool list, const Footprint& fp, PassPlan& plan)
+// nl: the shadow queues a path of the call has (its lights; 1 under TRT_FLAG_ONE_LIGHT)
+int planArena(trt_handle* h, const trt_params* p, uint32_t npix, uint32_t n_samples, bool list, const Footprint& fp, uint32_t nl, PassPlan& plan)
 {
-    const uint32_t nl = h->sc.n_lights;
     uint64_t budget = p->mem_budget;
     const bool own_budget = budget == 0;
     if (own_budget) {
@@ -1191,8 +1217,8 @@ int planArena(trt_handle* h, const trt_params* p, uint32_t npix, uint32_t n_samp
     const int n_slots = (fp.max_slots > 1 && n_samples >= 2 && (p->flags & TRT_FLAG_OVERLAP) && h->n_slots > 1) ? N_SLOTS : 1;
     for (;;) {
         if (!planPasses(npix, n_samples, nl, budget, n_slots, fp, plan))
-            return fail(TRT_ENOMEM, list ? "mem_budget too small for one sample of every listed pixel; render shorter lists"
-                                         : "mem_budget too small for one sample of every pixel of the tile; render smaller tiles");
+            return fail(TRT_ENOMEM, std::string(list ? "mem_budget too small for one sample of every listed pixel; render shorter lists"
+                                                     : "mem_budget too small for one sample of every pixel of the tile; render smaller tiles") + " (" + fp.stated + ")");
         const int e = h->arena.ensure(plan.slot_bytes * (size_t)plan.slots);
         if (e == TRT_OK) return TRT_OK;
         if (e != TRT_ENOMEM || !own_budget || budget / 2 < fp.per_path * npix) return e;
@@ -1253,9 +1279,13 @@ inline ShadowQueue queueAt(ShadowQueue q, uint64_t at) { return ShadowQueue{q.sa
 // its per-pixel sums.  The entry points have checked p and the sample range and made h's device current.
 int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_end, const RenderInput& in, hipStream_t stream, trt_stats* stats_out)
 {
-    const uint32_t n_samples = s_end - s_begin, npix = in.npix, nl = h->sc.n_lights, count_rows = h->count_rows;
+    const uint32_t n_samples = s_end - s_begin, npix = in.npix, count_rows = h->count_rows;
+    // nl: the shadow queues of the call — one per light, or the one queue of TRT_FLAG_ONE_LIGHT (rays to whichever light a vertex picked: the occlusion
+    // test of TRT_FLAG_FIXED_NEE needs neither the light's material nor its box, so launch 0's arguments serve them all)
+    const bool pick = picksOneLight(h, p);
+    const uint32_t nl = pick ? 1u : h->sc.n_lights;
     PassPlan plan;
-    if (int e = planArena(h, p, npix, n_samples, in.list, renderFootprint(nl), plan)) return e;
+    if (int e = planArena(h, p, npix, n_samples, in.list, renderFootprint(nl), nl, plan)) return e;
     // ---- small_buf: the row table or the staged pixel list, the counters of each slot, the block cleared first (DeviceStats; per slot the
     // length of its redo list and the blocks of k_trace_fix that are through; the list's maximum), the staged sums and sums of squares
     const size_t counts_bytes = (size_t)COUNT_STRIDE * count_rows * sizeof(uint32_t), acc_bytes = (size_t)npix * 3 * sizeof(double);
@@ -1289,9 +1319,10 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
         S.spill = (uint32_t*)h->spill.p + (size_t)k * h->spill_words_per_slot;
     }
     // k_shade's three flavours (trt_kernels.h): 512-thread blocks at 6 waves per SIMD for one light, 256-thread blocks at 5 for
-    // several; more than TRT_MAX_LIGHTS lights find their queues in the arena instead of in the kernel arguments
-    const int lights = nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY);
-    const uint32_t shade_block = lights == SHADE_ONE ? (uint32_t)TRT_SHADE1_BLOCK : (uint32_t)TRT_SHADEN_BLOCK;
+    // several; more than TRT_MAX_LIGHTS lights find their queues in the arena instead of in the kernel arguments.  The fourth, SHADE_PICK, is
+    // TRT_FLAG_ONE_LIGHT's: one queue as for one light, the light drawn per vertex.
+    const int lights = pick ? SHADE_PICK : (nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY));
+    const uint32_t shade_block = (uint32_t)shadeBlockOf(lights);
     const uint32_t rows_lds = (in.rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)in.rows.size() : 0u;  // 0 for a list
     // the kernels of this call: bounce 0 traces the camera rays of the tile or of the list, later bounces the queue
     const bool count = (p->flags & TRT_FLAG_COUNT) != 0;
@@ -1328,7 +1359,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const TileDesc& td = shade_args.td;
     if (h->dbg)
         std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"),
-                     lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many"), rows_lds, td.grid_ok);
+                     lights == SHADE_PICK ? "pick" : (lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many")), rows_lds, td.grid_ok);
     if (h->dbg) std::fprintf(stderr, "%s: fused primary %d\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"), (int)fuse);
     // The shadow walks of bounce b on the handle's side stream, beside closest hits and k_shade of bounce b + 1.  The loop stays
     // on one stream where per-kernel times or counters are asked for, where k_shade's queue flavour adds to Lacc itself (TRANSMISSION rays: a
@@ -1660,7 +1691,7 @@ int aovCore(trt_handle* h, const trt_params* p, const RenderInput& in, float* co
 {
     const uint32_t npix = in.npix, spp = (uint32_t)p->spp;
     PassPlan plan;
-    if (int e = planArena(h, p, npix, spp, false, aovFootprint(), plan)) return e;
+    if (int e = planArena(h, p, npix, spp, false, aovFootprint(), h->sc.n_lights, plan)) return e;
     // small_buf: the row table, the block cleared first (DeviceStats, the redo list's length and the blocks of k_trace_fix that are through),
     // the sums (albedo, normal: 3 per pixel; depth: 1 per pixel)
     const size_t table_bytes = in.rows.size() * sizeof(int32_t), sum_bytes = (size_t)npix * 7 * sizeof(double);
@@ -1753,7 +1784,7 @@ int aovRays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, co
     hipStream_t stream = host ? nullptr : (hipStream_t)hip_stream;
     const uint32_t n_samples = (uint32_t)(sample_end - sample_begin);
     PassPlan plan;
-    if (int e = planArena(h, p, n, n_samples, true, aovRaysFootprint(), plan)) return e;
+    if (int e = planArena(h, p, n, n_samples, true, aovRaysFootprint(), h->sc.n_lights, plan)) return e;
     // small_buf: the block cleared first (DeviceStats, the redo list's length and the blocks of k_trace_fix that are through, the number of valid
     // entries), then the host entry's sums (albedo, normal: 3 per entry; depth: 1 per entry)
     double* const user[3] = {albedo, normal, depth};
@@ -1824,6 +1855,7 @@ int aovRays(trt_handle* h, const trt_params* p, uint32_t n, const float* org, co
 int trt_render_device(trt_handle* h, const trt_params* p, float* out_dev, void* hip_stream, trt_stats* stats_out)
 {
     if (int e = checkParams(h, p)) return e;
+    if (int e = checkEstimator(p)) return e;
     if (!out_dev) return fail(TRT_EINVAL, "null output buffer");
     return renderTile(h, p, 0u, (uint32_t)p->spp, out_dev, nullptr, hip_stream, stats_out, nullptr);
 }
@@ -1831,6 +1863,7 @@ int trt_render_device(trt_handle* h, const trt_params* p, float* out_dev, void* 
 int trt_render_samples(trt_handle* h, const trt_params* p, int32_t sample_begin, int32_t sample_end, double* accum_host, float* out_host, trt_stats* stats)
 {
     if (int e = checkParams(h, p)) return e;
+    if (int e = checkEstimator(p)) return e;
     if (!accum_host) return fail(TRT_EINVAL, "null accumulator");
     if (sample_begin < 0 || sample_end <= sample_begin || sample_end > p->spp) return fail(TRT_EINVAL, "sample range must satisfy 0 <= begin < end <= spp");
     return renderTile(h, p, (uint32_t)sample_begin, (uint32_t)sample_end, nullptr, out_host, nullptr, stats, accum_host);
@@ -1845,6 +1878,7 @@ int renderPixels(trt_handle* h, const trt_params* p_in, uint32_t n_pixels, const
     if (!h || !p_in) return fail(TRT_EINVAL, "null handle/params");
     const trt_params p = wholeImage(*p_in);
     if (int e = checkParams(h, &p)) return e;
+    if (int e = checkEstimator(&p)) return e;
     bool empty = false;
     if (int e = listCall(sample_begin, sample_end, n_pixels, (n_pixels > 0 && (!pixels || !sum)) ? "null pixel list or sums" : nullptr,
                          "pixel list longer than the path ids of one pass can number (0x7FFF0000)", stats, empty))
@@ -1884,6 +1918,7 @@ int renderRays(trt_handle* h, const trt_params* p_in, uint32_t n, const float* o
     if (!h || !p_in) return fail(TRT_EINVAL, "null handle/params");
     if (p_in->spp < 1) return fail(TRT_EINVAL, "spp must be >= 1");
     if (p_in->max_depth < 0) return fail(TRT_EINVAL, "max_depth must be >= 0");
+    if (int e = checkEstimator(p_in)) return e;
     bool empty = false;
     if (int e = listCall(sample_begin, sample_end, n, (n > 0 && (!org || !dir || !sum)) ? "null ray arrays or sums" : nullptr,
                          "more rays per sample than the path ids of one pass can number (0x7FFF0000)", stats, empty))
@@ -1990,6 +2025,7 @@ int trt_camera_rays_device(int device, const trt_camera* cam, const trt_params* 
 int trt_render(trt_handle* h, const trt_params* p, float* out_host, trt_stats* stats)
 {
     if (int e = checkParams(h, p)) return e;
+    if (int e = checkEstimator(p)) return e;
     if (!out_host) return fail(TRT_EINVAL, "null output buffer");
     return renderTile(h, p, 0u, (uint32_t)p->spp, nullptr, out_host, nullptr, stats, nullptr);
 }
@@ -2372,6 +2408,7 @@ int trt_group_render_device(trt_group* g, const trt_params* p_in, float* out_dev
     p.row_mod = n;
     p.row_rem = 0;
     if (int e = checkParams(g->handles[0], &p)) return e;
+    if (int e = checkEstimator(&p)) return e;
     const uint32_t tile_rows = (uint32_t)(p.y1 - p.y0), tw = (uint32_t)(p.x1 - p.x0), row_floats = tw * 3u;
     // Rows are selected on absolute y (stripes are counted from image row 0), and k_uninterleave computes the packed index the
     // same way only if the tile starts on a stripe boundary of rank 0: require that.
@@ -2872,6 +2909,7 @@ struct RefitHost {
     std::vector<LightDev> lights;        // sources: the caller's light tables in device layout
     std::vector<LightTriDev> ltris;
     std::vector<float> cum;
+    std::vector<float> light_sel;        // the selection table of TRT_FLAG_ONE_LIGHT for the new areas (lightSelTable)
     std::vector<int32_t> light_of_mat;   // source (the first update)
     std::vector<uint32_t> light_box;     // source (the empty boxes), then landing place: 6 ordered keys per light
     uint32_t cursor = 0;                 // landing places: the numbering's node count (the first update), nodes[0], the 8-wide refit's flag
@@ -2959,7 +2997,7 @@ int checkUpdate(const trt_handle* h, const trt_geometry_update* u, uint32_t n_tr
     return TRT_OK;
 }
 
-// The caller's light tables, when given, checked and in device layout (H.lights, H.ltris, H.cum); nothing is enqueued
+// The caller's light tables, when given, checked and in device layout (H.lights, H.ltris, H.cum, H.light_sel); nothing is enqueued
 int updateLightTables(const trt_handle* h, const trt_geometry_update* u, const std::string& w, RefitHost& H)
 {
     if (!u->lights) return TRT_OK;
@@ -2974,6 +3012,8 @@ int updateLightTables(const trt_handle* h, const trt_geometry_update* u, const s
     HIPC(hipMemcpy(mats.data(), h->sc.materials, mats.size() * sizeof(MaterialDev), hipMemcpyDeviceToHost));
     H.lights.resize(u->n_lights);
     for (uint32_t l = 0; l < u->n_lights; ++l) H.lights[l] = makeLightDevFrom(u->lights[l], mats[(size_t)u->lights[l].mat].radiance);
+    H.light_sel.resize(u->n_lights);
+    lightSelTable(H.lights.data(), u->n_lights, H.light_sel.data());
     H.ltris.resize(u->n_light_tris);
     H.cum.resize(u->n_light_tris);
     for (uint32_t k = 0; k < u->n_light_tris; ++k) { H.ltris[k] = makeLightTriDev(u->light_tris[k]); H.cum[k] = u->light_tris[k].cum_area; }
@@ -3083,6 +3123,7 @@ int exchangeTables(trt_handle* h, bool new_lights, hipStream_t stream, RefitHost
         if (!H.lights.empty()) HIPC(hipMemcpyAsync((void*)h->sc.lights, H.lights.data(), H.lights.size() * sizeof(LightDev), hipMemcpyHostToDevice, stream));
         if (!H.ltris.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_tris, H.ltris.data(), H.ltris.size() * sizeof(LightTriDev), hipMemcpyHostToDevice, stream));
         if (h->sc.light_cum && !H.cum.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_cum, H.cum.data(), H.cum.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (h->sc.light_sel && !H.light_sel.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_sel, H.light_sel.data(), H.light_sel.size() * sizeof(float), hipMemcpyHostToDevice, stream));
     }
     if (h->lds_image) return packLdsImage(h, stream);
     return TRT_OK;

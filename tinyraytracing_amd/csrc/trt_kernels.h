@@ -74,7 +74,22 @@ constexpr int TRT_LDS_STACK_MAX = TRT_LDS_STACK_MAX_LEVELS;   // deepest LDS sta
 constexpr int SHADE_ONE = 0;   // exactly one light: the loop over the lights' stages is empty at compile time
 constexpr int SHADE_FEW = 1;   // 0 or 2..TRT_MAX_LIGHTS lights
 constexpr int SHADE_MANY = 2;  // more than TRT_MAX_LIGHTS lights
+// TRT_FLAG_ONE_LIGHT on a scene of two or more lights: SHADE_ONE's queue structure (one shadow queue, reserved with the extension ray in the one
+// blockStage2 stage; no per-light stages), the light a per-lane index from lightPick().  Its LightDev loads are per lane where SHADE_ONE's are scalar.
+constexpr int SHADE_PICK = 3;
 constexpr int TRT_MAX_LIGHTS = 8;
+// Block and waves: at SHADE_ONE's 512 threads x 6 waves per SIMD (80 VGPRs) the per-lane light record costs a spilled register (8 bytes of scratch per lane);
+// asked for 5 waves the flavour builds without scratch at 89-94 VGPRs in every instantiation.  512-thread blocks then stand two to a CU (4 waves per SIMD),
+// and the one queue counter takes half the reservations 256-thread blocks would send it (the reason SHADE_ONE has 512: see above); 256 x 5 also builds
+// without scratch (87-93 VGPRs, five blocks to a CU) and is the other arm of tools/one_light_cost.py's A/B (make variants: shadep256).
+#ifndef TRT_SHADEP_BLOCK
+#define TRT_SHADEP_BLOCK 512
+#endif
+#ifndef TRT_SHADEP_WAVES
+#define TRT_SHADEP_WAVES 5
+#endif
+constexpr int shadeBlockOf(int lights) { return lights == SHADE_ONE ? TRT_SHADE1_BLOCK : (lights == SHADE_PICK ? TRT_SHADEP_BLOCK : TRT_SHADEN_BLOCK); }
+constexpr int shadeWavesOf(int lights) { return lights == SHADE_ONE ? TRT_SHADE1_WAVES : (lights == SHADE_PICK ? TRT_SHADEP_WAVES : TRT_SHADEN_WAVES); }
 
 struct RayQueue {
     f4* ra;
@@ -1359,7 +1374,7 @@ struct RowsShade {
 // run-time choice the pointers are generic, the accesses FLAT, and each of them waits for vmcnt(0) — i.e. for the ray
 // stores issued before it — as well as for the LDS.
 // (Round 3's probe `short` — weight and throughput records stored as 8 bytes, wrong images — bought k_shade 3 %: profiles/r03_ab_oct.txt (8).)
-// LIGHTS: SHADE_ONE, SHADE_FEW or SHADE_MANY (where the shadow-queue descriptors come from).  LIST: the paths are those of a pixel list
+// LIGHTS: SHADE_ONE, SHADE_FEW, SHADE_MANY (where the shadow-queue descriptors come from) or SHADE_PICK (TRT_FLAG_ONE_LIGHT: sq[0] alone).  LIST: the paths are those of a pixel list
 // (trt_render_pixels; A.rows_lds is 0 there).  BLOCK threads, WAVES per SIMD asked of the compiler.
 // HIT8: the hit records are the 8-byte ones of the wave-uniform walk (storeResult), and the barycentrics of the winner are formed here, with the code
 // storeResult<false> runs for the 16-byte record: the same triangle test on the same ray, so the same bits.  The <= 64 intersection records of such a scene
@@ -1468,8 +1483,7 @@ __device__ inline ShadowQueue shadeQueue(const ShadeArgs& A, uint32_t li)
     if (LIGHTS == SHADE_MANY) return A.sq_arena.queue(li);
     return A.sq[li];
 }
-template <uint32_t TABS, int LIGHTS, bool LIST = false, int BLOCK = (LIGHTS == SHADE_ONE ? TRT_SHADE1_BLOCK : TRT_SHADEN_BLOCK),
-          int WAVES = (LIGHTS == SHADE_ONE ? TRT_SHADE1_WAVES : TRT_SHADEN_WAVES), bool HIT8 = false, bool FUSE = false>
+template <uint32_t TABS, int LIGHTS, bool LIST = false, int BLOCK = shadeBlockOf(LIGHTS), int WAVES = shadeWavesOf(LIGHTS), bool HIT8 = false, bool FUSE = false>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A)
 {
     static_assert(!FUSE || (HIT8 && !LIST && LIGHTS == SHADE_ONE), "the fused bounce 0 is built for tile renders of one-light scenes of the wave-uniform walk");
@@ -1623,7 +1637,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         uint32_t pend_rank = 0, pend_li = 0;
         f3 pend_wo = mk3(0, 0, 0), pend_w = mk3(0, 0, 0);
         float pend_tmax = TRT_INF;  // TRT_FLAG_FIXED_NEE: how far the occlusion test of the shadow ray reaches
-        const uint32_t nl = LIGHTS == SHADE_ONE ? 1u : sc.n_lights;
+        const uint32_t nl = (LIGHTS == SHADE_ONE || LIGHTS == SHADE_PICK) ? 1u : sc.n_lights;  // (SHADE_PICK: one queue, sq[0], whichever light the lane draws)
         for (uint32_t li = 0; li + 1 < nl; ++li) {  // every light but the last: a stage of its own
             bool emit = false;
             f3 wo = mk3(0, 0, 0), contrib = mk3(0, 0, 0);
@@ -1651,7 +1665,17 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         float tmax_s = TRT_INF;
         if (nl && c.shade_ok) {
             f3 contrib = mk3(0, 0, 0);
-            emit_s = lightSample(sc, c.vx, *c.m, nl - 1u, c.rng, wo_s, contrib, A.td.fixed_nee != 0u, tmax_s);
+            if constexpr (LIGHTS == SHADE_PICK) {
+                // TRT_FLAG_ONE_LIGHT (with TRT_FLAG_FIXED_NEE: trt_api.hip checks it): one draw picks the light, then its sample as ever, times 1 / p
+                uint32_t li;
+                float inv_p;
+                if (lightPick(sc, c.rng, li, inv_p)) {
+                    emit_s = lightSample(sc, c.vx, *c.m, li, c.rng, wo_s, contrib, true, tmax_s);
+                    contrib = mk3(contrib.x * inv_p, contrib.y * inv_p, contrib.z * inv_p);
+                }
+            } else {
+                emit_s = lightSample(sc, c.vx, *c.m, nl - 1u, c.rng, wo_s, contrib, A.td.fixed_nee != 0u, tmax_s);
+            }
             w_s = c.beta * contrib;
         }
         NextPlan plan;
@@ -1759,11 +1783,17 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_tail(SceneDev sc, TailArgs 
             if (c.had_hit) { any = true; deepest = c.depth > deepest ? c.depth : deepest; }
             if (c.add_L) { L.x = L.x + c.addL.x; L.y = L.y + c.addL.y; L.z = L.z + c.addL.z; }
             if (c.shade_ok) n_shaded++;
-            for (uint32_t li = 0; li < sc.n_lights; ++li) {
+            // TRT_FLAG_ONE_LIGHT (TileDesc::one_light): the loop over the lights is the one light lightPick() draws, its contribution times 1 / p
+            const bool pick = A.td.one_light != 0u;
+            const uint32_t n_loop = pick ? 1u : sc.n_lights;
+            for (uint32_t lk = 0; lk < n_loop; ++lk) {
                 f3 wo, contrib;
                 const bool fixed = A.td.fixed_nee != 0u;
                 float t_max = TRT_INF;
-                if (!c.shade_ok || !lightSample(sc, c.vx, *c.m, li, c.rng, wo, contrib, fixed, t_max)) continue;
+                uint32_t li = lk;
+                float inv_p = 1.0f;
+                if (!c.shade_ok || (pick && !lightPick(sc, c.rng, li, inv_p)) || !lightSample(sc, c.vx, *c.m, li, c.rng, wo, contrib, fixed, t_max)) continue;
+                if (pick) contrib = mk3(contrib.x * inv_p, contrib.y * inv_p, contrib.z * inv_p);
                 const f3 w = c.beta * contrib;
                 n_shadow++;
                 Hit sh;

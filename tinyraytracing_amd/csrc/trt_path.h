@@ -167,6 +167,8 @@ struct SceneDev {
     uint32_t plane_shift;        // 32 - log2(bits of the filter)
     float cull_alpha;   // what trt_cull_bound() gets on the 4-wide nodes: leaf_alpha where the boxes of the tree nest, +inf (never cull by distance) where they do not (trt_wide.h boxesNested)
     trt_camera cam;
+    // (behind everything the kernels had before: no existing field moves)
+    const float* light_sel;  // TRT_FLAG_ONE_LIGHT: the running sums of the lights' selection weights (lightPick), n_lights floats; null = form them from `lights`
 };
 
 // alpha of the leaf-box rule (trt_prims.h) for a tree: 2^-17 of the largest |coordinate| of the root's two child boxes.
@@ -874,6 +876,72 @@ TRT_HD inline bool lightSample(const SceneDev& sc, const Vertex& vx, const Mater
     return true;
 }
 
+// ---- TRT_FLAG_ONE_LIGHT: one light per vertex, picked in proportion to its power (include/trt.h states the contract) ----
+// The selection weight of a light: area * Rec. 709 luminance of the radiance lightSample() uses (the light material's), 0 unless both are finite and > 0.
+TRT_HD inline float lightWeight(const LightDev& L)
+{
+    const float lum = (0.2126f * L.radiance[0] + 0.7152f * L.radiance[1]) + 0.0722f * L.radiance[2];
+    const bool ok = L.area > 0.0f && L.area < __builtin_inff() && lum > 0.0f && lum < __builtin_inff();
+    return ok ? L.area * lum : 0.0f;
+}
+// The running sums cdf_l = cdf_{l-1} + w_l (fp32, index order) that SceneDev::light_sel holds: `out` gets n floats.
+TRT_HD inline void lightSelTable(const LightDev* lights, uint32_t n, float* out)
+{
+    float c = 0.0f;
+    for (uint32_t l = 0; l < n; ++l) { c = c + lightWeight(lights[l]); out[l] = c; }
+}
+// Draws the light a vertex samples: li, and inv_p = cdf_{L-1} / w_li, the factor its contribution takes.  -> false: no light is sampled at this vertex
+// (no lights, or a total weight that is 0 or not finite).  With fewer than two lights there is nothing to pick and no draw is taken; otherwise exactly one.
+// The pick is the first l with u * cdf_{L-1} < cdf_l — such an l has cdf_l > cdf_{l-1}, so w_l > 0: a light of weight zero is never picked — by bisection
+// on the table (the sums of non-negative terms never decrease), by a scan that forms the sums where there is none.  Where rounding finds no such l
+// (u * cdf_{L-1} == cdf_{L-1}) it is the last light of positive weight.  Every index returned lies in [0, n_lights).
+// lightPickAt: the pick for a given uniform u in [0, 1) on a scene of two or more lights; lightPick: the draw, then that.
+TRT_HD inline bool lightPickAt(const SceneDev& sc, float u, uint32_t& li, float& inv_p)
+{
+    const uint32_t n = sc.n_lights;
+    li = 0u;
+    inv_p = 1.0f;
+    float total;
+    if (sc.light_sel) {
+        total = sc.light_sel[n - 1u];
+    } else {
+        total = 0.0f;
+        for (uint32_t l = 0; l < n; ++l) total = total + lightWeight(sc.lights[l]);
+    }
+    if (!(total > 0.0f && total < __builtin_inff())) return false;
+    const float r = u * total;
+    uint32_t pick = n;
+    if (sc.light_sel) {
+        uint32_t lo = 0, hi = n;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (r < sc.light_sel[mid]) hi = mid; else lo = mid + 1;
+        }
+        pick = lo;
+    } else {
+        float c = 0.0f;
+        for (uint32_t l = 0; l < n; ++l) {
+            c = c + lightWeight(sc.lights[l]);
+            if (r < c) { pick = l; break; }
+        }
+    }
+    if (pick >= n) {
+        pick = 0u;  // (total > 0: some light has a positive weight)
+        for (uint32_t l = n; l-- > 0u;)
+            if (lightWeight(sc.lights[l]) > 0.0f) { pick = l; break; }
+    }
+    li = pick;
+    inv_p = total / lightWeight(sc.lights[pick]);
+    return true;
+}
+TRT_HD inline bool lightPick(const SceneDev& sc, Stream& rng, uint32_t& li, float& inv_p)
+{
+    li = 0u;
+    inv_p = 1.0f;
+    if (sc.n_lights < 2u) return sc.n_lights == 1u;
+    return lightPickAt(sc, rng.next(), li, inv_p);
+}
+
 // Path-state word carried with every queued ray.
 //   bits 0..15  next RNG draw index        bits 16..17 type of the ray being traced
 //   (3 = camera ray)                       bits 20..31 path depth (vertex index)
@@ -904,6 +972,7 @@ struct TileDesc {
     // the left and on the right, rows at the top and at the bottom, then (first, count) of a band of rows and of a band of columns that are
     // kept whatever the rectangle says.  All zero — every other entry point — culls nothing.
     int32_t cull[8];
+    uint32_t one_light;   // TRT_FLAG_ONE_LIGHT on a scene of two or more lights: a vertex samples the one light lightPick() draws (read by the light loops of k_shade and k_tail only)
 };
 
 // Is the camera ray of image pixel (y, x) culled?  (Outside the rectangle and in neither band.)
