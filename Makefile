@@ -32,8 +32,8 @@ HIP_HDR := $(wildcard $(PKG)/csrc/*.h) include/trt.h include/trt_prims.h include
 # test-only library of tests/test_shade_cases_cpu.py: part of `all` wherever its source is in the tree
 SHADE_MUTANTS := $(if $(wildcard tests/hostsim/shade_mutants.cpp),shademutants)
 
-.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu onelightcpu variants probe exactcheck nodecheck shadecheck shademutants clean
-all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu onelightcpu cli exactcheck nodecheck shadecheck $(SHADE_MUTANTS)
+.PHONY: all host hip lbvh oracle cli hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu onelightcpu nearlightscpu variants probe exactcheck nodecheck shadecheck shademutants clean
+all: host hip lbvh oracle hostsim denoisecpu reprojectcpu motioncpu momentscpu despecklecpu refitcpu rayscpu cullcpu schedcpu onelightcpu nearlightscpu cli exactcheck nodecheck shadecheck $(SHADE_MUTANTS)
 
 host: $(OUT)/libtrt_host.so
 hip: $(OUT)/libtrt_hip.so
@@ -89,6 +89,10 @@ tests/sched/libsched_cpu.so: tests/sched/sched_cpu.cpp $(PKG)/csrc/trt_sched.h
 onelightcpu: tests/onelight/libonelight_cpu.so
 tests/onelight/libonelight_cpu.so: tests/onelight/onelight_cpu.cpp tests/hostsim/hostsim.cpp $(wildcard tests/hostsim/*.h) $(wildcard tests/refit/*.h) tools/shade_cases.h $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/onelight/onelight_cpu.cpp
+# CPU build of TRT_FLAG_NEAR_LIGHTS: the same loop with the light picked by lightPickNear on buildLightTree's tree, for tests only (tests/test_*near_lights*.py)
+nearlightscpu: tests/nearlights/libnearlights_cpu.so
+tests/nearlights/libnearlights_cpu.so: tests/nearlights/nearlights_cpu.cpp tests/hostsim/hostsim.cpp $(wildcard tests/hostsim/*.h) $(wildcard tests/refit/*.h) tools/shade_cases.h $(HIP_HDR)
+	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/nearlights/nearlights_cpu.cpp
 
 $(OUT)/libtrt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(OUT)
@@ -119,7 +123,7 @@ variants: $(HIP_SRC) $(HIP_HDR)
 	  echo "variant $$name: $$defs"; $(HIPCC) $(HIPFLAGS) $$defs -shared -o $(OUT)/variants/libtrt_hip_$$name.so $(HIP_SRC) || exit 1; done
 
 clean:
-	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/hostsim/libshade_mutants.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/despeckle/libdespeckle_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so tests/cull/libcull_cpu.so tests/sched/libsched_cpu.so tests/onelight/libonelight_cpu.so
+	rm -rf $(OUT) tests/hostsim/libhostsim.so tests/hostsim/libshade_mutants.so tests/denoise/libdenoise_cpu.so tests/reproject/libreproject_cpu.so tests/motion/libmotion_cpu.so tests/moments/libmoments_cpu.so tests/despeckle/libdespeckle_cpu.so tests/refit/librefit_cpu.so tests/render_rays/librays_cpu.so tests/cull/libcull_cpu.so tests/sched/libsched_cpu.so tests/onelight/libonelight_cpu.so tests/nearlights/libnearlights_cpu.so
 	$(MAKE) -C oracle clean
 
 # exhaustive (2^32 inputs) proof that include/trt_exact.h returns the bits of sqrtf / 1.0f / sqrtf: run by tests/test_gpu_parity.py

@@ -186,6 +186,38 @@ typedef struct trt_scene {
                                   *   Fewer than 2 lights: the flag does nothing, no draw is taken (TRT_FLAG_FIXED_NEE's render bit for bit).
                                   *   Path memory: 132 + 48 bytes per path and sample whatever the light count (trt_params::mem_budget).  trt_stats::rays_shadow
                                   *   counts what is traced: at most one ray per shaded vertex. */
+#define TRT_FLAG_NEAR_LIGHTS 256u /* TRT_FLAG_ONE_LIGHT's one light picked where the vertex is: a stochastic descent of a binary tree over the lights, each child weighted
+                                  * by its power over its squared distance from the vertex, the realised probability divided out — unbiased like TRT_FLAG_ONE_LIGHT,
+                                  * with the same one queue, one shadow launch per bounce and 132 + 48 bytes per path.  Only the pick changes.
+                                  *   Needs TRT_FLAG_ONE_LIGHT (and with it TRT_FLAG_FIXED_NEE): without it the call is TRT_EINVAL from the check that guards
+                                  *   TRT_FLAG_ONE_LIGHT, the handle stays usable.  Honoured by the entries that honour TRT_FLAG_ONE_LIGHT (trt_render, _device, _samples,
+                                  *   trt_render_pixels*, trt_render_rays*, trt_group_render*); the AOV and ray-query entries ignore it.  Off = every other mode, bit
+                                  *   for bit.  Fewer than 2 lights: the flag does nothing, no draw is taken.
+                                  *   Tree lights: light l is one if w_l > 0 (TRT_FLAG_ONE_LIGHT's weight), tri_count > 0 and every vertex of its light_tris is finite;
+                                  *   M of them.  M == 0: no light is sampled at a vertex, no draw.  M == 1: that light, inv_p = 1, no draw.  M >= 2: the descent.
+                                  *   Box of a light: the exact min and max over the vertices of its light_tris; its centre: 0.5f * lo + 0.5f * hi per axis.
+                                  *   Tree (built on the host at trt_create whenever n_lights >= 2, deterministic): recurse on the list of tree lights, at first in
+                                  *   index order.  One light: a leaf.  n >= 2: the axis of the largest extent (max - min, fp32) of the centres' bounds, ties to x,
+                                  *   then y, then z; a stable sort by centre[axis]; the first floor(n / 2) lights go left, the rest right.  Nodes are numbered in
+                                  *   pre-order (node, left subtree, right subtree): M - 1 nodes, depth <= ceil(log2 M) <= 16.  A node (64 bytes) holds per child c
+                                  *   the box lo_c, hi_c of its lights, w_c = the fp32 sum of their weights in the child's list order (the order the split leaves,
+                                  *   before the child sorts), and a reference: bit 31 set = leaf, low bits the light's index.
+                                  *   Descent at P, the position of the path vertex, starting with inv_p = 1.  At each node, for each child c:
+                                  *   centre = 0.5f * lo_c + 0.5f * hi_c, r2 = |hi_c - centre|^2, d2 = |P - centre|^2 (each (x*x + y*y) + z*z), m = fmaxf(d2, r2),
+                                  *   imp_c = w_c / m.  s = imp0 + imp1; unless imp0 >= 0 && imp1 >= 0 && s > 0 && s < inf (a NaN fails it too) the node decides by
+                                  *   power alone: imp_c = w_c, s = w0 + w1.  One uniform u of the path's stream, r = u * s; child 0 iff r < imp0; if the picked
+                                  *   child's imp is not > 0, the other child.  inv_p = inv_p * (s / imp_picked).  Step into the picked child; stop at a leaf.
+                                  *   All of it fp32, in this order, no contraction.  The draws — one per level — sit where TRT_FLAG_ONE_LIGHT's one draw sits, BEFORE
+                                  *   the draws of the light sample, and the sample's contribution is multiplied by inv_p as under TRT_FLAG_ONE_LIGHT (the three
+                                  *   components, before the product with the path throughput).  inv_p not finite at the leaf: the draws are spent, no light is
+                                  *   sampled at the vertex.
+                                  *   Every tree light has positive probability at every P (where one child's imp underflows to zero beside a positive one, that
+                                  *   child's lights are the exception at that P), and the probability realised is 1 / inv_p up to the fp32 rounding of the
+                                  *   products and quotients (about 2^-23 per level) and the 24-bit uniform per level: that is the estimator's bias.
+                                  *   trt_update_geometry* with lights != NULL rebuilds the tree (and the weights) on the host from the new tables and uploads it:
+                                  *   the handle then answers as a fresh one would.  With lights == NULL the tree is not touched, like the sampling tables.
+                                  *   Memory: 64 bytes * (n_lights - 1) on the device for the nodes (M - 1 of them in use; an update may change M).  Path memory
+                                  *   as under TRT_FLAG_ONE_LIGHT: 132 + 48 bytes per path and sample. */
 
 typedef struct trt_params {
     int32_t width, height;   /* full image size (scene.img_width/height, scene.cpp:13-14) */

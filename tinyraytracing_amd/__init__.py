@@ -14,7 +14,7 @@ from typing import NamedTuple
 import numpy as np
 
 from . import _abi, adaptive
-from ._abi import Params, Stats, SceneFlat, Camera, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, TRT_FLAG_ONE_LIGHT, KERNEL_NAMES, TRT_K_DENOISE, TRT_K_REFIT, AOV_RAYS_BYTES_PER_PATH  # noqa: F401
+from ._abi import Params, Stats, SceneFlat, Camera, TRT_FLAG_COUNT, TRT_FLAG_TIMING, TRT_FLAG_OVERLAP, TRT_FLAG_FIXED_NEE, TRT_FLAG_FIXED_PIXELS, TRT_FLAG_RAY_OFFSET, TRT_FLAG_SPECULAR_KS, TRT_FLAG_ONE_LIGHT, TRT_FLAG_NEAR_LIGHTS, KERNEL_NAMES, TRT_K_DENOISE, TRT_K_REFIT, AOV_RAYS_BYTES_PER_PATH  # noqa: F401
 
 REPO_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCENES_DIR = os.path.join(REPO_ROOT, "scenes")

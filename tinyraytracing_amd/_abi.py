@@ -20,6 +20,7 @@ TRT_FLAG_FIXED_PIXELS = 16
 TRT_FLAG_RAY_OFFSET = 32
 TRT_FLAG_SPECULAR_KS = 64
 TRT_FLAG_ONE_LIGHT = 128  # one light per path vertex, picked by power; needs TRT_FLAG_FIXED_NEE (include/trt.h)
+TRT_FLAG_NEAR_LIGHTS = 256  # that one light picked by power over squared distance from the vertex (a light tree); needs TRT_FLAG_ONE_LIGHT (include/trt.h)
 TRT_MAX_KERNELS = 8
 # trt_aov_rays: bytes of mem_budget per path and sample in a pass (include/trt.h TRT_AOV_RAYS_BYTES_PER_PATH)
 AOV_RAYS_BYTES_PER_PATH = 52

@@ -21,6 +21,7 @@
 
 #include "trt.h"
 #include "trt_kernels.h"
+#include "trt_lighttree.h"
 #include "trt_cull.h"
 #include "trt_sched.h"
 #include "trt_wide.h"
@@ -367,6 +368,8 @@ int checkEstimator(const trt_params* p)
 {
     if ((p->flags & TRT_FLAG_ONE_LIGHT) && !(p->flags & TRT_FLAG_FIXED_NEE))
         return fail(TRT_EINVAL, "TRT_FLAG_ONE_LIGHT needs TRT_FLAG_FIXED_NEE (rays to different lights share one queue of occlusion tests)");
+    if ((p->flags & TRT_FLAG_NEAR_LIGHTS) && !(p->flags & TRT_FLAG_ONE_LIGHT))
+        return fail(TRT_EINVAL, "TRT_FLAG_NEAR_LIGHTS needs TRT_FLAG_ONE_LIGHT (it changes how that flag's one light is picked)");
     return TRT_OK;
 }
 
@@ -485,24 +488,26 @@ ShadeKernel fusedShadeKernel() { return k_shade<31u, SHADE_ONE, false, TRT_SHADE
 ShadeKernel shadeKernel(uint32_t tabs, int lights, bool list, bool hit8)
 {
     if (hit8) {  // trt_create sets hit8 only with tabs == 31
-        const ShadeKernel s[2][4] = {
+        const ShadeKernel s[2][5] = {
             {k_shade<31u, SHADE_ONE, false, TRT_SHADE1_BLOCK, TRT_SHADE1_WAVES, true>, k_shade<31u, SHADE_FEW, false, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>,
-             k_shade<31u, SHADE_MANY, false, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>, k_shade<31u, SHADE_PICK, false, TRT_SHADEP_BLOCK, TRT_SHADEP_WAVES, true>},
+             k_shade<31u, SHADE_MANY, false, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>, k_shade<31u, SHADE_PICK, false, TRT_SHADEP_BLOCK, TRT_SHADEP_WAVES, true>,
+             k_shade<31u, SHADE_NEAR, false, TRT_SHADEP_BLOCK, TRT_SHADEP_WAVES, true>},
             {k_shade<31u, SHADE_ONE, true, TRT_SHADE1_BLOCK, TRT_SHADE1_WAVES, true>, k_shade<31u, SHADE_FEW, true, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>,
-             k_shade<31u, SHADE_MANY, true, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>, k_shade<31u, SHADE_PICK, true, TRT_SHADEP_BLOCK, TRT_SHADEP_WAVES, true>}};
+             k_shade<31u, SHADE_MANY, true, TRT_SHADEN_BLOCK, TRT_SHADEN_WAVES, true>, k_shade<31u, SHADE_PICK, true, TRT_SHADEP_BLOCK, TRT_SHADEP_WAVES, true>,
+             k_shade<31u, SHADE_NEAR, true, TRT_SHADEP_BLOCK, TRT_SHADEP_WAVES, true>}};
         return s[list][lights];
     }
-    const ShadeKernel k[5][2][4] = {
-        {{k_shade<31u, SHADE_ONE>, k_shade<31u, SHADE_FEW>, k_shade<31u, SHADE_MANY>, k_shade<31u, SHADE_PICK>},
-         {k_shade<31u, SHADE_ONE, true>, k_shade<31u, SHADE_FEW, true>, k_shade<31u, SHADE_MANY, true>, k_shade<31u, SHADE_PICK, true>}},
-        {{k_shade<15u, SHADE_ONE>, k_shade<15u, SHADE_FEW>, k_shade<15u, SHADE_MANY>, k_shade<15u, SHADE_PICK>},
-         {k_shade<15u, SHADE_ONE, true>, k_shade<15u, SHADE_FEW, true>, k_shade<15u, SHADE_MANY, true>, k_shade<15u, SHADE_PICK, true>}},
-        {{k_shade<7u, SHADE_ONE>, k_shade<7u, SHADE_FEW>, k_shade<7u, SHADE_MANY>, k_shade<7u, SHADE_PICK>},
-         {k_shade<7u, SHADE_ONE, true>, k_shade<7u, SHADE_FEW, true>, k_shade<7u, SHADE_MANY, true>, k_shade<7u, SHADE_PICK, true>}},
-        {{k_shade<3u, SHADE_ONE>, k_shade<3u, SHADE_FEW>, k_shade<3u, SHADE_MANY>, k_shade<3u, SHADE_PICK>},
-         {k_shade<3u, SHADE_ONE, true>, k_shade<3u, SHADE_FEW, true>, k_shade<3u, SHADE_MANY, true>, k_shade<3u, SHADE_PICK, true>}},
-        {{k_shade<0u, SHADE_ONE>, k_shade<0u, SHADE_FEW>, k_shade<0u, SHADE_MANY>, k_shade<0u, SHADE_PICK>},
-         {k_shade<0u, SHADE_ONE, true>, k_shade<0u, SHADE_FEW, true>, k_shade<0u, SHADE_MANY, true>, k_shade<0u, SHADE_PICK, true>}}};
+    const ShadeKernel k[5][2][5] = {
+        {{k_shade<31u, SHADE_ONE>, k_shade<31u, SHADE_FEW>, k_shade<31u, SHADE_MANY>, k_shade<31u, SHADE_PICK>, k_shade<31u, SHADE_NEAR>},
+         {k_shade<31u, SHADE_ONE, true>, k_shade<31u, SHADE_FEW, true>, k_shade<31u, SHADE_MANY, true>, k_shade<31u, SHADE_PICK, true>, k_shade<31u, SHADE_NEAR, true>}},
+        {{k_shade<15u, SHADE_ONE>, k_shade<15u, SHADE_FEW>, k_shade<15u, SHADE_MANY>, k_shade<15u, SHADE_PICK>, k_shade<15u, SHADE_NEAR>},
+         {k_shade<15u, SHADE_ONE, true>, k_shade<15u, SHADE_FEW, true>, k_shade<15u, SHADE_MANY, true>, k_shade<15u, SHADE_PICK, true>, k_shade<15u, SHADE_NEAR, true>}},
+        {{k_shade<7u, SHADE_ONE>, k_shade<7u, SHADE_FEW>, k_shade<7u, SHADE_MANY>, k_shade<7u, SHADE_PICK>, k_shade<7u, SHADE_NEAR>},
+         {k_shade<7u, SHADE_ONE, true>, k_shade<7u, SHADE_FEW, true>, k_shade<7u, SHADE_MANY, true>, k_shade<7u, SHADE_PICK, true>, k_shade<7u, SHADE_NEAR, true>}},
+        {{k_shade<3u, SHADE_ONE>, k_shade<3u, SHADE_FEW>, k_shade<3u, SHADE_MANY>, k_shade<3u, SHADE_PICK>, k_shade<3u, SHADE_NEAR>},
+         {k_shade<3u, SHADE_ONE, true>, k_shade<3u, SHADE_FEW, true>, k_shade<3u, SHADE_MANY, true>, k_shade<3u, SHADE_PICK, true>, k_shade<3u, SHADE_NEAR, true>}},
+        {{k_shade<0u, SHADE_ONE>, k_shade<0u, SHADE_FEW>, k_shade<0u, SHADE_MANY>, k_shade<0u, SHADE_PICK>, k_shade<0u, SHADE_NEAR>},
+         {k_shade<0u, SHADE_ONE, true>, k_shade<0u, SHADE_FEW, true>, k_shade<0u, SHADE_MANY, true>, k_shade<0u, SHADE_PICK, true>, k_shade<0u, SHADE_NEAR, true>}}};
     return k[tabs == 31u ? 0 : (tabs == 15u ? 1 : (tabs == 7u ? 2 : (tabs == 3u ? 3 : 4)))][list][lights];
 }
 // (named in this order: named the other way round, k_tail<true, true> / <false, false> build 1 instruction shorter / longer, tools/isa_diff.py)
@@ -552,6 +557,7 @@ struct SceneImage {
     std::vector<MaterialDev> mats;
     std::vector<LightDev> lights;
     std::vector<float> light_sel;
+    LightTree light_tree;
     std::vector<LightTriDev> ltris;
     std::vector<float> cum;
     bool cum_monotone = true;
@@ -665,6 +671,7 @@ int buildSceneImage(const trt_scene* s, SceneImage& im)
     lightSelTable(im.lights.data(), s->n_lights, im.light_sel.data());
     im.ltris.resize(s->n_light_tris);
     for (uint32_t i = 0; i < s->n_light_tris; ++i) im.ltris[i] = makeLightTriDev(s->light_tris[i]);
+    buildLightTree(im.lights.data(), s->n_lights, im.ltris.data(), s->n_light_tris, im.light_tree);  // TRT_FLAG_NEAR_LIGHTS (lightPickNear, trt_path.h)
     // packed CDF for the bisection in lightSample; only when every light's CDF is non-decreasing and NaN-free
     im.cum.resize(s->n_light_tris);
     for (uint32_t k = 0; k < s->n_light_tris; ++k) im.cum[k] = s->light_tris[k].cum_area;
@@ -775,6 +782,17 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
     h->sc.light_sel = nullptr;  // (fewer than two lights: nothing is ever picked)
     if (s->n_lights >= 2)
         if (int e = upload(h.get(), im.light_sel.data(), im.light_sel.size(), &h->sc.light_sel)) return e;
+    // the light tree of TRT_FLAG_NEAR_LIGHTS: room for the n_lights - 1 nodes any later light table of this handle can need (trt_update_geometry keeps n_lights)
+    h->sc.light_nodes = nullptr;
+    h->sc.n_light_nodes = 0u;
+    h->sc.light_root = TRT_LIGHT_NONE;
+    if (s->n_lights >= 2) {
+        std::vector<LightNode> nodes(im.light_tree.nodes);
+        nodes.resize(s->n_lights - 1u, LightNode{});
+        if (int e = upload(h.get(), nodes.data(), nodes.size(), &h->sc.light_nodes)) return e;
+        h->sc.n_light_nodes = (uint32_t)im.light_tree.nodes.size();
+        h->sc.light_root = im.light_tree.root;
+    }
     if (int e = upload(h.get(), im.tex.data(), im.tex.size(), &h->sc.textures)) return e;
     if (int e = upload(h.get(), im.tex_bytes.data(), im.tex_bytes.size(), &h->sc.tex_bytes)) return e;
     lap("uploads");
@@ -862,7 +880,7 @@ int createOnDevice(const SceneImage& im, int device, trt_handle** out)
         // more than 64 KiB per block needs the opt-in; a refusal shows as a launch error, not as a silent no-op
         for (uint32_t tabs : {31u, 15u, 7u, 3u, 0u})
             for (bool list : {false, true})
-                for (int lights : {SHADE_ONE, SHADE_FEW, SHADE_MANY, SHADE_PICK})
+                for (int lights : {SHADE_ONE, SHADE_FEW, SHADE_MANY, SHADE_PICK, SHADE_NEAR})
                     for (bool hit8 : {false, true})
                         if (!hit8 || tabs == 31u)
                             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shadeKernel(tabs, lights, list, hit8)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->shade_pad_lds);
@@ -1042,6 +1060,8 @@ struct RenderInput {
 
 // TRT_FLAG_ONE_LIGHT takes effect on scenes of two or more lights (include/trt.h): the call then has ONE shadow queue whatever the light count
 inline bool picksOneLight(const trt_handle* h, const trt_params* p) { return (p->flags & TRT_FLAG_ONE_LIGHT) != 0 && h->sc.n_lights >= 2u; }
+// TRT_FLAG_NEAR_LIGHTS: that one light by a descent of the light tree (checkEstimator has seen to TRT_FLAG_ONE_LIGHT)
+inline bool picksNearLight(const trt_handle* h, const trt_params* p) { return picksOneLight(h, p) && (p->flags & TRT_FLAG_NEAR_LIGHTS) != 0; }
 
 // The arguments of k_shade that every bounce of a render call shares, its TileDesc among them (d_table: the row table or the list on the device)
 ShadeArgs shadeArgsOf(const trt_handle* h, const trt_params* p, const RenderInput& in, const void* d_table, uint32_t rows_lds, DeviceStats* d_stats)
@@ -1061,6 +1081,7 @@ ShadeArgs shadeArgsOf(const trt_handle* h, const trt_params* p, const RenderInpu
     td.ray_offset = (p->flags & TRT_FLAG_RAY_OFFSET) ? 1u : 0u;
     td.specular_ks = (p->flags & TRT_FLAG_SPECULAR_KS) ? 1u : 0u;
     td.one_light = picksOneLight(h, p) ? 1u : 0u;
+    td.near_lights = picksNearLight(h, p) ? 1u : 0u;
     td.npix_magic = magicOf(in.npix);
     td.tile_w_magic = magicOf((uint32_t)td.tile_w);
     td.grid_ok = (p->width >= 2 && p->height >= 2 && p->width <= 65536 && p->height <= 65536) ? 1u : 0u;
@@ -1320,8 +1341,8 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     }
     // k_shade's three flavours (trt_kernels.h): 512-thread blocks at 6 waves per SIMD for one light, 256-thread blocks at 5 for
     // several; more than TRT_MAX_LIGHTS lights find their queues in the arena instead of in the kernel arguments.  The fourth, SHADE_PICK, is
-    // TRT_FLAG_ONE_LIGHT's: one queue as for one light, the light drawn per vertex.
-    const int lights = pick ? SHADE_PICK : (nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY));
+    // TRT_FLAG_ONE_LIGHT's: one queue as for one light, the light drawn per vertex; the fifth, SHADE_NEAR, draws it from the light tree (TRT_FLAG_NEAR_LIGHTS).
+    const int lights = pick ? (picksNearLight(h, p) ? SHADE_NEAR : SHADE_PICK) : (nl == 1u ? SHADE_ONE : (nl <= (uint32_t)TRT_MAX_LIGHTS ? SHADE_FEW : SHADE_MANY));
     const uint32_t shade_block = (uint32_t)shadeBlockOf(lights);
     const uint32_t rows_lds = (in.rows.size() <= shadeRowsLds((int)shade_block) && p->height <= 65536) ? (uint32_t)in.rows.size() : 0u;  // 0 for a list
     // the kernels of this call: bounce 0 traces the camera rays of the tile or of the list, later bounces the queue
@@ -1359,7 +1380,7 @@ int renderCore(trt_handle* h, const trt_params* p, uint32_t s_begin, uint32_t s_
     const TileDesc& td = shade_args.td;
     if (h->dbg)
         std::fprintf(stderr, "%s: k_shade %s, rows in lds %u, grid_ok %u\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"),
-                     lights == SHADE_PICK ? "pick" : (lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many")), rows_lds, td.grid_ok);
+                     lights == SHADE_NEAR ? "near" : lights == SHADE_PICK ? "pick" : (lights == SHADE_ONE ? "one" : (lights == SHADE_FEW ? "few" : "many")), rows_lds, td.grid_ok);
     if (h->dbg) std::fprintf(stderr, "%s: fused primary %d\n", in.rays ? "trt_render_rays" : (in.list ? "trt_render_pixels" : "trt_render"), (int)fuse);
     // The shadow walks of bounce b on the handle's side stream, beside closest hits and k_shade of bounce b + 1.  The loop stays
     // on one stream where per-kernel times or counters are asked for, where k_shade's queue flavour adds to Lacc itself (TRANSMISSION rays: a
@@ -2910,6 +2931,7 @@ struct RefitHost {
     std::vector<LightTriDev> ltris;
     std::vector<float> cum;
     std::vector<float> light_sel;        // the selection table of TRT_FLAG_ONE_LIGHT for the new areas (lightSelTable)
+    LightTree light_tree;                // the light tree of TRT_FLAG_NEAR_LIGHTS over the new tables (buildLightTree)
     std::vector<int32_t> light_of_mat;   // source (the first update)
     std::vector<uint32_t> light_box;     // source (the empty boxes), then landing place: 6 ordered keys per light
     uint32_t cursor = 0;                 // landing places: the numbering's node count (the first update), nodes[0], the 8-wide refit's flag
@@ -2997,7 +3019,7 @@ int checkUpdate(const trt_handle* h, const trt_geometry_update* u, uint32_t n_tr
     return TRT_OK;
 }
 
-// The caller's light tables, when given, checked and in device layout (H.lights, H.ltris, H.cum, H.light_sel); nothing is enqueued
+// The caller's light tables, when given, checked and in device layout (H.lights, H.ltris, H.cum, H.light_sel, H.light_tree); nothing is enqueued
 int updateLightTables(const trt_handle* h, const trt_geometry_update* u, const std::string& w, RefitHost& H)
 {
     if (!u->lights) return TRT_OK;
@@ -3017,6 +3039,7 @@ int updateLightTables(const trt_handle* h, const trt_geometry_update* u, const s
     H.ltris.resize(u->n_light_tris);
     H.cum.resize(u->n_light_tris);
     for (uint32_t k = 0; k < u->n_light_tris; ++k) { H.ltris[k] = makeLightTriDev(u->light_tris[k]); H.cum[k] = u->light_tris[k].cum_area; }
+    buildLightTree(H.lights.data(), u->n_lights, H.ltris.data(), u->n_light_tris, H.light_tree);
     bool monotone = true;
     for (uint32_t l = 0; l < u->n_lights; ++l)
         for (uint32_t k = 0; k < u->lights[l].tri_count; ++k) {
@@ -3124,6 +3147,8 @@ int exchangeTables(trt_handle* h, bool new_lights, hipStream_t stream, RefitHost
         if (!H.ltris.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_tris, H.ltris.data(), H.ltris.size() * sizeof(LightTriDev), hipMemcpyHostToDevice, stream));
         if (h->sc.light_cum && !H.cum.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_cum, H.cum.data(), H.cum.size() * sizeof(float), hipMemcpyHostToDevice, stream));
         if (h->sc.light_sel && !H.light_sel.empty()) HIPC(hipMemcpyAsync((void*)h->sc.light_sel, H.light_sel.data(), H.light_sel.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+        if (h->sc.light_nodes && !H.light_tree.nodes.empty())  // (n_lights >= 2: the handle has room for n_lights - 1 nodes, and the update keeps n_lights)
+            HIPC(hipMemcpyAsync((void*)h->sc.light_nodes, H.light_tree.nodes.data(), H.light_tree.nodes.size() * sizeof(LightNode), hipMemcpyHostToDevice, stream));
     }
     if (h->lds_image) return packLdsImage(h, stream);
     return TRT_OK;
@@ -3146,6 +3171,10 @@ void commitUpdate(trt_handle* h, const trt_geometry_update* u, const RefitHost& 
             for (int a = 0; a < 3; ++a) { h->light_boxes[l].lo[a] = refitUnordered(H.light_box[6 * from + a]); h->light_boxes[l].hi[a] = refitUnordered(H.light_box[6 * from + 3 + a]); }
         }
     if (u->lights) h->sc.light0_area = nl ? u->lights[0].area : 0.0f;
+    if (u->lights && h->sc.light_nodes) {  // the light tree of the new tables (exchangeTables has sent its nodes)
+        h->sc.n_light_nodes = (uint32_t)H.light_tree.nodes.size();
+        h->sc.light_root = H.light_tree.root;
+    }
     // boxes that reach 2^40 (or an extent the bytes cannot hold): the tree no longer qualifies for the 8-wide nodes — the exact 4-wide ones from here on, for good
     if (refitsOct(h) && H.oct_failed) h->node_kind = 0;
 }

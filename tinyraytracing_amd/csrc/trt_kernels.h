@@ -77,6 +77,10 @@ constexpr int SHADE_MANY = 2;  // more than TRT_MAX_LIGHTS lights
 // TRT_FLAG_ONE_LIGHT on a scene of two or more lights: SHADE_ONE's queue structure (one shadow queue, reserved with the extension ray in the one
 // blockStage2 stage; no per-light stages), the light a per-lane index from lightPick().  Its LightDev loads are per lane where SHADE_ONE's are scalar.
 constexpr int SHADE_PICK = 3;
+// TRT_FLAG_NEAR_LIGHTS on top of it: SHADE_PICK with the light drawn by lightPickNear() — a descent of the light tree at the vertex, four per-lane 16-B
+// loads and one draw per level, in SHADE_PICK's block at SHADE_PICK's waves (89-93 VGPRs, no scratch).  A flavour of its own, so that SHADE_PICK's instructions and registers stay what they were (tools/near_lights_cost.py (4), (6)).
+constexpr int SHADE_NEAR = 4;
+constexpr bool shadePicks(int lights) { return lights == SHADE_PICK || lights == SHADE_NEAR; }
 constexpr int TRT_MAX_LIGHTS = 8;
 // Block and waves: at SHADE_ONE's 512 threads x 6 waves per SIMD (80 VGPRs) the per-lane light record costs a spilled register (8 bytes of scratch per lane);
 // asked for 5 waves the flavour builds without scratch at 89-94 VGPRs in every instantiation.  512-thread blocks then stand two to a CU (4 waves per SIMD),
@@ -88,8 +92,8 @@ constexpr int TRT_MAX_LIGHTS = 8;
 #ifndef TRT_SHADEP_WAVES
 #define TRT_SHADEP_WAVES 5
 #endif
-constexpr int shadeBlockOf(int lights) { return lights == SHADE_ONE ? TRT_SHADE1_BLOCK : (lights == SHADE_PICK ? TRT_SHADEP_BLOCK : TRT_SHADEN_BLOCK); }
-constexpr int shadeWavesOf(int lights) { return lights == SHADE_ONE ? TRT_SHADE1_WAVES : (lights == SHADE_PICK ? TRT_SHADEP_WAVES : TRT_SHADEN_WAVES); }
+constexpr int shadeBlockOf(int lights) { return lights == SHADE_ONE ? TRT_SHADE1_BLOCK : (shadePicks(lights) ? TRT_SHADEP_BLOCK : TRT_SHADEN_BLOCK); }
+constexpr int shadeWavesOf(int lights) { return lights == SHADE_ONE ? TRT_SHADE1_WAVES : (shadePicks(lights) ? TRT_SHADEP_WAVES : TRT_SHADEN_WAVES); }
 
 struct RayQueue {
     f4* ra;
@@ -1374,7 +1378,7 @@ struct RowsShade {
 // run-time choice the pointers are generic, the accesses FLAT, and each of them waits for vmcnt(0) — i.e. for the ray
 // stores issued before it — as well as for the LDS.
 // (Round 3's probe `short` — weight and throughput records stored as 8 bytes, wrong images — bought k_shade 3 %: profiles/r03_ab_oct.txt (8).)
-// LIGHTS: SHADE_ONE, SHADE_FEW, SHADE_MANY (where the shadow-queue descriptors come from) or SHADE_PICK (TRT_FLAG_ONE_LIGHT: sq[0] alone).  LIST: the paths are those of a pixel list
+// LIGHTS: SHADE_ONE, SHADE_FEW, SHADE_MANY (where the shadow-queue descriptors come from) or SHADE_PICK / SHADE_NEAR (TRT_FLAG_ONE_LIGHT, with TRT_FLAG_NEAR_LIGHTS: sq[0] alone).  LIST: the paths are those of a pixel list
 // (trt_render_pixels; A.rows_lds is 0 there).  BLOCK threads, WAVES per SIMD asked of the compiler.
 // HIT8: the hit records are the 8-byte ones of the wave-uniform walk (storeResult), and the barycentrics of the winner are formed here, with the code
 // storeResult<false> runs for the 16-byte record: the same triangle test on the same ray, so the same bits.  The <= 64 intersection records of such a scene
@@ -1637,7 +1641,7 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         uint32_t pend_rank = 0, pend_li = 0;
         f3 pend_wo = mk3(0, 0, 0), pend_w = mk3(0, 0, 0);
         float pend_tmax = TRT_INF;  // TRT_FLAG_FIXED_NEE: how far the occlusion test of the shadow ray reaches
-        const uint32_t nl = (LIGHTS == SHADE_ONE || LIGHTS == SHADE_PICK) ? 1u : sc.n_lights;  // (SHADE_PICK: one queue, sq[0], whichever light the lane draws)
+        const uint32_t nl = (LIGHTS == SHADE_ONE || shadePicks(LIGHTS)) ? 1u : sc.n_lights;  // (SHADE_PICK, SHADE_NEAR: one queue, sq[0], whichever light the lane draws)
         for (uint32_t li = 0; li + 1 < nl; ++li) {  // every light but the last: a stage of its own
             bool emit = false;
             f3 wo = mk3(0, 0, 0), contrib = mk3(0, 0, 0);
@@ -1665,11 +1669,12 @@ __global__ __launch_bounds__(BLOCK, WAVES) void k_shade(SceneDev sc, ShadeArgs A
         float tmax_s = TRT_INF;
         if (nl && c.shade_ok) {
             f3 contrib = mk3(0, 0, 0);
-            if constexpr (LIGHTS == SHADE_PICK) {
-                // TRT_FLAG_ONE_LIGHT (with TRT_FLAG_FIXED_NEE: trt_api.hip checks it): one draw picks the light, then its sample as ever, times 1 / p
+            if constexpr (shadePicks(LIGHTS)) {
+                // TRT_FLAG_ONE_LIGHT (with TRT_FLAG_FIXED_NEE: trt_api.hip checks it): one draw picks the light (TRT_FLAG_NEAR_LIGHTS: one per level of the
+                // light tree, descended at the vertex), then its sample as ever, times 1 / p
                 uint32_t li;
                 float inv_p;
-                if (lightPick(sc, c.rng, li, inv_p)) {
+                if (LIGHTS == SHADE_NEAR ? lightPickNear(sc, c.vx.P, c.rng, li, inv_p) : lightPick(sc, c.rng, li, inv_p)) {
                     emit_s = lightSample(sc, c.vx, *c.m, li, c.rng, wo_s, contrib, true, tmax_s);
                     contrib = mk3(contrib.x * inv_p, contrib.y * inv_p, contrib.z * inv_p);
                 }
@@ -1783,8 +1788,9 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_tail(SceneDev sc, TailArgs 
             if (c.had_hit) { any = true; deepest = c.depth > deepest ? c.depth : deepest; }
             if (c.add_L) { L.x = L.x + c.addL.x; L.y = L.y + c.addL.y; L.z = L.z + c.addL.z; }
             if (c.shade_ok) n_shaded++;
-            // TRT_FLAG_ONE_LIGHT (TileDesc::one_light): the loop over the lights is the one light lightPick() draws, its contribution times 1 / p
-            const bool pick = A.td.one_light != 0u;
+            // TRT_FLAG_ONE_LIGHT (TileDesc::one_light): the loop over the lights is the one light lightPick() draws (TileDesc::near_lights: lightPickNear()),
+            // its contribution times 1 / p
+            const bool pick = A.td.one_light != 0u, near = A.td.near_lights != 0u;
             const uint32_t n_loop = pick ? 1u : sc.n_lights;
             for (uint32_t lk = 0; lk < n_loop; ++lk) {
                 f3 wo, contrib;
@@ -1792,7 +1798,7 @@ __global__ __launch_bounds__(TRT_TRACE_BLOCK) void k_tail(SceneDev sc, TailArgs 
                 float t_max = TRT_INF;
                 uint32_t li = lk;
                 float inv_p = 1.0f;
-                if (!c.shade_ok || (pick && !lightPick(sc, c.rng, li, inv_p)) || !lightSample(sc, c.vx, *c.m, li, c.rng, wo, contrib, fixed, t_max)) continue;
+                if (!c.shade_ok || (pick && !(near ? lightPickNear(sc, c.vx.P, c.rng, li, inv_p) : lightPick(sc, c.rng, li, inv_p))) || !lightSample(sc, c.vx, *c.m, li, c.rng, wo, contrib, fixed, t_max)) continue;
                 if (pick) contrib = mk3(contrib.x * inv_p, contrib.y * inv_p, contrib.z * inv_p);
                 const f3 w = c.beta * contrib;
                 n_shadow++;

@@ -142,6 +142,18 @@ struct WideNode {
     f4 q[8];
 };
 
+// Node of the light tree of TRT_FLAG_NEAR_LIGHTS (include/trt.h states the contract; built by buildLightTree, trt_lighttree.h), 64 B = four 16-B loads, in
+// the spirit of trt_bvh_node: the exact boxes of the two children's lights, each child's weight (the fp32 sum of its lights' lightWeight() in the child's
+// list order) and the child references — bit 31 set: a leaf, the low bits the light's index; clear: the index of an inner node.
+#define TRT_LIGHT_LEAF 0x80000000u
+#define TRT_LIGHT_NONE 0xFFFFFFFFu  // SceneDev::light_root of a scene without a tree light
+struct alignas(16) LightNode {
+    float lo0[3], hi0[3], lo1[3], hi1[3];
+    float w0, w1;
+    uint32_t child0, child1;
+};
+static_assert(sizeof(LightNode) == 64, "LightNode must be four 16-byte words");
+
 struct OctNode;  // trt_oct.h
 struct SceneDev {
     const trt_bvh_node* nodes;   // the caller's BVH2: the wave-uniform walk of tiny trees (trt_kernels.h, WalkUniform)
@@ -169,6 +181,10 @@ struct SceneDev {
     trt_camera cam;
     // (behind everything the kernels had before: no existing field moves)
     const float* light_sel;  // TRT_FLAG_ONE_LIGHT: the running sums of the lights' selection weights (lightPick), n_lights floats; null = form them from `lights`
+    // TRT_FLAG_NEAR_LIGHTS: the light tree (lightPickNear), built wherever n_lights >= 2.  n_light_nodes = M - 1 inner nodes for M >= 2 tree lights, else 0 (null).
+    // light_root: where the descent starts — inner node 0 for M >= 2, TRT_LIGHT_LEAF | index of the one tree light for M == 1, TRT_LIGHT_NONE for M == 0.
+    const LightNode* light_nodes;
+    uint32_t n_light_nodes, light_root;
 };
 
 // alpha of the leaf-box rule (trt_prims.h) for a tree: 2^-17 of the largest |coordinate| of the root's two child boxes.
@@ -942,6 +958,52 @@ TRT_HD inline bool lightPick(const SceneDev& sc, Stream& rng, uint32_t& li, floa
     return lightPickAt(sc, rng.next(), li, inv_p);
 }
 
+// ---- TRT_FLAG_NEAR_LIGHTS: the one light of TRT_FLAG_ONE_LIGHT picked by a descent of the light tree, weighted by power over squared distance ----
+// (include/trt.h states the contract: every operation below is the fp32 operation it names, in that order.)
+// The importance of one child of a node at P: its weight over max(|P - centre|^2, |hi - centre|^2), centre = 0.5 lo + 0.5 hi per axis.
+TRT_HD inline float lightChildImportance(const float* lo, const float* hi, float w, f3 P)
+{
+    const f3 c = mk3(0.5f * lo[0] + 0.5f * hi[0], 0.5f * lo[1] + 0.5f * hi[1], 0.5f * lo[2] + 0.5f * hi[2]);
+    const f3 e = mk3(hi[0] - c.x, hi[1] - c.y, hi[2] - c.z), q = mk3(P.x - c.x, P.y - c.y, P.z - c.z);
+    const float r2 = (e.x * e.x + e.y * e.y) + e.z * e.z, d2 = (q.x * q.x + q.y * q.y) + q.z * q.z;
+    return w / fmaxf(d2, r2);
+}
+// One level of the descent for a given uniform u: -> the reference of the child picked, inv_p multiplied by the reciprocal of its probability.
+TRT_HD inline uint32_t lightNodeStep(const LightNode& n, f3 P, float u, float& inv_p)
+{
+    float imp0 = lightChildImportance(n.lo0, n.hi0, n.w0, P), imp1 = lightChildImportance(n.lo1, n.hi1, n.w1, P);
+    float s = imp0 + imp1;
+    if (!(imp0 >= 0.0f && imp1 >= 0.0f && s > 0.0f && s < __builtin_inff())) {  // (a NaN lands here too) by power alone at this node
+        imp0 = n.w0; imp1 = n.w1;
+        s = imp0 + imp1;
+    }
+    const float r = u * s;
+    bool first = r < imp0;
+    if (!((first ? imp0 : imp1) > 0.0f)) first = !first;
+    inv_p = inv_p * (s / (first ? imp0 : imp1));
+    return first ? n.child0 : n.child1;
+}
+// Draws the light the vertex at P samples: li, and inv_p, the factor its contribution takes.  -> false: no light is sampled at this vertex (no tree
+// light, or an inv_p that is not finite).  Fewer than two lights: nothing to pick, no draw (lightPick's answer); one tree light: that one, no draw;
+// otherwise one draw per level of the tree, at most 16.  Every index returned lies in [0, n_lights).
+TRT_HD inline bool lightPickNear(const SceneDev& sc, f3 P, Stream& rng, uint32_t& li, float& inv_p)
+{
+    li = 0u;
+    inv_p = 1.0f;
+    if (sc.n_lights < 2u) return sc.n_lights == 1u;
+    uint32_t ref = sc.light_root;
+    if (ref == TRT_LIGHT_NONE) return false;
+    float ip = 1.0f;
+    while (!(ref & TRT_LIGHT_LEAF)) {
+        const LightNode n = sc.light_nodes[ref];  // whole record: four 16-B loads
+        ref = lightNodeStep(n, P, rng.next(), ip);
+    }
+    li = ref & ~TRT_LIGHT_LEAF;
+    if (!(fabsf(ip) < __builtin_inff())) return false;  // not finite: the draws are spent
+    inv_p = ip;
+    return true;
+}
+
 // Path-state word carried with every queued ray.
 //   bits 0..15  next RNG draw index        bits 16..17 type of the ray being traced
 //   (3 = camera ray)                       bits 20..31 path depth (vertex index)
@@ -973,6 +1035,7 @@ struct TileDesc {
     // kept whatever the rectangle says.  All zero — every other entry point — culls nothing.
     int32_t cull[8];
     uint32_t one_light;   // TRT_FLAG_ONE_LIGHT on a scene of two or more lights: a vertex samples the one light lightPick() draws (read by the light loops of k_shade and k_tail only)
+    uint32_t near_lights; // TRT_FLAG_NEAR_LIGHTS with one_light: that light is lightPickNear()'s, by power over squared distance (read by k_tail's light loop; k_shade has a flavour for it)
 };
 
 // Is the camera ray of image pixel (y, x) culled?  (Outside the rectangle and in neither band.)

@@ -19,7 +19,7 @@ static void usage()
 {
     std::fprintf(stderr,
                  "usage: tinyrt <basedir> <mtl> <xml> <obj> <spp> [--width W --height H] [--seed S] [--device D | --gpus N | --devices a,b,..]\n"
-                 "              [--leaf N] [--gpu-bvh] [--max-depth D] [--out file.png] [--fixed | --fixed-nee | --fixed-pixels] [--one-light] [--ray-offset] [--specular-ks] [--polygons]\n"
+                 "              [--leaf N] [--gpu-bvh] [--max-depth D] [--out file.png] [--fixed | --fixed-nee | --fixed-pixels] [--one-light | --near-lights] [--ray-offset] [--specular-ks] [--polygons]\n"
                  "              [--every N] [--checkpoint file.acc] [--stop-after M] [--aov PREFIX [--aov-spp N]] [--denoise file.png]\n"
                  "                                                    progressive: N samples per step, image rewritten after\n"
                  "                                                    every step, accumulator kept in file.acc (resumes from it)\n"
@@ -74,6 +74,7 @@ int main(int argc, char** argv)
         else if (!std::strcmp(argv[i], "--out")) out_path = need("--out");
         else if (!std::strcmp(argv[i], "--fixed-nee")) opts.fixed_nee = true;
         else if (!std::strcmp(argv[i], "--one-light")) opts.fixed_nee = opts.one_light = true;  // TRT_FLAG_ONE_LIGHT needs TRT_FLAG_FIXED_NEE
+        else if (!std::strcmp(argv[i], "--near-lights")) opts.fixed_nee = opts.one_light = opts.near_lights = true;  // TRT_FLAG_NEAR_LIGHTS needs TRT_FLAG_ONE_LIGHT
         else if (!std::strcmp(argv[i], "--fixed-pixels")) opts.fixed_pixels = true;
         else if (!std::strcmp(argv[i], "--ray-offset")) opts.ray_offset = true;
         else if (!std::strcmp(argv[i], "--specular-ks")) opts.specular_ks = true;  // the look of the reference's own saved renders (TRT_FLAG_SPECULAR_KS)

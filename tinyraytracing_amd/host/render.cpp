@@ -152,7 +152,7 @@ void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stat
     p.x0 = 0; p.y0 = 0; p.x1 = p.width; p.y1 = p.height;
     p.row_block = 1; p.row_mod = 1; p.row_rem = 0;
     p.max_depth = opts.max_depth;
-    p.flags = (opts.timing ? TRT_FLAG_TIMING : 0u) | (opts.overlap ? TRT_FLAG_OVERLAP : 0u) | (opts.fixed_nee ? TRT_FLAG_FIXED_NEE : 0u) | (opts.one_light ? TRT_FLAG_ONE_LIGHT : 0u) | (opts.fixed_pixels ? TRT_FLAG_FIXED_PIXELS : 0u) | (opts.ray_offset ? TRT_FLAG_RAY_OFFSET : 0u) | (opts.specular_ks ? TRT_FLAG_SPECULAR_KS : 0u);
+    p.flags = (opts.timing ? TRT_FLAG_TIMING : 0u) | (opts.overlap ? TRT_FLAG_OVERLAP : 0u) | (opts.fixed_nee ? TRT_FLAG_FIXED_NEE : 0u) | (opts.one_light ? TRT_FLAG_ONE_LIGHT : 0u) | (opts.near_lights ? TRT_FLAG_NEAR_LIGHTS : 0u) | (opts.fixed_pixels ? TRT_FLAG_FIXED_PIXELS : 0u) | (opts.ray_offset ? TRT_FLAG_RAY_OFFSET : 0u) | (opts.specular_ks ? TRT_FLAG_SPECULAR_KS : 0u);
     p.mem_budget = opts.mem_budget;
     std::vector<float> out((size_t)p.width * p.height * 3);
     int rc = TRT_OK;
@@ -194,7 +194,7 @@ void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stat
         // progressive: the accumulator lives on the host between calls (and in the checkpoint file)
         std::vector<double> accum(out.size(), 0.0);
         int done = 0;
-        const uint32_t est_flags = p.flags & (TRT_FLAG_FIXED_NEE | TRT_FLAG_FIXED_PIXELS | TRT_FLAG_RAY_OFFSET | TRT_FLAG_SPECULAR_KS | TRT_FLAG_ONE_LIGHT);
+        const uint32_t est_flags = p.flags & (TRT_FLAG_FIXED_NEE | TRT_FLAG_FIXED_PIXELS | TRT_FLAG_RAY_OFFSET | TRT_FLAG_SPECULAR_KS | TRT_FLAG_ONE_LIGHT | TRT_FLAG_NEAR_LIGHTS);
         const uint64_t scene_hash = opts.checkpoint.empty() ? 0ull : sceneHash(flat.c_scene());
         try {
             Checkpoint ck;
@@ -202,7 +202,7 @@ void render(Scene& scene, const RenderOpts& opts, double* image, trt_stats* stat
             if (!opts.checkpoint.empty() && readCheckpoint(opts.checkpoint, ck, saved)) {
                 if (ck.width != p.width || ck.height != p.height || ck.spp != p.spp || ck.seed != p.seed || ck.max_depth != p.max_depth)
                     throw std::runtime_error("checkpoint " + opts.checkpoint + " belongs to another render (size, spp, seed or max depth differ)");
-                if (ck.flags != est_flags) throw std::runtime_error("checkpoint " + opts.checkpoint + " was accumulated with another estimator (--fixed-nee / --fixed-pixels / --ray-offset / --one-light differ)");
+                if (ck.flags != est_flags) throw std::runtime_error("checkpoint " + opts.checkpoint + " was accumulated with another estimator (--fixed-nee / --fixed-pixels / --ray-offset / --one-light / --near-lights differ)");
                 if (ck.n_triangles != flat.c_scene()->n_tris || ck.n_nodes != flat.c_scene()->n_nodes || ck.scene_hash != scene_hash)
                     throw std::runtime_error("checkpoint " + opts.checkpoint + " belongs to another scene (triangles, BVH or scene hash differ)");
                 accum.swap(saved);

@@ -31,6 +31,7 @@ struct RenderOpts {
     bool specular_ks = false; // TRT_FLAG_SPECULAR_KS: SPECULAR bounces weighted by Ks, the look of the reference's own saved renders (include/trt.h)
     bool fixed_nee = false;   // TRT_FLAG_FIXED_NEE: unbiased light sampling + occlusion-test shadow rays instead of quirks Q3-Q5
     bool one_light = false;   // TRT_FLAG_ONE_LIGHT: one light per path vertex, picked by power (with fixed_nee)
+    bool near_lights = false; // TRT_FLAG_NEAR_LIGHTS: that light picked by power over squared distance from the vertex (with one_light)
     // Progressive output (trt_render_samples): render `every` samples per call (0 = all in one call), hand the
     // image so far to `on_progress`, and keep the accumulator in `checkpoint` (written after every call, atomically;
     // read at start: a file that matches width/height/spp/seed/max_depth resumes where it stopped).
