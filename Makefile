@@ -45,7 +45,7 @@ oracle:
 hostsim: tests/hostsim/libhostsim.so
 tests/hostsim/libhostsim.so: tests/hostsim/hostsim.cpp $(wildcard tests/hostsim/*.h) $(wildcard tests/refit/*.h) tools/shade_cases.h $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/hostsim/hostsim.cpp
-# deliberately altered copies of three shading functions run through the sections of tools/shade_cases.h, for the sensitivity check of tests/test_shade_cases_cpu.py
+# deliberately altered copies of shading and light-picking functions run through the sections of tools/shade_cases.h, for the sensitivity check of tests/test_shade_cases_cpu.py
 shademutants: tests/hostsim/libshade_mutants.so
 tests/hostsim/libshade_mutants.so: tests/hostsim/shade_mutants.cpp tests/hostsim/shade_cases_host.h tools/shade_cases.h $(HIP_HDR)
 	$(CXX) $(CXXFLAGS) -fopenmp -I$(PKG)/csrc -shared -o $@ tests/hostsim/shade_mutants.cpp
@@ -136,7 +136,7 @@ nodecheck: tools/node_visit_check
 tools/node_visit_check: tools/node_visit_check.hip $(HIP_HDR)
 	$(HIPCC) $(HIPFLAGS) -o $@ tools/node_visit_check.hip
 
-# the shading functions (cameraRay, makeVertex, lightSample, nextRay, sampleDir, shadeBegin / shadeNext) and the primitives under them as gfx950 compiles
+# the shading functions (cameraRay, makeVertex, lightSample, nextRay, sampleDir, shadeBegin / shadeNext), the light pickers (lightPickAt, lightNodeStep, lightPickNear) and the primitives under them as gfx950 compiles
 # them (the flags of the library), one thread per case, and digests over all 2^24 uniforms: run by tests/test_gpu_shade_cases.py
 shadecheck: tools/shade_case_check
 tools/shade_case_check: tools/shade_case_check.hip tools/shade_cases.h $(HIP_HDR)

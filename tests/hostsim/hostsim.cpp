@@ -836,12 +836,18 @@ extern "C" int hostsim_shade_case_file(const uint8_t* buf, uint64_t size, uint32
 {
     return shadecases::runFileHost<shadecases::HeaderFns>(buf, size, out, n_words);
 }
-// digests first .. first + n - 1 of the tool's digest mode (digestAt)
+// digests first .. first + n - 1 of the tool's modes digest (digestAt) and, behind those, digest-pickers (pickerDigestAt)
 extern "C" int hostsim_shade_digests(uint32_t first, uint64_t n, uint64_t* out)
 {
-    if ((uint64_t)first + n > shadecases::digestTotal()) return 2;
+    const uint32_t fns = shadecases::digestTotal();
+    if ((uint64_t)first + n > (uint64_t)fns + shadecases::pickerDigestTotal()) return 2;
+    std::vector<shadecases::DigestPools> pools(1);
+    shadecases::digestPoolsFill(pools[0]);
 #pragma omp parallel for schedule(dynamic, 64)
-    for (long long i = 0; i < (long long)n; ++i) out[i] = shadecases::digestAt(first + (uint32_t)i);
+    for (long long i = 0; i < (long long)n; ++i) {
+        const uint32_t k = first + (uint32_t)i;
+        out[i] = k < fns ? shadecases::digestAt(k) : shadecases::pickerDigestAt(pools[0], k - fns);
+    }
     return 0;
 }
 // the table records a handle forms from the caller's (makeMaterialDev)

@@ -36,6 +36,14 @@ inline int runFileHost(const uint8_t* buf, uint64_t size, uint32_t* out, uint64_
     const auto next = section<NextCase>(v.next, h.n_next);
     const auto dir = section<DirCase>(v.dir, h.n_dir);
     const auto bounce = section<BounceCase>(v.bounce, h.n_bounce);
+    const auto plights = section<LightDev>(v.plights, h.n_plights);
+    const auto psel = section<float>(v.psel, h.n_psel);
+    const auto pnodes = section<LightNode>(v.pnodes, h.n_pnodes);  // (over-aligned type: the vector's storage is 16-byte aligned)
+    const auto sets = section<LightSet>(v.sets, h.n_sets);
+    const auto pick = section<PickCase>(v.pick, h.n_pick);
+    const auto step = section<StepCase>(v.step, h.n_step);
+    const auto near = section<NearCase>(v.near, h.n_near);
+    const Pools pl{plights.data(), psel.data(), pnodes.data(), sets.data()};
     std::vector<float> cum(h.n_ltris ? h.n_ltris : 1);
     for (uint32_t i = 0; i < h.n_ltris; ++i) cum[i] = ltris[i].cum_area;
     int32_t rows[BOUNCE_ROWS];
@@ -71,6 +79,15 @@ inline int runFileHost(const uint8_t* buf, uint64_t size, uint32_t* out, uint64_
     o += (size_t)W_DIR * h.n_dir;
 #pragma omp parallel for schedule(static)
     for (long long i = 0; i < (long long)h.n_bounce; ++i) runBounce(sc, rows, bounce[i], o + (size_t)W_BOUNCE * i);
+    o += (size_t)W_BOUNCE * h.n_bounce;
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)h.n_pick; ++i) runPick<F>(pl, pick[i], o + (size_t)W_PICK * i);
+    o += (size_t)W_PICK * h.n_pick;
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)h.n_step; ++i) runStep<F>(step[i], o + (size_t)W_STEP * i);
+    o += (size_t)W_STEP * h.n_step;
+#pragma omp parallel for schedule(dynamic, 256)
+    for (long long i = 0; i < (long long)h.n_near; ++i) runNear(pl, near[i], o + (size_t)W_NEAR * i);
     return 0;
 }
 

@@ -1,9 +1,13 @@
-// shade_mutants.cpp — TEST INFRASTRUCTURE.  Deliberately WRONG local copies of three functions of trt_path.h, run through the sections of
+// shade_mutants.cpp — TEST INFRASTRUCTURE.  Deliberately WRONG local copies of functions of trt_path.h, run through the sections of
 // tools/shade_cases.h, for the sensitivity check of tests/test_shade_cases_cpu.py: a corpus that cannot tell these from the headers' own functions
 // does not test the decision each of them bends.  Nothing else loads this library; the product headers are untouched.
 //   mutant 1: the CDF pick of lightSample compares `rnd <= cum` instead of `rnd < cum` (both the bisection and the scan)
 //   mutant 2: refract returns the zero vector for `k <= 0` instead of `k < 0`
 //   mutant 3: makeVertex takes the texel column (int)(icol * width) in fp32 instead of binary64
+//   mutant 4: the bisection of lightPickAt compares `r <= light_sel[mid]` instead of `r < light_sel[mid]`
+//   mutant 5: lightNodeStep picks the first child for `r <= imp0` instead of `r < imp0`
+//   mutant 6: lightNodeStep without the flip away from a child whose importance is not > 0
+//   mutant 7: lightChildImportance divides by d2 alone, without the fmaxf with r2
 #include "shade_cases_host.h"
 
 using namespace trtd;
@@ -72,6 +76,55 @@ Vertex makeVertexF32(const SceneDev& sc, const Hit& h, f3 o, f3 d, const TriShad
     return vx;
 }
 
+// lightPickAt (trt_path.h) with the one comparison of its bisection bent; the scan form is the header's
+bool lightPickAtLe(const SceneDev& sc, float u, uint32_t& li, float& inv_p)
+{
+    if (!sc.light_sel) return lightPickAt(sc, u, li, inv_p);
+    const uint32_t n = sc.n_lights;
+    li = 0u;
+    inv_p = 1.0f;
+    const float total = sc.light_sel[n - 1u];
+    if (!(total > 0.0f && total < __builtin_inff())) return false;
+    const float r = u * total;
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (r <= sc.light_sel[mid]) hi = mid; else lo = mid + 1;
+    }
+    uint32_t pick = lo;
+    if (pick >= n) {
+        pick = 0u;
+        for (uint32_t l = n; l-- > 0u;)
+            if (lightWeight(sc.lights[l]) > 0.0f) { pick = l; break; }
+    }
+    li = pick;
+    inv_p = total / lightWeight(sc.lights[pick]);
+    return true;
+}
+float childImportanceD2(const float* lo, const float* hi, float w, f3 P)
+{
+    const f3 c = mk3(0.5f * lo[0] + 0.5f * hi[0], 0.5f * lo[1] + 0.5f * hi[1], 0.5f * lo[2] + 0.5f * hi[2]);
+    const f3 q = mk3(P.x - c.x, P.y - c.y, P.z - c.z);
+    return w / ((q.x * q.x + q.y * q.y) + q.z * q.z);
+}
+// lightNodeStep (trt_path.h) with one decision bent: LE `r <= imp0`, FLIP the flip kept, R2 the fmaxf with r2 kept
+template <bool LE, bool FLIP, bool R2>
+uint32_t nodeStepBent(const LightNode& n, f3 P, float u, float& inv_p)
+{
+    float imp0 = R2 ? lightChildImportance(n.lo0, n.hi0, n.w0, P) : childImportanceD2(n.lo0, n.hi0, n.w0, P);
+    float imp1 = R2 ? lightChildImportance(n.lo1, n.hi1, n.w1, P) : childImportanceD2(n.lo1, n.hi1, n.w1, P);
+    float s = imp0 + imp1;
+    if (!(imp0 >= 0.0f && imp1 >= 0.0f && s > 0.0f && s < __builtin_inff())) {
+        imp0 = n.w0; imp1 = n.w1;
+        s = imp0 + imp1;
+    }
+    const float r = u * s;
+    bool first = LE ? r <= imp0 : r < imp0;
+    if (FLIP && !((first ? imp0 : imp1) > 0.0f)) first = !first;
+    inv_p = inv_p * (s / (first ? imp0 : imp1));
+    return first ? n.child0 : n.child1;
+}
+
 struct PickLe : shadecases::HeaderFns {
     static bool lightSample(const SceneDev& sc, const Vertex& vx, const MaterialDev& m, uint32_t li, Stream& rng, f3& wo, f3& contrib, bool fixed, float& t_max)
     {
@@ -85,6 +138,18 @@ struct RefractLe : shadecases::HeaderFns {
 struct TexelF32 : shadecases::HeaderFns {
     static Vertex makeVertex(const SceneDev& sc, const Hit& h, f3 o, f3 d, const TriShade& ts, const MaterialDev& m) { return makeVertexF32(sc, h, o, d, ts, m); }
 };
+struct BisectLe : shadecases::HeaderFns {
+    static bool lightPickAt(const SceneDev& sc, float u, uint32_t& li, float& inv_p) { return lightPickAtLe(sc, u, li, inv_p); }
+};
+struct StepLe : shadecases::HeaderFns {
+    static uint32_t lightNodeStep(const LightNode& n, f3 P, float u, float& inv_p) { return nodeStepBent<true, true, true>(n, P, u, inv_p); }
+};
+struct StepNoFlip : shadecases::HeaderFns {
+    static uint32_t lightNodeStep(const LightNode& n, f3 P, float u, float& inv_p) { return nodeStepBent<false, false, true>(n, P, u, inv_p); }
+};
+struct StepNoR2 : shadecases::HeaderFns {
+    static uint32_t lightNodeStep(const LightNode& n, f3 P, float u, float& inv_p) { return nodeStepBent<false, true, false>(n, P, u, inv_p); }
+};
 }  // namespace
 
 // mutant 0 is the headers' own functions (the control: the words of hostsim_shade_case_file)
@@ -95,6 +160,10 @@ extern "C" int shade_mutant_case_file(int mutant, const uint8_t* buf, uint64_t s
     case 1: return shadecases::runFileHost<PickLe>(buf, size, out, n_words);
     case 2: return shadecases::runFileHost<RefractLe>(buf, size, out, n_words);
     case 3: return shadecases::runFileHost<TexelF32>(buf, size, out, n_words);
+    case 4: return shadecases::runFileHost<BisectLe>(buf, size, out, n_words);
+    case 5: return shadecases::runFileHost<StepLe>(buf, size, out, n_words);
+    case 6: return shadecases::runFileHost<StepNoFlip>(buf, size, out, n_words);
+    case 7: return shadecases::runFileHost<StepNoR2>(buf, size, out, n_words);
     default: return 2;
     }
 }

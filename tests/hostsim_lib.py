@@ -339,7 +339,7 @@ def make_material_dev(raw):
 
 def shade_case_words(file_bytes, n_words, mutant=None):
     """The output words of a whole case file (shade_cases.case_bytes), in the tool's order; None for a file the tool refuses (exit code 2).
-    mutant 1..3: the same sections on the altered copies of tests/hostsim/shade_mutants.cpp (0: its copy of the headers' own)."""
+    mutant 1..7: the same sections on the altered copies of tests/hostsim/shade_mutants.cpp (0: its copy of the headers' own)."""
     buf = np.frombuffer(file_bytes, np.uint8)
     out = np.zeros(n_words, np.uint32)
     if mutant is None:

@@ -98,6 +98,46 @@ def tables_of(flat):
     return t
 
 
+def random_tables(L, seed):
+    rng = np.random.default_rng(seed)
+    area = rng.uniform(0.01, 10.0, L).astype(np.float32)
+    rad = rng.uniform(0.0, 40.0, (L, 3)).astype(np.float32)
+    area[rng.random(L) < 0.2] = 0.0  # lights without area
+    rad[rng.random(L) < 0.1] = 0.0   # black lights
+    centres = rng.uniform(-20.0, 20.0, (L, 3)) * np.array([1.0, 0.2, 0.5])
+    centres[rng.random(L) < 0.1] = centres[0]  # coincident lights
+    return Tables.quads(area, rad, centres, rng.uniform(0.0, 1.5, L))
+
+
+def shared_tables():
+    """(name, Tables): the corridors, lamps, staircase, random tables of 300 lights (tests/test_near_lights_cpu.py; the picker sections of tests/shade_cases.py)."""
+    import near_cases as NC
+    from conftest import get_scene
+    for K in (2, 3, 16):
+        yield f"corridor({K})", tables_of(NC.corridor(K, 24, 16).flat)
+    for key in ("coincident", "black", "degenerate"):
+        yield key, tables_of(NC.scene(key, 24, 16).flat)
+    for n in (7, 64, 300):
+        yield f"lamps n={n}", tables_of(get_scene("lamps", 24, 16, n=n).flat)
+    yield "staircase", tables_of(get_scene("staircase", 24, 16).flat)
+    for k in range(3):
+        yield f"random {k}, L=300", random_tables(300, 0x7EE0 + k)
+
+
+def hostile_tables():
+    """Fourteen lights of which only 11, 12 and 13 may enter the tree: NaN, negative, zero and infinite areas and radiances, a NaN and an infinite vertex, no triangles."""
+    inf, nan = np.float32(np.inf), np.float32(np.nan)
+    area = np.array([nan, -1.0, 0.0, inf, 2.0, 2.0, 2.0, 2.0, 1.0, 1.0, 1.0, 1.0, 1.5, 2.5], np.float32)
+    rad = np.ones((14, 3), np.float32)
+    rad[4], rad[5], rad[6], rad[7] = [nan, 1, 1], [-5, 0, 0], [inf, 0, 0], [0, 0, 0]
+    centres = np.arange(14 * 3, dtype=np.float32).reshape(14, 3)
+    t = Tables.quads(area, rad, centres, 0.5)
+    t.verts[2 * 8, 1, 2] = nan       # a NaN vertex
+    t.verts[2 * 9 + 1, 0, 0] = -inf  # an infinite one
+    t.tri_count[10] = 0              # no triangles
+    return t
+
+
 def tree(t):
     """buildLightTree on the tables -> (nodes [M - 1] of NODE, root reference, M)."""
     nodes = np.zeros(max(t.n, 2) - 1, NODE)

@@ -22,31 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ULP = 2.0 ** -23
 
 
-def _random_tables(L, seed):
-    rng = np.random.default_rng(seed)
-    area = rng.uniform(0.01, 10.0, L).astype(np.float32)
-    rad = rng.uniform(0.0, 40.0, (L, 3)).astype(np.float32)
-    area[rng.random(L) < 0.2] = 0.0  # lights without area
-    rad[rng.random(L) < 0.1] = 0.0   # black lights
-    centres = rng.uniform(-20.0, 20.0, (L, 3)) * np.array([1.0, 0.2, 0.5])
-    centres[rng.random(L) < 0.1] = centres[0]  # coincident lights
-    return NL.Tables.quads(area, rad, centres, rng.uniform(0.0, 1.5, L))
-
-
-def _tables():
-    """(name, Tables): the corridors, lamps, staircase, random tables of 300 lights."""
-    for K in (2, 3, 16):
-        yield f"corridor({K})", NL.tables_of(NC.corridor(K, 24, 16).flat)
-    for key in ("coincident", "black", "degenerate"):
-        yield key, NL.tables_of(NC.scene(key, 24, 16).flat)
-    for n in (7, 64, 300):
-        yield f"lamps n={n}", NL.tables_of(get_scene("lamps", 24, 16, n=n).flat)
-    yield "staircase", NL.tables_of(get_scene("staircase", 24, 16).flat)
-    for k in range(3):
-        yield f"random {k}, L=300", _random_tables(300, 0x7EE0 + k)
-
-
-TABLES = list(_tables())
+TABLES = list(NL.shared_tables())
 
 
 @pytest.mark.parametrize("name,t", TABLES, ids=[x[0] for x in TABLES])
@@ -130,15 +106,7 @@ def test_descent_against_the_restatement(name, t):
 
 
 def test_hostile_tables_never_enter_the_tree():
-    inf, nan = np.float32(np.inf), np.float32(np.nan)
-    area = np.array([nan, -1.0, 0.0, inf, 2.0, 2.0, 2.0, 2.0, 1.0, 1.0, 1.0, 1.0, 1.5, 2.5], np.float32)
-    rad = np.ones((14, 3), np.float32)
-    rad[4], rad[5], rad[6], rad[7] = [nan, 1, 1], [-5, 0, 0], [inf, 0, 0], [0, 0, 0]
-    centres = np.arange(14 * 3, dtype=np.float32).reshape(14, 3)
-    t = NL.Tables.quads(area, rad, centres, 0.5)
-    t.verts[2 * 8, 1, 2] = nan       # a NaN vertex
-    t.verts[2 * 9 + 1, 0, 0] = -inf  # an infinite one
-    t.tri_count[10] = 0              # no triangles
+    t = NL.hostile_tables()
     nodes, root, M = NL.tree(t)
     depth = NL.depth_of(nodes, root)
     assert sorted(depth) == [11, 12, 13] == [x[0] for x in NL.tree_lights(t)] and M == 3

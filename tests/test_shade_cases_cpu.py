@@ -1,10 +1,15 @@
 """The corpus of tests/shade_cases.py proves itself on the CPU build (tests/hostsim), without a GPU: (a) it reaches every branch it is meant to reach, counted on the
-CPU build's words; (b) deliberately altered copies of three functions (tests/hostsim/shade_mutants.cpp) change words of their sections; (c) the words agree with
+CPU build's words; (b) deliberately altered copies of seven functions (tests/hostsim/shade_mutants.cpp) change words of their sections; (c) the words agree with
 float64 restatements in numpy of the continuous functions.  tests/test_gpu_shade_cases.py then holds gfx950's words to the same CPU build's."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
 import hostsim_lib as H
+import nearlights_lib as NL
+import onelight_lib as OL
 import shade_cases as SC
 
 F32 = np.float32
@@ -186,8 +191,249 @@ def test_direction_cases_put_k_on_both_sides_of_zero(run):
     _atleast({k_: v for k_, v in counts.items() if k_ != "k == 0"})
 
 
+# ---- the light pickers: coverage, the words restated in binary32, table against scan, the float64 restatements ---------------------------------------------------
+def _same_words(got, want_bits):
+    """got words == expected words, any NaN being the one canonical NaN."""
+    return got == np.where(np.isnan(f32(want_bits)), np.uint32(0x7FC00000), np.asarray(want_bits, np.uint32))
+
+
+def _pick_at(d, u):
+    """lightPickAt restated in binary32 on the set's table -> (ok, li, inv_p, r, idx: the search's result before the fall-back)."""
+    cdf, w, n = d["cdf"], d["w"], d["n"]
+    total = cdf[-1]
+    u = np.asarray(u, F32)
+    if not (total > 0 and total < np.inf):
+        z = np.zeros(len(u), np.int64)
+        return np.zeros(len(u), bool), z, np.ones(len(u), F32), np.zeros(len(u), F32), z
+    with np.errstate(all="ignore"):
+        r = (u * total).astype(F32)
+        idx = np.searchsorted(cdf, r, side="right")
+        li = np.where(idx >= n, np.flatnonzero(w > 0)[-1], idx)
+        return np.ones(len(u), bool), li, (total / w[li]).astype(F32), r, idx
+
+
+def test_pick_cases_reach_every_exit_of_lightPickAt_and_match_its_restatement(run):
+    """Every pick case's words are those of lightPickAt / lightPick / lightWeight restated in binary32 on the CPU build's own table (the steered strata among them: r on a
+    table entry picks the next light of positive weight, one float below it the entry's own); the table form and the scan form give identical words; each exit is taken."""
+    c, w, meta = run["cases"]["pick"], run["words"]["pick"], run["tb"]["meta"]
+    at, stream, weight = c["op"] < 2, (c["op"] == SC.PICK_TABLE) | (c["op"] == SC.PICK_SCAN), c["op"] == SC.PICK_WEIGHT
+    counts = {k: 0 for k in ("total not positive", "total not finite", "pick by bisection", "pick by scan", "the pick >= n fall-back", "a pick behind a zero-weight plateau",
+                             "r on the value of a plateau", "r on a table entry", "r one float below a table entry", "r one float above a table entry",
+                             "lightPick, fewer than two lights", "lightPick, one draw", "weight zero", "weight positive", "weight subnormal")}
+    for k, d in enumerate(meta["sets"]):
+        n, cdf, wt = d["n"], d["cdf"], d["w"]
+        for kind, sel in (("at", at & (c["set"] == k)), ("stream", stream & (c["set"] == k))):
+            if not sel.any():
+                continue
+            u = c["u"][sel] if kind == "at" else SC.uniform(c["k0"][sel], c["k1"][sel], c["ctr"][sel])
+            got = w[sel]
+            if n < 2:
+                assert (got[:, 0] == (n == 1)).all() and (got[:, 1] == 0).all() and (f32(got[:, 2]) == 1).all() and (got[:, 3] == c["ctr"][sel]).all(), d["name"]
+                counts["lightPick, fewer than two lights"] += int(sel.sum())
+                continue
+            ok, li, ip, r, idx = _pick_at(d, u)
+            assert (got[:, 0] == ok).all() and (got[:, 1] == np.where(ok, li, 0)).all() and _same_words(got[:, 2], SC.bits(np.where(ok, ip, 1))).all(), d["name"]
+            if kind == "stream":
+                assert (got[:, 3] == c["ctr"][sel] + 1).all()
+                counts["lightPick, one draw"] += int(sel.sum())
+                continue
+            assert (got[:, 3] == c["ctr"][sel]).all()
+            if not ok.any():
+                counts["total not positive" if not cdf[-1] > 0 else "total not finite"] += int(sel.sum())
+                continue
+            assert (wt[li] > 0).all(), f"{d['name']}: a light of weight zero was picked"
+            counts["pick by bisection"] += int((c["op"][sel] == SC.PICK_AT_TABLE).sum())
+            counts["pick by scan"] += int((c["op"][sel] == SC.PICK_AT_SCAN).sum())
+            counts["the pick >= n fall-back"] += int((idx >= n).sum())
+            behind = (li >= 1) & (wt[np.maximum(li, 1) - 1] == 0) & (idx < n)
+            counts["a pick behind a zero-weight plateau"] += int(behind.sum())
+            counts["r on the value of a plateau"] += int((behind & (r == cdf[np.maximum(li, 1) - 1])).sum())
+            code = meta["pick_u"][sel]
+            on = np.isin(r, cdf)
+            counts["r on a table entry"] += int((on & (code == SC.U_AT)).sum())
+            counts["r one float below a table entry"] += int((np.isin(np.nextafter(r, F32(np.inf)), cdf) & (code == SC.U_BELOW)).sum())
+            counts["r one float above a table entry"] += int((np.isin(np.nextafter(r, F32(-np.inf)), cdf) & (code == SC.U_ABOVE)).sum())
+            assert (on == (code == SC.U_AT))[np.isin(code, [SC.U_AT])].all()
+            assert (cdf[np.minimum(li, n - 1)][on & (idx < n)] > r[on & (idx < n)]).all()  # the strict `<`: r on cdf_l never picks l
+        sel = weight & (c["set"] == k)
+        assert np.array_equal(w[sel][:, 2], SC.bits(wt)) and np.array_equal(w[sel][:, 1], np.arange(n)), d["name"]
+        counts["weight zero"] += int((wt == 0).sum())
+        counts["weight positive"] += int((wt > 0).sum())
+        counts["weight subnormal"] += int(((wt > 0) & (wt < FLT_MIN)).sum())
+    _atleast({k_: v for k_, v in counts.items() if k_ != "weight subnormal"})
+    _atleast({"weight subnormal": counts["weight subnormal"]}, 5)
+    # table against scan: adjacent cases, the same set and uniform (or stream)
+    for a, b in ((SC.PICK_AT_TABLE, SC.PICK_AT_SCAN), (SC.PICK_TABLE, SC.PICK_SCAN)):
+        i = np.flatnonzero(c["op"] == a)
+        assert (c["op"][i + 1] == b).all() and all(np.array_equal(c[f][i], c[f][i + 1]) for f in ("set", "u", "k0", "k1", "ctr"))
+        assert np.array_equal(w[i], w[i + 1]), f"{int((w[i] != w[i + 1]).any(1).sum())} cases differ between the table and the scan"
+
+
+def test_pick_cases_agree_with_the_float64_search(run):
+    """OL.pick_f64 (r = u cdf_{L-1} exact) on the strata that are not steered onto a table entry: a pick may differ only within 4 ulp of an entry, in at most 1 % of a
+    stratum's cases, and inv_p is the one binary32 division cdf_{L-1} / w where it agrees (tests/test_one_light_cpu.py's rule).  The steered strata sit on a decision
+    by construction and are held to their expected words by the test above."""
+    c, w, meta = run["cases"]["pick"], run["words"]["pick"], run["tb"]["meta"]
+    tally = {code: [0, 0, 0] for code in (SC.U_RANDOM, SC.U_ZERO, SC.U_ULP, SC.U_LAST)}
+    for k, d in enumerate(meta["sets"]):
+        cdf = d["cdf"]
+        if d["n"] < 2 or not (cdf[-1] > 0 and cdf[-1] < np.inf):
+            continue
+        for code in tally:
+            sel = (c["op"] < 2) & (c["set"] == k) & (meta["pick_u"] == code)
+            if not sel.any():
+                continue
+            want, margin = OL.pick_f64(d["w"], cdf, c["u"][sel])
+            differ = w[sel][:, 1] != want
+            assert not (differ & (margin > 4.0)).any(), d["name"]
+            same = ~differ
+            with np.errstate(over="ignore"):  # (a subnormal weight under a large total: inv_p is +inf on either side)
+                assert np.array_equal(w[sel][same, 2], SC.bits((cdf[-1] / d["w"][want[same]]).astype(F32))), d["name"]
+            tally[code][0] += int(sel.sum()); tally[code][1] += int((margin <= 4.0).sum()); tally[code][2] += int(differ.sum())
+    print({code: t for code, t in tally.items()})
+    for code, (cases, near, wrong) in tally.items():  # (an edge uniform is one case per set and form)
+        assert cases >= (100 if code == SC.U_RANDOM else 50) and wrong <= 0.01 * cases, (code, cases, near, wrong)
+
+
+def _step_f64(nd, P, u):
+    """One level of NL.descend: r = u s in float64 against the binary32 importances -> (takes child 0, the binary32 factor s / imp, |r - imp0| in ulps of r)."""
+    imp0, imp1, s = NL.importances(nd, P)
+    with np.errstate(all="ignore"):
+        r = u.astype(np.float64) * s.astype(np.float64)
+        first = r < imp0
+        first = np.where(np.where(first, imp0, imp1) > 0, first, ~first)
+        ulp = np.spacing(np.maximum(r, 1e-38).astype(F32)).astype(np.float64)
+        return first, (s / np.where(first, imp0, imp1).astype(F32)).astype(F32), np.abs(r - imp0) / ulp
+
+
+def test_step_cases_reach_every_branch_of_lightNodeStep_and_match_its_restatements(run):
+    """Every step case's words are lightNodeStep restated in binary32 (SC.step_f32: the hand-made nodes, the points at infinity and with a NaN among them); each branch is
+    taken, counted on that restatement, which the words confirm; on nodes buildLightTree made and finite points the float64 decision of NL.descend agrees but within 4 ulp
+    of imp0, in at most 1 % of the cases of each stratum that is not steered onto imp0, with inv_p bit for bit where it agrees."""
+    c, w, meta = run["cases"]["step"], run["words"]["step"], run["tb"]["meta"]
+    S = SC.step_f32(c["node"], c["P"], c["u"], c["inv_p"])
+    assert np.array_equal(w[:, 0], S["child"]), int((w[:, 0] != S["child"]).sum())
+    assert _same_words(w[:, 1], SC.bits(S["inv_p"])).all()
+    built = np.array([d["built"] for d in meta["sets"]])[meta["step_set"]]
+
+    def subnormal(x):
+        with np.errstate(invalid="ignore"):
+            return (np.abs(x) > 0) & (np.abs(x) < FLT_MIN)
+    fb = S["fallback"]
+    counts = {"importance as computed": int((fb == 0).sum()), "by power: a NaN importance": int((fb == 1).sum()), "by power: s == 0": int((fb == 2).sum()),
+              "by power: s == inf": int((fb == 3).sum()), "by power: a negative importance": int((fb == 4).sum()), "the flip": int(S["flipped"].sum()),
+              "the flip on a built node": int((S["flipped"] & built).sum()), "r == imp0": int((S["r"] == S["imp0"]).sum()),
+              "r one float below imp0": int((np.nextafter(S["r"], F32(np.inf)) == S["imp0"]).sum()), "r one float above imp0": int((np.nextafter(S["r"], F32(-np.inf)) == S["imp0"]).sum()),
+              "a subnormal importance": int(((fb == 0) & (subnormal(S["imp0"]) | subnormal(S["imp1"]))).sum()), "a subnormal s": int(((fb == 0) & subnormal(S["s"])).sum()),
+              "a subnormal r": int(((fb == 0) & subnormal(S["r"])).sum()), "a hand-made node": int((~built).sum()), "child 0": int((w[:, 0] == c["node"]["child0"]).sum()),
+              "child 1": int((w[:, 0] == c["node"]["child1"]).sum()), "inv_p not finite": int((~np.isfinite(f32(w[:, 1]))).sum())}
+    for p in range(8):
+        counts[f"P stratum {p}"] = int((meta["step_p"] == p).sum())
+    assert (fb != 5).all()  # every fall-back has one of the four causes
+    # a NaN importance without a NaN in the inputs: on the hand-made nodes whose box corners are infinite the centre is infinite (or -inf + inf), so that hi - centre, and
+    # with P at the same infinity P - centre, is inf - inf
+    corners = meta["step_set"] == meta["by_name"]["hand: infinite box corners"]
+    with np.errstate(invalid="ignore"):
+        clean = ~np.isnan(c["P"]).any(1)
+        counts["a NaN importance by inf - inf"] = int((corners & clean & (np.isnan(S["raw0"]) | np.isnan(S["raw1"]))).sum())
+        counts["an infinite centre beside a finite point"] = int((corners & np.isfinite(c["P"]).all(1)).sum())
+    steered = {SC.U_AT: S["r"] == S["imp0"], SC.U_BELOW: np.nextafter(S["r"], F32(np.inf)) == S["imp0"], SC.U_ABOVE: np.nextafter(S["r"], F32(-np.inf)) == S["imp0"]}
+    for code, hit in steered.items():
+        assert hit[meta["step_u"] == code].all()
+    at = (meta["step_u"] == SC.U_AT) & ~S["flipped"]
+    assert (w[at, 0] == c["node"]["child1"][at]).all()  # `r < imp0`, strictly
+    _atleast(counts)
+    tally = {}
+    for code in (SC.U_RANDOM, SC.U_ZERO, SC.U_ULP, SC.U_LAST):
+        sel = built & np.isin(meta["step_p"], SC.P_FINITE) & (meta["step_u"] == code)
+        first, factor, margin = _step_f64(c["node"][sel], c["P"][sel], c["u"][sel])
+        differ = (w[sel, 0] == c["node"]["child0"][sel]) != first
+        same_child = c["node"]["child0"][sel] == c["node"]["child1"][sel]
+        differ &= ~same_child
+        assert not (differ & (margin > 4.0)).any(), code
+        with np.errstate(all="ignore"):
+            want = (c["inv_p"][sel] * factor).astype(F32)
+        assert _same_words(w[sel, 1][~differ], SC.bits(want[~differ])).all(), code
+        tally[code] = (int(sel.sum()), int((margin <= 4.0).sum()), int(differ.sum()))
+        assert sel.sum() >= 100 and differ.sum() <= 0.01 * sel.sum(), tally
+    print(tally)
+
+
+def _descend_f32(d, P, k0, k1, ctr):
+    """lightPickNear restated in binary32 over SC.step_f32 -> (ok, li, inv_p, draws)."""
+    m = len(P)
+    if d["n"] < 2:
+        return np.full(m, d["n"] == 1), np.zeros(m, np.uint32), np.ones(m, F32), np.zeros(m, np.uint32)
+    if d["root"] == SC.NONE:
+        return np.zeros(m, bool), np.zeros(m, np.uint32), np.ones(m, F32), np.zeros(m, np.uint32)
+    ref, ip, draws = np.full(m, d["root"], np.uint32), np.ones(m, F32), np.zeros(m, np.uint32)
+    while True:
+        act = np.flatnonzero((ref & SC.LEAF) == 0)
+        if not len(act):
+            break
+        S = SC.step_f32(d["nodes"][ref[act]], P[act], SC.uniform(k0[act], k1[act], ctr[act] + draws[act]), ip[act])
+        ref[act], ip[act] = S["child"], S["inv_p"]
+        draws[act] += 1
+    ok = np.isfinite(ip)
+    return ok, ref & ~np.uint32(SC.LEAF), np.where(ok, ip, F32(1)), draws
+
+
+def test_near_cases_reach_every_exit_of_lightPickNear_and_match_its_restatements(run):
+    """Every near case's words are lightPickNear restated in binary32 (hand-made nodes, infinite and NaN points among them); each exit is taken; every wave of 64 consecutive
+    cases, the last one too, mixes descents of depth 1 and of depth 16; on built trees and finite points NL.descend agrees by tests/test_near_lights_cpu.py's rule.
+    The exit for an inv_p that is not finite is reached on built trees: in the set `absorbed` (weights 1e-44 and 1e30 under one node) the first child is taken with
+    s / imp0 = +inf whenever the keyed uniform 0 makes r = 0 < imp0, and in the set `total +inf` the weights of a node sum to +inf, so that s / imp is inf / inf."""
+    c, w, meta = run["cases"]["near"], run["words"]["near"], run["tb"]["meta"]
+    draws = w[:, 3] - c["ctr"]
+    counts = {k: 0 for k in ("fewer than two lights", "TRT_LIGHT_NONE", "a leaf root", "a full-depth descent", "inv_p not finite", "inv_p not finite on a built tree",
+                             "hand-made nodes", "a descent of depth 1")}
+    for p in range(8):
+        counts[f"P stratum {p}"] = int((meta["near_p"] == p).sum())
+    for u in range(7):
+        counts[f"stream stratum {u}"] = int((meta["near_u"] == u).sum())
+    tally = {code: [0, 0, 0] for code in (SC.U_RANDOM, SC.U_ZERO, SC.U_ULP, SC.U_LAST)}
+    for k, d in enumerate(meta["sets"]):
+        sel = c["set"] == k
+        ok, li, ip, n_draws = _descend_f32(d, c["P"][sel], c["k0"][sel], c["k1"][sel], c["ctr"][sel])
+        got = w[sel]
+        assert (got[:, 0] == ok).all() and (got[:, 1] == li).all() and _same_words(got[:, 2], SC.bits(ip)).all() and (draws[sel] == n_draws).all(), d["name"]
+        assert (li < max(d["n"], 1)).all()
+        inner = d["n"] >= 2 and d["root"] != SC.NONE and not d["root"] & SC.LEAF
+        counts["fewer than two lights"] += int(sel.sum()) if d["n"] < 2 else 0
+        counts["TRT_LIGHT_NONE"] += int(sel.sum()) if d["n"] >= 2 and d["root"] == SC.NONE else 0
+        counts["a leaf root"] += int(sel.sum()) if d["n"] >= 2 and d["root"] != SC.NONE and d["root"] & SC.LEAF else 0
+        counts["a full-depth descent"] += int((n_draws == 16).sum())
+        counts["a descent of depth 1"] += int((n_draws == 1).sum())
+        counts["inv_p not finite"] += int((~ok).sum()) if inner else 0
+        counts["inv_p not finite on a built tree"] += int((~ok).sum()) if inner and d["built"] else 0
+        counts["hand-made nodes"] += 0 if d["built"] else int(sel.sum())
+        if not (inner and d["built"]):
+            continue
+        # the float64 descent
+        U = np.stack([SC.uniform(c["k0"][sel], c["k1"][sel], c["ctr"][sel] + j) for j in range(NL.MAX_DEPTH)], 1)
+        finite = np.isin(meta["near_p"][sel], SC.P_FINITE)
+        want = NL.descend(d["nodes"].view(NL.NODE), d["root"], c["P"][sel][finite], U[finite])
+        g_li, g_ip, g_ok = got[finite, 1], got[finite, 2], got[finite, 0] == 1
+        differ = g_li != want["index"]
+        assert not (differ & (want["margin"] > 4.0)).any(), d["name"]
+        same = ~differ
+        assert (g_ok[same] == np.isfinite(want["inv_p32"][same])).all(), d["name"]
+        assert _same_words(g_ip[same & g_ok], SC.bits(want["inv_p32"][same & g_ok])).all(), d["name"]
+        for code in tally:
+            t = meta["near_u"][sel][finite] == code
+            tally[code][0] += int(t.sum()); tally[code][1] += int((want["margin"][t] <= 4.0).sum()); tally[code][2] += int(differ[t].sum())
+    _atleast(counts)
+    print(tally)
+    for code, (cases, near, wrong) in tally.items():
+        assert cases >= 100 and wrong <= 0.01 * cases, (code, cases, near, wrong)
+    waves = [draws[i:i + 64] for i in range(0, len(c), 64)]  # every wave, the last and partial one too
+    assert min((wv == 16).sum() for wv in waves) >= 4 and min((wv == 1).sum() for wv in waves) >= 4, "a wave without descents of depth 1 and of depth 16"
+
+
 # ---- (b) sensitivity ------------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mutant,section,what", [(1, "light", "`rnd <= cum` in the CDF pick"), (2, "dir", "`k <= 0` in refract"), (3, "vert", "the texel column taken in fp32")])
+@pytest.mark.parametrize("mutant,section,what", [(1, "light", "`rnd <= cum` in the CDF pick"), (2, "dir", "`k <= 0` in refract"), (3, "vert", "the texel column taken in fp32"),
+                                                 (4, "pick", "`r <= light_sel[mid]` in lightPickAt's bisection"), (5, "step", "`r <= imp0` in lightNodeStep"),
+                                                 (6, "step", "lightNodeStep without the flip"), (7, "step", "lightChildImportance with d2 alone")])
 def test_an_altered_function_changes_words_of_its_section(run, mutant, section, what):
     control = SC.split_words(H.shade_case_words(run["data"], run["n_words"], mutant=0), run["n"])
     for s in SC.SECTIONS:
@@ -199,7 +445,18 @@ def test_an_altered_function_changes_words_of_its_section(run, mutant, section, 
     assert all(v == 0 for s, v in changed.items() if s != section), changed
 
 
-def test_a_file_with_an_index_out_of_range_is_refused(run):
+def _tool_refuses(tmp_path, data, why):
+    """tools/shade_case_check itself on the file: exit code 2 with the rule's message and no result file — parse runs before the device is touched, so this needs no GPU."""
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "shade_case_check")
+    assert os.path.exists(exe), "tools/shade_case_check is not built (make shadecheck)"
+    case_file, result_file = str(tmp_path / "bad.bin"), str(tmp_path / "bad.out")
+    with open(case_file, "wb") as f:
+        f.write(data)
+    r = subprocess.run([exe, case_file, result_file], capture_output=True, text=True, timeout=60)
+    return r.returncode == 2 and why in r.stderr and not os.path.exists(result_file)
+
+
+def test_a_file_with_an_index_out_of_range_is_refused(run, tmp_path):
     tb = run["tb"]
     small = {s: run["cases"][s][:8].copy() for s in SC.SECTIONS}
 
@@ -228,23 +485,59 @@ def test_a_file_with_an_index_out_of_range_is_refused(run):
         assert refused(dict(tb, **{table: t})), (table, field)
     data, n = SC.case_bytes(tb, small)
     assert H.shade_case_words(data[:-16], sum(n[s] * SC.WORDS[s] for s in SC.SECTIONS)) is None
+    # the layout from before the light pickers (its magic, the first 64 B of the header, no pools) is read as a file without picker cases: the same words
+    seven = {s: small[s] for s in SC.SECTIONS[:7]}
+    data, n = SC.case_bytes(dict(tb, **SC.no_pools()), seven)
+    n_words = sum(n[s] * SC.WORDS[s] for s in SC.SECTIONS)
+    before = np.array([SC.MAGIC_1], "<u4").tobytes() + data[4:64] + data[96:]
+    assert np.array_equal(H.shade_case_words(before, n_words), H.shade_case_words(data, n_words))
+    assert H.shade_case_words(before[:-16], n_words) is None and H.shade_case_words(before[:60], n_words) is None
+    # the light sets: one file per rule.  Set `k`: corridor(16), fifteen nodes in pre-order, node 0 holds two inner references
+    k = tb["meta"]["by_name"]["corridor(16)"]
+    st = tb["sets"][k]
+    assert st["n_nodes"] == 15 and not (tb["pnodes"]["child0"][st["node_first"]] | tb["pnodes"]["child1"][st["node_first"]]) & SC.LEAF
+    for field, value, why in (("light_first", len(tb["plights"]), "lights leave the pool"), ("n_lights", len(tb["plights"]) + 1, "lights leave the pool"),
+                              ("sel_first", len(tb["psel"]), "selection table leaves the pool"), ("node_first", len(tb["pnodes"]), "nodes leave the pool"),
+                              ("n_nodes", len(tb["pnodes"]) + 1, "nodes leave the pool"), ("root", 15, "root is outside the set's nodes"),
+                              ("root", SC.LEAF | 16, "root names a light outside the set")):
+        sets = tb["sets"].copy()
+        sets[field][k] = value
+        assert refused(dict(tb, sets=sets)), field
+        assert _tool_refuses(tmp_path, SC.case_bytes(dict(tb, sets=sets), small)[0], why), field
+    sets = tb["sets"].copy()
+    sets["sel_first"][small["pick"]["set"][0]] = SC.NO_TABLE  # a set without a table is sound, a case that asks for its table is not
+    assert small["pick"]["op"][0] == SC.PICK_AT_TABLE and refused(dict(tb, sets=sets)) and not refused(dict(tb, sets=sets), pick=small["pick"][1:2])
+    leaf_at = int(np.flatnonzero(tb["pnodes"]["child0"][st["node_first"]:st["node_first"] + 15] & SC.LEAF)[0])
+    for node, value, why in ((leaf_at, SC.LEAF | 16, "a leaf reference names a light outside its set"), (leaf_at, SC.NONE, "a leaf reference names a light outside its set"),
+                             (3, 3, "an inner reference is not greater than the index of the node that holds it"),
+                             (3, 1, "an inner reference is not greater than the index of the node that holds it"), (0, 15, "an inner reference is outside the set's nodes")):
+        nodes = tb["pnodes"].copy()
+        nodes["child0"][st["node_first"] + node] = value
+        assert refused(dict(tb, pnodes=nodes)), (node, value)
+        assert _tool_refuses(tmp_path, SC.case_bytes(dict(tb, pnodes=nodes), small)[0], why), (node, value)
+    assert not _tool_refuses(tmp_path, b"", "a leaf reference")  # (the helper can tell: an empty file is refused for another reason)
+    assert refused(**edit("pick", "op", 5)) and refused(**edit("pick", "set", len(tb["sets"]))) and refused(**edit("near", "set", len(tb["sets"])))
+    one = tb["meta"]["by_name"]["random, L=1"]
+    c = small["pick"].copy()
+    c["op"][0], c["set"][0] = SC.PICK_AT_SCAN, one  # lightPickAt is for two or more lights
+    assert refused(pick=c)
+    c["op"][0], c["li"][0] = SC.PICK_WEIGHT, 1
+    assert refused(pick=c)
+    c["li"][0] = 0
+    assert not refused(pick=c)
 
 
 def test_a_digest_is_the_sum_over_its_chunks_explicit_words():
-    """The digests are what the explicit cases compute: chunk 0x123 of sincos2pi, of pow01(u, 1/(250+1)) and chunk 5 of the logf range, from the words of the primitive section."""
+    """The digests are what the explicit cases compute: chunk 0x123 of sincos2pi, of pow01(u, 1/(250+1)), chunk 5 of the logf range, ..., and chunks of every stream of the
+    light pickers, from the words of the primitive, pick and step sections."""
     starts = np.cumsum([0] + [s[2] for s in SC.DIGEST_STREAMS])
-    for stream, chunk in ((0, 0x123), (6, 4095), (19, 5), (22, 8191), (25, 7), (2, 0), (21, 17)):
-        c = SC.digest_chunk_cases(stream, chunk)
-        data, n = SC.case_bytes(SC.no_tables(), dict(prim=c))
-        w = H.shade_case_words(data, 4 * len(c)).reshape(-1, 4)
-        m = SC.DIGEST_STREAMS[stream][1] + chunk * SC.DIGEST_CHUNK + np.arange(SC.DIGEST_CHUNK, dtype=np.uint64)
-        if stream == 0:
-            want = SC.digest_of(w[:, :2].ravel(), np.stack([2 * m, 2 * m + 1], 1).ravel())
-        elif stream in (21, 22, 25):
-            want = SC.digest_of(w[:, :3].ravel(), np.stack([3 * m, 3 * m + 1, 3 * m + 2], 1).ravel())
-        else:
-            want = SC.digest_of(w[:, 0], m)
-        assert int(H.shade_digests(int(starts[stream]) + chunk, 1)[0]) == want, (stream, chunk)
+    assert len(SC.DIGEST_STREAMS) == 36 and SC.DIGEST_STEP0 + 4 == 36
+    for stream, chunk in ((0, 0x123), (6, 4095), (19, 5), (22, 8191), (25, 7), (2, 0), (21, 17), (26, 0x123), (27, 4095), (28, 0), (29, 2048), (30, 7), (31, 4095), (32, 0),
+                          (33, 4095), (34, 2048), (35, 2048)):
+        tb, section, c = SC.digest_chunk_cases(stream, chunk)
+        data, n = SC.case_bytes(tb, {section: c})
+        w = H.shade_case_words(data, SC.WORDS[section] * len(c)).reshape(-1, SC.WORDS[section])
+        assert int(H.shade_digests(int(starts[stream]) + chunk, 1)[0]) == SC.digest_chunk_want(stream, chunk, w), (stream, chunk)
 
 
 # ---- (c) float64 restatements ---------------------------------------------------------------------------------------------------------------------------------

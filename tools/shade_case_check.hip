@@ -1,10 +1,11 @@
 // shade_case_check.hip — the shading functions of trt_path.h and the primitives of trt_prims.h / trt_exact.h under them as gfx950 compiles them (the flags
 // of the library), one thread per case, for tests/test_gpu_shade_cases.py.  Sections and their output words: tools/shade_cases.h, which also holds the one
-// function per case that both this tool and tests/hostsim call; the kernels here only pick the case of their thread.  Reads one case file, writes one
+// function per case that both this tool and tests/hostsim call (the light pickers lightPickAt / lightPick / lightWeight, lightNodeStep and lightPickNear among them); the kernels here only pick the case of their thread.  Reads one case file, writes one
 // result file, one process, one pass.  Every index the file carries is checked on the host before any launch (shadecases::parse): a bad file is exit
 // code 2, and no kernel reads memory the file did not supply.
 // usage: shade_case_check <case file> <result file>
 //        shade_case_check digest <result file>     the 64-bit digests of the exhaustive sweeps (shade_cases.h: all 2^24 uniforms, ranges of floats)
+//        shade_case_check digest-pickers <result file>     those of the light pickers over all 2^24 uniforms (shade_cases.h: pickerDigestAt)
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
@@ -53,10 +54,30 @@ __global__ __launch_bounds__(256) void k_bounce(SceneDev sc, const int32_t* rows
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) runBounce(sc, rows, cases[i], out + (size_t)W_BOUNCE * i);
 }
+__global__ __launch_bounds__(256) void k_pick(Pools pl, const PickCase* cases, uint32_t n, uint32_t* out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) runPick<HeaderFns>(pl, cases[i], out + (size_t)W_PICK * i);
+}
+__global__ __launch_bounds__(256) void k_step(const StepCase* cases, uint32_t n, uint32_t* out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) runStep<HeaderFns>(cases[i], out + (size_t)W_STEP * i);
+}
+__global__ __launch_bounds__(256) void k_near(Pools pl, const NearCase* cases, uint32_t n, uint32_t* out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) runNear(pl, cases[i], out + (size_t)W_NEAR * i);
+}
 __global__ __launch_bounds__(256) void k_digest(uint64_t* out)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < digestTotal()) out[i] = digestAt(i);
+}
+__global__ __launch_bounds__(256) void k_picker_digest(const DigestPools* pools, uint64_t* out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < pickerDigestTotal()) out[i] = pickerDigestAt(*pools, i);
 }
 
 template <class T>
@@ -76,27 +97,35 @@ static int writeFile(const char* path, const void* data, size_t bytes)
     return 0;
 }
 
-static int digestMode(const char* result)
+static int digestMode(const char* result, bool pickers)
 {
-    const size_t n = digestTotal();
+    const size_t n = pickers ? pickerDigestTotal() : digestTotal();
     CK(hipSetDevice(0));
     uint64_t* d_out = nullptr;
     CK(hipMalloc(&d_out, n * 8));
     CK(hipMemset(d_out, 0, n * 8));
-    hipLaunchKernelGGL(k_digest, blocks(n), dim3(256), 0, 0, d_out);
+    if (pickers) {
+        std::vector<DigestPools> pools(1);
+        digestPoolsFill(pools[0]);
+        const DigestPools* d_pools = toDevice<DigestPools>(pools.data(), 1);
+        hipLaunchKernelGGL(k_picker_digest, blocks(n), dim3(256), 0, 0, d_pools, d_out);
+    } else {
+        hipLaunchKernelGGL(k_digest, blocks(n), dim3(256), 0, 0, d_out);
+    }
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
     std::vector<uint64_t> out(n);
     CK(hipMemcpy(out.data(), d_out, n * 8, hipMemcpyDeviceToHost));
     if (int e = writeFile(result, out.data(), n * 8)) return e;
-    std::printf("shade_case_check: %d streams, %u digests of %d inputs\n", (int)DIGEST_STREAMS, (unsigned)n, (int)DIGEST_CHUNK);
+    std::printf("shade_case_check: %d streams, %u digests of %d inputs\n", (int)(pickers ? PICKER_STREAMS : DIGEST_STREAMS), (unsigned)n, (int)DIGEST_CHUNK);
     return 0;
 }
 
 int main(int argc, char** argv)
 {
-    if (argc != 3) { std::fprintf(stderr, "usage: %s <case file> <result file> | digest <result file>\n", argv[0]); return 2; }
-    if (!std::strcmp(argv[1], "digest")) return digestMode(argv[2]);
+    if (argc != 3) { std::fprintf(stderr, "usage: %s <case file> <result file> | digest <result file> | digest-pickers <result file>\n", argv[0]); return 2; }
+    if (!std::strcmp(argv[1], "digest")) return digestMode(argv[2], false);
+    if (!std::strcmp(argv[1], "digest-pickers")) return digestMode(argv[2], true);
     std::FILE* f = std::fopen(argv[1], "rb");
     if (!f) { std::fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }
     std::fseek(f, 0, SEEK_END);
@@ -134,6 +163,14 @@ int main(int argc, char** argv)
     const NextCase* d_next = toDevice<NextCase>(v.next, h.n_next);
     const DirCase* d_dir = toDevice<DirCase>(v.dir, h.n_dir);
     const BounceCase* d_bounce = toDevice<BounceCase>(v.bounce, h.n_bounce);
+    Pools pl;
+    pl.lights = toDevice<LightDev>(v.plights, h.n_plights);
+    pl.sel = toDevice<float>(v.psel, h.n_psel);
+    pl.nodes = toDevice<LightNode>(v.pnodes, h.n_pnodes);  // (hipMalloc: aligned for the 16-byte loads of a node)
+    pl.sets = toDevice<LightSet>(v.sets, h.n_sets);
+    const PickCase* d_pick = toDevice<PickCase>(v.pick, h.n_pick);
+    const StepCase* d_step = toDevice<StepCase>(v.step, h.n_step);
+    const NearCase* d_near = toDevice<NearCase>(v.near, h.n_near);
     const size_t n_words = (size_t)v.n_words;
     uint32_t* d_out = nullptr;
     CK(hipMalloc(&d_out, (n_words ? n_words : 1) * 4));
@@ -152,12 +189,18 @@ int main(int argc, char** argv)
     if (h.n_dir) hipLaunchKernelGGL(k_dir, blocks(h.n_dir), dim3(256), 0, 0, d_dir, h.n_dir, o);
     o += (size_t)W_DIR * h.n_dir;
     if (h.n_bounce) hipLaunchKernelGGL(k_bounce, blocks(h.n_bounce), dim3(256), 0, 0, sc, d_rows, d_bounce, h.n_bounce, o);
+    o += (size_t)W_BOUNCE * h.n_bounce;
+    if (h.n_pick) hipLaunchKernelGGL(k_pick, blocks(h.n_pick), dim3(256), 0, 0, pl, d_pick, h.n_pick, o);
+    o += (size_t)W_PICK * h.n_pick;
+    if (h.n_step) hipLaunchKernelGGL(k_step, blocks(h.n_step), dim3(256), 0, 0, d_step, h.n_step, o);
+    o += (size_t)W_STEP * h.n_step;
+    if (h.n_near) hipLaunchKernelGGL(k_near, blocks(h.n_near), dim3(256), 0, 0, pl, d_near, h.n_near, o);
     CK(hipGetLastError());
     CK(hipDeviceSynchronize());
     std::vector<uint32_t> out(n_words);
     if (n_words) CK(hipMemcpy(out.data(), d_out, n_words * 4, hipMemcpyDeviceToHost));
     if (int e = writeFile(argv[2], out.data(), out.size() * 4)) return e;
-    std::printf("shade_case_check: %u prims, %u camera, %u vertex, %u light, %u next, %u direction, %u bounce cases\n", h.n_prim, h.n_cam, h.n_vert, h.n_light, h.n_next,
-                h.n_dir, h.n_bounce);
+    std::printf("shade_case_check: %u prims, %u camera, %u vertex, %u light, %u next, %u direction, %u bounce, %u pick, %u step, %u near cases\n", h.n_prim, h.n_cam, h.n_vert,
+                h.n_light, h.n_next, h.n_dir, h.n_bounce, h.n_pick, h.n_step, h.n_near);
     return 0;
 }
